@@ -7,16 +7,22 @@
 
 One process per GPU; clips are independent, so each rank runs its own shard of the batch with no data-path
 collective (weak scaling: per-GPU batch fixed).  A step = one Stlt.forward over the rank's resident batch.
-Rank 0 prints the contract's JSON line LAST (kept under 6 KB: `value`, `config`, `roofline`, `roofline_attn_temporal`, the fused
+A plain run sets up, warms up, times --steps steps and prints one JSON line: `metric`, `value` (clips/s), `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, `config`, ...  `--dump-outputs DIR` writes what the last timed step returned (rank 0's shard) as
+DIR/<name>.npy before that line; the inputs are seeded, so two builds can be compared output for output.
+
+    python bench.py --full                        # everything else the benchmark measures, after the timed steps
+
+With --full, rank 0 prints the contract's JSON line LAST (kept under 6 KB: `value`, `config`, `roofline`, `roofline_attn_temporal`, the fused
 kernel's rooflines, `cpu_baseline`, `logit_max_abs_diff` and `legs` = {name: [clips/s, ms per step, GEMM roofline fraction,
 temporal-attention-core HBM fraction]}); before it, every bounded side measurement is a JSON line of its own, {"leg": name, ...}.
 
     python bench.py --mode train [--gpus N]      # BASELINE.json config 3: one optimisation step per "step"
 (cfg2 shapes, 64 clips per GPU, dropout 0.1 as the reference trains: forward with the tape, fused criterion, native
-reverse sweep, gradient all-reduce over RCCL when N > 1, clipping + AdamW, scheduler; same JSON contract, `roofline` priced
-with the FLOPs of every matrix-core launch of the step, forward and backward).  After the timed region the same steps are replayed with hipEvents around every
-kernel launch (library-side, on the launch stream) for the `roofline` objects, and — at N=1 — the CPU oracle
-is timed on a bounded sample for `cpu_baseline`.
+reverse sweep, gradient all-reduce over RCCL when N > 1, clipping + AdamW, scheduler; same JSON contract).  With --full, `roofline` is
+priced with the FLOPs of every matrix-core launch of the step, forward and backward: after the timed region the same steps are replayed
+with hipEvents around every kernel launch (library-side, on the launch stream), and — at N=1 — the CPU oracle is timed on a bounded
+sample for `cpu_baseline`; at N > 1 the steps are also timed without the gradient exchange (`allreduce`).
 """
 import argparse
 import importlib
@@ -26,6 +32,8 @@ import sys
 import time
 from types import SimpleNamespace
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -34,6 +42,37 @@ PKG = "revisiting-spatial-temporal-layouts_amd"
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X f32-input MFMA dense peak (MI355X_MICROARCH.md, Chip-level parameters)
 HBM_PEAK_GBS = 8000.0         # HBM3E spec peak
 CPU_BASELINE_BUDGET_S = float(os.environ.get("STLT_BENCH_CPU_BUDGET_S", "10"))  # seconds of CPU work of the cpu_baseline leg (the test suite shortens it)
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much; a larger output is written as a fixed, seeded sample
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor} of what the timed path returned -> out_dir/<name>.npy (float64 stays float64, everything else float32).
+    An array above its share of DUMP_BUDGET_BYTES is written as out_dir/<name>_sample.npy: the elements at a fixed, seeded set of flat
+    indices (sorted), the same from run to run for the same shapes."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        fname = name
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a, fname = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(out_dir, fname + ".npy"), a)
+        written[fname] = list(a.shape)
+    return written
+
+
+def param_sample(model, n=1 << 20):
+    """A fixed, seeded sample of a model's parameters after a step, for --dump-outputs of --mode train: the elements at n seeded flat
+    indices of all parameters concatenated in named_parameters() order."""
+    import torch
+
+    flat = torch.cat([p.detach().reshape(-1) for _, p in model.named_parameters()])
+    idx = torch.randint(0, flat.numel(), (min(n, flat.numel()),), generator=torch.Generator().manual_seed(0)).sort().values
+    return flat[idx.to(flat.device)]
 
 
 def gemm_flops_per_step(B, T, N, d, n_sp, n_tp, classes, cls_only, fused_tp_layers=0, fused_sp_layers=0):
@@ -457,12 +496,27 @@ def bench_train(args, pkg, torch, dist, rank, world, dev, one_gpu, pin=None):
         res = tr.step(batch)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # what the last timed step left: its loss and gradient norm, and the parameters it updated
+        dump_outputs(args.dump_outputs, {"loss": res["loss"], "grad_norm": res["grad_norm"], "params_sample": param_sample(model)})
     ranks = rank_report(torch, dist, world, one_gpu, dev, elapsed / args.steps * 1e3, pin)
     if dist is not None:
         t = torch.tensor([elapsed], device="cpu" if one_gpu else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    out = {
+        "metric": "clips/s STLT train step (T=32, N_obj=7, d=768)" if args.config == "cfg2" else f"clips/s STLT train step ({args.config})",
+        "value": round(world * B * args.steps / elapsed, 2), "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.config}: STLT optimisation step (forward with tape, cross entropy, reverse sweep, clip 5.0, AdamW 5e-5 / wd 1e-3 "
+                               f"in two groups, warm-up schedule), T={T}, N={N}, d={d}, H={c['num_attention_heads']}, "
+                               f"{c['num_spatial_layers']}+{c['num_temporal_layers']} layers, {c['num_classes']} classes, dropout 0.1",
+                   "per_gpu_batch": B, "global_batch": B * world,
+                   "parallelism": f"batch-shard x{world}" + (", flat-gradient all-reduce (RCCL) in two slices overlapped with the reverse sweep" if world > 1 else ", no collective")},
+        "loss": float(res["loss"]), "grad_norm": float(res["grad_norm"]), "ranks": ranks,
+    }
+    if not args.full:
+        return out if rank == 0 else None
     # exposed all-reduce time: the same steps without the gradient exchange (every rank on its own shard, no collective inside)
     exposed = None
     if world > 1:
@@ -506,21 +560,14 @@ def bench_train(args, pkg, torch, dist, rank, world, dev, one_gpu, pin=None):
         return None
     gemm_ms, gemm_n = k_ms.get("gemm", (0.0, 0))
     gemm_tflops = gflops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    out = {
-        "metric": "clips/s STLT train step (T=32, N_obj=7, d=768)" if args.config == "cfg2" else f"clips/s STLT train step ({args.config})",
-        "value": round(world * B * args.steps / elapsed, 2), "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.config}: STLT optimisation step (forward with tape, cross entropy, reverse sweep, clip 5.0, AdamW 5e-5 / wd 1e-3 "
-                               f"in two groups, warm-up schedule), T={T}, N={N}, d={d}, H={c['num_attention_heads']}, "
-                               f"{c['num_spatial_layers']}+{c['num_temporal_layers']} layers, {c['num_classes']} classes, dropout 0.1",
-                   "per_gpu_batch": B, "global_batch": B * world,
-                   "parallelism": f"batch-shard x{world}" + (", flat-gradient all-reduce (RCCL) in two slices overlapped with the reverse sweep" if world > 1 else ", no collective")},
+    ranks = out.pop("ranks")
+    out.update({
         "roofline": {"kernel": "gemm_nt_kernel + gemm16_kernel, forward + backward (dX, dW) products of the step (event-timed on one stream: the timed steps run the dW products on the side stream)", "bound": "mfma", "achieved": round(gemm_tflops, 2),
                      "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(gemm_tflops / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
                      "launches_per_step": gemm_n, "ms_per_step": round(gemm_ms, 4), "flops_per_step": gflops},
         "kernel_ms_per_step": {k: round(v[0], 4) for k, v in k_ms.items()},
-        "loss": float(res["loss"]), "grad_norm": float(res["grad_norm"]), "ranks": ranks,
-    }
+        "ranks": ranks,
+    })
     if exposed is not None:
         out["allreduce"] = exposed
     if world == 1 and not args.no_cpu_baseline:
@@ -591,8 +638,25 @@ def _timed(torch, dev, fn, warmup, steps):
     return (time.perf_counter() - t0) / steps, res
 
 
+def contract_line(ctx, world, ms_per_step, ranks):
+    """The contract line of the timed forward as a plain run prints it: what the timed steps measured, and the workload."""
+    args, c, B, T, N, d, H = ctx.args, ctx.c, ctx.B, ctx.T, ctx.N, ctx.d, ctx.H
+    return {
+        "metric": ("clips/s STLT forward (T=32, N_obj=7, d=768)" if args.config == "cfg2" else f"clips/s STLT forward ({args.config})") + (" [PROFILING RUN: split-bf16 products in the timed region]" if args.split_bf16_main else ""),
+        "value": round(ctx.clips_per_s, 2), "unit": "clips/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.config}: STLT forward, T={T}, N={N}, d={d}, H={H}, "
+                               f"{c['num_spatial_layers']}+{c['num_temporal_layers']} layers, {c['num_classes']} classes",
+                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"batch-shard x{world}, no collective",
+                   "cls_only_last_spatial": not args.no_cls_only,
+                   "flops_per_clip_dense": ctx.pkg.synth.flops_per_clip(T, N, d, c["num_spatial_layers"], c["num_temporal_layers"], c["num_classes"])},
+        "ranks": ranks,
+    }
+
+
 def headline_objects(ctx, world, ms_per_step, ranks):
-    """The contract line's objects for the timed forward: per-kernel durations from the library's hipEvents (same workload, replayed
+    """--full: the contract line's objects for the timed forward: per-kernel durations from the library's hipEvents (same workload, replayed
     after the timed region), priced against the MFMA / HBM peaks.  Long notes go to out["_detail"] (printed as a line of its own)."""
     pkg, torch, dev, args, c, B, T, N, d, H = ctx.pkg, ctx.torch, ctx.dev, ctx.args, ctx.c, ctx.B, ctx.T, ctx.N, ctx.d, ctx.H
     try:
@@ -643,16 +707,9 @@ def headline_objects(ctx, world, ms_per_step, ranks):
         traffic = {"gemm": tj.get("gemm_avg_bytes_per_launch"), "attn_temporal": tj.get("attn_temporal_avg_bytes_per_launch"),
                    "attn_spatial": tj.get("attn_spatial_avg_bytes_per_launch"), "mhsa": tj.get("mhsa_fused_avg_bytes_per_launch"),
                    "mhsa_spatial": tj.get("mhsa_fused_spatial_avg_bytes_per_launch")}
-    out = {
-        "metric": ("clips/s STLT forward (T=32, N_obj=7, d=768)" if args.config == "cfg2" else f"clips/s STLT forward ({args.config})") + (" [PROFILING RUN: split-bf16 products in the timed region]" if args.split_bf16_main else ""),
-        "value": round(ctx.clips_per_s, 2), "unit": "clips/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.config}: STLT forward, T={T}, N={N}, d={d}, H={H}, "
-                               f"{c['num_spatial_layers']}+{c['num_temporal_layers']} layers, {c['num_classes']} classes",
-                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"batch-shard x{world}, no collective",
-                   "cls_only_last_spatial": cls_only,
-                   "flops_per_clip_dense": pkg.synth.flops_per_clip(T, N, d, c["num_spatial_layers"], c["num_temporal_layers"], c["num_classes"])},
+    out = contract_line(ctx, world, ms_per_step, ranks)
+    ranks = out.pop("ranks")
+    out.update({
         "roofline": {"kernel": "gemm_nt_kernel + gemm16_kernel (every nn.Linear product of the step)", "bound": "mfma", "achieved": round(gemm_tflops, 2),
                      "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(gemm_tflops / MFMA_F32_PEAK_TFLOPS, 4),
                      "traffic": traffic.get("gemm"), "launches_per_step": gemm_n, "ms_per_step": round(gemm_ms, 4), "flops_per_step": gflops},
@@ -663,7 +720,7 @@ def headline_objects(ctx, world, ms_per_step, ranks):
         "roofline_attn_spatial": {"bound": "hbm", "achieved": round(as_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(as_gbs / HBM_PEAK_GBS, 4),
                                   "traffic": traffic.get("attn_spatial"), "launches_per_step": as_n, "us_per_launch": round(as_ms / max(as_n, 1) * 1e3, 2)},
         "ranks": ranks,
-    }
+    })
     for tower, key, tk in (("temporal", "roofline_mhsa_fused", "mhsa"), ("spatial", "roofline_mhsa_fused_spatial", "mhsa_spatial")):
         if (fused_tp if tower == "temporal" else fused_sp):
             r = mhsa_fused_roofline(k_ms, plan, tower)
@@ -869,6 +926,9 @@ def main():
     ap.add_argument("--no-side-legs", action="store_true", help="skip the bounded sub-measurements of the default line (train_step, cfg4, small_batch, cfg5)")
     ap.add_argument("--side-legs", action="store_true", help="run the sub-measurements at any --batch (they ride on the default cfg2 / 1024-clip line only otherwise)")
     ap.add_argument("--no-cls-only", action="store_true", help="dense schedule: run the last spatial / last temporal layer on every token")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else the benchmark measures: per-kernel rooflines, the side "
+                                                        "legs, the opt-in variants, the CPU baseline (the --no-* options above thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (rank 0's shard) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 1024 if args.mode == "forward" else 64
@@ -876,6 +936,8 @@ def main():
         args.steps = 50 if args.mode == "forward" else 20
     if args.warmup is None:
         args.warmup = 10 if args.mode == "forward" else 5
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -945,6 +1007,8 @@ def main():
         logits = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # Stlt.forward's {"stlt": (B, num_classes)} of the last timed step
+        dump_outputs(args.dump_outputs, {"stlt": logits})
     ranks = rank_report(torch, dist, world, one_gpu, dev, elapsed / args.steps * 1e3, pin)
     if dist is not None:
         t = torch.tensor([elapsed], device="cpu" if one_gpu else dev, dtype=torch.float64)
@@ -956,6 +1020,9 @@ def main():
     if rank == 0:
         ctx = SimpleNamespace(pkg=pkg, torch=torch, dev=dev, args=args, c=c, model=model, sd=sd, batch=batch, cpu_batch=cpu_batch, step=step,
                               logits=logits, clips_per_s=clips_per_s, B=B, T=T, N=N, d=d, H=c["num_attention_heads"], x3_logits=None)
+    if rank == 0 and not args.full:
+        print(json.dumps(contract_line(ctx, world, ms_per_step, ranks)), flush=True)
+    elif rank == 0:
         out = headline_objects(ctx, world, ms_per_step, ranks)
         legs = {}
 

@@ -1,5 +1,5 @@
 // Host-side fuzz of libstlt_hip's launchers under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_host_sanitizers.py builds the
-// library's sources with `hipcc --offload-host-only -fsanitize=address,undefined` and links this driver against them; no GPU is involved).
+// library's sources with `hipcc --offload-host-only -fsanitize=address,undefined -fno-gpu-sanitize` and links this driver against them; no GPU is involved).
 //
 // What runs on the host inside the C-ABI is plan arithmetic: byte-size functions, workspace / tape / scratch layouts, the small-tile cost
 // tables and routing estimates, stream-K and grouped-launch plans, persistent-grid sizing, argument checks.  This driver feeds every entry

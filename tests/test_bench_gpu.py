@@ -1,18 +1,22 @@
 """bench.py end to end: the single-process line, and the multi-rank launch the driver uses (two ranks sharing cuda:0 through
-STLT_BENCH_ONE_GPU=1 / gloo, since the test box has one GPU): one JSON line on rank 0 with the contract's fields."""
+STLT_BENCH_ONE_GPU=1 / gloo, since the test box has one GPU): one JSON line on rank 0 with the contract's fields.  A plain run prints
+that line alone (and writes the last timed step's outputs with --dump-outputs); --full adds the rooflines, side legs and CPU baseline."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
-            "data", "config", "roofline"}
+PLAIN = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+         "data", "config"}
+REQUIRED = PLAIN | {"roofline"}
 
 
 def _last_json(stdout: str, with_legs=False):
@@ -36,7 +40,7 @@ def _last_json(stdout: str, with_legs=False):
 
 
 def test_single_process_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "64"], cwd=ROOT, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "64"], cwd=ROOT, capture_output=True, text=True,
                        timeout=600, env=dict(os.environ, STLT_BENCH_CPU_BUDGET_S="2"))
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -48,9 +52,52 @@ def test_single_process_line():
     assert j["roofline_attn_temporal"]["bound"] == "hbm" and j["roofline_attn_temporal"]["frac"] > 0
 
 
+def test_plain_line_is_the_timed_steps_and_dumps_the_last_one(pkg, tmp_path):
+    """A plain run: the contract line alone, priced on exactly --steps timed steps; --dump-outputs holds the logits of the last one, which
+    are the oracle's for the seeded batch."""
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "64", "--dump-outputs", str(out)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert PLAIN <= set(j) and not {"roofline", "legs", "cpu_baseline"} & set(j), sorted(j)
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["n_gpus"] == 1 and j["config"]["per_gpu_batch"] == 64
+    assert j["unit"] == "clips/s" and j["higher_is_better"] is True and j["dtype"] == "f32" and j["metric"].startswith("clips/s STLT forward")
+    assert j["ms_per_step"] > 0 and abs(j["value"] - 64 / (j["ms_per_step"] * 1e-3)) <= 1e-3 * j["value"]
+    assert sorted(os.listdir(out)) == ["stlt.npy"]
+    logits = np.load(out / "stlt.npy")
+    c = pkg.synth.CONFIGS["cfg2"]
+    assert logits.dtype == np.float32 and logits.shape == (64, c["num_classes"]) and np.isfinite(logits).all()
+    from oracle import stlt_oracle as O
+    model = pkg.Stlt(pkg.StltModelConfig(**pkg.synth.model_kwargs("cfg2")))
+    sd = pkg.synth.make_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()}, seed=1234)
+    batch = pkg.synth.make_batch(64, c["T"], c["N"], dataset=c["dataset"], seed=1000)
+    with torch.no_grad():
+        ref = O.stlt_forward(sd, {k: v[:4] for k, v in batch.items()}, c["num_attention_heads"])["stlt"].numpy()
+    assert np.abs(logits[:4] - ref).max() <= 1e-4
+
+
+def test_train_mode_plain_line_dumps_the_last_step(tmp_path):
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--mode", "train", "--steps", "2", "--warmup", "1", "--batch", "8", "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert PLAIN <= set(j) and not {"roofline", "cpu_baseline", "kernel_ms_per_step"} & set(j), sorted(j)
+    assert j["steps"] == 2 and "train step" in j["metric"] and j["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["grad_norm.npy", "loss.npy", "params_sample.npy"]
+    loss, gn, prm = (np.load(out / f"{n}.npy") for n in ("loss", "grad_norm", "params_sample"))
+    assert loss.dtype == np.float32 and abs(float(loss[0]) - j["loss"]) <= 1e-6 * max(1.0, abs(j["loss"])) and float(gn[0]) > 0
+    assert prm.dtype == np.float32 and prm.shape == (1 << 20,) and np.isfinite(prm).all()
+
+
 def test_side_legs_ride_on_the_default_line():
     """train_step / cfg4 / small_batch sub-objects (BASELINE configs 3, 4 and the reference's default batch) next to `value`."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "256", "--side-legs", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "256", "--side-legs", "--no-cpu-baseline",
                         "--no-skip-padding"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     head, j = _last_json(r.stdout, with_legs=True)
@@ -97,7 +144,7 @@ def test_two_rank_launch_line():
         port = s.getsockname()[1]
     env = dict(os.environ, STLT_BENCH_ONE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64"],
+                        "--master-port", str(port), "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -107,7 +154,7 @@ def test_two_rank_launch_line():
 
 
 def test_train_mode_single_process_line():
-    r = subprocess.run([sys.executable, "bench.py", "--mode", "train", "--steps", "2", "--warmup", "1", "--batch", "8"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--mode", "train", "--steps", "2", "--warmup", "1", "--batch", "8"], cwd=ROOT,
                        capture_output=True, text=True, timeout=900, env=dict(os.environ, STLT_BENCH_CPU_BUDGET_S="2"))
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)
@@ -123,7 +170,7 @@ def test_train_mode_two_rank_launch_line():
         port = s.getsockname()[1]
     env = dict(os.environ, STLT_BENCH_ONE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), "bench.py", "--mode", "train", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8"],
+                        "--master-port", str(port), "bench.py", "--full", "--mode", "train", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _last_json(r.stdout)

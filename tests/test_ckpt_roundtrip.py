@@ -1,7 +1,10 @@
 """Checkpoint round trip (reference src/train.py:147-152 -> src/inference.py:59-69): tests/golden/ckpt_trained_nano.npz holds the tensors of
 a checkpoint file that `Trainer.fit_epochs` WROTE on an MI355X after training (tools/make_ckpt_fixture.py) and the logits the package
-computed from it there.  The oracle (pinned to the reference) and — in the build container, where /root/reference exists — the
-reference's own `Stlt` with strict=True reproduce those logits from the same tensors; on a GPU the package's module does."""
+computed from it there.  The oracle (pinned to the reference) reproduces those logits from the same tensors, and so did the reference's own
+`Stlt` loaded with strict=True (its schemas and logits are stored beside the checkpoint, tests/golden/ckpt_trained_nano_reference.*,
+recorded by tools/check_ckpt_roundtrip.py --write-golden); on a GPU the package's module does."""
+import importlib.util
+import json
 import os
 
 import numpy as np
@@ -36,22 +39,25 @@ def test_written_checkpoint_has_the_reference_schema_and_the_oracle_reproduces_i
     assert float((got.argmax(1) == labels).mean()) == float(z["__top1__"][z["__saved_epochs__"]][-1])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference tree exists in the build container only")
-def test_written_checkpoint_loads_strictly_into_the_reference_model():
-    import importlib.util
+def test_written_checkpoint_loads_strictly_into_the_reference_model(pkg):
+    """load_state_dict(strict=True) into the reference's Stlt, and into its StltBackbone for the backbone file the trainer writes beside
+    it (src/train.py:152 -> models.py:130-134), compares names and shapes: the checkpoint's must be the recorded ones.  The reference's CPU
+    forward from these very tensors (same digest) gave the logits the package computed on the GPU and the accuracy of the saved epoch."""
+    z, sd, val = _load(pkg)
+    ref = np.load(os.path.join(GOLDEN, "ckpt_trained_nano_reference.npz"))
+    with open(os.path.join(GOLDEN, "ckpt_trained_nano_reference_schema.json")) as f:
+        meta = json.load(f)
     spec = importlib.util.spec_from_file_location("check_ckpt_roundtrip", os.path.join(ROOT, "tools", "check_ckpt_roundtrip.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    saved_path, saved_mods = list(__import__("sys").path), set(__import__("sys").modules)
-    try:
-        r = mod.check()
-    finally:  # the reference's `modelling` / `utils` packages must not leak into the other tests of this process
-        import sys
-        sys.path[:] = saved_path
-        for m in set(sys.modules) - saved_mods:
-            if m.split(".")[0] in ("modelling", "utils"):
-                del sys.modules[m]
-    assert r["ok"] and r["max_abs_logit_diff"] <= 1e-4, r
+    assert mod.checkpoint_digest(sd) == meta["checkpoint_digest"]
+    schema = lambda tensors: {k: [list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in tensors.items()}
+    assert schema(sd) == meta["stlt"]
+    assert schema({k[len("backbone."):]: v for k, v in sd.items() if k.startswith("backbone.")}) == meta["backbone"]
+    assert np.abs(ref["logits"] - z["__logits__"]).max() <= 1e-4
+    labels = torch.cat([b["labels"] for b in val]).numpy()
+    top1 = float((ref["logits"].argmax(1) == labels).mean())
+    assert top1 == meta["top1_reference_forward"] == float(z["__top1__"][z["__saved_epochs__"]][-1])
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 """The host halves of every launcher under AddressSanitizer + UndefinedBehaviorSanitizer (SURVEY §5 "race detection / sanitizers"; GPU
 sanitizers are not available on the pool, and what runs on the host is exactly what they would not see anyway: ~3 k lines of plan
 arithmetic — stream-K and grouped-launch plans, the small-tile cost tables, workspace / tape / scratch layouts, overflow guards, argument
-checks).  The library's sources are compiled `--offload-host-only` with `-fsanitize=address,undefined -fno-sanitize-recover`, linked with
+checks).  The library's sources are compiled `--offload-host-only` with `-fsanitize=address,undefined -fno-gpu-sanitize -fno-sanitize-recover`, linked with
 tests/host_fuzz.hip (the driver) and tests/host_fuzz_stubs.cpp (a stand-in HIP runtime that checks every launch configuration and then
 "succeeds", so each entry point runs its whole host-side launch sequence), and the driver calls every C-ABI entry point with random,
 tile-boundary and extreme shapes and fake device pointers.  No GPU is involved: it runs in the build container."""
@@ -20,7 +20,8 @@ OUT = os.path.join(ROOT, "build", "host_san")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 NM = shutil.which("nm") or "/usr/bin/nm"
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-O1", "-g"]
+# host code only: -fno-gpu-sanitize keeps every device pass (none runs under --offload-host-only) uninstrumented
+SAN = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-O1", "-g"]
 ITERS = 1500
 
 
@@ -64,7 +65,7 @@ def build_host_fuzz():
     stubs_o = os.path.join(OUT, "host_fuzz_stubs.o")
     subprocess.run([CLANG, *SAN, "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-c", os.path.join(ROOT, "tests", "host_fuzz_stubs.cpp"), "-o", stubs_o],
                    check=True)
-    r = subprocess.run([HIPCC, "-fsanitize=address,undefined", *objs, fat_o, stubs_o, "-o", exe], capture_output=True, text=True)
+    r = subprocess.run([HIPCC, "-fsanitize=address,undefined", "-fno-gpu-sanitize", *objs, fat_o, stubs_o, "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     return exe
 

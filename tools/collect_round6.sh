@@ -8,7 +8,7 @@ O=$R/gpurun_out/round6
 mkdir -p $O
 cd $R
 export TMPDIR=/tmp
-NS="--no-cpu-baseline --no-skip-padding --no-split-bf16 --no-side-legs"
+NS="--full --no-cpu-baseline --no-skip-padding --no-split-bf16 --no-side-legs"  # --full: the rooflines (per-kernel replay) stay in
 if [ "$1" == "suites" ]; then
   python tools/soak.py --reps 200 > $O/round6_soak.jsonl 2>/dev/null
   python -m pytest tests -q -m gpu > $O/round6_pytest_gpu.log 2>&1
@@ -23,8 +23,8 @@ PY
   exit 0
 fi
 # 1. the default line (what the driver runs) and the training line
-python bench.py > $O/round6_bench_b1024.jsonl 2> $O/round6_bench_b1024.err   # one JSON line per side leg, the contract line last
-python bench.py --mode train > $O/round6_bench_train_b64.json 2> $O/round6_bench_train_b64.err
+python bench.py --full > $O/round6_bench_b1024.jsonl 2> $O/round6_bench_b1024.err   # one JSON line per side leg, the contract line last
+python bench.py --full --mode train > $O/round6_bench_train_b64.json 2> $O/round6_bench_train_b64.err
 # 2. batch / config sweep of the forward (the reference's real layouts included), and the 64-clip points with the small-tile routing off
 : > $O/round6_bench_sweep.jsonl
 for args in "--config cfg2 --batch 64" "--config cfg2 --batch 256" "--config cfg2p --batch 64" "--config cfg2p --batch 1024" "--config refdef --batch 64" \
@@ -72,7 +72,7 @@ python3 $R/tools/pmc_traffic.py $O/round6_traffic_pmc_cfg2p.json /tmp/pf2 /tmp/p
 # 6. the training step under the tracer: kernel statistics + the timeline of one step (two streams = default; one stream beside it)
 for mode in 1 0; do
   rm -rf /tmp/pt$mode
-  STLT_TRAIN_DW_STREAM=$mode rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt$mode -o o -- python3 $R/bench.py --mode train --no-cpu-baseline --steps 6 --warmup 2 > $O/round6_train_under_rocprof_dw$mode.log 2>&1
+  STLT_TRAIN_DW_STREAM=$mode rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt$mode -o o -- python3 $R/bench.py --full --mode train --no-cpu-baseline --steps 6 --warmup 2 > $O/round6_train_under_rocprof_dw$mode.log 2>&1
   python3 $R/tools/step_trace.py $(find /tmp/pt$mode -name '*kernel_trace.csv' | head -1) --summary --back 6 > $O/round6_train_step_timeline_b64_dw$mode.txt
 done
 cp $(find /tmp/pt1 -name '*kernel_stats.csv' | head -1) $O/round6_train_step_kernel_stats_b64.csv

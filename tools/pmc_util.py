@@ -60,7 +60,7 @@ def main():
                     e[nm] = round(a[c][0] / w[0], 4)
         res[k] = e
     json.dump({"command": "rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY "
-                          "SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -- python3 bench.py --steps 2 --warmup 1 "
+                          "SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 "
                           "--no-cpu-baseline --no-skip-padding  [cfg2, 1024 clips]", "kernels": res}, open(out, "w"), indent=1)
     for k in sorted(res):
         if "gemm_nt" in k or "attn_core" in k or "attn16" in k:

@@ -7,7 +7,7 @@ kernel (default: embed_kernel, the first kernel of a forward), with its duration
 import argparse, csv, re, collections
 ap = argparse.ArgumentParser()
 ap.add_argument("trace"); ap.add_argument("--marker", default=r"(^|::| )embed_kernel<", help="regex of the kernel that starts a step"); ap.add_argument("--summary", action="store_true")
-ap.add_argument("--back", type=int, default=0, help="take the step that ends N markers before the last one (bench.py --mode train ends with `steps` event-timed replays on one stream)")
+ap.add_argument("--back", type=int, default=0, help="take the step that ends N markers before the last one (bench.py --full --mode train ends with `steps` event-timed replays on one stream)")
 a = ap.parse_args()
 rows = list(csv.DictReader(open(a.trace)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
