@@ -331,6 +331,57 @@ int stlt_caf_forward_flags(const stlt_caf_params* p, const stlt_inputs* in, cons
                            size_t workspace_bytes, int flags, float* logits_caf, float* logits_stlt, float* logits_resnet3d,
                            float* logits_ensemble, stlt_stream_t stream);
 
+/* ---- R3D-50 video trunk (reference src/modelling/resnets3d.py:93-214, generate_model(50) minus avgpool / fc; models.py:198-228) ----
+ * Internal activations are channels-last (NDHWC).  A Conv3d is an implicit GEMM on the f32 MFMA (csrc/r3d.hip): M = B·To·Ho·Wo
+ * output positions, N = c_out, K = kt·kh·kw·c_in, with the weight repacked to (c_out, kt, kh, kw, c_in) by stlt_conv3d_repack.
+ * Epilogue, in this order: eval BatchNorm3d from its buffers (γ·(v - mean)/sqrt(var + eps) + β; bn_w == NULL: none), + residual
+ * (same NDHWC shape as y; NULL: none), ReLU when relu != 0 — Bottleneck's relu(bn3(conv3(x)) + shortcut), resnets3d.py:70-91.
+ * c_in (channels as stored, in x and in the packed weight) must be a multiple of 4: the stem's 3 input channels are padded to 4 by
+ * stlt_ncdhw_to_ndhwc / stlt_conv3d_repack.  Padding taps read as zeros.
+ * n_split splits the contraction: 1 = whole tiles; > 1 = that many k-ranges, whose partial products go to `workspace`
+ * (stlt_conv3d_workspace_bytes(d, n_split) bytes) and are summed in split order by a second launch — deterministic, bit-identical
+ * from run to run; 0 = the library's plan for the shape (host arithmetic over the shape alone), split only when the workspace lent
+ * holds what the plan needs. */
+typedef struct {
+  int64_t B, T, H, W, c_in;   /* input (B, T, H, W, c_in) NDHWC */
+  int64_t c_out;
+  int64_t kt, kh, kw;         /* kernel */
+  int64_t st, sh, sw;         /* stride */
+  int64_t pt, ph, pw;         /* zero padding, each in [0, kernel) */
+} stlt_conv3d_desc;
+size_t stlt_conv3d_workspace_bytes(const stlt_conv3d_desc* d, int n_split);  /* 0 for a bad descriptor or an unsplit launch */
+int stlt_conv3d_fwd(const stlt_conv3d_desc* d, const float* x, const float* w_packed, const float* bn_w, const float* bn_b, const float* bn_mean,
+                    const float* bn_var, float bn_eps, const float* residual, int relu, int n_split, void* workspace, size_t workspace_bytes,
+                    float* y, stlt_stream_t stream);
+/* PyTorch Conv3d weight (c_out, c_in, kt, kh, kw) -> (c_out, kt, kh, kw, c_pad), channels c_in .. c_pad-1 zero */
+int stlt_conv3d_repack(const float* w, int64_t c_out, int64_t c_in, int64_t kt, int64_t kh, int64_t kw, int64_t c_pad, float* out, stlt_stream_t stream);
+/* layouts: (B, C, T, H, W) -> (B, T, H, W, c_pad) with channels C .. c_pad-1 zero; (B, P, C) -> (B, C, P) */
+int stlt_ncdhw_to_ndhwc(const float* x, int64_t B, int64_t C, int64_t T, int64_t H, int64_t W, int64_t c_pad, float* y, stlt_stream_t stream);
+int stlt_ndhwc_to_ncdhw(const float* x, int64_t B, int64_t P, int64_t C, float* y, stlt_stream_t stream);
+/* MaxPool3d(kernel_size=3, stride=2, padding=1) (resnets3d.py:124) in NDHWC: y (B, To, Ho, Wo, C), To = (T - 1) / 2 + 1 etc.; -inf padding */
+int stlt_maxpool3d_ndhwc(const float* x, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, float* y, stlt_stream_t stream);
+/* AdaptiveAvgPool3d((1, 1, 1)) of NDHWC (B, P, C) -> (B, C) (Resnet3D's head, models.py:225): positions summed in order, / P */
+int stlt_avgpool_ndhwc(const float* x, int64_t B, int64_t P, int64_t C, float* y, stlt_stream_t stream);
+
+/* The whole trunk: the 53 convolutions in state-dict order — the stem (resnet.0 / resnet.1), then per Bottleneck conv1, conv2,
+ * conv3 and, in the first block of each layer, downsample.0 (shortcut type B) — each with the BatchNorm3d that follows it. */
+#define STLT_R3D_CONVS 53
+typedef struct {
+  const float* w;             /* packed (c_out, kt, kh, kw, c_in): stlt_conv3d_repack; the stem's c_in padded to 4 */
+  const float *bn_w, *bn_b, *bn_mean, *bn_var;
+} stlt_r3d_conv;
+typedef struct {
+  stlt_r3d_conv conv[STLT_R3D_CONVS];
+  float bn_eps;               /* 1e-5 */
+} stlt_r3d_params;
+/* workspace of stlt_r3d_forward for video (B, 3, T, H, W): pure host arithmetic, callable without a GPU; 0 for B <= 0 */
+size_t stlt_r3d_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
+/* Resnet3D.forward_features (models.py:221-222) on video (B, 3, T, H, W) NCDHW fp32 -> features (B, 2048, To, Ho, Wo) NCDHW
+ * ((B, 2048, 2, 4, 4) for 32 x 112 x 112 clips) and/or pooled (B, 2048), its global average (either may be NULL, not both).
+ * BatchNorm in eval semantics always (Resnet3D.train keeps it there, models.py:215-219).  The workspace is 256-byte aligned. */
+int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
+                     float* features, float* pooled, stlt_stream_t stream);
+
 /* ---- training step (reference src/train.py:119-135: forward, loss.backward(); optimiser step further below) ----
  * stlt_train_forward runs every layer on every row — except that the last layer of each tower runs its out-proj /
  * norms / FFN only on the rows read afterwards (CLS row per frame, frame lengths-1 per clip; same loss and gradients,

@@ -88,6 +88,21 @@ class Inputs(C.Structure):
         ("n_real_tokens", C.c_int64), ("n_real_frames", C.c_int64)]
 
 
+class Conv3dDesc(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("B", "T", "H", "W", "c_in", "c_out", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw")]
+
+
+class R3dConv(C.Structure):
+    _fields_ = [(n, _vp) for n in ("w", "bn_w", "bn_b", "bn_mean", "bn_var")]
+
+
+R3D_CONVS = 53
+
+
+class R3dParams(C.Structure):
+    _fields_ = [("conv", R3dConv * R3D_CONVS), ("bn_eps", C.c_float)]
+
+
 # symbol -> (restype, argtypes); the not-gpu tests check that every one of these is exported
 SIGNATURES = {
     "stlt_version": (C.c_int, []),
@@ -189,6 +204,15 @@ SIGNATURES = {
     "stlt_prof_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "stlt_prof_launches": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64)]),
     "stlt_debug_set_buffer": (C.c_int, [_vp]),
+    "stlt_conv3d_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc), C.c_int]),
+    "stlt_conv3d_fwd": (C.c_int, [C.POINTER(Conv3dDesc), _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "stlt_conv3d_repack": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_ncdhw_to_ndhwc": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_ndhwc_to_ncdhw": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_maxpool3d_ndhwc": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_avgpool_ndhwc": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_r3d_workspace_bytes": (C.c_size_t, [C.c_int64] * 4),
+    "stlt_r3d_forward": (C.c_int, [C.POINTER(R3dParams), _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_size_t, _vp, _vp, _vp]),
 }
 
 _lib = None

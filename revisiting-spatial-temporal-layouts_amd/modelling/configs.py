@@ -39,7 +39,8 @@ class StltModelConfig:
 class MultimodalModelConfig:
     """Attribute surface of the reference's ``MultimodalModelConfig`` (src/modelling/configs.py:128-175) for CAF / CACNF
     on precomputed appearance features: ``stlt_config`` for the layout branch plus the appearance / fusion sizes.
-    ``resnet_model_path`` is accepted and ignored (the R3D-50 trunk does not run here)."""
+    ``resnet_model_path`` is read only with ``appearance_trunk=True`` (then the R3D-50 trunk is part of the model and runs on
+    ``video_frames``); by default the appearance branch starts from precomputed features and the path is ignored."""
 
     def __init__(self, **kwargs):
         self.stlt_config = StltModelConfig(**dict(kwargs))
@@ -55,8 +56,42 @@ class MultimodalModelConfig:
         self.num_fusion_layers = kwargs.pop("num_fusion_layers", 4)
         self.load_backbone_path = kwargs.pop("load_backbone_path", None)
         self.freeze_backbone = kwargs.pop("freeze_backbone", False)
+        # opt-in: the appearance branch carries the R3D-50 trunk (the reference's `appearance_branch.resnet.*` keys) and runs it on
+        # `video_frames` when a batch has no `appearance_features`.  Off: the branch starts from precomputed features, as before.
+        self.appearance_trunk = bool(kwargs.pop("appearance_trunk", False))
         self.appearance_config = self
         self.stlt_config.load_backbone_path = None  # the fusion models build a fresh layout branch (models.py:439)
 
 
-model_configs_factory = {"stlt": StltModelConfig, "caf": MultimodalModelConfig, "cacnf": MultimodalModelConfig}
+class AppearanceModelConfig:
+    """Attribute surface of the reference's ``AppearanceModelConfig`` (src/modelling/configs.py:129-145).  ``resnet_model_path`` is
+    optional here: without it the trunk keeps its fresh initialisation (load a state dict afterwards)."""
+
+    def __init__(self, **kwargs):
+        self.num_classes = kwargs.pop("num_classes", None)
+        assert self.num_classes, "num_classes must not be None!"
+        self.hidden_size = kwargs.pop("hidden_size", 768)
+        self.hidden_dropout_prob = kwargs.pop("hidden_dropout_prob", 0.1)
+        self.layer_norm_eps = kwargs.pop("layer_norm_eps", 1e-12)
+        self.num_attention_heads = kwargs.pop("num_attention_heads", 12)
+        self.appearance_num_frames = kwargs.pop("appearance_num_frames", None)
+        assert self.appearance_num_frames, "appearance_num_frames must not be None!"
+        self.resnet_model_path = kwargs.pop("resnet_model_path", None)
+        self.num_appearance_layers = kwargs.pop("num_appearance_layers", 4)
+
+    def __repr__(self):
+        rows = [("Number of classes", self.num_classes), ("Max number of appearance frames", self.appearance_num_frames),
+                ("Hidden size", self.hidden_size), ("If Transformer: Number of attention heads", self.num_attention_heads),
+                ("If Transformer: Number of layers", self.num_appearance_layers),
+                ("If Transformer: Hidden dropout probability", self.hidden_dropout_prob)]
+        return "\n".join(f"- {k}: {v}" for k, v in rows)
+
+
+model_configs_factory = {
+    "stlt": StltModelConfig,
+    "resnet3d": AppearanceModelConfig,
+    "resnet3d-transformer": AppearanceModelConfig,
+    "lcf": MultimodalModelConfig,
+    "caf": MultimodalModelConfig,
+    "cacnf": MultimodalModelConfig,
+}

@@ -2,9 +2,12 @@
 on PRECOMPUTED appearance features (reference src/modelling/models.py:230-271, 286-322, 328-549; BASELINE config 5).
 
 Differences from the reference, by design of the scope:
-  * the R3D-50 trunk does not run: the batch carries ``appearance_features`` (B, 2048, 2, 4, 4) — what
-    ``Resnet3D.forward_features`` returns — instead of ``video_frames``; the state dict therefore has every reference
-    key EXCEPT ``…appearance_branch.resnet.*`` (load reference checkpoints with ``strict=False``);
+  * by default the R3D-50 trunk is not part of the model: the batch carries ``appearance_features`` (B, 2048, 2, 4, 4) — what
+    ``Resnet3D.forward_features`` returns — instead of ``video_frames``, and the state dict has every reference key EXCEPT
+    ``…appearance_branch.resnet.*`` (load reference checkpoints with ``strict=False``).  ``MultimodalModelConfig(appearance_trunk=True)``
+    adds the trunk (``modelling/resnet3d.py``) with the reference's 320 ``…resnet.*`` keys in their place (reference checkpoints then load
+    with ``strict=True``); a batch with ``video_frames`` and no ``appearance_features`` runs it natively, without a tape — a trainable
+    trunk under autograd is an error (Conv3d backward is not built), a frozen one feeds the training composition below;
   * inference is one native call (``stlt_caf_forward``).  Training — with autograd enabled and trainable parameters —
     composes the same arithmetic from the op-level autograd Functions of ``ops.py`` (native forward AND backward kernels
     per op: linear, attention, add+LayerNorm, GELU, the two embedding kernels); a frozen layout branch runs through the
@@ -26,6 +29,7 @@ from .. import _lib as L
 from .. import ops
 from .configs import MultimodalModelConfig
 from .models import ClassificationHead, StltBackbone, _dev_ptr, _EncoderLayerParams, _EncoderStack, _prep_inputs, _SelfAttnParams, _Workspace
+from .resnet3d import Resnet3D
 
 
 class _AttnBlock(nn.Module):
@@ -69,16 +73,73 @@ class CrossModalModule(nn.Module):
 
 
 class TransformerResnetFeatures(nn.Module):
-    """``TransformerResnet`` minus the R3D trunk (models.py:230-252): projector, CLS token, position table, ReLU encoder."""
+    """``TransformerResnet`` (models.py:230-252): projector, CLS token, position table, ReLU encoder — and, with
+    ``config.appearance_trunk``, the R3D-50 trunk as ``resnet`` (a native ``Resnet3D``, at the reference's key position)."""
 
     def __init__(self, config):
         super().__init__()
         d = config.hidden_size
+        if getattr(config, "appearance_trunk", False):
+            self.resnet = Resnet3D(config)
         self.projector = nn.Conv3d(2048, d, kernel_size=(1, 1, 1))
         self.transformer = _EncoderStack(_EncoderLayerParams(d), config.num_appearance_layers)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, d))
         self.pos_embed = nn.Parameter(torch.zeros(config.appearance_num_frames + 1, 1, d))
         self.classifier = nn.Linear(d, config.num_classes)  # unused by CAF/CACNF, present in reference checkpoints
+
+
+def _appearance_tokens(ab, feats, H: int, p: float):
+    """projector, CLS token, position table and the ReLU encoder layers of TransformerResnet.forward_features (models.py:257-271) on the
+    trunk's feature map (B, 2048, ...), batch-major (B, S+1, d), on the op-level native Functions."""
+    B, Cc = feats.shape[0], feats.shape[1]
+    d = ab.projector.weight.shape[0]
+    x = ops.LinearFn.apply(feats.flatten(2).transpose(1, 2).contiguous(), ab.projector.weight.view(d, Cc), ab.projector.bias)
+    x = torch.cat((ab.cls_token.view(1, 1, d).expand(B, -1, -1), x), dim=1) + ab.pos_embed.view(1, -1, d)
+    for l in ab.transformer.layers:  # nn.TransformerEncoderLayer defaults: ReLU, post-norm, eps 1e-5, dropout 0.1
+        sa = l.self_attn
+        x = ops.AttnBlockFn.apply(x, None, None, False, H, 1e-5, p, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias,
+                                  l.norm1.weight, l.norm1.bias)
+        x = ops.FfnBlockFn.apply(x, 1e-5, L.ACT_RELU, True, p, l.linear1.weight, l.linear1.bias, l.linear2.weight, l.linear2.bias,
+                                 l.norm2.weight, l.norm2.bias)
+    return x
+
+
+def _trunk_path(owner: nn.Module, trunk: nn.Module) -> str:
+    """the attribute path of the trunk's parameters for the error message (e.g. ``model.backbone.appearance_branch.resnet.resnet``)"""
+    for name, m in owner.named_modules():
+        if m is trunk:
+            return f"….{name}.resnet" if name else "….resnet"
+    return "….resnet"
+
+
+class TransformerResnet(nn.Module):
+    """``TransformerResnet`` (models.py:230-283) on ``video_frames``: the native R3D-50 trunk, then the projector, CLS token, position table
+    and ReLU encoder on the native op-level Functions; ``forward(batch) -> {"resnet3d": classifier(CLS state)}``."""
+
+    def __init__(self, config):
+        super().__init__()
+        d = config.hidden_size
+        self.config = config
+        self.resnet = Resnet3D(config)
+        self.projector = nn.Conv3d(2048, d, kernel_size=(1, 1, 1))
+        self.transformer = _EncoderStack(_EncoderLayerParams(d), config.num_appearance_layers)
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, d))
+        self.pos_embed = nn.Parameter(torch.zeros(config.appearance_num_frames + 1, 1, d))
+        self.classifier = nn.Linear(d, config.num_classes)
+        self.logit_names = ("resnet3d",)
+
+    def forward_features(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """(S+1, B, d), sequence-first like the reference's (models.py:271)"""
+        feats = self.resnet._runner.run(self.resnet.resnet, batch["video_frames"], name="….resnet.resnet")[0]
+        return _appearance_tokens(self, feats, self.config.num_attention_heads, 0.1 if self.training else 0.0).transpose(0, 1)
+
+    def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        feats = self.resnet._runner.run(self.resnet.resnet, batch["video_frames"], name="….resnet.resnet")[0]
+        x = _appearance_tokens(self, feats, self.config.num_attention_heads, 0.1 if self.training else 0.0)
+        return {"resnet3d": ops.LinearFn.apply(x[:, 0].contiguous(), self.classifier.weight, self.classifier.bias)}
+
+    def no_weight_decay(self):
+        return {"pos_embed", "cls_token"}
 
 
 class FusionHead(nn.Module):
@@ -124,20 +185,17 @@ class CrossAttentionFusionBackbone(nn.Module):
 
     def _appearance_train(self, feats):
         """TransformerResnet.forward_features from the feature map on (models.py:257-271), batch-major (B, S+1, d)."""
-        ab = self.appearance_branch
-        B, Cc = feats.shape[0], feats.shape[1]
-        d = ab.projector.weight.shape[0]
-        x = ops.LinearFn.apply(feats.flatten(2).transpose(1, 2).contiguous(), ab.projector.weight.view(d, Cc), ab.projector.bias)
-        x = torch.cat((ab.cls_token.view(1, 1, d).expand(B, -1, -1), x), dim=1) + ab.pos_embed.view(1, -1, d)
-        H = self.config.num_attention_heads
-        p = 0.1 if self.training else 0.0
-        for l in ab.transformer.layers:  # nn.TransformerEncoderLayer defaults: ReLU, post-norm, eps 1e-5, dropout 0.1
-            sa = l.self_attn
-            x = ops.AttnBlockFn.apply(x, None, None, False, H, 1e-5, p, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias,
-                                      l.norm1.weight, l.norm1.bias)
-            x = ops.FfnBlockFn.apply(x, 1e-5, L.ACT_RELU, True, p, l.linear1.weight, l.linear1.bias, l.linear2.weight, l.linear2.bias,
-                                     l.norm2.weight, l.norm2.bias)
-        return x
+        return _appearance_tokens(self.appearance_branch, feats, self.config.num_attention_heads, 0.1 if self.training else 0.0)
+
+    def _features(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """The appearance branch's input: ``appearance_features`` when the batch carries them, else (``appearance_trunk`` on) the native
+        trunk on ``video_frames``, without a tape."""
+        if "appearance_features" in batch:
+            return ops._chk(batch["appearance_features"].contiguous(), torch.float32, "appearance_features")
+        trunk = getattr(self.appearance_branch, "resnet", None)
+        if trunk is None or "video_frames" not in batch:
+            raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))")
+        return trunk._runner.run(trunk.resnet, batch["video_frames"], name=_trunk_path(self, trunk))[0]
 
     def _head_train(self, h, x):
         eps = self.config.layer_norm_eps
@@ -147,7 +205,7 @@ class CrossAttentionFusionBackbone(nn.Module):
 
     def run_train(self, batch: Dict[str, torch.Tensor], fusion_head, layout_head=None, appearance_head=None):
         """Differentiable forward (see the module docstring).  -> same tuple as run()."""
-        feats = ops._chk(batch["appearance_features"].contiguous(), torch.float32, "appearance_features")
+        feats = self._features(batch)
         if any(q.requires_grad for q in self.layout_branch.parameters()):
             Lh = self.layout_branch.forward_train(batch)  # (B,T,d) with its autograd graph (op-level composition)
         else:  # frozen (load_backbone_path + freeze_backbone): one native call, no tape
@@ -195,7 +253,7 @@ class CrossAttentionFusionBackbone(nn.Module):
             return self.run_train(batch, fusion_head, layout_head, appearance_head)
         lib = L.load()
         inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
-        feats = ops._chk(batch["appearance_features"].contiguous(), torch.float32, "appearance_features")
+        feats = self._features(batch)
         ab = self.appearance_branch
         Cc = ab.projector.weight.shape[1]
         S = ab.pos_embed.shape[0] - 1
@@ -309,3 +367,5 @@ from .models import models_factory  # noqa: E402
 models_factory["caf"] = CrossAttentionFusion
 models_factory["cacnf"] = CrossAttentionCentralNetFusion
 models_factory["lcf"] = LateConcatenationFusion
+models_factory["resnet3d"] = Resnet3D
+models_factory["resnet3d-transformer"] = TransformerResnet

@@ -243,6 +243,47 @@ def make_appearance_features(B: int, seed: int = 0, channels: int = 2048) -> tor
     return torch.from_numpy((u * 1.5).astype(np.float32).reshape(B, channels, 2, 4, 4))
 
 
+def make_r3d_state_dict(shapes: Dict[str, tuple], seed: int = 1234) -> Dict[str, torch.Tensor]:
+    """Deterministic fp32 values for a model whose keys include an R3D-50 trunk (keys containing ``resnet.<digit>``): Conv3d weights
+    He-uniform over their fan-in (activations stay O(1) through the ReLUs), BatchNorm with non-trivial gamma / beta / running mean,
+    a positive running variance and num_batches_tracked = 0.  Every other key goes through ``make_state_dict``."""
+    import re
+
+    trunk = re.compile(r"(^|\.)resnet\.\d")
+    out: Dict[str, torch.Tensor] = {}
+    rest = {}
+    for name, shape in shapes.items():
+        shape = tuple(shape)
+        if not trunk.search(name):
+            rest[name] = shape
+            continue
+        key = fnv1a64("r3d:" + name) ^ (seed * 0x9E3779B97F4A7C15 & _MASK64)
+        leaf = name.rsplit(".", 1)[-1]
+        if leaf == "num_batches_tracked":
+            out[name] = torch.zeros(shape, dtype=torch.int64)
+        elif len(shape) == 5:
+            fan_in = shape[1] * shape[2] * shape[3] * shape[4]
+            out[name] = _sym(key, shape, (6.0 / fan_in) ** 0.5)
+        elif leaf == "weight":
+            out[name] = 0.75 + _sym(key, shape, 0.25)
+        elif leaf == "bias":
+            out[name] = _sym(key, shape, 0.1)
+        elif leaf == "running_mean":
+            out[name] = _sym(key, shape, 0.1)
+        elif leaf == "running_var":
+            out[name] = torch.from_numpy((0.6 + 0.8 * uniform01(key, int(np.prod(shape)))).astype(np.float32).reshape(shape))
+        else:
+            raise KeyError(f"no init rule for {name} {shape}")
+    other = make_state_dict(rest, seed=seed)
+    return {k: (out[k] if k in out else other[k]) for k in shapes}
+
+
+def make_video(B: int, T: int = 32, H: int = 112, W: int = 112, seed: int = 0) -> torch.Tensor:
+    """Stand-in for ``video_frames`` (reference datasets.py:198-206): (B, 3, T, H, W) fp32, normalised-pixel-like values in [-1.5, 1.5)."""
+    u = uniform01(fnv1a64("video_frames") ^ (seed * 0x9E3779B97F4A7C15 & _MASK64), B * 3 * T * H * W)
+    return torch.from_numpy(((2.0 * u - 1.0) * 1.5).astype(np.float32).reshape(B, 3, T, H, W))
+
+
 def flops_per_clip(T: int, N: int, d: int, n_sp: int, n_tp: int, classes: int) -> float:
     """Algorithmic dense forward FLOPs per clip."""
     return (
