@@ -382,6 +382,50 @@ size_t stlt_r3d_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
 int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
                      float* features, float* pooled, stlt_stream_t stream);
 
+/* ---- R3D-50 backward (training the trunk; csrc/r3d.hip).  BatchNorm stays eval, so bn(conv(x))'s backward is a per-channel multiply
+ * by sc = γ/sqrt(var + eps).  Op level, for the forward conv described by d (x (B, T, H, W, c_in), y (B, To, Ho, Wo, c_out)):
+ *   stlt_conv3d_repack_dgrad: torch weight (c_out, c_in, kt, kh, kw) -> the data-gradient copy (as many floats): per parity class of the
+ *     stride (s^3 classes, strides 1 or 2, equal in t / h / w), the class's own taps flipped to (c_in, kt', kh', kw', c_out), times
+ *     scale[co] (NULL: 1).  Classes without taps take no floats.
+ *   stlt_conv3d_bwd_data: dx (B, T, H, W, c_in) = Σ_co dy·w (implicit GEMM over dy, class by class: no zero taps), then
+ *     · scale[ci] (NULL: none), + add (dx's shape; NULL: none; may be dx itself), then 0 where mask (dx's shape) <= 0 (NULL: none).
+ *     c_out must be a multiple of 4.  n_split as in stlt_conv3d_fwd (0: the library's plan, which needs its workspace).
+ *   stlt_conv3d_bwd_weight: dw (c_out, c_in_w, kt, kh, kw) (+)= scale[co] · Σ_m dy[m, co] · x_taps[m, ...]; c_in_w <= c_in drops
+ *     padded input channels (the stem's 4th).  The contraction over m splits into ranges whose partials are summed in a fixed order
+ *     (n_split 0: the library's plan); the workspace is always needed.  accumulate != 0 adds into dw.
+ *   stlt_maxpool3d_ndhwc_train: stlt_maxpool3d_ndhwc that also writes each output's window argmax (0..26, first maximum in scan order);
+ *   stlt_maxpool3d_ndhwc_bwd: dx (B, T, H, W, C) from dy and argmax, a deterministic gather, then 0 where mask <= 0 (NULL: none).
+ * Every result is bit-identical from run to run. */
+size_t stlt_conv3d_bwd_data_workspace_bytes(const stlt_conv3d_desc* d, int n_split);
+size_t stlt_conv3d_bwd_weight_workspace_bytes(const stlt_conv3d_desc* d, int n_split);
+int stlt_conv3d_repack_dgrad(const float* w, const stlt_conv3d_desc* d, const float* scale, float* out, stlt_stream_t stream);
+int stlt_conv3d_bwd_data(const stlt_conv3d_desc* d, const float* dy, const float* w_dgrad, const float* scale, const float* mask, const float* add,
+                         int n_split, void* workspace, size_t workspace_bytes, float* dx, stlt_stream_t stream);
+int stlt_conv3d_bwd_weight(const stlt_conv3d_desc* d, const float* x, const float* dy, const float* scale, int64_t c_in_w, int accumulate, int n_split,
+                           void* workspace, size_t workspace_bytes, float* dw, stlt_stream_t stream);
+int stlt_maxpool3d_ndhwc_train(const float* x, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, float* y, uint8_t* argmax, stlt_stream_t stream);
+int stlt_maxpool3d_ndhwc_bwd(const float* dy, const uint8_t* argmax, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, const float* mask, float* dx,
+                             stlt_stream_t stream);
+
+/* Whole trunk.  stlt_r3d_repack_all: ONE launch writing, from the 53 torch weights, every forward copy (fwd[i], as stlt_conv3d_repack)
+ * and every data-gradient copy of the 52 non-stem convs (dgrad[i], as stlt_conv3d_repack_dgrad scaled by the conv's BN scale;
+ * dgrad[0] is ignored); BN buffers from p (p->conv[i].w is not read).  The shapes are the fixed R3D-50 plan's (the torch weights of
+ * conv i in state-dict order); every destination but dgrad[0] must be 16-byte aligned, as the conv kernels read the copies.
+ * stlt_r3d_train_forward: stlt_r3d_forward (same outputs, bit for bit, same workspace) that also records the tape: the stem's padded
+ * NDHWC input, the stem output, the max-pool output and argmax, and each block's conv1, conv2 and block outputs
+ * (stlt_r3d_tape_bytes, pure host arithmetic; 256-byte aligned).
+ * stlt_r3d_backward: from the tape and exactly one of dfeatures (B, 2048, To, Ho, Wo) NCDHW or dpooled (B, 2048), writes (accumulate 0)
+ * or adds (accumulate != 0) the 53 weight gradients dweight[i] in the torch layout (c_out, c_in, kt, kh, kw).  dgrad_w[i] are the
+ * copies of stlt_r3d_repack_all.  The video gets no gradient.  Workspace: stlt_r3d_backward_workspace_bytes. */
+size_t stlt_r3d_tape_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
+size_t stlt_r3d_backward_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
+int stlt_r3d_repack_all(const float* const* weights, const stlt_r3d_params* p, float* const* fwd, float* const* dgrad, stlt_stream_t stream);
+int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
+                           void* tape, size_t tape_bytes, float* features, float* pooled, stlt_stream_t stream);
+int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H, int64_t W,
+                      const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, void* workspace, size_t workspace_bytes,
+                      stlt_stream_t stream);
+
 /* ---- training step (reference src/train.py:119-135: forward, loss.backward(); optimiser step further below) ----
  * stlt_train_forward runs every layer on every row — except that the last layer of each tower runs its out-proj /
  * norms / FFN only on the rows read afterwards (CLS row per frame, frame lengths-1 per clip; same loss and gradients,

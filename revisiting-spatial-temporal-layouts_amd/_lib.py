@@ -103,6 +103,9 @@ class R3dParams(C.Structure):
     _fields_ = [("conv", R3dConv * R3D_CONVS), ("bn_eps", C.c_float)]
 
 
+R3dPointers = C.c_void_p * R3D_CONVS  # the `const float* const*` / `float* const*` arrays of stlt_r3d_repack_all / stlt_r3d_backward
+
+
 # symbol -> (restype, argtypes); the not-gpu tests check that every one of these is exported
 SIGNATURES = {
     "stlt_version": (C.c_int, []),
@@ -213,6 +216,20 @@ SIGNATURES = {
     "stlt_avgpool_ndhwc": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "stlt_r3d_workspace_bytes": (C.c_size_t, [C.c_int64] * 4),
     "stlt_r3d_forward": (C.c_int, [C.POINTER(R3dParams), _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "stlt_conv3d_bwd_data_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc), C.c_int]),
+    "stlt_conv3d_bwd_weight_workspace_bytes": (C.c_size_t, [C.POINTER(Conv3dDesc), C.c_int]),
+    "stlt_conv3d_repack_dgrad": (C.c_int, [_vp, C.POINTER(Conv3dDesc), _vp, _vp, _vp]),
+    "stlt_conv3d_bwd_data": (C.c_int, [C.POINTER(Conv3dDesc), _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "stlt_conv3d_bwd_weight": (C.c_int, [C.POINTER(Conv3dDesc), _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "stlt_maxpool3d_ndhwc_train": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "stlt_maxpool3d_ndhwc_bwd": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "stlt_r3d_tape_bytes": (C.c_size_t, [C.c_int64] * 4),
+    "stlt_r3d_backward_workspace_bytes": (C.c_size_t, [C.c_int64] * 4),
+    "stlt_r3d_repack_all": (C.c_int, [_vp, C.POINTER(R3dParams), _vp, _vp, _vp]),
+    "stlt_r3d_train_forward": (C.c_int, [C.POINTER(R3dParams), _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp,
+                                         _vp]),
+    "stlt_r3d_backward": (C.c_int, [C.POINTER(R3dParams), _vp, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, _vp,
+                                    C.c_size_t, _vp]),
 }
 
 _lib = None

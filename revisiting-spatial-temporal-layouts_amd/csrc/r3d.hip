@@ -51,11 +51,37 @@ __device__ __forceinline__ void bn_coeffs(const float* bn_w, const float* bn_b, 
 // same for both operands, so a lane fetches its eight k of a row with two 16-byte LDS reads.  Staging: eight lanes cover one row's
 // 128-byte slab (coalesced), a thread keeps BM/32 (BN/32) fixed rows and one fixed k-quad.
 // gridDim.z > 1: blockIdx.z takes k-slabs [z·per, (z+1)·per) and stores the raw partial to y + z·M·N (no epilogue).
-template <int BN>
+// Backward epilogue (BWD = true, the data gradient of csrc/r3d.hip's stlt_conv3d_bwd_data): output row gm of the (compact) launch
+// grid lands at row dest(gm) of the full dx grid (Tf, Hf, Wf): position os·(t, h, w) + (ot, oh, ow), so one parity class of a
+// stride-2 convolution writes only its own rows.  v = acc · sc[n] (sc NULL: 1), + add[row] (NULL: none), then 0 unless mask[row] > 0
+// (NULL: no mask).  `add` may be dx itself (each element is read and then written by the same thread).
+struct DgEpi {
+  const float* sc;
+  const float* mask;
+  const float* add;
+  int Tf, Hf, Wf, os, ot, oh, ow;
+};
+
+__device__ __forceinline__ int64_t dg_row(const ConvGeom& g, const DgEpi& e, int gm) {
+  int q = gm;
+  const int wo = q % g.Wo; q /= g.Wo;
+  const int ho = q % g.Ho; q /= g.Ho;
+  const int to = q % g.To; const int b = q / g.To;
+  return (((int64_t)b * e.Tf + e.os * to + e.ot) * e.Hf + e.os * ho + e.oh) * e.Wf + e.os * wo + e.ow;
+}
+
+__device__ __forceinline__ float dg_apply(const DgEpi& e, float v, int n, int64_t o) {
+  if (e.sc) v *= e.sc[n];
+  if (e.add) v += e.add[o];
+  if (e.mask && !(e.mask[o] > 0.f)) v = 0.f;
+  return v;
+}
+
+template <int BN, bool BWD = false>
 __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float* __restrict__ x, const float* __restrict__ w, ConvGeom g,
                                                            const float* __restrict__ bn_w, const float* __restrict__ bn_b,
                                                            const float* __restrict__ bn_mean, const float* __restrict__ bn_var, float eps,
-                                                           const float* __restrict__ res, int relu, float* __restrict__ y, int slabs_per_split) {
+                                                           const float* __restrict__ res, int relu, float* y, int slabs_per_split, DgEpi de) {
   constexpr int RA = BM / 32, RB = BN / 32, MI = BM / 32, NJ = BN / 32;
   __shared__ __attribute__((aligned(16))) float As[BM][LDS_PITCH];
   __shared__ __attribute__((aligned(16))) float Bs[BN][LDS_PITCH];
@@ -158,7 +184,7 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float* __restri
     const int gn = n0 + wn + 16 * j + li;
     if (gn >= g.N) continue;
     float sc = 1.f, sh = 0.f;
-    if (!split) bn_coeffs(bn_w, bn_b, bn_mean, bn_var, eps, gn, &sc, &sh);
+    if (!BWD && !split) bn_coeffs(bn_w, bn_b, bn_mean, bn_var, eps, gn, &sc, &sh);
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -167,6 +193,11 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float* __restri
         if (gm >= g.M) continue;
         const int64_t o = (int64_t)gm * g.N + gn;
         if (split) { y[o] = acc[i][j][q]; continue; }
+        if constexpr (BWD) {
+          const int64_t od = dg_row(g, de, gm) * g.N + gn;
+          y[od] = dg_apply(de, acc[i][j][q], gn, od);
+          continue;
+        }
         float v = fmaf(acc[i][j][q], sc, sh);
         if (res) v += res[o];
         if (relu) v = fmaxf(v, 0.f);
@@ -312,10 +343,11 @@ int launch_conv(const ConvGeom& g, const float* x, const float* w, const float* 
   splits = cdiv(slabs, per);
   const dim3 grid((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.N, bn), (unsigned)splits), block(256);
   float* dst = splits > 1 ? part : y;
+  const DgEpi none{};
   if (bn == 64)
-    hipLaunchKernelGGL(conv3d_igemm_kernel<64>, grid, block, 0, s, x, w, g, bn_w, bn_b, bn_mean, bn_var, eps, res, relu, dst, (int)per);
+    hipLaunchKernelGGL(conv3d_igemm_kernel<64>, grid, block, 0, s, x, w, g, bn_w, bn_b, bn_mean, bn_var, eps, res, relu, dst, (int)per, none);
   else
-    hipLaunchKernelGGL(conv3d_igemm_kernel<128>, grid, block, 0, s, x, w, g, bn_w, bn_b, bn_mean, bn_var, eps, res, relu, dst, (int)per);
+    hipLaunchKernelGGL(conv3d_igemm_kernel<128>, grid, block, 0, s, x, w, g, bn_w, bn_b, bn_mean, bn_var, eps, res, relu, dst, (int)per, none);
   if (int e = stlt_check_launch("conv3d_igemm_kernel")) return e;
   if (splits > 1) {
     hipLaunchKernelGGL(conv3d_split_finish_kernel, dim3((unsigned)cdiv((int64_t)g.M * g.N, 256)), dim3(256), 0, s, part, (int)splits, g.M, g.N, bn_w, bn_b,
@@ -550,6 +582,840 @@ int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, in
   if (pooled)
     if (int e = stlt_avgpool_ndhwc(cur, B, P, cin, pooled, stream)) return e;
   return 0;
+}
+
+}  // extern "C"
+
+// =====================================================================================================================================
+// Backward (training the trunk).  BatchNorm is always eval (frozen affine, running statistics), so the backward of bn(conv(x)) is
+// a per-channel multiply by sc = γ/sqrt(var + eps); ReLU masks by its saved output > 0.
+//
+// Data gradient (dgrad): dx = the forward kernel (conv3d_igemm_kernel<BN, true>) run over dy with a repacked weight
+//   W'[ci][taps'][co] = sc[co] · W[co][ci][flipped taps]
+// and the backward epilogue (scale, add-source, mask, scattered rows: DgEpi).  A stride-s dimension splits into s parity classes
+// r (input positions s·a + r): class r takes exactly the taps dt with (r + p - dt) ≡ 0 mod s, as a dense stride-1 convolution over dy
+// with k' = their count and padding p' (sub_dims).  Stride 1 is the single class with the full flipped kernel and p' = k - 1 - p;
+// a 3x3x3 stride-2 conv becomes 8 classes of 1 or 2 taps per dimension (27 taps in all, none of them zero); a 1x1x1 stride-2 conv
+// has one class with its tap and seven with none (those rows get only the add-source, masked).  The classes' weights lie back to
+// back in class order (rt, rh, rw row-major), so the dgrad copy has as many floats as the weight.
+//
+// Weight gradient (wgrad): dW[co][tap, c] = Σ_m dy[m][co] · x_taps[m][tap, c] over M = B·To·Ho·Wo.  Both operands are M-major with
+// channels contiguous; a thread stages one m row (one decode per slab) and fixed channel quads, written transposed into LDS
+// ([co or k][m], pitch 36) so the MFMA loop is the forward's.  M splits into ranges whose partial (c_out, K) slabs are summed in split
+// order by a finishing pass, which applies sc[co], drops padded channels, writes the torch layout (c_out, c_in, kt, kh, kw) and
+// optionally accumulates into it — deterministic, no float atomics.
+// =====================================================================================================================================
+namespace {
+
+constexpr int WG_TK = 128;                 // wgrad tile: k columns per workgroup (co rows: 64 or 128)
+constexpr int64_t WG_TARGET_WG = 1024;     // split M until ~4 workgroups per CU of a 256-CU part
+constexpr int64_t WG_MIN_SLABS = 8;        // ... keeping at least 8 m-slabs (256 rows) per split
+constexpr int64_t WG_SPLIT_MAX = 256;
+
+// the taps of parity class r of one dimension (kernel k, stride s, pad p): k' taps (0: none), padding p' of the stride-1 sub-conv
+__host__ __device__ inline void sub_dims(int k, int s, int p, int r, int* kk, int* pp) {
+  int qmin = 1 << 30, qmax = -(1 << 30);
+  for (int dt = 0; dt < k; ++dt) {
+    const int num = r + p - dt;
+    if (((num % s) + s) % s) continue;
+    const int q = (num >= 0) ? num / s : -((-num) / s);
+    qmin = q < qmin ? q : qmin;
+    qmax = q > qmax ? q : qmax;
+  }
+  *kk = qmax >= qmin ? qmax - qmin + 1 : 0;
+  *pp = qmax >= qmin ? -qmin : 0;
+}
+
+// (c_out, c_in, kt, kh, kw) -> the dgrad copy (classes back to back, each (c_in, kt', kh', kw', c_out)), scaled by sc[co]
+// (sc from `scale`, or from BatchNorm weight / running var, or 1)
+// (I: the index type — int inside the trunk's batched repack, int64_t for an arbitrary op-level shape)
+template <typename I>
+__device__ inline void dgrad_repack_elem(const float* w, I idx, int Cout, int Cin, int kt, int kh, int kw, int st, int sh, int sw, int pt, int ph,
+                                         int pw, float sc, float* out) {
+  // idx walks the source (co, ci, dt, dh, dw)
+  I q = idx;
+  const int dw = (int)(q % kw); q /= kw;
+  const int dh = (int)(q % kh); q /= kh;
+  const int dt = (int)(q % kt); q /= kt;
+  const int ci = (int)(q % Cin);
+  const int co = (int)(q / Cin);
+  const int rt = ((dt - pt) % st + st) % st, rh = ((dh - ph) % sh + sh) % sh, rw = ((dw - pw) % sw + sw) % sw;
+  int64_t base = 0;
+  int kt_ = 0, kh_ = 0, kw_ = 0, pt_ = 0, ph_ = 0, pw_ = 0;
+  for (int a = 0; a < st; ++a)
+    for (int b = 0; b < sh; ++b)
+      for (int c = 0; c < sw; ++c) {
+        int k1, k2, k3, p1, p2, p3;
+        sub_dims(kt, st, pt, a, &k1, &p1);
+        sub_dims(kh, sh, ph, b, &k2, &p2);
+        sub_dims(kw, sw, pw, c, &k3, &p3);
+        if (a == rt && b == rh && c == rw) {
+          kt_ = k1; kh_ = k2; kw_ = k3; pt_ = p1; ph_ = p2; pw_ = p3;
+          a = st; b = sh; break;
+        }
+        base += (int64_t)k1 * k2 * k3 * Cin * Cout;
+      }
+  const int jt = (rt + pt - dt) / st + pt_, jh = (rh + ph - dh) / sh + ph_, jw = (rw + pw - dw) / sw + pw_;
+  out[base + ((((int64_t)ci * kt_ + jt) * kh_ + jh) * kw_ + jw) * Cout + co] = sc * w[idx];
+}
+
+__global__ __launch_bounds__(256) void conv3d_repack_dgrad_kernel(const float* __restrict__ w, int Cout, int Cin, int kt, int kh, int kw, int st, int sh,
+                                                                  int sw, int pt, int ph, int pw, const float* __restrict__ scale, float* __restrict__ out) {
+  const int64_t n = (int64_t)Cout * Cin * kt * kh * kw;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * 256) {
+    const int co = (int)(idx / ((int64_t)Cin * kt * kh * kw));
+    dgrad_repack_elem(w, idx, Cout, Cin, kt, kh, kw, st, sh, sw, pt, ph, pw, scale ? scale[co] : 1.f, out);
+  }
+}
+
+// the trunk's fixed plan, conv i in state-dict order: (c_out, c_in, k, stride); the stem is 7x7x7 stride (1, 2, 2) pad 3
+struct R3dConvMeta { int cout, cin, k, s; };
+__host__ __device__ inline R3dConvMeta r3d_conv_meta(int i) {
+  if (i == 0) return {64, 3, 7, 2};
+  const int blocks[4] = {3, 4, 6, 3}, planes[4] = {64, 128, 256, 512};
+  int idx = 1, cin = 64;
+  for (int L = 0; L < 4; ++L)
+    for (int b = 0; b < blocks[L]; ++b) {
+      const int pl = planes[L], s = (L > 0 && b == 0) ? 2 : 1;
+      if (i == idx) return {pl, cin, 1, 1};
+      if (i == idx + 1) return {pl, pl, 3, s};
+      if (i == idx + 2) return {pl * 4, pl, 1, 1};
+      if (b == 0 && i == idx + 3) return {pl * 4, cin, 1, s};
+      idx += b == 0 ? 4 : 3;
+      cin = pl * 4;
+    }
+  return {0, 0, 0, 0};
+}
+
+constexpr int REPACK_ITEMS = 4;  // elements per thread of r3d_repack_all_kernel (1 024 per workgroup)
+
+struct R3dRepackArgs {
+  const float* w[STLT_R3D_CONVS];
+  const float* bn_w[STLT_R3D_CONVS];
+  const float* bn_var[STLT_R3D_CONVS];
+  float* fwd[STLT_R3D_CONVS];
+  float* dgrad[STLT_R3D_CONVS];
+  int block0[STLT_R3D_CONVS + 1];  // conv i owns workgroups [block0[i], block0[i + 1]): one flat index space, sized per conv
+  float eps;
+};
+
+// conv i's elements in r3d_repack_all_kernel: its forward copy, then (but for the stem) its dgrad copy
+__host__ __device__ inline void r3d_repack_counts(int i, int* nf, int* nw) {
+  const R3dConvMeta m = r3d_conv_meta(i);
+  const int taps = m.k * m.k * m.k;
+  *nf = m.cout * taps * ((m.cin + 3) / 4 * 4);
+  *nw = i > 0 ? m.cout * m.cin * taps : 0;
+}
+
+// one workgroup = 1 024 consecutive elements of one conv: the forward copy (c_out, k, k, k, c_pad), walked in destination order
+// (coalesced stores), then the BN-scaled dgrad copy, walked in source order (coalesced loads)
+__global__ __launch_bounds__(256) void r3d_repack_all_kernel(R3dRepackArgs a) {
+  int i = 0;
+  while (i + 1 < STLT_R3D_CONVS && (int)blockIdx.x >= a.block0[i + 1]) ++i;
+  const R3dConvMeta m = r3d_conv_meta(i);
+  const int taps = m.k * m.k * m.k, cpad = (m.cin + 3) / 4 * 4;
+  int nf, nw;
+  r3d_repack_counts(i, &nf, &nw);
+  const float* w = a.w[i];
+  const int base = ((int)blockIdx.x - a.block0[i]) * 256 * REPACK_ITEMS + threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < REPACK_ITEMS; ++e) {
+    const int idx = base + 256 * e;
+    if (idx < nf) {
+      if (!a.fwd[i]) continue;
+      const int c = idx % cpad;
+      const int r = idx / cpad;
+      const int tap = r % taps;
+      const int n = r / taps;
+      a.fwd[i][idx] = c < m.cin ? w[((int64_t)n * m.cin + c) * taps + tap] : 0.f;
+    } else if (idx - nf < nw && a.dgrad[i]) {
+      const int j = idx - nf;
+      const int co = j / (m.cin * taps);
+      const float sc = a.bn_w[i][co] / sqrtf(a.bn_var[i][co] + a.eps);
+      const int pd = m.k / 2;
+      dgrad_repack_elem(w, j, m.cout, m.cin, m.k, m.k, m.k, m.s, m.s, m.s, pd, pd, pd, sc, a.dgrad[i]);
+    }
+  }
+}
+
+// split dgrad launch, second half: row gm of the compact grid = Σ_z part[z] (split order), then the backward epilogue at dest(gm)
+__global__ __launch_bounds__(256) void conv3d_dgrad_finish_kernel(const float* __restrict__ part, int splits, ConvGeom g, DgEpi de, float* y) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t total = (int64_t)g.M * g.N;
+  if (idx >= total) return;
+  const int n = (int)(idx % g.N);
+  const int gm = (int)(idx / g.N);
+  float v = 0.f;
+  for (int z = 0; z < splits; ++z) v += part[(int64_t)z * total + idx];
+  const int64_t od = dg_row(g, de, gm) * g.N + n;
+  y[od] = dg_apply(de, v, n, od);
+}
+
+// wgrad main loop: tile TA (co) x WG_TK (k); blockIdx.z = split: m-slabs [z·per, (z+1)·per); raw partial -> part + z·N·K
+// (g is the FORWARD geometry: x (B, Ti, Hi, Wi, C), dy (M, N))
+template <int TA>
+__global__ __launch_bounds__(256) void conv3d_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy, ConvGeom g, float* __restrict__ part,
+                                                           int slabs_per_split) {
+  constexpr int TB = WG_TK, RA = TA / 32, RB = TB / 32, MI = TA / 32, NJ = TB / 32;
+  __shared__ __attribute__((aligned(16))) float As[TA][LDS_PITCH];
+  __shared__ __attribute__((aligned(16))) float Bs[TB][LDS_PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  const int wm = (wave >> 1) * (TA / 2), wn = (wave & 1) * (TB / 2);
+  const int co0 = blockIdx.x * TA, k0 = blockIdx.y * TB;
+  const int mr = tid & 31, cq = tid >> 5;  // this thread's m row within a slab; its channel quads are cq + 8e
+
+  // fixed k-quads of the x operand: tap offsets and channel
+  int dt[RB], dh[RB], dw[RB], cc[RB];
+  bool kin[RB];
+#pragma unroll
+  for (int e = 0; e < RB; ++e) {
+    const int k = k0 + 4 * (cq + 8 * e);
+    kin[e] = k < g.K;
+    int tap = kin[e] ? k / g.C : 0;
+    cc[e] = kin[e] ? k - tap * g.C : 0;
+    dw[e] = tap % g.kw; tap /= g.kw;
+    dh[e] = tap % g.kh; dt[e] = tap / g.kh;
+  }
+
+  const int n_slabs = (g.M + CK - 1) / CK;
+  const int s_begin = blockIdx.z * slabs_per_split, s_end = min(n_slabs, s_begin + slabs_per_split);
+  part += (int64_t)blockIdx.z * g.N * g.K;
+
+  f32x4 ra[RA], rb[RB];
+  auto load_slab = [&](int slab) {
+    const int m = slab * CK + mr;
+    const bool min_ = m < g.M;
+    int64_t xb = 0;
+    int t0 = 0, h0 = 0, w0 = 0;
+    if (min_) {
+      int q = m;
+      const int wo = q % g.Wo; q /= g.Wo;
+      const int ho = q % g.Ho; q /= g.Ho;
+      const int to = q % g.To; const int b = q / g.To;
+      xb = (int64_t)b * g.Ti * g.Hi * g.Wi * g.C;
+      t0 = to * g.st - g.pt; h0 = ho * g.sh - g.ph; w0 = wo * g.sw - g.pw;
+    }
+#pragma unroll
+    for (int e = 0; e < RA; ++e) {
+      const int co = co0 + 4 * (cq + 8 * e);
+      ra[e] = (min_ && co < g.N) ? *reinterpret_cast<const f32x4*>(dy + (int64_t)m * g.N + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int e = 0; e < RB; ++e) {
+      const int ti = t0 + dt[e], hi = h0 + dh[e], wi = w0 + dw[e];
+      if (min_ && kin[e] && (unsigned)ti < (unsigned)g.Ti && (unsigned)hi < (unsigned)g.Hi && (unsigned)wi < (unsigned)g.Wi)
+        rb[e] = *reinterpret_cast<const f32x4*>(x + xb + (((int64_t)ti * g.Hi + hi) * g.Wi + wi) * g.C + cc[e]);
+      else
+        rb[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+
+  f32x4 acc[MI][NJ];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (s_begin < s_end) load_slab(s_begin);
+  for (int slab = s_begin; slab < s_end; ++slab) {
+#pragma unroll
+    for (int e = 0; e < RA; ++e)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) As[4 * (cq + 8 * e) + j][mr] = ra[e][j];
+#pragma unroll
+    for (int e = 0; e < RB; ++e)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Bs[4 * (cq + 8 * e) + j][mr] = rb[e][j];
+    __syncthreads();
+    if (slab + 1 < s_end) load_slab(slab + 1);
+    f32x4 a[MI][2], b[NJ][2];
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      a[i][0] = *reinterpret_cast<const f32x4*>(&As[wm + 16 * i + li][8 * lg]);
+      a[i][1] = *reinterpret_cast<const f32x4*>(&As[wm + 16 * i + li][8 * lg + 4]);
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      b[j][0] = *reinterpret_cast<const f32x4*>(&Bs[wn + 16 * j + li][8 * lg]);
+      b[j][1] = *reinterpret_cast<const f32x4*>(&Bs[wn + 16 * j + li][8 * lg + 4]);
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][s >> 2][s & 3], b[j][s >> 2][s & 3], acc[i][j], 0, 0, 0);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int k = k0 + wn + 16 * j + li;
+    if (k >= g.K) continue;
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int co = co0 + wm + 16 * i + 4 * lg + q;
+        if (co < g.N) part[(int64_t)co * g.K + k] = acc[i][j][q];
+      }
+  }
+}
+
+// wgrad finish: dw[co][ci][tap] (+)= sc[co] · Σ_z part[z][co][tap·C + ci], ci < Cin_w (padded channels dropped)
+__global__ __launch_bounds__(256) void conv3d_wgrad_finish_kernel(const float* __restrict__ part, int splits, int N, int K, int C, int Cin_w, int taps,
+                                                                  const float* __restrict__ scale, const float* __restrict__ bn_w,
+                                                                  const float* __restrict__ bn_var, float eps, int accumulate, float* __restrict__ dw) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)N * Cin_w * taps) return;
+  const int tap = (int)(idx % taps);
+  const int64_t r = idx / taps;
+  const int ci = (int)(r % Cin_w);
+  const int co = (int)(r / Cin_w);
+  const int64_t src = (int64_t)co * K + (int64_t)tap * C + ci;
+  const int64_t slab = (int64_t)N * K;
+  float v = 0.f;
+  for (int z = 0; z < splits; ++z) v += part[z * slab + src];
+  if (bn_w) v *= bn_w[co] / sqrtf(bn_var[co] + eps);
+  else if (scale) v *= scale[co];
+  dw[idx] = accumulate ? dw[idx] + v : v;
+}
+
+// MaxPool3d(3, 2, 1) forward that also records the argmax (0..26, first maximum in scan order, as torch) of every output
+__global__ __launch_bounds__(256) void maxpool3d_argmax_kernel(const float* __restrict__ x, int B, int T, int H, int W, int C, int To, int Ho, int Wo,
+                                                               float* __restrict__ y, uint8_t* __restrict__ am) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * To * Ho * Wo * C) return;
+  const int c = (int)(idx % C);
+  int64_t q = idx / C;
+  const int wo = (int)(q % Wo); q /= Wo;
+  const int ho = (int)(q % Ho); q /= Ho;
+  const int to = (int)(q % To);
+  const int64_t b = q / To;
+  float m = -INFINITY;
+  int best = 0;
+  bool first = true;
+  for (int dt = 0; dt < 3; ++dt) {
+    const int t = 2 * to - 1 + dt;
+    if ((unsigned)t >= (unsigned)T) continue;
+    for (int dh = 0; dh < 3; ++dh) {
+      const int h = 2 * ho - 1 + dh;
+      if ((unsigned)h >= (unsigned)H) continue;
+      for (int dw = 0; dw < 3; ++dw) {
+        const int ww = 2 * wo - 1 + dw;
+        if ((unsigned)ww >= (unsigned)W) continue;
+        const float v = x[(((b * T + t) * H + h) * W + ww) * C + c];
+        if (first || v > m) { best = (dt * 3 + dh) * 3 + dw; }  // strict: the first maximum keeps its place
+        m = fmaxf(m, v);                                           // the value exactly as maxpool3d_ndhwc_kernel forms it
+        first = false;
+      }
+    }
+  }
+  y[idx] = m;
+  am[idx] = (uint8_t)best;
+}
+
+// MaxPool3d backward as a gather: every input element sums, in window scan order, the gradients of the (at most 8) windows whose
+// argmax it is; then 0 unless mask[x] > 0 (NULL: no mask — the stem's ReLU mask is passed here)
+__global__ __launch_bounds__(256) void maxpool3d_bwd_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ am, int B, int T, int H, int W, int C,
+                                                            int To, int Ho, int Wo, const float* __restrict__ mask, float* __restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * T * H * W * C) return;
+  const int c = (int)(idx % C);
+  int64_t q = idx / C;
+  const int w = (int)(q % W); q /= W;
+  const int h = (int)(q % H); q /= H;
+  const int t = (int)(q % T);
+  const int64_t b = q / T;
+  float v = 0.f;
+  if (!mask || mask[idx] > 0.f) {
+    // window o covers input i when 2o - 1 <= i <= 2o + 1: o in [(i) / 2, (i + 1) / 2]
+    for (int to = t / 2; to <= (t + 1) / 2 && to < To; ++to)
+      for (int ho = h / 2; ho <= (h + 1) / 2 && ho < Ho; ++ho)
+        for (int wo = w / 2; wo <= (w + 1) / 2 && wo < Wo; ++wo) {
+          const int pos = ((t - 2 * to + 1) * 3 + (h - 2 * ho + 1)) * 3 + (w - 2 * wo + 1);
+          const int64_t o = (((b * To + to) * Ho + ho) * Wo + wo) * C + c;
+          if (am[o] == pos) v += dy[o];
+        }
+  }
+  dx[idx] = v;
+}
+
+// gradient entering the trunk at its last block output y (B, P, C) NDHWC, masked by y > 0 (the last ReLU):
+// from dpooled (B, C): dpooled / P at every position; from dfeatures (B, C, P) NCDHW: its transpose
+__global__ __launch_bounds__(256) void r3d_grad_in_kernel(const float* __restrict__ dpooled, const float* __restrict__ dfeat, const float* __restrict__ y,
+                                                          int64_t B, int P, int C, float* __restrict__ g) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= B * P * C) return;
+  const int c = (int)(idx % C);
+  const int64_t r = idx / C;
+  const int p = (int)(r % P);
+  const int64_t b = r / P;
+  float v = dpooled ? dpooled[b * C + c] / (float)P : dfeat[(b * C + c) * P + p];
+  g[idx] = y[idx] > 0.f ? v : 0.f;
+}
+
+// ---- host plans ----
+struct SubConv { ConvGeom g; DgEpi e; int64_t w_off; };
+
+// the parity classes of a dgrad (forward geometry f, f.C = c_in of the forward conv, f.N = c_out); sc/mask/add per DgEpi
+int dgrad_plan(const ConvGeom& f, SubConv* out) {
+  int n = 0;
+  int64_t off = 0;
+  for (int a = 0; a < f.st; ++a)
+    for (int b = 0; b < f.sh; ++b)
+      for (int c = 0; c < f.sw; ++c) {
+        int k1, k2, k3, p1, p2, p3;
+        sub_dims(f.kt, f.st, f.pt, a, &k1, &p1);
+        sub_dims(f.kh, f.sh, f.ph, b, &k2, &p2);
+        sub_dims(f.kw, f.sw, f.pw, c, &k3, &p3);
+        const int nt = f.Ti > a ? (f.Ti - a + f.st - 1) / f.st : 0, nh = f.Hi > b ? (f.Hi - b + f.sh - 1) / f.sh : 0,
+                  nw = f.Wi > c ? (f.Wi - c + f.sw - 1) / f.sw : 0;
+        SubConv& s = out[n++];
+        // input of the sub-conv: dy (B, To, Ho, Wo, N); output: class rows (B, nt, nh, nw, C)
+        const bool empty = k1 == 0 || k2 == 0 || k3 == 0;
+        // row a reads dy at a - p' + j (a stride-1 conv with padding p'); a class without taps has K = 0 (its rows get the epilogue alone)
+        s.g = ConvGeom{f.B, f.To, f.Ho, f.Wo, f.N, nt, nh, nw, f.C, empty ? 1 : k1, empty ? 1 : k2, empty ? 1 : k3, 1, 1, 1, p1, p2, p3,
+                       f.B * nt * nh * nw, empty ? 0 : k1 * k2 * k3 * f.N};
+        s.e = DgEpi{nullptr, nullptr, nullptr, f.Ti, f.Hi, f.Wi, f.st, a, b, c};
+        s.w_off = off;
+        off += (int64_t)(empty ? 0 : k1 * k2 * k3) * f.N * f.C;
+      }
+  return n;
+}
+
+int64_t dgrad_splits(const ConvGeom& s) { return s.K > 0 ? conv_plan_splits(s.M, s.N, s.K) : 1; }
+
+int64_t dgrad_ws_bytes(const ConvGeom& f) {
+  SubConv sub[8];
+  const int n = dgrad_plan(f, sub);
+  int64_t mx = 0;
+  for (int i = 0; i < n; ++i) mx = std::max(mx, conv_split_bytes(sub[i].g, dgrad_splits(sub[i].g)));
+  return mx;
+}
+
+// skip_empty: leave the rows of tap-less classes as they are (the caller's dx already holds add, masked: an in-place add-source)
+int launch_dgrad(const ConvGeom& f, const float* dy, const float* wd, const float* sc, const float* mask, const float* add, float* dx, float* part,
+                 int64_t part_bytes, int n_split, hipStream_t s, bool skip_empty = false) {
+  if (f.st != f.sh || f.st != f.sw) {
+    // mixed strides: os differs per dimension, which DgEpi does not carry
+    return stlt_set_error(STLT_EINVAL, "conv3d backward: the data gradient needs equal strides in t, h and w, got (%d, %d, %d)", f.st, f.sh, f.sw);
+  }
+  SubConv sub[8];
+  const int n = dgrad_plan(f, sub);
+  for (int i = 0; i < n; ++i) {
+    SubConv& c = sub[i];
+    if (c.g.M == 0 || (skip_empty && c.g.K == 0)) continue;
+    c.e.sc = sc; c.e.mask = mask; c.e.add = add;
+    const int bn = conv_bn_tile(c.g.N);
+    const int64_t slabs = cdiv(c.g.K, CK);
+    int64_t splits = n_split > 0 ? n_split : dgrad_splits(c.g);
+    if (slabs > 0 && splits > slabs) splits = slabs;
+    if (slabs == 0) splits = 1;
+    const int64_t per = slabs > 0 ? cdiv(slabs, splits) : 1;
+    if (slabs > 0) splits = cdiv(slabs, per);
+    if (splits > 1 && (!part || part_bytes < conv_split_bytes(c.g, splits)))
+      return stlt_set_error(STLT_EWORKSPACE, "stlt_conv3d_bwd_data: %lld splits need %lld workspace bytes, %lld lent", (long long)splits,
+                            (long long)conv_split_bytes(c.g, splits), (long long)part_bytes);
+    const dim3 grid((unsigned)cdiv(c.g.M, BM), (unsigned)cdiv(c.g.N, bn), (unsigned)splits), block(256);
+    const float* w = wd + c.w_off;
+    if (splits == 1) {
+      if (bn == 64)
+        hipLaunchKernelGGL((conv3d_igemm_kernel<64, true>), grid, block, 0, s, dy, w, c.g, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, dx, (int)per, c.e);
+      else
+        hipLaunchKernelGGL((conv3d_igemm_kernel<128, true>), grid, block, 0, s, dy, w, c.g, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, dx, (int)per, c.e);
+      if (int e = stlt_check_launch("conv3d_igemm_kernel<bwd>")) return e;
+    } else {
+      if (bn == 64)
+        hipLaunchKernelGGL((conv3d_igemm_kernel<64, true>), grid, block, 0, s, dy, w, c.g, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, part, (int)per, c.e);
+      else
+        hipLaunchKernelGGL((conv3d_igemm_kernel<128, true>), grid, block, 0, s, dy, w, c.g, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, part, (int)per, c.e);
+      if (int e = stlt_check_launch("conv3d_igemm_kernel<bwd>")) return e;
+      hipLaunchKernelGGL(conv3d_dgrad_finish_kernel, dim3((unsigned)cdiv((int64_t)c.g.M * c.g.N, 256)), dim3(256), 0, s, part, (int)splits, c.g, c.e, dx);
+      if (int e = stlt_check_launch("conv3d_dgrad_finish_kernel")) return e;
+    }
+  }
+  return 0;
+}
+
+inline int wgrad_tile(int64_t N) { return N <= 64 ? 64 : 128; }
+
+int64_t wgrad_plan_splits(const ConvGeom& g) {
+  const int64_t tiles = cdiv(g.N, wgrad_tile(g.N)) * cdiv(g.K, WG_TK);
+  const int64_t slabs = cdiv(g.M, CK);
+  int64_t splits = cdiv(WG_TARGET_WG, tiles);
+  splits = std::min(splits, slabs / WG_MIN_SLABS);
+  splits = std::min(splits, WG_SPLIT_MAX);
+  if (splits < 1) splits = 1;
+  const int64_t per = cdiv(slabs, splits);
+  return cdiv(slabs, per);
+}
+
+int64_t wgrad_ws_bytes(const ConvGeom& g, int64_t splits) { return splits * (int64_t)g.N * g.K * (int64_t)sizeof(float); }
+
+int launch_wgrad(const ConvGeom& g, const float* x, const float* dy, int cin_w, const float* scale, const float* bn_w, const float* bn_var, float eps,
+                 int accumulate, float* dw, int64_t splits, float* part, hipStream_t s) {
+  const int64_t slabs = cdiv(g.M, CK);
+  if (splits > slabs) splits = slabs;
+  if (splits < 1) splits = 1;
+  const int64_t per = cdiv(slabs, splits);
+  splits = cdiv(slabs, per);
+  const int ta = wgrad_tile(g.N);
+  const dim3 grid((unsigned)cdiv(g.N, ta), (unsigned)cdiv(g.K, WG_TK), (unsigned)splits), block(256);
+  if (ta == 64)
+    hipLaunchKernelGGL(conv3d_wgrad_kernel<64>, grid, block, 0, s, x, dy, g, part, (int)per);
+  else
+    hipLaunchKernelGGL(conv3d_wgrad_kernel<128>, grid, block, 0, s, x, dy, g, part, (int)per);
+  if (int e = stlt_check_launch("conv3d_wgrad_kernel")) return e;
+  const int taps = g.kt * g.kh * g.kw;
+  hipLaunchKernelGGL(conv3d_wgrad_finish_kernel, dim3((unsigned)cdiv((int64_t)g.N * cin_w * taps, 256)), dim3(256), 0, s, part, (int)splits, g.N, g.K, g.C,
+                     cin_w, taps, scale, bn_w, bn_var, eps, accumulate, dw);
+  return stlt_check_launch("conv3d_wgrad_finish_kernel");
+}
+
+// ---- the whole trunk's geometry: every conv's ConvGeom (forward), the tape's layout and the backward's workspace ----
+struct TrunkPlan {
+  ConvGeom g[STLT_R3D_CONVS];
+  int64_t xin = 0, stem = 0, pool = 0, argmax = 0;       // tape offsets (bytes)
+  int64_t a1[16], a2[16], y[16];                         // per block
+  int64_t tape_bytes = 0;
+  int64_t stem_elems = 0, pool_elems = 0, act_elems = 0; // act: largest block-level activation
+  int64_t bwd_part_bytes = 0;                            // largest dgrad / wgrad partial
+  int Tp = 0, Hp = 0, Wp = 0;                            // max-pool output
+  bool ok = false;
+};
+
+bool trunk_plan(int64_t B, int64_t T, int64_t H, int64_t W, TrunkPlan* P) {
+  TrunkPlan& p = *P;
+  if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || T > 4096 || H > 4096 || W > 4096 || B > (1 << 20)) return false;
+  const int64_t f = sizeof(float);
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { const int64_t o = off; off += align256(bytes); return o; };
+  auto geom = [&](int i, int64_t t, int64_t h, int64_t w, int64_t cin, int64_t cout, int k, int st, int sp, int pad) -> bool {
+    const stlt_conv3d_desc d{B, t, h, w, cin, cout, k, k, k, st, sp, sp, pad, pad, pad};
+    return check_desc(&d, &p.g[i]) == 0;
+  };
+  if (!geom(0, T, H, W, 4, 64, 7, 1, 2, 3)) return false;
+  const ConvGeom& s0 = p.g[0];
+  p.stem_elems = (int64_t)s0.M * 64;
+  const int64_t Tp = out_dim(s0.To, 3, 2, 1), Hp = out_dim(s0.Ho, 3, 2, 1), Wp = out_dim(s0.Wo, 3, 2, 1);
+  p.Tp = (int)Tp; p.Hp = (int)Hp; p.Wp = (int)Wp;
+  p.pool_elems = B * Tp * Hp * Wp * 64;
+  p.xin = take(B * T * H * W * 4 * f);
+  p.stem = take(p.stem_elems * f);
+  p.pool = take(p.pool_elems * f);
+  p.argmax = take(p.pool_elems);
+  p.act_elems = p.pool_elems;
+  int64_t t = Tp, h = Hp, w = Wp, cin = 64;
+  int ci = 1, blk_i = 0;
+  for (int L = 0; L < 4; ++L) {
+    const int64_t planes = R3D_PLANES[L];
+    for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk, ++blk_i) {
+      const int s = (L > 0 && blk == 0) ? 2 : 1;
+      if (!geom(ci, t, h, w, cin, planes, 1, 1, 1, 0)) return false;
+      const ConvGeom& c1 = p.g[ci];
+      if (!geom(ci + 1, c1.To, c1.Ho, c1.Wo, planes, planes, 3, s, s, 1)) return false;
+      const ConvGeom& c2 = p.g[ci + 1];
+      if (!geom(ci + 2, c2.To, c2.Ho, c2.Wo, planes, planes * 4, 1, 1, 1, 0)) return false;
+      if (blk == 0 && !geom(ci + 3, t, h, w, cin, planes * 4, 1, s, s, 0)) return false;
+      const ConvGeom& c3 = p.g[ci + 2];
+      p.a1[blk_i] = take((int64_t)c1.M * c1.N * f);
+      p.a2[blk_i] = take((int64_t)c2.M * c2.N * f);
+      p.y[blk_i] = take((int64_t)c3.M * c3.N * f);
+      p.act_elems = std::max({p.act_elems, (int64_t)c1.M * c1.N, (int64_t)c2.M * c2.N, (int64_t)c3.M * c3.N});
+      t = c3.To; h = c3.Ho; w = c3.Wo;
+      cin = planes * 4;
+      ci += blk == 0 ? 4 : 3;
+    }
+  }
+  p.tape_bytes = off;
+  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
+    p.bwd_part_bytes = std::max(p.bwd_part_bytes, wgrad_ws_bytes(p.g[i], wgrad_plan_splits(p.g[i])));
+    if (i > 0) p.bwd_part_bytes = std::max(p.bwd_part_bytes, dgrad_ws_bytes(p.g[i]));
+  }
+  p.ok = true;
+  return true;
+}
+
+int check_r3d_params(const stlt_r3d_params* p, const char* who) {
+  if (!p) return stlt_set_error(STLT_EINVAL, "%s: null parameters", who);
+  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
+    const stlt_r3d_conv& c = p->conv[i];
+    if (!c.w || !c.bn_w || !c.bn_b || !c.bn_mean || !c.bn_var) return stlt_set_error(STLT_EINVAL, "%s: conv %d has a null weight or BatchNorm buffer", who, i);
+    if ((uintptr_t)c.w & 15) return stlt_set_error(STLT_EINVAL, "%s: packed weight %d is not 16-byte aligned", who, i);
+  }
+  return 0;
+}
+
+int64_t r3d_bwd_ws_bytes(const TrunkPlan& p) {
+  const int64_t f = sizeof(float);
+  return 4 * align256(p.act_elems * f) + align256(p.stem_elems * f) + align256(p.bwd_part_bytes);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t stlt_conv3d_bwd_data_workspace_bytes(const stlt_conv3d_desc* d, int n_split) {
+  ConvGeom g;
+  if (check_desc(d, &g)) return 0;
+  if (n_split <= 0) return (size_t)dgrad_ws_bytes(g);
+  SubConv sub[8];
+  const int n = dgrad_plan(g, sub);
+  int64_t mx = 0;
+  for (int i = 0; i < n; ++i)
+    if (sub[i].g.K > 0 && n_split > 1) mx = std::max(mx, conv_split_bytes(sub[i].g, std::min<int64_t>(n_split, cdiv(sub[i].g.K, CK))));
+  return (size_t)mx;
+}
+
+int stlt_conv3d_repack_dgrad(const float* w, const stlt_conv3d_desc* d, const float* scale, float* out, stlt_stream_t stream) {
+  ConvGeom g;
+  if (int e = check_desc(d, &g)) return e;
+  if (!w || !out) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_repack_dgrad: null pointer");
+  if (g.st > 2 || g.sh > 2 || g.sw > 2) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_repack_dgrad: strides above 2 are not supported");
+  const int64_t n = (int64_t)g.N * g.C * g.kt * g.kh * g.kw;
+  hipLaunchKernelGGL(conv3d_repack_dgrad_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 4096)), dim3(256), 0, (hipStream_t)stream, w, g.N, g.C,
+                     g.kt, g.kh, g.kw, g.st, g.sh, g.sw, g.pt, g.ph, g.pw, scale, out);
+  return stlt_check_launch("conv3d_repack_dgrad_kernel");
+}
+
+int stlt_conv3d_bwd_data(const stlt_conv3d_desc* d, const float* dy, const float* w_dgrad, const float* scale, const float* mask, const float* add,
+                         int n_split, void* workspace, size_t workspace_bytes, float* dx, stlt_stream_t stream) {
+  ConvGeom g;
+  if (int e = check_desc(d, &g)) return e;
+  if (!dy || !w_dgrad || !dx) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: null pointer");
+  if (g.N % 4) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: c_out must be a multiple of 4 (it is the contraction's channel count), got %d", g.N);
+  if (g.st > 2 || g.sh > 2 || g.sw > 2 || g.st != g.sh || g.st != g.sw)
+    return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: strides must be equal and at most 2");
+  if (((uintptr_t)dy & 15) || ((uintptr_t)w_dgrad & 15)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: dy and w_dgrad must be 16-byte aligned");
+  if (n_split < 0 || n_split > 1024) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: n_split must lie in [0, 1024]");
+  const size_t need = stlt_conv3d_bwd_data_workspace_bytes(d, n_split);
+  if (need && (!workspace || workspace_bytes < need))
+    return stlt_set_error(STLT_EWORKSPACE, "stlt_conv3d_bwd_data: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  return launch_dgrad(g, dy, w_dgrad, scale, mask, add, dx, (float*)workspace, (int64_t)workspace_bytes, n_split, (hipStream_t)stream);
+}
+
+size_t stlt_conv3d_bwd_weight_workspace_bytes(const stlt_conv3d_desc* d, int n_split) {
+  ConvGeom g;
+  if (check_desc(d, &g)) return 0;
+  if (n_split < 0 || n_split > 4096) return 0;
+  const int64_t slabs = cdiv(g.M, CK);
+  int64_t splits = n_split == 0 ? wgrad_plan_splits(g) : std::min<int64_t>(n_split, slabs);
+  splits = cdiv(slabs, cdiv(slabs, splits));
+  return (size_t)wgrad_ws_bytes(g, splits);
+}
+
+int stlt_conv3d_bwd_weight(const stlt_conv3d_desc* d, const float* x, const float* dy, const float* scale, int64_t c_in_w, int accumulate, int n_split,
+                           void* workspace, size_t workspace_bytes, float* dw, stlt_stream_t stream) {
+  ConvGeom g;
+  if (int e = check_desc(d, &g)) return e;
+  if (!x || !dy || !dw) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: null pointer");
+  if (g.N % 4) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: c_out must be a multiple of 4, got %d", g.N);
+  if (c_in_w <= 0 || c_in_w > g.C) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: c_in_w must lie in [1, c_in]");
+  if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: x and dy must be 16-byte aligned");
+  if (n_split < 0 || n_split > 4096) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: n_split must lie in [0, 4096]");
+  const size_t need = stlt_conv3d_bwd_weight_workspace_bytes(d, n_split);
+  if (!workspace || workspace_bytes < need)
+    return stlt_set_error(STLT_EWORKSPACE, "stlt_conv3d_bwd_weight: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  const int64_t splits = n_split == 0 ? wgrad_plan_splits(g) : n_split;
+  return launch_wgrad(g, x, dy, (int)c_in_w, scale, nullptr, nullptr, 0.f, accumulate, dw, splits, (float*)workspace, (hipStream_t)stream);
+}
+
+int stlt_maxpool3d_ndhwc_train(const float* x, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, float* y, uint8_t* argmax, stlt_stream_t stream) {
+  if (!x || !y || !argmax) return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_train: null pointer");
+  if (B < 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || T > (1 << 24) || H > (1 << 24) || W > (1 << 24) || C > (1 << 24) || B * T * H * W * C > (1LL << 40))
+    return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_train: bad shape");
+  const int64_t To = out_dim(T, 3, 2, 1), Ho = out_dim(H, 3, 2, 1), Wo = out_dim(W, 3, 2, 1);
+  const int64_t n = B * To * Ho * Wo * C;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(maxpool3d_argmax_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, (int)B, (int)T, (int)H, (int)W, (int)C,
+                     (int)To, (int)Ho, (int)Wo, y, argmax);
+  return stlt_check_launch("maxpool3d_argmax_kernel");
+}
+
+int stlt_maxpool3d_ndhwc_bwd(const float* dy, const uint8_t* argmax, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, const float* mask, float* dx,
+                             stlt_stream_t stream) {
+  if (!dy || !argmax || !dx) return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_bwd: null pointer");
+  if (B < 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || T > (1 << 24) || H > (1 << 24) || W > (1 << 24) || C > (1 << 24) || B * T * H * W * C > (1LL << 40))
+    return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_bwd: bad shape");
+  const int64_t To = out_dim(T, 3, 2, 1), Ho = out_dim(H, 3, 2, 1), Wo = out_dim(W, 3, 2, 1);
+  const int64_t n = B * T * H * W * C;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(maxpool3d_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, dy, argmax, (int)B, (int)T, (int)H, (int)W,
+                     (int)C, (int)To, (int)Ho, (int)Wo, mask, dx);
+  return stlt_check_launch("maxpool3d_bwd_kernel");
+}
+
+size_t stlt_r3d_tape_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
+  TrunkPlan p;
+  if (!trunk_plan(B, T, H, W, &p)) return 0;
+  return (size_t)p.tape_bytes;
+}
+
+size_t stlt_r3d_backward_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
+  TrunkPlan p;
+  if (!trunk_plan(B, T, H, W, &p)) return 0;
+  return (size_t)r3d_bwd_ws_bytes(p);
+}
+
+int stlt_r3d_repack_all(const float* const* weights, const stlt_r3d_params* p, float* const* fwd, float* const* dgrad, stlt_stream_t stream) {
+  if (!weights || !p || !fwd || !dgrad) return stlt_set_error(STLT_EINVAL, "stlt_r3d_repack_all: null pointer");
+  R3dRepackArgs a;
+  a.eps = p->bn_eps;
+  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
+    if (!weights[i] || !p->conv[i].bn_w || !p->conv[i].bn_var || (!fwd[i] && !dgrad[i]))
+      return stlt_set_error(STLT_EINVAL, "stlt_r3d_repack_all: conv %d has a null weight, BatchNorm buffer or destination", i);
+    if (((uintptr_t)fwd[i] & 15) || (i > 0 && ((uintptr_t)dgrad[i] & 15)))
+      return stlt_set_error(STLT_EINVAL, "stlt_r3d_repack_all: the copies of conv %d must be 16-byte aligned (the conv kernels load them as float4)", i);
+    a.w[i] = weights[i]; a.bn_w[i] = p->conv[i].bn_w; a.bn_var[i] = p->conv[i].bn_var; a.fwd[i] = fwd[i]; a.dgrad[i] = i > 0 ? dgrad[i] : nullptr;
+  }
+  a.block0[0] = 0;
+  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
+    int nf, nw;
+    r3d_repack_counts(i, &nf, &nw);
+    a.block0[i + 1] = a.block0[i] + (int)cdiv((int64_t)nf + nw, 256 * REPACK_ITEMS);
+  }
+  hipLaunchKernelGGL(r3d_repack_all_kernel, dim3((unsigned)a.block0[STLT_R3D_CONVS]), dim3(256), 0, (hipStream_t)stream, a);
+  return stlt_check_launch("r3d_repack_all_kernel");
+}
+
+int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
+                           void* tape, size_t tape_bytes, float* features, float* pooled, stlt_stream_t stream) {
+  if (int e = check_r3d_params(p, "stlt_r3d_train_forward")) return e;
+  if (!video || !tape || (!features && !pooled)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_train_forward: null pointer");
+  TrunkPlan P;
+  if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_train_forward: bad video shape or too small for the trunk");
+  const size_t need = stlt_r3d_workspace_bytes(B, T, H, W);
+  if (!workspace || workspace_bytes < need)
+    return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_train_forward: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  if (tape_bytes < (size_t)P.tape_bytes) return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_train_forward: tape of %zu bytes, %lld needed", tape_bytes, (long long)P.tape_bytes);
+  if (((uintptr_t)workspace & 255) || ((uintptr_t)tape & 255)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_train_forward: workspace and tape must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  char* tp = (char*)tape;
+  const TrunkDims d = trunk_dims(B, T, H, W);
+  // the forward's workspace layout: [xin][X0][X1][DS][T1 | T2][part]; only DS and part are used here
+  char* base = (char*)workspace;
+  base += align256(B * T * H * W * 4 * (int64_t)sizeof(float)) + 2 * align256(d.act_elems * (int64_t)sizeof(float));
+  float* DS = (float*)base;
+  base += align256(d.act_elems * (int64_t)sizeof(float)) + align256(std::max(d.stem_elems, 2 * d.act_elems) * (int64_t)sizeof(float));
+  float* part = (float*)base;
+  const float eps = p->bn_eps;
+  auto conv = [&](int i, const float* x, const float* res, int relu, float* y) -> int {
+    const ConvGeom& g = P.g[i];
+    const stlt_r3d_conv& c = p->conv[i];
+    return launch_conv(g, x, c.w, c.bn_w, c.bn_b, c.bn_mean, c.bn_var, eps, res, relu, y, conv_plan_splits(g.M, g.N, g.K), part, s);
+  };
+  float* xin = (float*)(tp + P.xin);
+  if (int e = stlt_ncdhw_to_ndhwc(video, B, 3, T, H, W, 4, xin, stream)) return e;
+  float* stem = (float*)(tp + P.stem);
+  if (int e = conv(0, xin, nullptr, 1, stem)) return e;
+  float* pool = (float*)(tp + P.pool);
+  if (int e = stlt_maxpool3d_ndhwc_train(stem, B, P.g[0].To, P.g[0].Ho, P.g[0].Wo, 64, pool, (uint8_t*)(tp + P.argmax), stream)) return e;
+  const float* cur = pool;
+  int ci = 1, bi = 0;
+  for (int L = 0; L < 4; ++L)
+    for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk, ++bi) {
+      float* a1 = (float*)(tp + P.a1[bi]);
+      float* a2 = (float*)(tp + P.a2[bi]);
+      float* y = (float*)(tp + P.y[bi]);
+      if (int e = conv(ci, cur, nullptr, 1, a1)) return e;
+      if (int e = conv(ci + 1, a1, nullptr, 1, a2)) return e;
+      const float* shortcut = cur;
+      if (blk == 0) {
+        if (int e = conv(ci + 3, cur, nullptr, 0, DS)) return e;
+        shortcut = DS;
+      }
+      if (int e = conv(ci + 2, a2, shortcut, 1, y)) return e;
+      cur = y;
+      ci += blk == 0 ? 4 : 3;
+    }
+  const ConvGeom& last = P.g[STLT_R3D_CONVS - 1];  // conv3 of the last block (no downsample there)
+  const int64_t Pn = (int64_t)last.To * last.Ho * last.Wo;
+  if (features)
+    if (int e = stlt_ndhwc_to_ncdhw(cur, B, Pn, last.N, features, stream)) return e;
+  if (pooled)
+    if (int e = stlt_avgpool_ndhwc(cur, B, Pn, last.N, pooled, stream)) return e;
+  return 0;
+}
+
+int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H, int64_t W,
+                      const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, void* workspace, size_t workspace_bytes,
+                      stlt_stream_t stream) {
+  if (int e = check_r3d_params(p, "stlt_r3d_backward")) return e;
+  if (!dgrad_w || !tape || !dweight) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: null pointer");
+  if ((dfeatures == nullptr) == (dpooled == nullptr)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: pass exactly one of dfeatures and dpooled");
+  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
+    if (!dweight[i]) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: weight gradient %d is null", i);
+    if (i > 0 && (!dgrad_w[i] || ((uintptr_t)dgrad_w[i] & 15))) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: dgrad copy %d is null or not 16-byte aligned", i);
+  }
+  TrunkPlan P;
+  if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: bad video shape or too small for the trunk");
+  if (tape_bytes < (size_t)P.tape_bytes) return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_backward: tape of %zu bytes, %lld needed", tape_bytes, (long long)P.tape_bytes);
+  const int64_t need = r3d_bwd_ws_bytes(P);
+  if (!workspace || workspace_bytes < (size_t)need)
+    return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_backward: workspace of %zu bytes, %lld needed", workspace_bytes, (long long)need);
+  if (((uintptr_t)workspace & 255) || ((uintptr_t)tape & 255)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: workspace and tape must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const char* tp = (const char*)tape;
+  const int64_t f = sizeof(float);
+  char* base = (char*)workspace;
+  float* G3 = (float*)base; base += align256(P.act_elems * f);   // masked pre-ReLU gradient at the block's output
+  float* G2 = (float*)base; base += align256(P.act_elems * f);
+  float* G1 = (float*)base; base += align256(P.act_elems * f);
+  float* GX = (float*)base; base += align256(P.act_elems * f);   // ... at its input (the previous block's G3)
+  float* GS = (float*)base; base += align256(P.stem_elems * f);  // at the stem's output
+  float* part = (float*)base;
+  const float eps = p->bn_eps;
+  auto wgrad = [&](int i, const float* x, const float* g) {
+    const ConvGeom& c = P.g[i];
+    const int cin_w = i == 0 ? 3 : c.C;
+    return launch_wgrad(c, x, g, cin_w, nullptr, p->conv[i].bn_w, p->conv[i].bn_var, eps, accumulate, dweight[i], wgrad_plan_splits(c), part, s);
+  };
+  auto dgrad = [&](int i, const float* g, const float* mask, const float* add, float* dx) {
+    return launch_dgrad(P.g[i], g, dgrad_w[i], nullptr, mask, add, dx, part, P.bwd_part_bytes, 0, s, add == dx);
+  };
+  // blocks in order: their conv index and tape slots
+  int first_conv[16];
+  {
+    int ci = 1, bi = 0;
+    for (int L = 0; L < 4; ++L)
+      for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk, ++bi) { first_conv[bi] = ci; ci += blk == 0 ? 4 : 3; }
+  }
+  {
+    const ConvGeom& last = P.g[STLT_R3D_CONVS - 1];
+    const int64_t Pn = (int64_t)last.To * last.Ho * last.Wo;
+    const int64_t n = B * Pn * last.N;
+    hipLaunchKernelGGL(r3d_grad_in_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, dpooled, dfeatures, (const float*)(tp + P.y[15]), B, (int)Pn,
+                       last.N, G3);
+    if (int e = stlt_check_launch("r3d_grad_in_kernel")) return e;
+  }
+  for (int bi = 15; bi >= 0; --bi) {
+    const int ci = first_conv[bi];
+    const bool has_ds = bi == 0 || bi == 3 || bi == 7 || bi == 13;
+    const float* a1 = (const float*)(tp + P.a1[bi]);
+    const float* a2 = (const float*)(tp + P.a2[bi]);
+    const float* x = bi == 0 ? (const float*)(tp + P.pool) : (const float*)(tp + P.y[bi - 1]);
+    const float* xmask = bi == 0 ? nullptr : x;  // the max-pool output has no ReLU after it
+    if (int e = wgrad(ci + 2, a2, G3)) return e;
+    if (int e = dgrad(ci + 2, G3, a2, nullptr, G2)) return e;
+    if (int e = wgrad(ci + 1, a1, G2)) return e;
+    if (int e = dgrad(ci + 1, G2, a1, nullptr, G1)) return e;
+    if (int e = wgrad(ci, x, G1)) return e;
+    // block input: conv1's data gradient + the shortcut's (identity: G3 itself), masked by the input's ReLU
+    if (int e = dgrad(ci, G1, xmask, has_ds ? nullptr : G3, GX)) return e;
+    if (has_ds) {
+      if (int e = wgrad(ci + 3, x, G3)) return e;
+      if (int e = dgrad(ci + 3, G3, xmask, GX, GX)) return e;
+    }
+    std::swap(G3, GX);
+  }
+  // G3 now holds the gradient at the max-pool output: max-pool backward with the stem's ReLU mask, then the stem's weight gradient
+  const ConvGeom& s0 = P.g[0];
+  const float* stem = (const float*)(tp + P.stem);
+  if (int e = stlt_maxpool3d_ndhwc_bwd(G3, (const uint8_t*)(tp + P.argmax), B, s0.To, s0.Ho, s0.Wo, 64, stem, GS, stream)) return e;
+  return wgrad(0, (const float*)(tp + P.xin), GS);
 }
 
 }  // extern "C"

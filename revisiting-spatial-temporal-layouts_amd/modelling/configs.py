@@ -59,6 +59,9 @@ class MultimodalModelConfig:
         # opt-in: the appearance branch carries the R3D-50 trunk (the reference's `appearance_branch.resnet.*` keys) and runs it on
         # `video_frames` when a batch has no `appearance_features`.  Off: the branch starts from precomputed features, as before.
         self.appearance_trunk = bool(kwargs.pop("appearance_trunk", False))
+        # opt-in: a grad-enabled forward trains the trunk's 53 Conv3d weights (native Conv3d backward, modelling/resnet3d.py).
+        # Off: a trainable trunk under autograd is an error, as before.
+        self.train_trunk = bool(kwargs.pop("train_trunk", False))
         self.appearance_config = self
         self.stlt_config.load_backbone_path = None  # the fusion models build a fresh layout branch (models.py:439)
 
@@ -78,6 +81,9 @@ class AppearanceModelConfig:
         assert self.appearance_num_frames, "appearance_num_frames must not be None!"
         self.resnet_model_path = kwargs.pop("resnet_model_path", None)
         self.num_appearance_layers = kwargs.pop("num_appearance_layers", 4)
+        # opt-in: a grad-enabled forward trains the trunk's 53 Conv3d weights (native Conv3d backward, modelling/resnet3d.py).
+        # Off: a trainable trunk under autograd is an error, as before.
+        self.train_trunk = bool(kwargs.pop("train_trunk", False))
 
     def __repr__(self):
         rows = [("Number of classes", self.num_classes), ("Max number of appearance frames", self.appearance_num_frames),

@@ -6,8 +6,9 @@ Differences from the reference, by design of the scope (SURVEY §2 row 17, §8f 
     ``Resnet3D.forward_features`` returns — instead of ``video_frames``, and the state dict has every reference key EXCEPT
     ``…appearance_branch.resnet.*`` (load reference checkpoints with ``strict=False``).  ``MultimodalModelConfig(appearance_trunk=True)``
     adds the trunk (``modelling/resnet3d.py``) with the reference's 320 ``…resnet.*`` keys in their place (reference checkpoints then load
-    with ``strict=True``); a batch with ``video_frames`` and no ``appearance_features`` runs it natively, without a tape — a trainable
-    trunk under autograd is an error (Conv3d backward is not built), a frozen one feeds the training composition below;
+    with ``strict=True``); a batch with ``video_frames`` and no ``appearance_features`` runs it natively.  A frozen trunk runs without a
+    tape and feeds the training composition below; a trainable one under autograd needs ``train_trunk=True`` (then its conv weights
+    train through ``resnet3d.R3dTrunkFn``), else it is an error;
   * inference is one native call (``stlt_caf_forward``).  Training — with autograd enabled and trainable parameters —
     composes the same arithmetic from the op-level autograd Functions of ``ops.py`` (native forward AND backward kernels
     per op: linear, attention, add+LayerNorm, GELU, the two embedding kernels); a frozen layout branch runs through the

@@ -6,8 +6,14 @@ BatchNorm, ``resnet.4`` .. ``resnet.7`` the four layers of Bottleneck blocks, th
 ``stlt_r3d_forward`` (csrc/r3d.hip): channels-last implicit-GEMM convolutions on the f32 MFMA with BatchNorm, residual and ReLU in
 their epilogues.  BatchNorm always has eval semantics, as ``Resnet3D.train`` keeps it (models.py:215-219).
 
-The trunk has no backward here (Conv3d backward is not built): with autograd on, a trainable trunk parameter is an error that names
-the fix (``….resnet.requires_grad_(False)``); a frozen trunk runs without a tape and its consumers train on its output.
+Training the trunk is opt-in (``train_trunk=True`` in the model's config).  With it on, a grad-enabled forward with trainable conv
+weights runs ``R3dTrunkFn``: ``stlt_r3d_train_forward`` records a tape (its own, from torch's allocator, held by the autograd context)
+and ``stlt_r3d_backward`` writes the 53 conv weight gradients — straight into a Trainer's flat gradient buffer inside its step
+(``ops.grad_targets``).  The packed weight copies are then re-made by one batched repack whenever the weights may have changed: a
+parameter's storage or ``_version`` moved, or the fused optimiser (which writes through raw pointers and leaves ``_version`` alone)
+stepped since (``ops.raw_param_writes``).  With it off (the default) nothing changes: with autograd on, a
+trainable trunk parameter is an error that names the fix (``….resnet.requires_grad_(False)``); a frozen trunk runs without a tape and
+its consumers train on its output.
 """
 from __future__ import annotations
 
@@ -99,11 +105,47 @@ def load_full_resnet_state(trunk: nn.Sequential, path: str) -> None:
 
 class TrunkRunner:
     """Launch state of one trunk: packed weight copies (re-made when a parameter's storage or ``_version`` changes) and the workspace.
-    Held outside the module's parameters and buffers, so it never reaches a state dict; copies and pickles start empty."""
+    Held outside the module's parameters and buffers, so it never reaches a state dict; copies and pickles start empty.
+    ``train_trunk``: a trainable trunk under autograd runs R3dTrunkFn; its forward and dgrad copies are re-made by one batched launch
+    whenever the weights may have changed (``_weights_key``)."""
 
-    def __init__(self):
+    def __init__(self, train_trunk: bool = False):
         self.packed: Dict[int, Tuple[Tuple, torch.Tensor]] = {}
         self.ws = _Workspace()
+        self.bws = _Workspace()
+        self.train_trunk = train_trunk
+        self.copies = None  # (device, forward copies, dgrad copies) of the trainable trunk: stlt_r3d_repack_all's destinations
+        self.copies_key = None  # _weights_key of the weights the copies were made from
+
+    @staticmethod
+    def _weights_key(pairs, device):
+        """What the copies depend on: every conv weight and BN scale (storage, _version) and the raw-pointer writes of the fused optimiser."""
+        return (device, ops.raw_param_writes(),
+                tuple((t.data_ptr(), t._version) for conv, bn in pairs for t in (conv.weight, bn.weight, bn.running_var)))
+
+    def _refresh(self, trunk: nn.Sequential, p, device) -> None:
+        """Point p at the forward copies, re-made first (stlt_r3d_repack_all: every forward copy and every BN-scaled dgrad copy, one
+        launch) when the weights may have changed since they were made."""
+        pairs = trunk_convs(trunk)
+        key = self._weights_key(pairs, device)
+        if self.copies is None or self.copies[0] != device:
+            fwd, dgr = [], []
+            for i, (conv, _) in enumerate(pairs):
+                co, ci, kt, kh, kw = conv.weight.shape
+                fwd.append(torch.empty(co, kt, kh, kw, (ci + 3) // 4 * 4, device=device, dtype=torch.float32))
+                dgr.append(torch.empty(conv.weight.numel() if i else 4, device=device, dtype=torch.float32))
+            self.copies = (device, fwd, dgr)
+            self.copies_key = None
+        _, fwd, dgr = self.copies
+        if key != self.copies_key:
+            ws = L.R3dPointers(*[_dev_ptr(conv.weight) for conv, _ in pairs])
+            L.check(L.load().stlt_r3d_repack_all(ws, C.byref(p), L.R3dPointers(*[t.data_ptr() for t in fwd]),
+                                                 L.R3dPointers(*[t.data_ptr() for t in dgr]), torch.cuda.current_stream().cuda_stream),
+                    "stlt_r3d_repack_all")
+            self.copies_key = key
+            self.packed.clear()  # the per-conv cache would be stale after an in-place optimiser step
+        for i, t in enumerate(fwd):
+            p.conv[i].w = t.data_ptr()
 
     def _packed_weight(self, i: int, w: torch.Tensor) -> torch.Tensor:
         key = (w.data_ptr(), w._version, w.device, tuple(w.shape))
@@ -119,11 +161,16 @@ class TrunkRunner:
         return out
 
     def run(self, trunk: nn.Sequential, video: torch.Tensor, features: bool = True, pooled: bool = False, name: str = "resnet"):
-        """-> (features (B, 2048, To, Ho, Wo) | None, pooled (B, 2048) | None); no autograd tape."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in trunk.parameters()):
+        """-> (features (B, 2048, To, Ho, Wo) | None, pooled (B, 2048) | None); an autograd tape only with ``train_trunk`` on."""
+        trainable = any(p.requires_grad for p in trunk.parameters())
+        with_grad = torch.is_grad_enabled() and trainable
+        if with_grad and not self.train_trunk:
             raise L.StltHipError(
                 f"the R3D-50 trunk ({name}) has trainable parameters, but Conv3d backward is not built: freeze it with "
-                f"`{name}.requires_grad_(False)` (training then goes on through the layers after it), or run under torch.no_grad()")
+                f"`{name}.requires_grad_(False)` (training then goes on through the layers after it), or run under torch.no_grad() "
+                f"(or train it: train_trunk=True in the model config)")
+        if with_grad and features == pooled:
+            raise L.StltHipError("a trained trunk forward returns either the feature map or the pooled features, not both")
         video = ops._chk(video, torch.float32, "video_frames")
         if video.dim() != 5 or video.shape[1] != 3:
             raise L.StltHipError(f"video_frames must be (B, 3, T, H, W), got {tuple(video.shape)}")
@@ -134,21 +181,74 @@ class TrunkRunner:
         p.bn_eps = BN_EPS
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream().cuda_stream
+            refresh = self.train_trunk and trainable
             for i, (conv, bn) in enumerate(trunk_convs(trunk)):
                 if abs(bn.eps - BN_EPS) > 0:
                     raise L.StltHipError(f"BatchNorm3d eps must be {BN_EPS} (resnets3d.py), got {bn.eps}")
-                pw = self._packed_weight(i, conv.weight)
-                p.conv[i] = L.R3dConv(pw.data_ptr(), _dev_ptr(bn.weight), _dev_ptr(bn.bias), _dev_ptr(bn.running_mean), _dev_ptr(bn.running_var))
+                pw = None if refresh else self._packed_weight(i, conv.weight).data_ptr()
+                p.conv[i] = L.R3dConv(pw, _dev_ptr(bn.weight), _dev_ptr(bn.bias), _dev_ptr(bn.running_mean), _dev_ptr(bn.running_var))
+            if refresh:
+                self._refresh(trunk, p, device)
             nbytes = int(lib.stlt_r3d_workspace_bytes(B, T, H, W))
             if nbytes == 0:
                 raise L.StltHipError(f"video_frames {tuple(video.shape)}: no trunk for this shape")
             ws = self.ws.get(nbytes, device)
+            if with_grad:
+                out = R3dTrunkFn.apply(self, p, video, bool(pooled), *[conv.weight for conv, _ in trunk_convs(trunk)])
+                return (None, out) if pooled else (out, None)
             To, Ho, Wo = _trunk_out(T), _trunk_out(H, 2), _trunk_out(W, 2)
             feats = torch.empty(B, FEATURE_CHANNELS, To, Ho, Wo, device=device, dtype=torch.float32) if features else None
             pool = torch.empty(B, FEATURE_CHANNELS, device=device, dtype=torch.float32) if pooled else None
             L.check(lib.stlt_r3d_forward(C.byref(p), video.data_ptr(), B, T, H, W, ws.data_ptr(), ws.numel(), None if feats is None else feats.data_ptr(),
                                          None if pool is None else pool.data_ptr(), stream), "stlt_r3d_forward")
         return feats, pool
+
+
+class R3dTrunkFn(torch.autograd.Function):
+    """The trunk with a tape: forward = stlt_r3d_train_forward (the features or the pooled features, bit for bit those of
+    stlt_r3d_forward), backward = stlt_r3d_backward into the 53 conv weights' gradients (in place into a Trainer's flat buffer inside
+    its step, fresh tensors anywhere else: ops.grad_targets).  Each call owns its tape; video_frames gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, runner, p, video, pooled, *weights):
+        lib = L.load()
+        B, _, T, H, W = video.shape
+        device = video.device
+        stream = torch.cuda.current_stream().cuda_stream
+        tape = torch.empty(int(lib.stlt_r3d_tape_bytes(B, T, H, W)), dtype=torch.uint8, device=device)
+        ws = runner.ws.get(int(lib.stlt_r3d_workspace_bytes(B, T, H, W)), device)
+        if pooled:
+            out = torch.empty(B, FEATURE_CHANNELS, device=device, dtype=torch.float32)
+        else:
+            out = torch.empty(B, FEATURE_CHANNELS, _trunk_out(T), _trunk_out(H, 2), _trunk_out(W, 2), device=device, dtype=torch.float32)
+        L.check(lib.stlt_r3d_train_forward(C.byref(p), video.data_ptr(), B, T, H, W, ws.data_ptr(), ws.numel(), tape.data_ptr(), tape.numel(),
+                                           None if pooled else out.data_ptr(), out.data_ptr() if pooled else None, stream), "stlt_r3d_train_forward")
+        ctx.runner, ctx.params, ctx.tape, ctx.shape, ctx.pooled = runner, L.R3dParams.from_buffer_copy(p), tape, (B, T, H, W), pooled
+        # the dgrad copies are the runner's, shared by every forward and re-made when the weights change: the backward checks that they
+        # still come from the weights this forward saw (a changed weight between a forward and its backward is an error, as in torch)
+        ctx.dgrad, ctx.copies_key = list(runner.copies[2]), runner.copies_key
+        ctx.weights = weights  # the parameters themselves: grad_targets looks at their Trainer binding
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        B, T, H, W = ctx.shape
+        if ctx.tape is None:
+            raise L.StltHipError("R3dTrunkFn: the tape of this forward was already consumed by a backward (retain_graph is not supported)")
+        if ctx.runner.copies_key != ctx.copies_key or ctx.runner.copies[2][0] is not ctx.dgrad[0]:
+            raise L.StltHipError("R3dTrunkFn: the trunk's weights changed between this forward and its backward (an optimiser step or a load in "
+                                 "between); run the backward before changing the weights")
+        dout = dout.contiguous()
+        targets, grads = ops.grad_targets(ctx.weights, ctx.needs_input_grad[4:])
+        dws = [t if t is not None else torch.empty_like(w) for t, w in zip(targets, ctx.weights)]  # frozen convs: a scratch target
+        ws = ctx.runner.bws.get(int(lib.stlt_r3d_backward_workspace_bytes(B, T, H, W)), dout.device)
+        L.check(lib.stlt_r3d_backward(C.byref(ctx.params), L.R3dPointers(*[t.data_ptr() for t in ctx.dgrad]), ctx.tape.data_ptr(), ctx.tape.numel(),
+                                      B, T, H, W, None if ctx.pooled else dout.data_ptr(), dout.data_ptr() if ctx.pooled else None,
+                                      L.R3dPointers(*[t.data_ptr() for t in dws]), 1, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                "stlt_r3d_backward")
+        ctx.tape = None
+        return (None, None, None, None, *grads)
 
 
 def _trunk_out(n: int, stem_stride: int = 1) -> int:
@@ -176,7 +276,8 @@ class Resnet3D(nn.Module):
             self.classifier = nn.Linear(FEATURE_CHANNELS, config.num_classes)
         self.logit_names = ("resnet3d",)
         self.trunk_name = "resnet"
-        object.__setattr__(self, "_runner", TrunkRunner())
+        self.train_trunk = bool(getattr(config, "train_trunk", False))
+        object.__setattr__(self, "_runner", TrunkRunner(self.train_trunk))
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -185,7 +286,7 @@ class Resnet3D(nn.Module):
 
     def __setstate__(self, state):
         self.__dict__.update(state)
-        object.__setattr__(self, "_runner", TrunkRunner())
+        object.__setattr__(self, "_runner", TrunkRunner(self.__dict__.get("train_trunk", False)))
 
     def train(self, mode: bool = True):
         super().train(mode)

@@ -694,6 +694,19 @@ def _block_dropout(p: float):
     return p, int(torch.randint(0, 2 ** 62, (1,)).item()), 0x400000
 
 
+_RAW_PARAM_WRITES = [0]
+
+
+def note_raw_param_writes() -> None:
+    """Called by whatever updates parameters through raw device pointers (train.FusedAdamW): such writes leave torch's `_version`
+    counters alone, so caches of derived weight copies (the R3D-50 trunk's packed copies) key on this counter as well."""
+    _RAW_PARAM_WRITES[0] += 1
+
+
+def raw_param_writes() -> int:
+    return _RAW_PARAM_WRITES[0]
+
+
 def grad_targets(ws, needs):
     """Where a block's backward accumulates its parameter gradients.  Inside a Trainer step (BoundFlatGrads.accumulating) a
     parameter whose .grad is a view of the trainer's flat gradient buffer is accumulated into IN PLACE by the native call (and

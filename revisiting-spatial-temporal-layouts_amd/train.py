@@ -155,6 +155,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._bind(layout, flat.device)
         stream = torch.cuda.current_stream().cuda_stream
         self._opt_called = True  # what torch's wrapped step() records for the LR scheduler's call-order check
+        ops.note_raw_param_writes()  # the update kernel writes the parameters through raw pointers: their _version does not move
         out = self._scratch[1024:]
         L.check(lib.stlt_grad_norm(flat.data_ptr(), flat.numel(), float(max_norm), self._scratch.data_ptr(), out.data_ptr(), stream),
                 "stlt_grad_norm")
