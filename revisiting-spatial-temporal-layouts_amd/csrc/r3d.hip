@@ -986,7 +986,8 @@ int dgrad_plan(const ConvGeom& f, SubConv* out) {
   return n;
 }
 
-int64_t dgrad_splits(const ConvGeom& s) { return s.K > 0 ? conv_plan_splits(s.M, s.N, s.K) : 1; }
+// a class without taps (K = 0) or without rows (M = 0: an input extent of 1 under stride 2) is never split
+int64_t dgrad_splits(const ConvGeom& s) { return s.K > 0 && s.M > 0 ? conv_plan_splits(s.M, s.N, s.K) : 1; }
 
 int64_t dgrad_ws_bytes(const ConvGeom& f) {
   SubConv sub[8];

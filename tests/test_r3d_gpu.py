@@ -69,7 +69,13 @@ CASES = {
     "1x1x1_s2_downsample": (2, 64, 5, 7, 7, 256, (1, 1, 1), (2, 2, 2), (0, 0, 0), False, False, 1),
     "3x3x3_split3": (1, 256, 2, 4, 4, 130, (3, 3, 3), (1, 1, 1), (1, 1, 1), True, True, 3),
     "1x1x1_split_auto": (4, 512, 2, 4, 4, 512, (1, 1, 1), (1, 1, 1), (0, 0, 0), False, True, 0),
+    # layer 4's conv2 at B = 2 (M = 64, 432 k-slabs), with BN and a residual: the automatic plan's 54 splits of 8 slabs
+    "with_split54_3x3x3_s2_residual": (2, 512, 4, 7, 7, 512, (3, 3, 3), (2, 2, 2), (1, 1, 1), True, True, 0),
+    # 108 k-slabs in an explicit 5 splits: four of 22 slabs, the last of 20
+    "with_split5_uneven_3x3x3": (1, 128, 3, 4, 5, 96, (3, 3, 3), (1, 1, 1), (1, 1, 1), True, False, 5),
 }
+# the split count each splitting case reaches (stlt_conv3d_workspace_bytes ÷ one M·c_out slab: tests/test_r3d_plans_cpu.py)
+PLANNED_SPLITS = {"3x3x3_split3": 3, "1x1x1_split_auto": 2, "with_split54_3x3x3_s2_residual": 54, "with_split5_uneven_3x3x3": 5}
 
 
 @pytest.mark.parametrize("case", sorted(CASES))

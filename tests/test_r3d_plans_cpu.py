@@ -1,0 +1,122 @@
+"""What the R3D-50 GPU tests reach, asserted on the host from the library's own workspace queries (pure host arithmetic, no GPU): a
+split launch needs one slab of partial sums per split, so workspace bytes ÷ slab bytes is the split count the library plans.
+
+- each splitting op-level case of tests/test_r3d_gpu.py and tests/test_r3d_train_gpu.py reaches the count its comment names
+  (PLANNED_SPLITS), so a change of the plans cannot make a case stop splitting unnoticed;
+- the whole-trunk sweep of tests/test_r3d_shapes_gpu.py reaches an unsplit and a >= 32-split forward, a >= 200-split weight gradient, a
+  split stride-2 data gradient, a stride-2 parity class without rows and odd input extents under stride 2 in t, h and w."""
+import ctypes
+
+import pytest
+
+import test_r3d_gpu as FWD
+import test_r3d_shapes_gpu as SWEEP
+import test_r3d_train_gpu as BWD
+
+BLOCKS = (3, 4, 6, 3)
+PLANES = (64, 128, 256, 512)
+
+
+def _out(n, k, s, p):
+    return (n + 2 * p - k) // s + 1
+
+
+def trunk_descs(B, T, H, W):
+    """The trunk's 53 convs for video (B, 3, T, H, W) in state-dict order: (B, T, H, W, c_in, c_out, k, stride (t, h, w), pad), the
+    stem's c_in padded to 4 as the trunk stores it."""
+    out = [(B, T, H, W, 4, 64, 7, (1, 2, 2), 3)]
+    t, h, w = _out(T, 7, 1, 3), _out(H, 7, 2, 3), _out(W, 7, 2, 3)
+    t, h, w = _out(t, 3, 2, 1), _out(h, 3, 2, 1), _out(w, 3, 2, 1)  # max-pool
+    cin = 64
+    for L, (n, planes) in enumerate(zip(BLOCKS, PLANES)):
+        for b in range(n):
+            s = 2 if (L > 0 and b == 0) else 1
+            t2, h2, w2 = _out(t, 3, s, 1), _out(h, 3, s, 1), _out(w, 3, s, 1)
+            out += [(B, t, h, w, cin, planes, 1, (1, 1, 1), 0), (B, t, h, w, planes, planes, 3, (s, s, s), 1),
+                    (B, t2, h2, w2, planes, planes * 4, 1, (1, 1, 1), 0)]
+            if b == 0:
+                out.append((B, t, h, w, cin, planes * 4, 1, (s, s, s), 0))
+            t, h, w, cin = t2, h2, w2, planes * 4
+    return out
+
+
+def _desc(pkg, B, T, H, W, ci, co, k, s, p):
+    return pkg._lib.Conv3dDesc(B, T, H, W, ci, co, *k, *s, *p)
+
+
+def _dims(B, T, H, W, co, k, s, p):
+    To, Ho, Wo = [_out(n, kk, ss, pp) for n, kk, ss, pp in zip((T, H, W), k, s, p)]
+    return B * To * Ho * Wo, (To, Ho, Wo)
+
+
+def fwd_splits(lib, d, M, co, n_split=0):
+    return int(lib.stlt_conv3d_workspace_bytes(ctypes.byref(d), n_split)) // (M * co * 4) or 1
+
+
+def wgrad_splits(lib, d, co, K, n_split=0):
+    return int(lib.stlt_conv3d_bwd_weight_workspace_bytes(ctypes.byref(d), n_split)) // (co * K * 4)
+
+
+def dgrad_bytes(lib, d, n_split=0):
+    return int(lib.stlt_conv3d_bwd_data_workspace_bytes(ctypes.byref(d), n_split))
+
+
+@pytest.mark.parametrize("case", sorted(FWD.PLANNED_SPLITS))
+def test_forward_cases_split_as_planned(pkg, case):
+    lib = pkg._lib.load()
+    B, Ci, T, H, W, Co, k, s, p, _, _, n_split = FWD.CASES[case]
+    M, _ = _dims(B, T, H, W, Co, k, s, p)
+    assert fwd_splits(lib, _desc(pkg, B, T, H, W, (Ci + 3) // 4 * 4, Co, k, s, p), M, Co, n_split) == FWD.PLANNED_SPLITS[case]
+
+
+@pytest.mark.parametrize("case", sorted(BWD.PLANNED_SPLITS))
+def test_backward_cases_split_as_planned(pkg, case):
+    lib = pkg._lib.load()
+    B, Ci, T, H, W, Co, k, s, p, n_split = BWD.CASES[case]
+    want_wg, want_dg = BWD.PLANNED_SPLITS[case]
+    c_pad = (Ci + 3) // 4 * 4
+    d = _desc(pkg, B, T, H, W, c_pad, Co, k, s, p)
+    assert wgrad_splits(lib, d, Co, k[0] * k[1] * k[2] * c_pad, n_split) == want_wg
+    nbytes = dgrad_bytes(lib, d, n_split)
+    if s == (1, 1, 1):
+        assert nbytes // (B * T * H * W * Ci * 4) == want_dg or (want_dg == 1 and nbytes == 0)
+    else:  # parity classes of different sizes: only "some class splits" (nonzero workspace) or not
+        assert (nbytes > 0) == (want_dg > 1)
+    if any(n == 1 for n, ss in zip((T, H, W), s) if ss == 2):  # an input extent of 1 under stride 2: classes without rows
+        assert "rowless" in case
+
+
+def test_trunk_descs_match_the_trunk(pkg):
+    for shape in list(SWEEP.SHAPES) + [SWEEP.BIG]:
+        descs = trunk_descs(*shape)
+        assert len(descs) == 53
+        B, t, h, w, ci, co, k, s, p = descs[-1]
+        _, (To, Ho, Wo) = _dims(B, t, h, w, co, (k,) * 3, s, (p,) * 3)
+        R = pkg.modelling.resnet3d
+        assert (co, To, Ho, Wo) == (2048, R._trunk_out(shape[1]), R._trunk_out(shape[2], 2), R._trunk_out(shape[3], 2))
+
+
+def test_sweep_reaches_the_plans(pkg):
+    lib = pkg._lib.load()
+    fwd, wg_max, dg_s2_split, rowless, odd = set(), 0, False, False, [False] * 3
+    for shape in list(SWEEP.SHAPES) + [SWEEP.BIG]:
+        grad = SWEEP.SHAPES.get(shape) == "grad"
+        # the training trunk plans every shape (T <= 8 once divided by zero planning layer 4's row-less parity classes)
+        assert lib.stlt_r3d_tape_bytes(*shape) > 0 and lib.stlt_r3d_backward_workspace_bytes(*shape) > 0, shape
+        for B, T, H, W, ci, co, k, s, p in trunk_descs(*shape):
+            kk, pp = (k,) * 3, (p,) * 3
+            d = _desc(pkg, B, T, H, W, ci, co, kk, s, pp)
+            M, _ = _dims(B, T, H, W, co, kk, s, pp)
+            fwd.add(fwd_splits(lib, d, M, co))
+            if not grad:
+                continue
+            wg_max = max(wg_max, wgrad_splits(lib, d, co, k ** 3 * ci))
+            if s == (2, 2, 2):
+                dg_s2_split |= dgrad_bytes(lib, d) > 0
+                rowless |= min(T, H, W) == 1
+            for i, (n, st) in enumerate(zip((T, H, W), s)):
+                odd[i] |= st == 2 and n % 2 == 1
+    assert 1 in fwd and max(fwd) >= 32, sorted(fwd)
+    assert wg_max >= 200, wg_max
+    assert dg_s2_split and rowless
+    assert all(odd), odd

@@ -43,6 +43,32 @@ CASES = {
     "1x1x1_s2": (2, 64, 5, 7, 7, 128, (1, 1, 1), (2, 2, 2), (0, 0, 0), 1),
     "3x3x3_split3": (1, 128, 2, 4, 4, 64, (3, 3, 3), (1, 1, 1), (1, 1, 1), 3),
     "1x1x1_split_auto": (4, 256, 2, 4, 4, 512, (1, 1, 1), (1, 1, 1), (0, 0, 0), 0),
+    # M = 65 536 (2048 m-slabs), one 64 x 64 wgrad tile: the automatic plan stops at WG_SPLIT_MAX = 256 splits of 8 slabs
+    "with_wgsplit256_1x1x1": (4, 64, 16, 32, 32, 64, (1, 1, 1), (1, 1, 1), (0, 0, 0), 0),
+    # 98 m-slabs: automatic wgrad plan of 11 splits (ten of 9 slabs, the last of 8); the dgrad plan splits 54 k-slabs 6 ways
+    "with_wgsplit11_3x3x3": (2, 64, 8, 14, 14, 64, (3, 3, 3), (1, 1, 1), (1, 1, 1), 0),
+    # explicit 7: wgrad 19 m-slabs (the last a partial one) as 6 x 3 + 1; dgrad 41 k-slabs as 6 x 6 + 5
+    "with_split7_uneven_3x3x3": (1, 32, 6, 10, 10, 48, (3, 3, 3), (1, 1, 1), (1, 1, 1), 7),
+    # layer 4's conv2 at B = 2: the automatic dgrad plan splits each parity class (up to 16 ways: 128 k-slabs of the 2x2x2-tap class)
+    "with_split_auto_3x3x3_s2": (2, 512, 4, 7, 7, 512, (3, 3, 3), (2, 2, 2), (1, 1, 1), 0),
+    # explicit 3 on a stride-2 dgrad with odd extents (classes of 2 to 16 k-slabs: 2 or 3 splits); wgrad 2 m-slabs, 2 splits
+    "with_split3_3x3x3_s2": (1, 64, 6, 7, 5, 64, (3, 3, 3), (2, 2, 2), (1, 1, 1), 3),
+    # Ti = 1 under stride 2: the four classes of odd t have no rows (layer 4's conv2 at T <= 8); explicit 3 splits the others
+    "with_rowless_split3_3x3x3_s2_t1": (2, 64, 1, 6, 5, 64, (3, 3, 3), (2, 2, 2), (1, 1, 1), 3),
+    # Hi = 1 under a 1x1x1 stride 2 (the downsample): classes without rows beside classes without taps; unsplit
+    "with_rowless_1x1x1_s2_h1": (2, 64, 3, 1, 5, 128, (1, 1, 1), (2, 2, 2), (0, 0, 0), 0),
+}
+# (wgrad splits, dgrad splits) each case reaches, from the library's workspace queries (tests/test_r3d_plans_cpu.py): wgrad = bytes ÷ one
+# c_out·K slab; dgrad at stride 1 = bytes ÷ one B·T·H·W·c_in slab; at stride 2 the classes differ, so 2 there means "some class splits"
+PLANNED_SPLITS = {
+    "3x3x3_split3": (1, 3),
+    "with_wgsplit256_1x1x1": (256, 1),
+    "with_wgsplit11_3x3x3": (11, 6),
+    "with_split7_uneven_3x3x3": (7, 7),
+    "with_split_auto_3x3x3_s2": (1, 2),
+    "with_split3_3x3x3_s2": (2, 2),
+    "with_rowless_split3_3x3x3_s2_t1": (1, 2),
+    "with_rowless_1x1x1_s2_h1": (1, 1),
 }
 
 
@@ -99,6 +125,11 @@ def test_conv3d_dgrad_against_float64(pkg, case):
     tol_e = tol * scale_ci.max().item() + 4 * EPS32 * add.abs().max().item()
     assert (got_e - ref_e).abs().max().item() <= tol_e, (case, (got_e - ref_e).abs().max().item(), tol_e)
     assert torch.equal(got_e, run(True))  # a repeated launch is bit-identical
+    # add == dx (the trunk's shortcut gradient): each element is read, then written, by one thread — bit for bit the out-of-place result
+    dx = add_d.clone()
+    pkg._lib.check(lib.stlt_conv3d_bwd_data(ctypes.byref(d), dy_d.data_ptr(), wd.data_ptr(), sc_d.data_ptr(), mask_d.data_ptr(), dx.data_ptr(), n_split,
+                                            ws.data_ptr(), nbytes, dx.data_ptr(), _stream()), "stlt_conv3d_bwd_data (add == dx)")
+    assert torch.equal(dx.permute(0, 4, 1, 2, 3).cpu().double(), got_e), case
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
