@@ -81,16 +81,40 @@ class Dropout:
         return x * (torch.from_numpy(keep).to(x.dtype) * self.scale)
 
     def attention(self, site: int, probs: torch.Tensor) -> torch.Tensor:
-        """probs (S,H,L,L): element (s,h,i,j) has idx = (((s*L+i)*H + h) << 8) | j."""
+        """probs (S,H,Lq,Lk): element (s,h,i,j) has idx = (((s*Lq+i)*H + h) << 8) | (j & 0xff) — the query token's row in the
+        (S*Lq, d) activations, the head, the key position inside its sequence (csrc/attn.hip, attn_any.hip, bwd_api.hip)."""
         import numpy as np
         if self.p <= 0:
             return probs
-        S, H, L, _ = probs.shape
+        S, H, Lq, Lk = probs.shape
         s_, h_, i_, j_ = np.meshgrid(np.arange(S, dtype=np.uint64), np.arange(H, dtype=np.uint64),
-                                     np.arange(L, dtype=np.uint64), np.arange(L, dtype=np.uint64), indexing="ij")
-        idx = ((((s_ * np.uint64(L) + i_) * np.uint64(H)) + h_) << np.uint64(8)) | j_
+                                     np.arange(Lq, dtype=np.uint64), np.arange(Lk, dtype=np.uint64), indexing="ij")
+        idx = ((((s_ * np.uint64(Lq) + i_) * np.uint64(H)) + h_) << np.uint64(8)) | (j_ & np.uint64(0xFF))
         keep = dropout_keep(self.p, self.seed, site, idx)
         return probs * (torch.from_numpy(keep).to(probs.dtype) * self.scale)
+
+
+class CallSeeds:
+    """Train-mode dropout of the op-level composition (ops.py): every native call that drops — ``DropoutFn`` (site
+    ``SITE_DROPOUT``), a block call (``AttnBlockFn`` / ``FfnBlockFn``: sites ``SITE_BLOCK`` and ``SITE_BLOCK + 1``) or the
+    layout branch's native tape (one seed, the STLT sites above) — draws one seed from torch's CPU generator, and a call at
+    p = 0 draws none.  ``seeds`` are those draws in forward order; ``take`` hands out the next one as a ``Dropout`` and logs
+    (kind, shape, seed) so a test can hold the native calls to the same sequence.  ``layout`` names the layout branch's
+    schedule in a fusion model: "tape" (``_BackboneTrainFn``), "ops" (skip_padding: the op-level composition) or "frozen"
+    (the native no-grad forward, no dropout)."""
+
+    SITE_DROPOUT, SITE_BLOCK = 0x200000, 0x400000
+
+    def __init__(self, seeds, layout: str = "tape"):
+        assert layout in ("tape", "ops", "frozen"), layout
+        self.seeds, self.layout, self.log = [int(s) for s in seeds], layout, []
+
+    def take(self, kind: str, shape, p: float) -> Optional["Dropout"]:
+        if p <= 0:
+            return None
+        seed = self.seeds[len(self.log)]
+        self.log.append((kind, tuple(int(n) for n in shape), seed))
+        return Dropout(p, seed)
 
 
 SITE_EMBED, SITE_FRAMES = 0xE0, 0xE1
@@ -140,17 +164,23 @@ def attention_core(qkv: torch.Tensor, mask_add: torch.Tensor, H: int, drop: Opti
 
 
 def encoder_layer(x: torch.Tensor, sd: Dict[str, torch.Tensor], prefix: str, mask_add: torch.Tensor, H: int,
-                  drop: Optional["Dropout"] = None, site0: int = 0) -> torch.Tensor:
+                  drop: Optional["Dropout"] = None, site0: int = 0, ffn_drop: Optional["Dropout"] = None) -> torch.Tensor:
     """nn.TransformerEncoderLayer as configured at models.py:46-52,118-124:
-    post-norm, gelu, dim_feedforward=4d, LN eps = torch default 1e-5 (config eps is NOT forwarded)."""
+    post-norm, gelu, dim_feedforward=4d, LN eps = torch default 1e-5 (config eps is NOT forwarded).
+    Dropout: one mask source at sites site0 .. site0 + 3 (the native tape), or — with ``ffn_drop`` — two block calls:
+    ``drop`` at site0 / site0 + 1 (probabilities, dropout1), ``ffn_drop`` at site0 / site0 + 1 (inner, dropout2)."""
     p = lambda k: sd[prefix + k]
     qkv = x @ p("self_attn.in_proj_weight").t() + p("self_attn.in_proj_bias")
     dz = (lambda k, t: drop.elementwise(site0 + k, t)) if drop is not None else (lambda k, t: t)
+    if ffn_drop is not None:
+        dzf = lambda k, t: ffn_drop.elementwise(site0 + k - 2, t)
+    else:
+        dzf = dz
     a = attention_core(qkv, mask_add, H, drop, site0)
     x = layer_norm(x + dz(1, a @ p("self_attn.out_proj.weight").t() + p("self_attn.out_proj.bias")),
                    p("norm1.weight"), p("norm1.bias"), 1e-5)
-    h = dz(2, gelu(x @ p("linear1.weight").t() + p("linear1.bias")))
-    x = layer_norm(x + dz(3, h @ p("linear2.weight").t() + p("linear2.bias")), p("norm2.weight"), p("norm2.bias"), 1e-5)
+    h = dzf(2, gelu(x @ p("linear1.weight").t() + p("linear1.bias")))
+    x = layer_norm(x + dzf(3, h @ p("linear2.weight").t() + p("linear2.bias")), p("norm2.weight"), p("norm2.bias"), 1e-5)
     return x
 
 
@@ -160,9 +190,13 @@ def _neg_inf_mask(masked: torch.Tensor, dtype) -> torch.Tensor:
 
 def backbone_forward(sd: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], num_heads: int,
                      layer_norm_eps: float = 1e-12, prefix: str = "", dtype=torch.float32,
-                     taps: Optional[Dict[str, torch.Tensor]] = None, drop: Optional["Dropout"] = None) -> torch.Tensor:
+                     taps: Optional[Dict[str, torch.Tensor]] = None, drop=None, drop_p: float = 0.0) -> torch.Tensor:
     """StltBackbone.forward — models.py:136-152 — returned batch-major (B,T,d)
-    (the reference returns the (T,B,d) transpose of this)."""
+    (the reference returns the (T,B,d) transpose of this).  ``drop``: a ``Dropout`` (the native tape's masks), or a
+    ``CallSeeds`` (the op-level composition of ``StltBackbone.forward_train`` at rate ``drop_p``: one seed per call)."""
+    calls = drop if isinstance(drop, CallSeeds) else None
+    if calls is not None:
+        drop = None
     sd = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items() if k.startswith(prefix)}
     FE = prefix + "frames_embeddings."
     LE = FE + "layout_embedding."
@@ -171,6 +205,8 @@ def backbone_forward(sd: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor]
     x = category_box_embeddings(sd, LE + "category_box_embeddings.", batch, layer_norm_eps)  # (B,T,N,d)
     if drop is not None:
         x = drop.elementwise(SITE_EMBED, x)
+    elif calls is not None and drop_p > 0:
+        x = calls.take("dropout", x.shape, drop_p).elementwise(CallSeeds.SITE_DROPOUT, x)
     if taps is not None:
         taps["embed"] = x.clone()
     d = x.shape[-1]
@@ -179,7 +215,11 @@ def backbone_forward(sd: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor]
     m_sp = _neg_inf_mask(kpm[:, None, :].expand(B * T, N, N), x.dtype)
     n_sp = 0
     while f"{LE}transformer.layers.{n_sp}.norm1.weight" in sd:
-        x = encoder_layer(x, sd, f"{LE}transformer.layers.{n_sp}.", m_sp, num_heads, drop, 8 * (n_sp + 1))
+        if calls is not None:
+            da, df = calls.take("attn", (B * T, N, N), drop_p), calls.take("ffn", (B * T * N,), drop_p)
+            x = encoder_layer(x, sd, f"{LE}transformer.layers.{n_sp}.", m_sp, num_heads, da, CallSeeds.SITE_BLOCK, df)
+        else:
+            x = encoder_layer(x, sd, f"{LE}transformer.layers.{n_sp}.", m_sp, num_heads, drop, 8 * (n_sp + 1))
         if taps is not None:
             taps[f"spatial{n_sp}"] = x.reshape(B, T, N, d).clone()
         n_sp += 1
@@ -191,6 +231,8 @@ def backbone_forward(sd: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor]
                    sd[FE + "layer_norm.bias"], layer_norm_eps)
     if drop is not None:
         g = drop.elementwise(SITE_FRAMES, g)
+    elif calls is not None and drop_p > 0:
+        g = calls.take("dropout", g.shape, drop_p).elementwise(CallSeeds.SITE_DROPOUT, g)
     if taps is not None:
         taps["frames"] = g.clone()
     # --- temporal transformer models.py:140-150; causal mask utils/model_utils.py:4-7 (True strictly above diag)
@@ -200,7 +242,11 @@ def backbone_forward(sd: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor]
     n_tp = 0
     x = g
     while f"{prefix}transformer.layers.{n_tp}.norm1.weight" in sd:
-        x = encoder_layer(x, sd, f"{prefix}transformer.layers.{n_tp}.", m_tp, num_heads, drop, 8 * (n_sp + n_tp + 1))
+        if calls is not None:
+            da, df = calls.take("attn", (B, T, T), drop_p), calls.take("ffn", (B * T,), drop_p)
+            x = encoder_layer(x, sd, f"{prefix}transformer.layers.{n_tp}.", m_tp, num_heads, da, CallSeeds.SITE_BLOCK, df)
+        else:
+            x = encoder_layer(x, sd, f"{prefix}transformer.layers.{n_tp}.", m_tp, num_heads, drop, 8 * (n_sp + n_tp + 1))
         if taps is not None:
             taps[f"temporal{n_tp}"] = x.clone()
         n_tp += 1

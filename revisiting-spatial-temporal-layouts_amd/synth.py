@@ -236,11 +236,12 @@ def fit_batch(split: str, epoch: int, index: int) -> Dict[str, torch.Tensor]:
     return b
 
 
-def make_appearance_features(B: int, seed: int = 0, channels: int = 2048) -> torch.Tensor:
+def make_appearance_features(B: int, seed: int = 0, channels: int = 2048, grid=(2, 4, 4)) -> torch.Tensor:
     """Stand-in for the R3D-50 feature map of Resnet3D.forward_features (reference models.py:221-222):
-    (B, 2048, 2, 4, 4), non-negative like a post-ReLU map."""
-    u = uniform01(fnv1a64("appearance_features") ^ (seed * 0x9E3779B97F4A7C15 & _MASK64), B * channels * 32)
-    return torch.from_numpy((u * 1.5).astype(np.float32).reshape(B, channels, 2, 4, 4))
+    (B, 2048, *grid) — (2, 4, 4) by default, S = prod(grid) appearance tokens — non-negative like a post-ReLU map."""
+    grid = tuple(int(g) for g in grid)
+    u = uniform01(fnv1a64("appearance_features") ^ (seed * 0x9E3779B97F4A7C15 & _MASK64), B * channels * int(np.prod(grid)))
+    return torch.from_numpy((u * 1.5).astype(np.float32).reshape(B, channels, *grid))
 
 
 def make_r3d_state_dict(shapes: Dict[str, tuple], seed: int = 1234) -> Dict[str, torch.Tensor]:

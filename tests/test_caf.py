@@ -146,7 +146,8 @@ def test_fusion_training_path_matches_golden_and_oracle_gradients(pkg, model_nam
 
 @pytest.mark.gpu
 def test_backbone_forward_train_matches_native_forward(pkg):
-    """StltBackbone under autograd (op-level composition) against its own native no-grad forward, cfg1 with scores."""
+    """StltBackbone under autograd (the native tape, _BackboneTrainFn: skip_padding is off) against its own native no-grad forward,
+    cfg1 with scores.  The op-level composition (skip_padding on) is held to the fp64 oracle in test_fusion_train_gpu.py."""
     c = pkg.synth.CONFIGS[NAME]
     m = pkg.StltBackbone(pkg.StltModelConfig(**pkg.synth.model_kwargs(NAME)))
     m.load_state_dict(pkg.synth.make_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed=9, gain=1.5))
