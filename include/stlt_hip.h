@@ -221,6 +221,32 @@ int stlt_collate_fwd(const int64_t* categories_ragged, const float* boxes_ragged
                      int64_t cls_id, int64_t* categories, float* boxes, float* scores, int64_t* frame_types,
                      uint8_t* kpm_boxes, uint8_t* kpm_frames, stlt_stream_t stream);
 
+/* Device video collater (csrc/video.hip) — the per-frame transforms of AppearanceDataset.__getitem__ (src/modelling/datasets.py:163-208):
+ * Resize(floor(1.15 S)) with Pillow's 8-bit antialiased bilinear resampling, VideoColorJitter in training (src/utils/data_utils.py:110-137),
+ * the crop, ToTensor + Normalize, written as video_frames (B, 3, T, S, S) float32 — the reference's values bit for bit.
+ * One descriptor per clip; its T frames lie in `frames` (device memory) at src_offset as (T, h, w, 3) uint8.  A resample table for an
+ * axis of size in -> out holds `out` (first, count) pairs of int32 followed by out x ksize int32 weights (22 fraction bits); an axis
+ * whose size stays has no table (offset -1), as Pillow runs no pass there.  `clips`, `tables` (n_table int32) and `lut` (256 float32:
+ * the normalised value of each uint8) are HOST memory: every descriptor and table entry is checked against the frame sizes, the crop,
+ * the packed buffer and the table buffer before anything is copied or launched (STLT_EINVAL otherwise), then they are copied into the
+ * workspace on `stream`; pinned host memory must stay untouched until the stream has passed the call. */
+typedef struct {
+  int64_t src_offset;      /* byte offset of the clip's first frame in `frames` */
+  int32_t h, w;            /* source frame size */
+  int32_t rh, rw;          /* resized frame size */
+  int32_t top, left;       /* crop origin in the resized frame; the S x S crop lies inside it */
+  int32_t tab_x, ksize_x;  /* horizontal table: offset in `tables` and taps per output column; -1 when rw == w */
+  int32_t tab_y, ksize_y;  /* vertical table: likewise; -1 when rh == h */
+  int32_t jitter;          /* 0: evaluation; 1: colour jitter, the four ops in order[] */
+  int32_t order[4];        /* a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue */
+  float brightness, contrast, saturation;
+  int32_t hue_shift;       /* np.uint8(hue_factor * 255), 0..255 */
+} stlt_video_clip;
+size_t stlt_video_prep_workspace_bytes(int64_t B, int64_t T, int64_t n_table); /* 0 for a bad shape */
+int stlt_video_prep_fwd(const uint8_t* frames, int64_t frames_bytes, const stlt_video_clip* clips, const int32_t* tables, int64_t n_table,
+                        const float* lut, int64_t B, int64_t T, int64_t S, float* out, void* workspace, size_t workspace_bytes,
+                        stlt_stream_t stream);
+
 /* ---- whole-path entry points (host-side orchestration in native code) ---- */
 
 typedef struct {

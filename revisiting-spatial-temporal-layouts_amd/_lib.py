@@ -103,6 +103,13 @@ class R3dParams(C.Structure):
     _fields_ = [("conv", R3dConv * R3D_CONVS), ("bn_eps", C.c_float)]
 
 
+class VideoClip(C.Structure):  # stlt_video_clip
+    _fields_ = ([("src_offset", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "rh", "rw", "top", "left", "tab_x", "ksize_x", "tab_y", "ksize_y",
+                                                                      "jitter")]
+                + [("order", C.c_int32 * 4), ("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float),
+                   ("hue_shift", C.c_int32)])
+
+
 R3dPointers = C.c_void_p * R3D_CONVS  # the `const float* const*` / `float* const*` arrays of stlt_r3d_repack_all / stlt_r3d_backward
 
 
@@ -151,6 +158,9 @@ SIGNATURES = {
     "stlt_gather_last_fwd": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "stlt_collate_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp]),
+    "stlt_video_prep_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "stlt_video_prep_fwd": (C.c_int, [_vp, C.c_int64, C.POINTER(VideoClip), _vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp,
+                                      C.c_size_t, _vp]),
     "stlt_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "stlt_backbone_forward": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "stlt_forward": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, _vp, _vp, _vp]),
