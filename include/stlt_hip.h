@@ -247,6 +247,44 @@ int stlt_video_prep_fwd(const uint8_t* frames, int64_t frames_bytes, const stlt_
                         const float* lut, int64_t B, int64_t T, int64_t S, float* out, void* workspace, size_t workspace_bytes,
                         stlt_stream_t stream);
 
+/* Device layout dataset (csrc/layout_data.hip, layout_data.py) — StltDataset.__getitem__ (src/modelling/datasets.py:52-125) and
+ * StltCollater (datasets.py:239-288) over annotation tables uploaded once.
+ * stlt_layout_boxes_fwd: fix_box (src/utils/data_utils.py:205-231) and `torch.tensor(box) / video_size` (datasets.py:75-80) for
+ * n_objects kept objects.  raw_boxes (n, 4) int32 hold max(0, int(b)) saturated at 2^30, sizes (n, 2) int32 the (w, h) of each
+ * object's video (1 <= w, h <= 2^24, not checked: device memory); boxes (n, 4) float32.  raw_boxes / boxes 16-byte aligned.
+ * stlt_layout_batch_fwd: one batch, written the way StltCollater pads it.  batch_host is HOST memory of B * (2 + T) int32: the
+ * video index of each clip, its number of sampled frames (<= T), then B rows of T frame indices (the first count[b] used).  Every
+ * index and every offset it leads to (video_frames_host, frame_objects_host, the action lists) is checked on the host (STLT_EINVAL)
+ * before it is copied to batch_dev (device, same size) on `stream` and the kernel is launched; pinned host memory must stay
+ * untouched until the stream has passed the call.  Outputs (L >= 1 + the largest count): categories (B, L, N) int64, boxes
+ * (B, L, N, 4) float32 (16-byte aligned), scores (B, L, N) float32 or NULL, frame_types (B, L) int64, kpm_boxes (B, L, N) and
+ * kpm_frames (B, L) uint8 (1 = padded), lengths (B) int64 = count + 1, labels: (B) int64 video_label when n_classes == 0, else
+ * (B, n_classes) float32 multi-hot of the video's actions.  Sampled frames carry CLS (cls_id, [0,0,1,1], score 1), their kept
+ * objects, then zero slots, and type empty / regular by frame_empty; frame count[b] is the extract frame; later frames are padding
+ * (CLS alone, type 0).  No synchronisation, no allocation: the call can be captured. */
+typedef struct {
+  int64_t n_videos, n_frames, n_objects, n_actions;
+  int64_t n_classes;                               /* 0: single-label (video_label); > 0: multi-hot width */
+  int64_t cls_id, type_regular, type_empty, type_extract;  /* category2id["cls"], frame2type (configs.py:25-90); "pad" is 0 */
+  const int64_t* video_frames_host;   /* HOST (n_videos + 1): video v owns frames [video_frames[v], video_frames[v + 1]) */
+  const int64_t* frame_objects_host;  /* HOST (n_frames + 1): frame f owns kept objects [frame_objects[f], frame_objects[f + 1]) */
+  const int64_t* video_actions_host;  /* HOST (n_videos + 1), multi-hot only: video v owns actions [video_actions[v], ...[v + 1]) */
+  const int32_t* actions_host;        /* HOST (n_actions), multi-hot only: class indices */
+  const int64_t* video_frames;        /* device copies of the four above, then the device-only tables */
+  const int64_t* frame_objects;
+  const uint8_t* frame_empty;         /* (n_frames): frame_objects was empty before thresholding */
+  const int32_t* object_category;     /* (n_objects) */
+  const float* object_score;          /* (n_objects) */
+  const float* object_box;            /* (n_objects, 4): stlt_layout_boxes_fwd's output */
+  const int64_t* video_label;         /* (n_videos), single-label only */
+  const int64_t* video_actions;
+  const int32_t* actions;
+} stlt_layout_table;
+int stlt_layout_boxes_fwd(const int32_t* raw_boxes, const int32_t* sizes, int64_t n_objects, float* boxes, stlt_stream_t stream);
+int stlt_layout_batch_fwd(const stlt_layout_table* table, const int32_t* batch_host, int32_t* batch_dev, int64_t B, int64_t T, int64_t L,
+                          int64_t N, int64_t* categories, float* boxes, float* scores, int64_t* frame_types, uint8_t* kpm_boxes,
+                          uint8_t* kpm_frames, int64_t* lengths, void* labels, stlt_stream_t stream);
+
 /* ---- whole-path entry points (host-side orchestration in native code) ---- */
 
 typedef struct {

@@ -110,6 +110,14 @@ class VideoClip(C.Structure):  # stlt_video_clip
                    ("hue_shift", C.c_int32)])
 
 
+class LayoutTable(C.Structure):  # stlt_layout_table
+    _fields_ = ([(n, C.c_int64) for n in ("n_videos", "n_frames", "n_objects", "n_actions", "n_classes", "cls_id", "type_regular", "type_empty",
+                                          "type_extract")]
+                + [(n, C.c_void_p) for n in ("video_frames_host", "frame_objects_host", "video_actions_host", "actions_host", "video_frames",
+                                             "frame_objects", "frame_empty", "object_category", "object_score", "object_box", "video_label",
+                                             "video_actions", "actions")])
+
+
 R3dPointers = C.c_void_p * R3D_CONVS  # the `const float* const*` / `float* const*` arrays of stlt_r3d_repack_all / stlt_r3d_backward
 
 
@@ -161,6 +169,9 @@ SIGNATURES = {
     "stlt_video_prep_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "stlt_video_prep_fwd": (C.c_int, [_vp, C.c_int64, C.POINTER(VideoClip), _vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp,
                                       C.c_size_t, _vp]),
+    "stlt_layout_boxes_fwd": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
+    "stlt_layout_batch_fwd": (C.c_int, [C.POINTER(LayoutTable), _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp]),
     "stlt_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "stlt_backbone_forward": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "stlt_forward": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, _vp, _vp, _vp]),

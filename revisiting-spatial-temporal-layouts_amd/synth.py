@@ -293,3 +293,98 @@ def flops_per_clip(T: int, N: int, d: int, n_sp: int, n_tp: int, classes: int) -
         + 2.0 * d * d
         + 2.0 * d * classes
     )
+
+
+# Templates of the seeded "something" annotation sets: some carry the bracketed placeholders the reference strips before its label
+# lookup (datasets.py:131), so a lookup that forgot the stripping fails on them.
+LAYOUT_TEMPLATES = ("Putting [something] on [something]", "Pushing [something] from left to right", "Holding [something]",
+                    "Dropping [something] into [something]", "Opening [something]", "Turning the camera left while filming [something]",
+                    "Pretending to pick [something] up", "Moving [part] of [something]", "Showing that [something] is empty",
+                    "Poking a stack of [something] without the stack collapsing")
+LAYOUT_EDGE_FRAMES = (0, 1, 15, 16, 17, 300)  # videos of 0, 1, T - 1, T, T + 1 and many frames at the reference's T = 16
+
+
+def make_layout_annotations(dataset: str, n_videos: int, seed: int, max_frames: int = 40, max_objects: int = 5):
+    """Seeded annotation set in the reference's file formats (what StltDataset reads, src/modelling/datasets.py:31-47):
+    -> (videos, labels, videoid2size), the contents of dataset_path, labels_path and videoid2size_path.
+
+    videos: [{"id", "frames": [{"frame_objects": [{"category", "score", "x1", "y1", "x2", "y2"}, ...]}, ...], "template" (something) or
+    "actions" (action_genome)}].  The first videos have 0, 1, 15, 16, 17 and 300 frames; the rest 0..max_frames.  Boxes include
+    x1 > x2 / y1 > y2, negative, zero-width, out-of-frame, fractional and very large coordinates; frames include empty
+    `frame_objects`, frames whose objects all score below 0.5, and scores exactly 0.5; one video is 1 x 2 pixels."""
+    from .layout_data import CATEGORY2ID  # the reference's vocabularies (configs.py:25-90)
+
+    rng = np.random.Generator(np.random.PCG64(seed))
+    names = [c for c in CATEGORY2ID[dataset] if c not in ("pad", "cls")]
+    n_classes = 174 if dataset == "something" else 157
+    if dataset == "something":
+        ids = rng.permutation(n_classes)[: len(LAYOUT_TEMPLATES)]
+        labels = {t.replace("[", "").replace("]", ""): str(int(i)) for t, i in zip(LAYOUT_TEMPLATES, ids)}
+    else:
+        labels = {f"c{i:03d}": f"action {i}" for i in range(n_classes)}
+
+    def coord(size):
+        kind = rng.integers(0, 10)
+        if kind == 0:
+            return int(rng.integers(-40, 0))  # negative
+        if kind == 1:
+            return int(size + rng.integers(0, 60))  # at or past the frame's edge
+        if kind == 2:
+            return float(np.round(rng.uniform(-1.0, size + 1.0), 2))  # fractional (int() truncates toward zero)
+        if kind == 3 and rng.integers(0, 4) == 0:
+            return int(rng.integers(1 << 31, 1 << 40))  # beyond int32
+        return int(rng.integers(0, size))
+
+    def frame_objects(w, h):
+        kind = rng.integers(0, 8)
+        if kind == 0:
+            return []
+        k = int(rng.integers(1, max_objects + 1))
+        out = []
+        for _ in range(k):
+            s = rng.random()
+            if kind == 1:
+                score = float(s * 0.5)  # every object below the threshold
+            elif rng.integers(0, 6) == 0:
+                score = 0.5  # exactly the threshold: kept (datasets.py:42, 72 compare with <)
+            else:
+                score = float(np.round(s, 4))
+            x1, y1, x2, y2 = coord(w), coord(h), coord(w), coord(h)
+            if rng.integers(0, 8) == 0:
+                x2 = x1  # zero width
+            if rng.integers(0, 8) == 0:
+                y2 = y1
+            out.append({"category": names[int(rng.integers(0, len(names)))], "score": score, "x1": x1, "y1": y1, "x2": x2, "y2": y2})
+        return out
+
+    videos, sizes = [], {}
+    for i in range(n_videos):
+        vid = f"{dataset[:2]}{seed}_{i:05d}"
+        n = LAYOUT_EDGE_FRAMES[i] if i < len(LAYOUT_EDGE_FRAMES) else int(rng.integers(0, max_frames + 1))
+        w, h = (1, 2) if i == len(LAYOUT_EDGE_FRAMES) else (int(rng.integers(64, 641)), int(rng.integers(64, 481)))
+        sizes[vid] = [w, h]
+        v = {"id": vid, "frames": [{"frame_objects": frame_objects(w, h)} for _ in range(n)]}
+        if dataset == "something":
+            v["template"] = LAYOUT_TEMPLATES[int(rng.integers(0, len(LAYOUT_TEMPLATES)))]
+        else:
+            v["actions"] = [f"c{int(a):03d}" for a in rng.choice(n_classes, size=int(rng.integers(0, 5)), replace=False)]
+        videos.append(v)
+    return videos, labels, sizes
+
+
+def write_layout_annotations(directory: str, dataset: str, n_videos: int, seed: int, **kw):
+    """make_layout_annotations written as the reference's three files under `directory` ->
+    ({"annotations", "labels", "sizes"}: paths, sha256 hex digest of the three files' bytes)."""
+    import hashlib
+    import json
+    import os
+
+    h = hashlib.sha256()
+    paths = {}
+    for k, obj in zip(("annotations", "labels", "sizes"), make_layout_annotations(dataset, n_videos, seed, **kw)):
+        paths[k] = os.path.join(directory, f"layout_{dataset}_{seed}_{k}.json")
+        data = json.dumps(obj, separators=(",", ":")).encode()
+        h.update(data)
+        with open(paths[k], "wb") as f:
+            f.write(data)
+    return paths, h.hexdigest()
