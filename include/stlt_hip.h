@@ -285,6 +285,43 @@ int stlt_layout_batch_fwd(const stlt_layout_table* table, const int32_t* batch_h
                           int64_t N, int64_t* categories, float* boxes, float* scores, int64_t* frame_types, uint8_t* kpm_boxes,
                           uint8_t* kpm_frames, int64_t* lengths, void* labels, stlt_stream_t stream);
 
+/* Device frame store (csrc/frame_store.hip, frame_data.py) — AppearanceDataset.__getitem__ (src/modelling/datasets.py:163-208) split at
+ * the step that does not depend on the batch: the reference resizes every frame on its own before any random transform
+ * (datasets.py:172-177), and Pillow's result is an 8-bit image, so the resized frame is computed once and kept on the device as uint8.
+ * stlt_frames_resize_fwd: the Resize of datasets.py:147,173 for n frames (n, h, w, 3) uint8 in device memory `src`: Pillow's antialiased
+ * bilinear filter as two 8-bit passes, horizontal then vertical, each only on an axis whose size changes; (n, rh, rw, 3) uint8 is
+ * written at store + dst_offset.  tab_x / tab_y are HOST tables in stlt_video_clip's layout (`out` (first, count) pairs, then
+ * out x ksize int32 weights), NULL for an axis that keeps its size; every entry is checked against the source axis (STLT_EINVAL)
+ * before they are copied into the workspace and anything is launched.  Workspace: stlt_frames_resize_workspace_bytes (0 for a bad shape).
+ * stlt_frames_batch_fwd: VideoColorJitter in training (src/utils/data_utils.py:110-137), the crop (datasets.py:181-194), ToTensor +
+ * Normalize (datasets.py:149-152) and AppearanceCollater's stack (datasets.py:291-300): video_frames (B, 3, T, S, S) float32 (16-byte
+ * aligned), the reference's values bit for bit, from resized frames.  batch_host is HOST memory of stlt_frames_batch_block_bytes(B, T):
+ * B x T int64 byte offsets, one per sampled frame (frames of a clip need not be contiguous or distinct), then B descriptors.  An
+ * offset below store_bytes addresses `store`, one in [store_bytes, store_bytes + spill_bytes) the spill area `spill` (frames of
+ * videos that are not resident, resized for this batch); both are device memory, start on a 4-byte boundary and have sizes that
+ * are multiples of 4, because rows are read as whole aligned dwords (either may be NULL with size 0).  Every descriptor, crop and
+ * offset is checked on the host against the frame and buffer sizes (STLT_EINVAL) before the block is copied to batch_dev (device, same
+ * size, 8-byte aligned) on `stream` and the kernels are launched; pinned host memory must stay untouched until the stream has passed
+ * the call.  lut: 256 float32 in DEVICE memory, the normalised value of each uint8.  sums: B x T uint64 of device scratch, needed
+ * when any clip has jitter = 1 (the contrast step's grey mean of the whole frame).  S <= 1024.  No synchronisation, no allocation:
+ * the call can be captured. */
+typedef struct {
+  int32_t rh, rw;          /* resized frame size: every frame of the clip holds rh x rw x 3 bytes */
+  int32_t top, left;       /* crop origin in the resized frame; the S x S crop lies inside it */
+  int32_t jitter;          /* 0: evaluation; 1: colour jitter, the four ops in order[] */
+  int32_t order[4];        /* a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue */
+  float brightness, contrast, saturation;
+  int32_t hue_shift;       /* np.uint8(hue_factor * 255), 0..255 */
+  int32_t reserved;        /* keeps the descriptor a multiple of 8 bytes */
+} stlt_frames_clip;
+size_t stlt_frames_resize_workspace_bytes(int64_t n, int64_t h, int64_t w, int64_t rh, int64_t rw, int64_t ksize_x, int64_t ksize_y);
+int stlt_frames_resize_fwd(const uint8_t* src, int64_t n, int64_t h, int64_t w, int64_t rh, int64_t rw, const int32_t* tab_x, int64_t ksize_x,
+                           const int32_t* tab_y, int64_t ksize_y, uint8_t* store, int64_t store_bytes, int64_t dst_offset, void* workspace,
+                           size_t workspace_bytes, stlt_stream_t stream);
+size_t stlt_frames_batch_block_bytes(int64_t B, int64_t T); /* 0 for a bad shape */
+int stlt_frames_batch_fwd(const uint8_t* store, int64_t store_bytes, const uint8_t* spill, int64_t spill_bytes, const void* batch_host,
+                          void* batch_dev, const float* lut, int64_t B, int64_t T, int64_t S, uint64_t* sums, float* out, stlt_stream_t stream);
+
 /* ---- whole-path entry points (host-side orchestration in native code) ---- */
 
 typedef struct {

@@ -110,6 +110,12 @@ class VideoClip(C.Structure):  # stlt_video_clip
                    ("hue_shift", C.c_int32)])
 
 
+class FramesClip(C.Structure):  # stlt_frames_clip
+    _fields_ = ([(n, C.c_int32) for n in ("rh", "rw", "top", "left", "jitter")]
+                + [("order", C.c_int32 * 4), ("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float),
+                   ("hue_shift", C.c_int32), ("reserved", C.c_int32)])
+
+
 class LayoutTable(C.Structure):  # stlt_layout_table
     _fields_ = ([(n, C.c_int64) for n in ("n_videos", "n_frames", "n_objects", "n_actions", "n_classes", "cls_id", "type_regular", "type_empty",
                                           "type_extract")]
@@ -172,6 +178,11 @@ SIGNATURES = {
     "stlt_layout_boxes_fwd": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
     "stlt_layout_batch_fwd": (C.c_int, [C.POINTER(LayoutTable), _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _vp]),
+    "stlt_frames_resize_workspace_bytes": (C.c_size_t, [C.c_int64] * 7),
+    "stlt_frames_resize_fwd": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                         C.c_int64, _vp, C.c_size_t, _vp]),
+    "stlt_frames_batch_block_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "stlt_frames_batch_fwd": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "stlt_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "stlt_backbone_forward": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "stlt_forward": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, _vp, _vp, _vp]),

@@ -34,9 +34,15 @@ def shard_bounds(n: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def batch_size(batch: Dict[str, torch.Tensor]) -> int:
+    """Clips in a collated batch: layout and multimodal batches hold `categories`, appearance-only ones (frame_data.DeviceAppearanceDataset)
+    only `video_frames`."""
+    return int((batch["categories"] if "categories" in batch else batch["video_frames"]).shape[0])
+
+
 def shard_batch(batch: Dict[str, torch.Tensor], rank: int, world: int) -> Dict[str, torch.Tensor]:
     """This rank's contiguous slice of every per-clip tensor of a collated batch (non-tensor entries pass through)."""
-    n = batch["categories"].shape[0]
+    n = batch_size(batch)
     lo, hi = shard_bounds(n, rank, world)
     out = {}
     for k, v in batch.items():

@@ -47,10 +47,10 @@ def run_inference(model, batches: Iterable[Dict[str, torch.Tensor]], device, ran
     counts = torch.zeros(3, dtype=torch.int64, device=device)  # top1, top5, n
     kept = []
     for batch in batches:
-        n_total = batch["categories"].shape[0]
+        n_total = D.batch_size(batch)
         mine = D.shard_batch(batch, rank, world)
         mine = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in mine.items()}
-        if mine["categories"].shape[0] > 0:
+        if D.batch_size(mine) > 0:
             logits = forward(mine) if forward is not None else model(mine)["stlt"]
             c = topk_counts(logits, mine["labels"])
             counts[:2] += c

@@ -290,15 +290,22 @@ class DeviceStltDataset:
             self._ring[i] = s
         return s
 
-    def collate(self, indices, real_counts: bool = False) -> Dict[str, object]:
-        """StltCollater(cfg)([StltDataset(cfg)[i] for i in indices]) on the device (see the module docstring)."""
+    def collate(self, indices, real_counts: bool = False, sampled=None) -> Dict[str, object]:
+        """StltCollater(cfg)([StltDataset(cfg)[i] for i in indices]) on the device (see the module docstring).  `sampled`: (frame
+        indices (B, T), sampled counts (B,)) the caller drew already, in sample_indices' form (frame_data.DeviceMultimodalDataset draws
+        them sample by sample, interleaved with the appearance indices); the default draws them here, one call per batch."""
         v = np.asarray([int(i) for i in indices], np.int64)
         B = len(v)
         if B == 0:
             raise L.StltHipError("DeviceStltDataset.collate: empty batch")
         if (v < 0).any() or (v >= len(self)).any():
             raise IndexError(f"video index out of range for {len(self)} videos")
-        frames, counts = self.sample_indices(v)
+        if sampled is None:
+            frames, counts = self.sample_indices(v)
+        else:
+            frames, counts = np.asarray(sampled[0], np.int64), np.asarray(sampled[1], np.int64)
+            if frames.shape != (B, self.T) or counts.shape != (B,):
+                raise L.StltHipError(f"DeviceStltDataset.collate: sampled indices {frames.shape} / counts {counts.shape} for {B} clips of {self.T} frames")
         self.upload()
         lib = L.load()
         dev, T, N = self.device, self.T, self.N

@@ -433,7 +433,7 @@ class Trainer:
         """Run over an iterable of GLOBAL batches, each rank taking its contiguous shard."""
         log = []
         for batch in batches:
-            n = batch["categories"].shape[0]
+            n = D.batch_size(batch)
             if self.world > 1 and n % self.world != 0:
                 # the loss is a batch mean and the gradients are averaged with 1/world: unequal shards would weight clips
                 # unequally, and a rank without clips would leave the others waiting in the all-reduce
@@ -470,7 +470,7 @@ class Trainer:
             with torch.no_grad():
                 for batch in (val_batches(epoch) if callable(val_batches) else val_batches):
                     mine = D.shard_batch(batch, self.rank, self.world)
-                    if mine["categories"].shape[0] == 0:  # more ranks than clips in the last batch
+                    if D.batch_size(mine) == 0:  # more ranks than clips in the last batch
                         continue
                     mine = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in mine.items()}
                     evaluator.process(self.model(mine), mine["labels"])
