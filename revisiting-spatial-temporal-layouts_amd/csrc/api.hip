@@ -319,8 +319,6 @@ int stlt_gather_last_fwd(const float* x, const int64_t* lengths, int64_t B, int6
 
 // ------------------------------------------------------------------ whole path
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct WsLayout {
   size_t x, x1, qkv, ctx, tmp, hh, head, sk, ridx, total;
 };
@@ -330,7 +328,7 @@ static WsLayout ws_layout(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_
   const size_t f = sizeof(float);
   WsLayout w;
   size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+  auto take = [&](size_t bytes) { size_t o = off; off = stlt_align256(off + bytes); return o; };
   w.x = take(tok * d * f);
   w.x1 = take(tok * d * f);
   w.qkv = take(tok * 3 * d * f);
@@ -349,8 +347,6 @@ size_t stlt_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t 
   return ws_layout(B, T, N, d, n_classes < 0 ? 0 : n_classes).total;
 }
 
-#define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
-
 // The residual adds of a post-norm layer ride in the out-proj / FFN2 epilogues and the LayerNorm passes read one tensor
 // instead of two (bit-identical logits: the accumulators start from the bias, the residual is added last).  Round 2 measured
 // it a wash (the residual tile was read inside the exposed epilogue: LayerNorm 3.06 -> 2.00 ms, GEMMs +1.0 ms); with the
@@ -362,37 +358,36 @@ static bool fuse_residual() {
   return on;
 }
 
-// qkv projection + attention core of a layer: ctx (M,d) from x (M,d)
+// in-projection + attention core of a layer: ctx (M,d) from x (M,d).  seg_start / seg_end != null: the M rows are compacted rows cut
+// into variable-length segments (ragged.hip) and the attention is restricted to the row's own segment (no padded keys exist; S, L and
+// kpm are not read); that form never takes the fused launch.
 static int qkv_attention(const stlt_layer_params& lp, int64_t d, int64_t H, const float* x, int64_t M, int64_t S, int64_t L,
-                         const uint8_t* kpm, int causal, int kid, float* qkv, float* ctx, hipStream_t s) {
+                         const uint8_t* kpm, const int* seg_start, const int* seg_end, int causal, int kid, float* qkv, float* ctx,
+                         hipStream_t s) {
   // with the opt-in split-bf16 products on, a temporal in-projection they take is faster as its own launch (+ the attention core)
   // than inside the fused f32-MFMA kernel
-  if (stlt_fused_mhsa_on(causal) && stlt_mhsa_fused_pays(S, L, H, d, causal) && !stlt_split_bf16_takes(M, 3 * d, d, d, d))
+  if (!seg_start && stlt_fused_mhsa_on(causal) && stlt_mhsa_fused_pays(S, L, H, d, causal) && !stlt_split_bf16_takes(M, 3 * d, d, d, d))
     return launch_mhsa_fused(x, lp.in_proj_w, lp.in_proj_b, kpm, S, L, H, d, ctx, s, causal);
-  if (int e = launch_linear(x, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, M, 3 * d, d, STLT_ACT_NONE, s)) return e;
+  TRY(launch_linear(x, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, M, 3 * d, d, STLT_ACT_NONE, s));
+  if (seg_start) return launch_attn_ragged(qkv, seg_start, seg_end, causal, M, H, d / H, ctx, kid, s);
   return launch_attn(qkv, kpm, causal, S, L, H, d / H, ctx, kid, s);
 }
 
-// One post-norm encoder layer (nn.TransformerEncoderLayer as configured at models.py:46-52,118-124) on M
-// compact rows of width d.  `out` may alias `x` (x is last read by the norm1 residual); x1 must not.
-static int encoder_layer(const stlt_layer_params& lp, int64_t d, int64_t H, const float* x, int64_t M, int64_t S,
-                         int64_t L, const uint8_t* kpm, int causal, int kid, float* qkv, float* ctx, float* tmp,
-                         float* x1, float* hh, float* out, hipStream_t s) {
-  TRY(qkv_attention(lp, d, H, x, M, S, L, kpm, causal, kid, qkv, ctx, s));
-  if (fuse_residual()) {  // the residual adds ride in the out-proj / FFN2 epilogues: the norm passes read one tensor
-    TRY(launch_linear_add(ctx, d, lp.out_proj_w, lp.out_proj_b, x, d, tmp, d, M, d, d, s));
-    TRY(launch_add_layernorm(tmp, d, nullptr, 0, lp.norm1_w, lp.norm1_b, 1e-5f, M, d, x1, d, s));
-    TRY(launch_linear(x1, d, lp.lin1_w, lp.lin1_b, hh, 4 * d, M, 4 * d, d, STLT_ACT_GELU, s));
-    TRY(launch_linear_add(hh, 4 * d, lp.lin2_w, lp.lin2_b, x1, d, tmp, d, M, d, 4 * d, s));
-    TRY(launch_add_layernorm(tmp, d, nullptr, 0, lp.norm2_w, lp.norm2_b, 1e-5f, M, d, out, d, s));
-    return 0;
-  }
-  TRY(launch_linear(ctx, d, lp.out_proj_w, lp.out_proj_b, tmp, d, M, d, d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(tmp, d, x, d, lp.norm1_w, lp.norm1_b, 1e-5f, M, d, x1, d, s));
-  TRY(launch_linear(x1, d, lp.lin1_w, lp.lin1_b, hh, 4 * d, M, 4 * d, d, STLT_ACT_GELU, s));
-  TRY(launch_linear(hh, 4 * d, lp.lin2_w, lp.lin2_b, tmp, d, M, d, 4 * d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(tmp, d, x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, M, d, out, d, s));
-  return 0;
+// The part of a post-norm encoder layer (nn.TransformerEncoderLayer as configured at models.py:46-52,118-124) behind the attention
+// core, on M rows of width d: ctx (stride ldctx) holds their attention outputs, x (stride ldx) their layer inputs.  x1 (M,d) receives
+// the post-norm1 rows.  `out` may alias `x` (x is last read by the norm1 residual) or `ctx` (last read by the out-projection); x1 must not.
+static int encoder_tail(const stlt_layer_params& lp, int64_t d, const float* ctx, int64_t ldctx, const float* x, int64_t ldx, int64_t M,
+                        bool fuse, float* tmp, float* x1, float* hh, float* out, hipStream_t s) {
+  TRY(stlt_linear_add_norm(ctx, ldctx, d, lp.out_proj_w, lp.out_proj_b, x, ldx, lp.norm1_w, lp.norm1_b, 1e-5f, M, d, fuse, tmp, x1, s));
+  return stlt_ffn_norm(x1, d, lp.lin1_w, lp.lin1_b, STLT_ACT_GELU, lp.lin2_w, lp.lin2_b, lp.norm2_w, lp.norm2_b, 1e-5f, M, d, fuse, hh, tmp, out, s);
+}
+
+// One post-norm encoder layer on M compact rows of width d, padded layout or (seg_start / seg_end) ragged.  Aliasing as encoder_tail.
+static int encoder_layer(const stlt_layer_params& lp, int64_t d, int64_t H, const float* x, int64_t M, int64_t S, int64_t L,
+                         const uint8_t* kpm, const int* seg_start, const int* seg_end, int causal, int kid, float* qkv, float* ctx,
+                         float* tmp, float* x1, float* hh, float* out, hipStream_t s) {
+  TRY(qkv_attention(lp, d, H, x, M, S, L, kpm, seg_start, seg_end, causal, kid, qkv, ctx, s));
+  return encoder_tail(lp, d, ctx, d, x, d, M, fuse_residual(), tmp, x1, hh, out, s);
 }
 
 static int check_params(const stlt_params* p, const stlt_inputs* in, bool need_head) {
@@ -411,6 +406,35 @@ static int check_params(const stlt_params* p, const stlt_inputs* in, bool need_h
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ the post-norm block, written once (declared in common.h)
+// Every forward of the library ends its half-blocks and its heads here; the callers keep their projections, attention launches, gathers
+// and buffers (and their aliasing contracts).  No profiling scope, no GEMM scratch, no memory of their own.
+
+int stlt_linear_add_norm(const float* x, int64_t ldx, int64_t K, const float* w, const float* b, const float* res, int64_t ldres,
+                         const float* ln_w, const float* ln_b, float eps, int64_t M, int64_t d, bool fuse, float* tmp, float* out,
+                         hipStream_t s) {
+  if (fuse) {  // the residual add rides in the product's epilogue: the norm pass reads one tensor
+    TRY(launch_linear_add(x, ldx, w, b, res, ldres, tmp, d, M, d, K, s));
+    return launch_add_layernorm(tmp, d, nullptr, 0, ln_w, ln_b, eps, M, d, out, d, s);
+  }
+  TRY(launch_linear(x, ldx, w, b, tmp, d, M, d, K, STLT_ACT_NONE, s));
+  return launch_add_layernorm(tmp, d, res, ldres, ln_w, ln_b, eps, M, d, out, d, s);
+}
+
+int stlt_ffn_norm(const float* x, int64_t ldx, const float* w1, const float* b1, int act, const float* w2, const float* b2,
+                  const float* ln_w, const float* ln_b, float eps, int64_t M, int64_t d, bool fuse, float* hh, float* tmp, float* out,
+                  hipStream_t s) {
+  TRY(launch_linear(x, ldx, w1, b1, hh, 4 * d, M, 4 * d, d, act, s));
+  return stlt_linear_add_norm(hh, 4 * d, 4 * d, w2, b2, x, ldx, ln_w, ln_b, eps, M, d, fuse, tmp, out, s);
+}
+
+int stlt_head(const stlt_head_params& h, const float* x, int64_t ldx, int64_t in_dim, int64_t B, int64_t d, int64_t K, float eps,
+              float* h1, float* h2, float* logits, hipStream_t s) {
+  TRY(launch_linear(x, ldx, h.fc1_w, h.fc1_b, h1, d, B, d, in_dim, STLT_ACT_GELU, s));  // gelu(fc1(x))
+  TRY(launch_add_layernorm(h1, d, nullptr, 0, h.ln_w, h.ln_b, eps, B, d, h2, d, s));
+  return launch_linear(h2, d, h.fc2_w, h.fc2_b, logits, K, B, K, d, STLT_ACT_NONE, s);
+}
 
 // Backbone body.  With last_rows != nullptr the final temporal layer only produces the rows the head reads
 // (Stlt.forward, models.py:189-192: out[lengths-1, arange(B)]) into last_rows (B,d): K/V/Q are projected for every
@@ -438,7 +462,7 @@ static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* work
   const bool cls_only = (flags & STLT_FLAG_CLS_ONLY_LAST_SPATIAL) && p->n_spatial > 0 && N > 1;
   const int64_t full_layers = cls_only ? p->n_spatial - 1 : p->n_spatial;
   for (int64_t l = 0; l < full_layers; ++l)
-    TRY(encoder_layer(p->spatial[l], d, H, x, tok, BT, N, in->kpm_boxes, 0, STLT_K_ATTN_SPATIAL, qkv, ctx, tmp, x1, hh, x, s));
+    TRY(encoder_layer(p->spatial[l], d, H, x, tok, BT, N, in->kpm_boxes, nullptr, nullptr, 0, STLT_K_ATTN_SPATIAL, qkv, ctx, tmp, x1, hh, x, s));
   const float* cls_rows = x;
   int64_t cls_stride = N * d;
   if (cls_only) {
@@ -450,11 +474,7 @@ static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* work
     // non-CLS query rows of qkv hold stale scratch; each attention output row depends on its own query row
     // only, and only the CLS rows of ctx are read below.
     TRY(launch_attn(qkv, in->kpm_boxes, 0, BT, N, H, d / H, ctx, STLT_K_ATTN_SPATIAL, s));
-    TRY(launch_linear(ctx, N * d, lp.out_proj_w, lp.out_proj_b, tmp, d, BT, d, d, STLT_ACT_NONE, s));
-    TRY(launch_add_layernorm(tmp, d, x, N * d, lp.norm1_w, lp.norm1_b, 1e-5f, BT, d, x1, d, s));
-    TRY(launch_linear(x1, d, lp.lin1_w, lp.lin1_b, hh, 4 * d, BT, 4 * d, d, STLT_ACT_GELU, s));
-    TRY(launch_linear(hh, 4 * d, lp.lin2_w, lp.lin2_b, tmp, d, BT, d, 4 * d, STLT_ACT_NONE, s));
-    TRY(launch_add_layernorm(tmp, d, x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, BT, d, ctx, d, s));
+    TRY(encoder_tail(lp, d, ctx, N * d, x, N * d, BT, false, tmp, x1, hh, ctx, s));  // compact CLS rows land in ctx's first BT rows
     cls_rows = ctx;
     cls_stride = d;
   }
@@ -469,7 +489,7 @@ static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* work
   const int64_t n_full = last_rows ? p->n_temporal - 1 : p->n_temporal;
   for (int64_t l = 0; l < n_full; ++l) {
     float* dst = (l == p->n_temporal - 1) ? out_btd : tbuf;
-    TRY(encoder_layer(p->temporal[l], d, H, tbuf, BT, B, T, in->kpm_frames, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, tmp,
+    TRY(encoder_layer(p->temporal[l], d, H, tbuf, BT, B, T, in->kpm_frames, nullptr, nullptr, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, tmp,
                       x, hh, dst, s));
   }
   if (last_rows) {
@@ -477,38 +497,11 @@ static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* work
     float* g_ctx = x;                      // (B,d) gathered attention rows
     float* g_res = x + (size_t)B * d;      // (B,d) gathered layer-input rows (residual)
     float* g_x1 = hh + (size_t)B * 4 * d;  // (B,d) post-norm1, behind the (B,4d) FFN hidden (T > 1 => hh holds >= 2*B*4d)
-    TRY(qkv_attention(lp, d, H, tbuf, BT, B, T, in->kpm_frames, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, s));
+    TRY(qkv_attention(lp, d, H, tbuf, BT, B, T, in->kpm_frames, nullptr, nullptr, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, s));
     TRY(launch_gather_last(ctx, in->lengths, B, T, d, g_ctx, s));
     TRY(launch_gather_last(tbuf, in->lengths, B, T, d, g_res, s));
-    TRY(launch_linear(g_ctx, d, lp.out_proj_w, lp.out_proj_b, tmp, d, B, d, d, STLT_ACT_NONE, s));
-    TRY(launch_add_layernorm(tmp, d, g_res, d, lp.norm1_w, lp.norm1_b, 1e-5f, B, d, g_x1, d, s));
-    TRY(launch_linear(g_x1, d, lp.lin1_w, lp.lin1_b, hh, 4 * d, B, 4 * d, d, STLT_ACT_GELU, s));
-    TRY(launch_linear(hh, 4 * d, lp.lin2_w, lp.lin2_b, tmp, d, B, d, 4 * d, STLT_ACT_NONE, s));
-    TRY(launch_add_layernorm(tmp, d, g_x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, B, d, last_rows, d, s));
+    TRY(encoder_tail(lp, d, g_ctx, d, g_res, d, B, false, tmp, g_x1, hh, last_rows, s));
   }
-  return 0;
-}
-
-// One encoder layer over M compacted rows cut into variable-length segments (ragged.hip): same arithmetic as
-// encoder_layer, attention restricted to the row's own segment (no padded keys exist).
-static int encoder_layer_ragged(const stlt_layer_params& lp, int64_t d, int64_t H, const float* x, int64_t M, const int* seg_start,
-                                const int* seg_end, int causal, int kid, float* qkv, float* ctx, float* tmp, float* x1,
-                                float* hh, float* out, hipStream_t s) {
-  TRY(launch_linear(x, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, M, 3 * d, d, STLT_ACT_NONE, s));
-  TRY(launch_attn_ragged(qkv, seg_start, seg_end, causal, M, H, d / H, ctx, kid, s));
-  if (fuse_residual()) {  // the residual adds ride in the out-proj / FFN2 epilogues: the norm passes read one tensor
-    TRY(launch_linear_add(ctx, d, lp.out_proj_w, lp.out_proj_b, x, d, tmp, d, M, d, d, s));
-    TRY(launch_add_layernorm(tmp, d, nullptr, 0, lp.norm1_w, lp.norm1_b, 1e-5f, M, d, x1, d, s));
-    TRY(launch_linear(x1, d, lp.lin1_w, lp.lin1_b, hh, 4 * d, M, 4 * d, d, STLT_ACT_GELU, s));
-    TRY(launch_linear_add(hh, 4 * d, lp.lin2_w, lp.lin2_b, x1, d, tmp, d, M, d, 4 * d, s));
-    TRY(launch_add_layernorm(tmp, d, nullptr, 0, lp.norm2_w, lp.norm2_b, 1e-5f, M, d, out, d, s));
-    return 0;
-  }
-  TRY(launch_linear(ctx, d, lp.out_proj_w, lp.out_proj_b, tmp, d, M, d, d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(tmp, d, x, d, lp.norm1_w, lp.norm1_b, 1e-5f, M, d, x1, d, s));
-  TRY(launch_linear(x1, d, lp.lin1_w, lp.lin1_b, hh, 4 * d, M, 4 * d, d, STLT_ACT_GELU, s));
-  TRY(launch_linear(hh, 4 * d, lp.lin2_w, lp.lin2_b, tmp, d, M, d, 4 * d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(tmp, d, x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, M, d, out, d, s));
   return 0;
 }
 
@@ -518,12 +511,7 @@ static int encoder_tail_rows(const stlt_layer_params& lp, int64_t d, const float
                              float* g_ctx, float* g_res, float* g_x1, float* tmp, float* hh, float* out, hipStream_t s) {
   TRY(launch_gather_rows(ctx, d, rows, n, d, g_ctx, s));
   TRY(launch_gather_rows(x, d, rows, n, d, g_res, s));
-  TRY(launch_linear(g_ctx, d, lp.out_proj_w, lp.out_proj_b, tmp, d, n, d, d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(tmp, d, g_res, d, lp.norm1_w, lp.norm1_b, 1e-5f, n, d, g_x1, d, s));
-  TRY(launch_linear(g_x1, d, lp.lin1_w, lp.lin1_b, hh, 4 * d, n, 4 * d, d, STLT_ACT_GELU, s));
-  TRY(launch_linear(hh, 4 * d, lp.lin2_w, lp.lin2_b, tmp, d, n, d, 4 * d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(tmp, d, g_x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, n, d, out, d, s));
-  return 0;
+  return encoder_tail(lp, d, g_ctx, d, g_res, d, n, false, tmp, g_x1, hh, out, s);
 }
 
 // Stlt.forward up to the rows the head reads, computed on the real tokens / frames only (STLT_FLAG_SKIP_PADDING).
@@ -548,30 +536,17 @@ static int forward_ragged(const stlt_params* p, const stlt_inputs* in, void* wor
   const RaggedIndex ix = ragged_index_carve(base + w.ridx, B, T, N);
   TRY(launch_ragged_index(in->kpm_boxes, in->kpm_frames, in->lengths, B, T, N, ix, s));
   int64_t Ms = 0, Mf = 0;
-  const bool host_counts = in->n_real_tokens > 0 || in->n_real_frames > 0;  // the caller knows the two row counts: no read-back, no synchronisation
-  if (host_counts) {
-    Ms = in->n_real_tokens; Mf = in->n_real_frames;
-    TRY(launch_ragged_host_counts(ix, Ms, Mf, B * T * N, B * T, s));
-  } else {
-    int counts[4] = {0, 0, 0, 0};
-    if (hipError_t e = hipMemcpyAsync(counts, ix.counts, sizeof(counts), hipMemcpyDeviceToHost, s); e != hipSuccess)
-      return stlt_set_error((int)e, "skip-padding: count read-back: %s", hipGetErrorString(e));
-    if (hipError_t e = hipStreamSynchronize(s); e != hipSuccess)
-      return stlt_set_error((int)e, "skip-padding: count read-back: %s", hipGetErrorString(e));
-    if (counts[2] != 0)
-      return stlt_set_error(STLT_EINVAL, "skip-padding needs collater-shaped masks: slot 0 of every real frame unmasked and frame lengths-1 real (datasets.py:247-288)");
-    Ms = counts[0]; Mf = counts[1];
-  }
+  bool host_counts = false;  // the caller knows the two row counts: no read-back, no synchronisation
+  TRY(read_ragged_counts(ix, in, true, Ms, Mf, &host_counts, s));
   TRY(launch_embed(in->categories, in->boxes, in->scores, p->cat_emb, p->n_categories, p->box_w, p->box_b, p->score_w,
                    p->score_b, p->emb_ln_w, p->emb_ln_b, p->ln_eps, Ms, d, x, s, nullptr, StltDrop{0u, 1.0f, 0ull}, ix.t_orig));
   // spatial transformer: segments = frames; after it only each frame's CLS row is read (models.py:79)
   for (int64_t l = 0; l + 1 < p->n_spatial; ++l)
-    TRY(encoder_layer_ragged(p->spatial[l], d, H, x, Ms, ix.t_seg_start, ix.t_seg_end, 0, STLT_K_ATTN_SPATIAL, qkv, ctx, tmp, x1, hh, x, s));
+    TRY(encoder_layer(p->spatial[l], d, H, x, Ms, 0, 0, nullptr, ix.t_seg_start, ix.t_seg_end, 0, STLT_K_ATTN_SPATIAL, qkv, ctx, tmp, x1, hh, x, s));
   float* cls = ctx;  // (Mf, d)
   if (p->n_spatial > 0) {
     const stlt_layer_params& lp = p->spatial[p->n_spatial - 1];
-    TRY(launch_linear(x, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, Ms, 3 * d, d, STLT_ACT_NONE, s));
-    TRY(launch_attn_ragged(qkv, ix.t_seg_start, ix.t_seg_end, 0, Ms, H, d / H, ctx, STLT_K_ATTN_SPATIAL, s));
+    TRY(qkv_attention(lp, d, H, x, Ms, 0, 0, nullptr, ix.t_seg_start, ix.t_seg_end, 0, STLT_K_ATTN_SPATIAL, qkv, ctx, s));
     // qkv is dead once ctx exists: it holds the gathered rows; the layer output lands in ctx's first Mf rows
     // (ctx rows are read by the gather before anything is written back)
     TRY(encoder_tail_rows(lp, d, ctx, x, ix.f_cls_row, Mf, qkv, qkv + (size_t)Mf * d, x1, tmp, hh, qkv + (size_t)2 * Mf * d, s));
@@ -586,15 +561,14 @@ static int forward_ragged(const stlt_params* p, const stlt_inputs* in, void* wor
   // temporal transformer: segments = clips, causal
   const int64_t tp_full = out_btd ? p->n_temporal : p->n_temporal - 1;
   for (int64_t l = 0; l < tp_full; ++l)
-    TRY(encoder_layer_ragged(p->temporal[l], d, H, tbuf, Mf, ix.f_seg_start, ix.f_seg_end, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, tmp, x, hh, tbuf, s));
+    TRY(encoder_layer(p->temporal[l], d, H, tbuf, Mf, 0, 0, nullptr, ix.f_seg_start, ix.f_seg_end, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, tmp, x, hh, tbuf, s));
   if (out_btd) {
     TRY(launch_scatter_rows(tbuf, ix.f_orig, Mf, d, out_btd, B * T, s, host_counts ? ix.counts + 1 : nullptr));
     return host_counts ? launch_ragged_poison(ix, Ms, Mf, true, out_btd, B * T * d, s) : 0;
   }
   if (p->n_temporal > 0) {
     const stlt_layer_params& lp = p->temporal[p->n_temporal - 1];
-    TRY(launch_linear(tbuf, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, Mf, 3 * d, d, STLT_ACT_NONE, s));
-    TRY(launch_attn_ragged(qkv, ix.f_seg_start, ix.f_seg_end, 1, Mf, H, d / H, ctx, STLT_K_ATTN_TEMPORAL, s));
+    TRY(qkv_attention(lp, d, H, tbuf, Mf, 0, 0, nullptr, ix.f_seg_start, ix.f_seg_end, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, s));
     TRY(encoder_tail_rows(lp, d, ctx, tbuf, ix.last_row, B, x, qkv, qkv + (size_t)B * d, tmp, hh, h0, s));  // qkv is dead once ctx exists
   } else {
     TRY(launch_gather_rows(tbuf, d, ix.last_row, B, d, h0, s));
@@ -604,7 +578,7 @@ static int forward_ragged(const stlt_params* p, const stlt_inputs* in, void* wor
   return host_counts ? launch_ragged_poison(ix, Ms, Mf, true, h0, B * d, s) : 0;
 }
 
-// exported to caf.hip (same library, C++ linkage)
+// for caf.hip (declared in common.h)
 int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags,
                          float* out_btd, hipStream_t s) {
   TRY(check_params(p, in, false));
@@ -655,10 +629,8 @@ int stlt_forward(const stlt_params* p, const stlt_inputs* in, void* workspace, s
     TRY(backbone_impl(p, in, workspace, workspace_bytes, flags, bb_out, nullptr, s));
     TRY(launch_gather_last(bb_out, in->lengths, B, T, d, h0, s));                                 // models.py:189-192
   }
-  TRY(launch_linear(h0, d, p->fc1_w, p->fc1_b, h1, d, B, d, d, STLT_ACT_GELU, s));                // gelu(fc1(h))
-  TRY(launch_add_layernorm(h1, d, nullptr, 0, p->head_ln_w, p->head_ln_b, p->ln_eps, B, d, h2, d, s));
-  TRY(launch_linear(h2, d, p->fc2_w, p->fc2_b, logits, p->n_classes, B, p->n_classes, d, STLT_ACT_NONE, s));
-  return 0;
+  const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
+  return stlt_head(head, h0, d, d, B, d, p->n_classes, p->ln_eps, h1, h2, logits, s);
 }
 
 }  // extern "C"

@@ -10,9 +10,6 @@
 
 namespace {
 
-#define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 // A block backward's device memory comes in two buffers.  `keep` holds what the block's QUEUED weight-gradient products read (their dY
 // operands): while a context defers them (stlt_ctx_dw_defer) the caller keeps this buffer — a few rows x d floats — alive until the flush.
 // `work` holds everything that is dead when the call returns its launches (stream-K partial tiles, the attention context gradient, reduction
@@ -39,7 +36,7 @@ BlockScratch block_scratch(char* keep, char* work, int64_t rows, int64_t d, int 
   const size_t f = sizeof(float);
   size_t off = 0;
   char* base = work;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off = align256(off + bytes); return p; };
+  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off = stlt_align256(off + bytes); return p; };
   b.lin_bytes = stlt_linear_bwd_scratch_bytes(4 * d);
   b.lin = take(b.lin_bytes);
   b.dctx = (float*)take(kind == BLOCK_ATTN ? (size_t)rows * d * f : 0);

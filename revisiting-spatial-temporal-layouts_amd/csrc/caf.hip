@@ -3,14 +3,7 @@
 // form, residual+LayerNorm, gather) plus three tiny data-movement kernels.
 #include "common.h"
 
-int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags,
-                         float* out_btd, hipStream_t s);
-size_t stlt_workspace_bytes_public(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes);
-
 namespace {
-
-#define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // (B, C, S) feature map -> token-major (B*S, C)
 __global__ __launch_bounds__(256) void feat_transpose_kernel(const float* __restrict__ f, int C, int S, float* __restrict__ out) {
@@ -66,7 +59,7 @@ CafWs caf_ws(int64_t B, int64_t T, int64_t N, int64_t d, int64_t C, int64_t S, i
   const size_t f = sizeof(float);
   const size_t rows = (size_t)B * (T > S + 1 ? T : S + 1);
   size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
+  auto take = [&](size_t bytes) { size_t o = off; off = stlt_align256(off + bytes); return o; };
   w.bb = take(stlt_workspace_bytes_public(B, T, N, d, K));
   w.lh = take((size_t)B * T * d * f);
   w.ah = take((size_t)B * (S + 1) * d * f);
@@ -97,8 +90,7 @@ int self_attn_block(const stlt_attn_block_params& p, int64_t d, int64_t H, float
   const int64_t M = S * L;
   TRY(launch_linear(x, d, p.in_proj_w, p.in_proj_b, b.q, 3 * d, M, 3 * d, d, STLT_ACT_NONE, s));
   TRY(launch_attn(b.q, kpm ? kpm : b.zero, causal, S, L, H, d / H, b.ctx, causal ? STLT_K_ATTN_TEMPORAL : STLT_K_ATTN_SPATIAL, s));
-  TRY(launch_linear(b.ctx, d, p.out_proj_w, p.out_proj_b, b.tmp, d, M, d, d, STLT_ACT_NONE, s));
-  return launch_add_layernorm(b.tmp, d, x, d, p.ln_w, p.ln_b, eps, M, d, out, d, s);
+  return stlt_linear_add_norm(b.ctx, d, d, p.out_proj_w, p.out_proj_b, x, d, p.ln_w, p.ln_b, eps, M, d, false, b.tmp, out, s);
 }
 
 // CrossAttentionLayer (models.py:362-382): out = LN(MHA(x, ctx, ctx, key_padding_mask) + x)
@@ -107,15 +99,7 @@ int cross_attn_block(const stlt_attn_block_params& p, int64_t d, int64_t H, floa
   TRY(launch_linear(x, d, p.in_proj_w, p.in_proj_b, b.q, d, S * Lq, d, d, STLT_ACT_NONE, s));                      // q rows of in_proj
   TRY(launch_linear(c, d, p.in_proj_w + d * d, p.in_proj_b + d, b.kv, 2 * d, S * Lk, 2 * d, d, STLT_ACT_NONE, s));  // k,v rows
   TRY(launch_attn_general(b.q, d, b.kv, b.kv + d, 2 * d, kpm_k ? kpm_k : b.zero, 0, S, Lq, Lk, H, d / H, b.ctx, STLT_K_ATTN_SPATIAL, s));
-  TRY(launch_linear(b.ctx, d, p.out_proj_w, p.out_proj_b, b.tmp, d, S * Lq, d, d, STLT_ACT_NONE, s));
-  return launch_add_layernorm(b.tmp, d, x, d, p.ln_w, p.ln_b, eps, S * Lq, d, out, d, s);
-}
-
-int head_block(const stlt_head_params& h, const float* x, int64_t ldx, int64_t in_dim, int64_t B, int64_t d, int64_t K, float eps,
-               float* h1, float* h2, float* logits, hipStream_t s) {
-  TRY(launch_linear(x, ldx, h.fc1_w, h.fc1_b, h1, d, B, d, in_dim, STLT_ACT_GELU, s));
-  TRY(launch_add_layernorm(h1, d, nullptr, 0, h.ln_w, h.ln_b, eps, B, d, h2, d, s));
-  return launch_linear(h2, d, h.fc2_w, h.fc2_b, logits, K, B, K, d, STLT_ACT_NONE, s);
+  return stlt_linear_add_norm(b.ctx, d, d, p.out_proj_w, p.out_proj_b, x, d, p.ln_w, p.ln_b, eps, S * Lq, d, false, b.tmp, out, s);
 }
 
 }  // namespace
@@ -176,17 +160,14 @@ extern "C" int stlt_caf_forward_flags(const stlt_caf_params* p, const stlt_input
     const stlt_layer_params& e = p->app_layers[l];
     TRY(launch_linear(Ah, d, e.in_proj_w, e.in_proj_b, b.q, 3 * d, MA, 3 * d, d, STLT_ACT_NONE, s));
     TRY(launch_attn(b.q, b.zero, 0, B, LA, H, d / H, b.ctx, STLT_K_ATTN_SPATIAL, s));
-    TRY(launch_linear(b.ctx, d, e.out_proj_w, e.out_proj_b, b.tmp, d, MA, d, d, STLT_ACT_NONE, s));
-    TRY(launch_add_layernorm(b.tmp, d, Ah, d, e.norm1_w, e.norm1_b, 1e-5f, MA, d, aa, d, s));
-    TRY(launch_linear(aa, d, e.lin1_w, e.lin1_b, b.hh, 4 * d, MA, 4 * d, d, STLT_ACT_RELU, s));
-    TRY(launch_linear(b.hh, 4 * d, e.lin2_w, e.lin2_b, b.tmp, d, MA, d, 4 * d, STLT_ACT_NONE, s));
-    TRY(launch_add_layernorm(b.tmp, d, aa, d, e.norm2_w, e.norm2_b, 1e-5f, MA, d, Ah, d, s));
+    TRY(stlt_linear_add_norm(b.ctx, d, d, e.out_proj_w, e.out_proj_b, Ah, d, e.norm1_w, e.norm1_b, 1e-5f, MA, d, false, b.tmp, aa, s));
+    TRY(stlt_ffn_norm(aa, d, e.lin1_w, e.lin1_b, STLT_ACT_RELU, e.lin2_w, e.lin2_b, e.norm2_w, e.norm2_b, 1e-5f, MA, d, false, b.hh, b.tmp, Ah, s));
   }
   // ---- unimodal states before fusion (models.py:459-460) -> CACNF heads
   if (cacnf) {
     TRY(launch_gather_last(Lh, in->lengths, B, T, d, F(w.hl), s));
-    TRY(head_block(p->layout_head, F(w.hl), d, d, B, d, K, eps, F(w.h1), F(w.h2), logits_stlt, s));
-    TRY(head_block(p->appearance_head, Ah, LA * d, d, B, d, K, eps, F(w.h1), F(w.h2), logits_resnet3d, s));  // rows (b, token 0)
+    TRY(stlt_head(p->layout_head, F(w.hl), d, d, B, d, K, eps, F(w.h1), F(w.h2), logits_stlt, s));
+    TRY(stlt_head(p->appearance_head, Ah, LA * d, d, B, d, K, eps, F(w.h1), F(w.h2), logits_resnet3d, s));  // rows (b, token 0)
   }
   // ---- multimodal fusion (models.py:462-468, 403-431)
   for (int64_t l = 0; l < p->n_fusion; ++l) {
@@ -196,9 +177,8 @@ extern "C" int stlt_caf_forward_flags(const stlt_caf_params* p, const stlt_input
     TRY(self_attn_block(m.layout_attn, d, H, eps, la, B, T, in->kpm_frames, 1, b, Lh, s));           // Lh = layout self-attn
     TRY(self_attn_block(m.appearance_attn, d, H, eps, aa, B, LA, nullptr, 0, b, Ah, s));             // Ah = appearance self-attn
     // layout_ffn: LN(lin2(gelu(lin1(x))) + x)
-    TRY(launch_linear(Lh, d, m.layout_ffn.lin1_w, m.layout_ffn.lin1_b, b.hh, 4 * d, ML, 4 * d, d, STLT_ACT_GELU, s));
-    TRY(launch_linear(b.hh, 4 * d, m.layout_ffn.lin2_w, m.layout_ffn.lin2_b, b.tmp, d, ML, d, 4 * d, STLT_ACT_NONE, s));
-    TRY(launch_add_layernorm(b.tmp, d, Lh, d, m.layout_ffn.ln_w, m.layout_ffn.ln_b, eps, ML, d, la, d, s));
+    const stlt_ffn_block_params& f = m.layout_ffn;
+    TRY(stlt_ffn_norm(Lh, d, f.lin1_w, f.lin1_b, STLT_ACT_GELU, f.lin2_w, f.lin2_b, f.ln_w, f.ln_b, eps, ML, d, false, b.hh, b.tmp, la, s));
     // appearance_ffn is a SelfAttentionLayer in the reference (models.py:401)
     TRY(self_attn_block(m.appearance_ffn, d, H, eps, Ah, B, LA, nullptr, 0, b, aa, s));
     float* t1 = Lh; Lh = la; la = t1;   // outputs of this module feed the next one
@@ -208,7 +188,7 @@ extern "C" int stlt_caf_forward_flags(const stlt_caf_params* p, const stlt_input
   TRY(launch_gather_last(Lh, in->lengths, B, T, d, F(w.hl), s));
   hipLaunchKernelGGL(concat2_kernel, dim3((unsigned)B), dim3(256), 0, s, F(w.hl), d, Ah, LA * d, (int)d, F(w.fused));
   TRY(stlt_check_launch("concat2_kernel"));
-  TRY(head_block(p->fusion_head, F(w.fused), 2 * d, 2 * d, B, d, K, eps, F(w.h1), F(w.h2), logits_caf, s));
+  TRY(stlt_head(p->fusion_head, F(w.fused), 2 * d, 2 * d, B, d, K, eps, F(w.h1), F(w.h2), logits_caf, s));
   if (cacnf) {
     hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, s, logits_stlt, logits_resnet3d, logits_caf,
                        logits_ensemble, B * K);

@@ -13,6 +13,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // error plumbing (api.hip)
 int stlt_set_error(int code, const char* fmt, ...);
 int stlt_check_launch(const char* what);
+#define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
+constexpr size_t stlt_align256(size_t v) { return (v + 255) / 256 * 256; }  // workspace / tape / scratch carving: every buffer starts on 256 bytes
 
 // Per-device state (api.hip).  Nothing in the library caches a property of "the first device it saw": CU counts,
 // occupancy answers and one-time function attributes are kept per HIP device, looked up by the device that is current
@@ -331,6 +333,24 @@ int launch_attn_general(const float* q, int64_t ldq, const float* k, const float
 int launch_add_layernorm(const float* x, int64_t ldx, const float* res, int64_t ldres, const float* w, const float* b,
                          float eps, int64_t M, int64_t d, float* out, int64_t ldout, hipStream_t s, StltDrop dr = StltDrop{0u, 1.0f, 0ull},
                          uint32_t site = 0, const int* drop_rows = nullptr);  // drop_rows: row -> row index used for the dropout mask
+// The post-norm block of every native forward, written once (api.hip).  Plain launch sequences on the caller's buffers: they own no
+// memory (the aliasing contracts are the callers'), open no StltProfScope and lend no GEMM scratch.  `fuse`: the residual rides in the
+// product's epilogue (launch_linear_add) and the LayerNorm reads one tensor; else it is added in the LayerNorm pass.  tmp: (M,d).
+// out (M,d) = LN_eps(res + x·Wᵀ + b), W (d,K): the out-projection behind an attention core (K = d), the second Linear of an FFN (K = 4d)
+int stlt_linear_add_norm(const float* x, int64_t ldx, int64_t K, const float* w, const float* b, const float* res, int64_t ldres,
+                         const float* ln_w, const float* ln_b, float eps, int64_t M, int64_t d, bool fuse, float* tmp, float* out,
+                         hipStream_t s);
+// out (M,d) = LN_eps(x + act(x·W1ᵀ + b1)·W2ᵀ + b2), act = STLT_ACT_GELU or STLT_ACT_RELU; hh: (M,4d)
+int stlt_ffn_norm(const float* x, int64_t ldx, const float* w1, const float* b1, int act, const float* w2, const float* b2,
+                  const float* ln_w, const float* ln_b, float eps, int64_t M, int64_t d, bool fuse, float* hh, float* tmp, float* out,
+                  hipStream_t s);
+// logits (B,K) = fc2(LN_eps(gelu(fc1(x)))), x: B rows of in_dim values, stride ldx (ClassificationHead: in_dim = d; FusionHead: 2d); h1, h2: (B,d)
+int stlt_head(const stlt_head_params& h, const float* x, int64_t ldx, int64_t in_dim, int64_t B, int64_t d, int64_t K, float eps,
+              float* h1, float* h2, float* logits, hipStream_t s);
+// api.hip, for the fusion models (caf.hip): the StltBackbone forward into out_btd (B,T,d) with its argument checks, and its workspace size
+int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags,
+                         float* out_btd, hipStream_t s);
+size_t stlt_workspace_bytes_public(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes);
 int launch_frames_embed(const float* spatial, int64_t row_stride, const int64_t* frame_types, const float* pos_table,
                         const float* type_table, const float* ln_w, const float* ln_b, float eps, int64_t B, int64_t T,
                         int64_t d, float* out, hipStream_t s, float* pre_out = nullptr, StltDrop dr = StltDrop{0u, 1.0f, 0ull},
@@ -361,6 +381,9 @@ int launch_gather_rows(const float* src, int64_t ld, const int* rows, int64_t n,
 // the caller's row counts instead of a read-back: index entries up to the caller's counts made safe, and the result poisoned (NaN) when they are not the index's
 int launch_ragged_host_counts(const RaggedIndex& idx, int64_t n_tok, int64_t n_frm, int64_t max_tok, int64_t max_frm, hipStream_t s);
 int launch_ragged_poison(const RaggedIndex& idx, int64_t n_tok, int64_t n_frm, bool allow_more, float* out, int64_t n, hipStream_t s);
+// Row counts of the ragged index: the caller's (stlt_inputs.n_real_tokens / n_real_frames, no synchronisation; `pad`: the forward makes the
+// index safe for them, the backward finds it so), else one device->host copy + stream synchronisation.
+int read_ragged_counts(const RaggedIndex& ix, const stlt_inputs* in, bool pad, int64_t& Ms, int64_t& Mf, bool* from_host, hipStream_t s);
 // hidden size / head count a model or block may have: any head dim up to 256 (64: the MFMA kernels; others: attn_any.hip); rows are
 // moved 16 bytes at a time (hidden sizes that are not multiples of 32 run their products on gemm_any.hip)
 inline bool stlt_heads_ok(int64_t d, int64_t H) { return d > 0 && H > 0 && d % H == 0 && d / H <= 256 && d % 4 == 0; }

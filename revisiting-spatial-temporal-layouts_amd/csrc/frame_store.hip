@@ -60,8 +60,6 @@ __global__ __launch_bounds__(FS_THREADS) void fs_pass_kernel(const uint8_t* __re
   }
 }
 
-constexpr size_t fs_align(size_t n) { return (n + 255) & ~size_t(255); }
-
 struct FsResizeLayout {
   size_t tab_x, tab_y, mid, total;
 };
@@ -69,9 +67,9 @@ struct FsResizeLayout {
 FsResizeLayout fs_resize_layout(int64_t n, int64_t h, int64_t w, int64_t rh, int64_t rw, int64_t ksize_x, int64_t ksize_y) {
   FsResizeLayout l;
   l.tab_x = 0;
-  l.tab_y = l.tab_x + fs_align(w != rw ? (size_t)(rw * (2 + ksize_x)) * sizeof(int32_t) : 0);
-  l.mid = l.tab_y + fs_align(h != rh ? (size_t)(rh * (2 + ksize_y)) * sizeof(int32_t) : 0);
-  l.total = l.mid + fs_align(w != rw && h != rh ? (size_t)(n * h * rw * 3) : 0);
+  l.tab_y = l.tab_x + stlt_align256(w != rw ? (size_t)(rw * (2 + ksize_x)) * sizeof(int32_t) : 0);
+  l.mid = l.tab_y + stlt_align256(h != rh ? (size_t)(rh * (2 + ksize_y)) * sizeof(int32_t) : 0);
+  l.total = l.mid + stlt_align256(w != rw && h != rh ? (size_t)(n * h * rw * 3) : 0);
   return l;
 }
 

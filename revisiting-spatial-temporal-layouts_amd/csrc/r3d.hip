@@ -414,7 +414,6 @@ TrunkDims trunk_dims(int64_t B, int64_t T, int64_t H, int64_t W) {
   return d;
 }
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
 }  // namespace
 
@@ -498,8 +497,8 @@ size_t stlt_r3d_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
   const TrunkDims d = trunk_dims(B, T, H, W);
   if (!d.ok) return 0;
   const int64_t f = sizeof(float);
-  return (size_t)(align256(B * T * H * W * 4 * f) + 3 * align256(d.act_elems * f) + align256(std::max(d.stem_elems, 2 * d.act_elems) * f) +
-                  align256(d.part_bytes));
+  return (size_t)(stlt_align256(B * T * H * W * 4 * f) + 3 * stlt_align256(d.act_elems * f) + stlt_align256(std::max(d.stem_elems, 2 * d.act_elems) * f) +
+                  stlt_align256(d.part_bytes));
 }
 
 int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
@@ -520,13 +519,13 @@ int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, in
   hipStream_t s = (hipStream_t)stream;
   const int64_t f = sizeof(float);
   char* base = (char*)workspace;
-  float* xin = (float*)base; base += align256(B * T * H * W * 4 * f);
-  float* X0 = (float*)base; base += align256(d.act_elems * f);
-  float* X1 = (float*)base; base += align256(d.act_elems * f);
-  float* DS = (float*)base; base += align256(d.act_elems * f);
+  float* xin = (float*)base; base += stlt_align256(B * T * H * W * 4 * f);
+  float* X0 = (float*)base; base += stlt_align256(d.act_elems * f);
+  float* X1 = (float*)base; base += stlt_align256(d.act_elems * f);
+  float* DS = (float*)base; base += stlt_align256(d.act_elems * f);
   float* T1 = (float*)base;
   float* T2 = T1 + d.act_elems;
-  base += align256(std::max(d.stem_elems, 2 * d.act_elems) * f);
+  base += stlt_align256(std::max(d.stem_elems, 2 * d.act_elems) * f);
   float* part = (float*)base;
   const float eps = p->bn_eps;
 
@@ -1093,7 +1092,7 @@ bool trunk_plan(int64_t B, int64_t T, int64_t H, int64_t W, TrunkPlan* P) {
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || T > 4096 || H > 4096 || W > 4096 || B > (1 << 20)) return false;
   const int64_t f = sizeof(float);
   int64_t off = 0;
-  auto take = [&](int64_t bytes) { const int64_t o = off; off += align256(bytes); return o; };
+  auto take = [&](int64_t bytes) { const int64_t o = off; off += stlt_align256(bytes); return o; };
   auto geom = [&](int i, int64_t t, int64_t h, int64_t w, int64_t cin, int64_t cout, int k, int st, int sp, int pad) -> bool {
     const stlt_conv3d_desc d{B, t, h, w, cin, cout, k, k, k, st, sp, sp, pad, pad, pad};
     return check_desc(&d, &p.g[i]) == 0;
@@ -1152,7 +1151,7 @@ int check_r3d_params(const stlt_r3d_params* p, const char* who) {
 
 int64_t r3d_bwd_ws_bytes(const TrunkPlan& p) {
   const int64_t f = sizeof(float);
-  return 4 * align256(p.act_elems * f) + align256(p.stem_elems * f) + align256(p.bwd_part_bytes);
+  return 4 * stlt_align256(p.act_elems * f) + stlt_align256(p.stem_elems * f) + stlt_align256(p.bwd_part_bytes);
 }
 
 }  // namespace
@@ -1298,9 +1297,9 @@ int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t
   const TrunkDims d = trunk_dims(B, T, H, W);
   // the forward's workspace layout: [xin][X0][X1][DS][T1 | T2][part]; only DS and part are used here
   char* base = (char*)workspace;
-  base += align256(B * T * H * W * 4 * (int64_t)sizeof(float)) + 2 * align256(d.act_elems * (int64_t)sizeof(float));
+  base += stlt_align256(B * T * H * W * 4 * (int64_t)sizeof(float)) + 2 * stlt_align256(d.act_elems * (int64_t)sizeof(float));
   float* DS = (float*)base;
-  base += align256(d.act_elems * (int64_t)sizeof(float)) + align256(std::max(d.stem_elems, 2 * d.act_elems) * (int64_t)sizeof(float));
+  base += stlt_align256(d.act_elems * (int64_t)sizeof(float)) + stlt_align256(std::max(d.stem_elems, 2 * d.act_elems) * (int64_t)sizeof(float));
   float* part = (float*)base;
   const float eps = p->bn_eps;
   auto conv = [&](int i, const float* x, const float* res, int relu, float* y) -> int {
@@ -1362,11 +1361,11 @@ int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, con
   const char* tp = (const char*)tape;
   const int64_t f = sizeof(float);
   char* base = (char*)workspace;
-  float* G3 = (float*)base; base += align256(P.act_elems * f);   // masked pre-ReLU gradient at the block's output
-  float* G2 = (float*)base; base += align256(P.act_elems * f);
-  float* G1 = (float*)base; base += align256(P.act_elems * f);
-  float* GX = (float*)base; base += align256(P.act_elems * f);   // ... at its input (the previous block's G3)
-  float* GS = (float*)base; base += align256(P.stem_elems * f);  // at the stem's output
+  float* G3 = (float*)base; base += stlt_align256(P.act_elems * f);   // masked pre-ReLU gradient at the block's output
+  float* G2 = (float*)base; base += stlt_align256(P.act_elems * f);
+  float* G1 = (float*)base; base += stlt_align256(P.act_elems * f);
+  float* GX = (float*)base; base += stlt_align256(P.act_elems * f);   // ... at its input (the previous block's G3)
+  float* GS = (float*)base; base += stlt_align256(P.stem_elems * f);  // at the stem's output
   float* part = (float*)base;
   const float eps = p->bn_eps;
   auto wgrad = [&](int i, const float* x, const float* g) {

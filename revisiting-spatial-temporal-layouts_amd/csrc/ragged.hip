@@ -195,6 +195,28 @@ int launch_ragged_host_counts(const RaggedIndex& ix, int64_t n_tok, int64_t n_fr
   hipLaunchKernelGGL(ragged_host_counts_kernel, dim3((unsigned)((n_tok + 255) / 256)), dim3(256), 0, s, ix, (int)n_tok, (int)n_frm);
   return stlt_check_launch("ragged_host_counts_kernel");
 }
+
+int read_ragged_counts(const RaggedIndex& ix, const stlt_inputs* in, bool pad, int64_t& Ms, int64_t& Mf, bool* from_host, hipStream_t s) {
+  *from_host = in->n_real_tokens > 0 || in->n_real_frames > 0;
+  if (*from_host) {
+    Ms = in->n_real_tokens;
+    Mf = in->n_real_frames;
+    if (pad) return launch_ragged_host_counts(ix, Ms, Mf, in->B * in->T * in->N, in->B * in->T, s);
+    if (Ms <= 0 || Mf <= 0 || Ms > in->B * in->T * in->N || Mf > in->B * in->T || Mf > Ms) return stlt_set_error(STLT_EINVAL, "skip-padding: n_real_tokens / n_real_frames do not fit the batch");
+    return 0;
+  }
+  int counts[4] = {0, 0, 0, 0};
+  if (hipError_t e = hipMemcpyAsync(counts, ix.counts, sizeof(counts), hipMemcpyDeviceToHost, s); e != hipSuccess)
+    return stlt_set_error((int)e, "skip-padding: count read-back: %s", hipGetErrorString(e));
+  if (hipError_t e = hipStreamSynchronize(s); e != hipSuccess)
+    return stlt_set_error((int)e, "skip-padding: count read-back: %s", hipGetErrorString(e));
+  if (counts[2] != 0)
+    return stlt_set_error(STLT_EINVAL, "skip-padding needs collater-shaped masks: slot 0 of every real frame unmasked and frame lengths-1 real (datasets.py:247-288)");
+  Ms = counts[0];
+  Mf = counts[1];
+  return 0;
+}
+
 int launch_ragged_poison(const RaggedIndex& ix, int64_t n_tok, int64_t n_frm, bool allow_more, float* out, int64_t n, hipStream_t s) {
   if (!out || n <= 0) return 0;
   StltProfScope ps(STLT_K_MISC, s);

@@ -16,9 +16,6 @@
 namespace {
 
 inline int64_t up32(int64_t v) { return (v + 31) / 32 * 32; }
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-#define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
 
 struct LayerTape { float *x, *qkv, *ctx, *a, *x1, *u, *h, *f; };
 
@@ -41,7 +38,7 @@ static Tape tape_layout(char* base, int64_t B, int64_t T, int64_t N, int64_t d, 
   Tape t;
   t.tokp = up32(B * T * N); t.btp = up32(B * T); t.bp = up32(B);
   size_t off = 0;
-  auto take = [&](int64_t rows, int64_t width) { float* p = base ? (float*)(base + off) : nullptr; off = align256(off + (size_t)rows * width * sizeof(float)); return p; };
+  auto take = [&](int64_t rows, int64_t width) { float* p = base ? (float*)(base + off) : nullptr; off = stlt_align256(off + (size_t)rows * width * sizeof(float)); return p; };
   t.s_embed = take(t.tokp, d);
   auto take_layer = [&](LayerTape& l, int64_t rows) {
     l.x = take(rows, d); l.qkv = take(rows, 3 * d); l.ctx = take(rows, d); l.a = take(rows, d);
@@ -102,7 +99,7 @@ static Scratch scratch_layout(char* base, int64_t B, int64_t T, int64_t N, int64
   Scratch s;
   const int64_t tokp = up32(B * T * N), btp = up32(B * T), bp = up32(B);
   size_t off = 0;
-  auto take = [&](int64_t floats) { float* p = base ? (float*)(base + off) : nullptr; off = align256(off + (size_t)floats * sizeof(float)); return p; };
+  auto take = [&](int64_t floats) { float* p = base ? (float*)(base + off) : nullptr; off = stlt_align256(off + (size_t)floats * sizeof(float)); return p; };
   s.sA = take(tokp * d); s.sB = take(tokp * d); s.sC = take(tokp * d); s.sD = take(tokp * d); s.sE = take(tokp * d); s.sQKV = take(tokp * 3 * d); s.sH = take(tokp * 4 * d);
   s.tA = take(btp * d); s.tB = take(btp * d); s.tC = take(btp * d); s.tD = take(btp * d); s.tE = take(btp * d); s.tQKV = take(btp * 3 * d); s.tH = take(btp * 4 * d);
   s.hA = take(bp * d); s.hB = take(bp * d);
@@ -419,34 +416,29 @@ static int qkv_attention_train(const stlt_layer_params& lp, int64_t d, int64_t H
   return launch_attn(t.qkv, kpm, causal, S, L, H, d / H, t.ctx, kid, s, dr, site0);
 }
 
-static int layer_forward(const stlt_layer_params& lp, int64_t d, int64_t H, const LayerTape& t, int64_t M, int64_t S, int64_t L,
-                         const uint8_t* kpm, int causal, int kid, float* y, StltDrop dr, uint32_t site0, hipStream_t s,
-                         const int* seg_start = nullptr, const int* seg_end = nullptr) {
-  TRY(qkv_attention_train(lp, d, H, t, M, S, L, kpm, causal, kid, dr, site0, s, seg_start, seg_end));
-  TRY(launch_linear(t.ctx, d, lp.out_proj_w, lp.out_proj_b, t.a, d, M, d, d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(t.a, d, t.x, d, lp.norm1_w, lp.norm1_b, 1e-5f, M, d, t.x1, d, s, dr, site0 + 1));
-  TRY(launch_linear_gelu_keep(t.x1, d, lp.lin1_w, lp.lin1_b, t.u, t.h, M, 4 * d, d, dr, site0 + 2, nullptr, s));
-  TRY(launch_linear(t.h, 4 * d, lp.lin2_w, lp.lin2_b, t.f, d, M, d, 4 * d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(t.f, d, t.x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, M, d, y, d, s, dr, site0 + 3));
-  return 0;
-}
-
-// Last layer of a tower when only n of its M output rows are read afterwards (the CLS row of every frame after
+// One layer of the training forward.  rows == nullptr: every row (n = M; t.ctx / t.x are read in place, no gathers).
+// rows != nullptr: the last layer of a tower when only n of its M output rows are read afterwards (the CLS row of every frame after
 // the spatial tower, models.py:79; frame lengths-1 of every clip after the temporal tower, models.py:189-192): the
 // in-projection and the attention run on all rows (every row is a key / value), out-proj, norms and FFN on the picked
 // rows only.  Tape: x, qkv, ctx hold M rows; a, x1, u, h, f hold n rows; the gathered ctx / x rows are parked in the
 // unused upper part of a / x1 (rows n..2n-1, hence the 2n <= M condition at the call sites) and re-gathered by the
 // reverse sweep.  Dropout masks keep the indices of the rows' original positions.
-static int layer_forward_tail(const stlt_layer_params& lp, int64_t d, int64_t H, const LayerTape& t, int64_t M, int64_t S, int64_t L,
-                              const uint8_t* kpm, int causal, int kid, const int* seg_start, const int* seg_end, const int* rows,
-                              int64_t n, float* y, StltDrop dr, uint32_t site0, hipStream_t s) {
+static int layer_forward(const stlt_layer_params& lp, int64_t d, int64_t H, const LayerTape& t, int64_t M, int64_t S, int64_t L,
+                         const uint8_t* kpm, int causal, int kid, const int* seg_start, const int* seg_end, const int* rows, int64_t n,
+                         float* y, StltDrop dr, uint32_t site0, hipStream_t s) {
   TRY(qkv_attention_train(lp, d, H, t, M, S, L, kpm, causal, kid, dr, site0, s, seg_start, seg_end));
-  float* g_ctx = t.a + n * d;
-  float* g_x = t.x1 + n * d;
-  TRY(launch_gather_rows(t.ctx, d, rows, n, d, g_ctx, s));
-  TRY(launch_gather_rows(t.x, d, rows, n, d, g_x, s));
-  TRY(launch_linear(g_ctx, d, lp.out_proj_w, lp.out_proj_b, t.a, d, n, d, d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(t.a, d, g_x, d, lp.norm1_w, lp.norm1_b, 1e-5f, n, d, t.x1, d, s, dr, site0 + 1, rows));
+  const float* ctx = t.ctx;
+  const float* x = t.x;
+  if (rows) {
+    float* g_ctx = t.a + n * d;
+    float* g_x = t.x1 + n * d;
+    TRY(launch_gather_rows(t.ctx, d, rows, n, d, g_ctx, s));
+    TRY(launch_gather_rows(t.x, d, rows, n, d, g_x, s));
+    ctx = g_ctx;
+    x = g_x;
+  }
+  TRY(launch_linear(ctx, d, lp.out_proj_w, lp.out_proj_b, t.a, d, n, d, d, STLT_ACT_NONE, s));
+  TRY(launch_add_layernorm(t.a, d, x, d, lp.norm1_w, lp.norm1_b, 1e-5f, n, d, t.x1, d, s, dr, site0 + 1, rows));
   TRY(launch_linear_gelu_keep(t.x1, d, lp.lin1_w, lp.lin1_b, t.u, t.h, n, 4 * d, d, dr, site0 + 2, rows, s));
   TRY(launch_linear(t.h, 4 * d, lp.lin2_w, lp.lin2_b, t.f, d, n, d, 4 * d, STLT_ACT_NONE, s));
   TRY(launch_add_layernorm(t.f, d, t.x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, n, d, y, d, s, dr, site0 + 3, rows));
@@ -460,7 +452,7 @@ static int zero_rows(float* buf, int64_t width, int64_t r0, int64_t r1, hipStrea
   return 0;
 }
 
-// Reverse of layer_forward_tail.  dy: gradient wrt the n output rows; on return bufA holds the gradient wrt all M
+// Reverse of layer_forward's picked-rows form.  dy: gradient wrt the n output rows; on return bufA holds the gradient wrt all M
 // input rows.  Scratch roles as in layer_backward; the gradient-side operands of the weight-gradient products are
 // zeroed between n and its round-up to 32 first (those rows belong to other layers' data in the shared buffers).
 static int layer_backward_tail(const stlt_layer_params& lp, const stlt_layer_params* g, const LayerTape& t, int64_t d, int64_t H,
@@ -535,29 +527,6 @@ size_t stlt_train_scratch_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int6
   return scratch_layout(nullptr, B, T, N, d, n_categories).bytes;
 }
 
-// Row counts of the ragged index: the caller's (stlt_inputs.n_real_tokens / n_real_frames, no synchronisation; `pad`: the forward makes the
-// index safe for them, the backward finds it so), else one device->host copy + stream synchronisation.
-static int read_ragged_counts(const RaggedIndex& ix, const stlt_inputs* in, bool pad, int64_t& Ms, int64_t& Mf, bool* from_host, hipStream_t s) {
-  *from_host = in->n_real_tokens > 0 || in->n_real_frames > 0;
-  if (*from_host) {
-    Ms = in->n_real_tokens;
-    Mf = in->n_real_frames;
-    if (pad) return launch_ragged_host_counts(ix, Ms, Mf, in->B * in->T * in->N, in->B * in->T, s);
-    if (Ms <= 0 || Mf <= 0 || Ms > in->B * in->T * in->N || Mf > in->B * in->T || Mf > Ms) return stlt_set_error(STLT_EINVAL, "skip-padding: n_real_tokens / n_real_frames do not fit the batch");
-    return 0;
-  }
-  int counts[4] = {0, 0, 0, 0};
-  if (hipError_t e = hipMemcpyAsync(counts, ix.counts, sizeof(counts), hipMemcpyDeviceToHost, s); e != hipSuccess)
-    return stlt_set_error((int)e, "skip-padding: count read-back: %s", hipGetErrorString(e));
-  if (hipError_t e = hipStreamSynchronize(s); e != hipSuccess)
-    return stlt_set_error((int)e, "skip-padding: count read-back: %s", hipGetErrorString(e));
-  if (counts[2] != 0)
-    return stlt_set_error(STLT_EINVAL, "skip-padding needs collater-shaped masks: slot 0 of every real frame unmasked and frame lengths-1 real (datasets.py:247-288)");
-  Ms = counts[0];
-  Mf = counts[1];
-  return 0;
-}
-
 int stlt_train_forward(const stlt_params* p, const stlt_inputs* in, void* tape_mem, size_t tape_bytes, float* logits,
                        float dropout_p, uint64_t dropout_seed, int flags, stlt_stream_t stream) {
   const bool backbone_only = (flags & STLT_FLAG_TRAIN_BACKBONE) != 0;  // `logits` is then the (B*T, d) backbone output
@@ -585,21 +554,17 @@ int stlt_train_forward(const stlt_params* p, const stlt_inputs* in, void* tape_m
   } else {
     TRY(launch_padded_rows(in->lengths, B, T, N, ix, s));  // rows the tail layers pick: f*N and b*T + lengths-1
   }
-  // the last layer of each tower only has to produce the rows that are read afterwards (layer_forward_tail)
+  // the last layer of each tower only has to produce the rows that are read afterwards (layer_forward with picked rows)
   const bool sp_tail = p->n_spatial > 0 && 2 * BT <= tok, tp_tail = !backbone_only && p->n_temporal > 0 && 2 * B <= BT;
   float* x0 = p->n_spatial > 0 ? t.sp[0].x : t.sp_out;
   TRY(launch_embed(in->categories, in->boxes, in->scores, p->cat_emb, p->n_categories, p->box_w, p->box_b, p->score_w,
                    p->score_b, p->emb_ln_w, p->emb_ln_b, p->ln_eps, tok, d, x0, s, t.s_embed, dr, ragged ? ix.t_orig : nullptr));
   for (int64_t l = 0; l < p->n_spatial; ++l) {
     const uint32_t site = (uint32_t)(8 * (l + 1));
-    if (l == p->n_spatial - 1 && sp_tail) {
-      TRY(layer_forward_tail(p->spatial[l], d, H, t.sp[l], tok, B * T, N, in->kpm_boxes, 0, STLT_K_ATTN_SPATIAL,
-                             ragged ? ix.t_seg_start : nullptr, ragged ? ix.t_seg_end : nullptr, ix.f_cls_row, BT, t.sp_out, dr, site, s));
-    } else {
-      float* y = l + 1 < p->n_spatial ? t.sp[l + 1].x : t.sp_out;
-      TRY(layer_forward(p->spatial[l], d, H, t.sp[l], tok, B * T, N, in->kpm_boxes, 0, STLT_K_ATTN_SPATIAL, y, dr, site, s,
-                        ragged ? ix.t_seg_start : nullptr, ragged ? ix.t_seg_end : nullptr));
-    }
+    const bool tail = l == p->n_spatial - 1 && sp_tail;
+    float* y = l + 1 < p->n_spatial ? t.sp[l + 1].x : t.sp_out;
+    TRY(layer_forward(p->spatial[l], d, H, t.sp[l], tok, B * T, N, in->kpm_boxes, 0, STLT_K_ATTN_SPATIAL, ragged ? ix.t_seg_start : nullptr,
+                      ragged ? ix.t_seg_end : nullptr, tail ? ix.f_cls_row : nullptr, tail ? BT : tok, y, dr, site, s));
   }
   float* tp_dst = backbone_only ? logits : t.tp_out;  // where the temporal tower's output rows land
   float* g0 = p->n_temporal > 0 ? t.tp[0].x : tp_dst;
@@ -617,14 +582,10 @@ int stlt_train_forward(const stlt_params* p, const stlt_inputs* in, void* tape_m
                           d, g0, s, t.s_frames, dr, ragged ? ix.f_orig : nullptr, BT));
   for (int64_t l = 0; l < p->n_temporal; ++l) {
     const uint32_t site = (uint32_t)(8 * (p->n_spatial + l + 1));
-    if (l == p->n_temporal - 1 && tp_tail) {
-      TRY(layer_forward_tail(p->temporal[l], d, H, t.tp[l], BT, B, T, in->kpm_frames, 1, STLT_K_ATTN_TEMPORAL,
-                             ragged ? ix.f_seg_start : nullptr, ragged ? ix.f_seg_end : nullptr, ix.last_row, B, t.h0, dr, site, s));
-    } else {
-      float* y = l + 1 < p->n_temporal ? t.tp[l + 1].x : tp_dst;
-      TRY(layer_forward(p->temporal[l], d, H, t.tp[l], BT, B, T, in->kpm_frames, 1, STLT_K_ATTN_TEMPORAL, y, dr, site, s,
-                        ragged ? ix.f_seg_start : nullptr, ragged ? ix.f_seg_end : nullptr));
-    }
+    const bool tail = l == p->n_temporal - 1 && tp_tail;
+    float* y = tail ? t.h0 : l + 1 < p->n_temporal ? t.tp[l + 1].x : tp_dst;
+    TRY(layer_forward(p->temporal[l], d, H, t.tp[l], BT, B, T, in->kpm_frames, 1, STLT_K_ATTN_TEMPORAL, ragged ? ix.f_seg_start : nullptr,
+                      ragged ? ix.f_seg_end : nullptr, tail ? ix.last_row : nullptr, tail ? B : BT, y, dr, site, s));
   }
   if (backbone_only) return 0;
   if (!tp_tail) TRY(launch_gather_rows(t.tp_out, d, ix.last_row, B, d, t.h0, s));                    // models.py:189-192

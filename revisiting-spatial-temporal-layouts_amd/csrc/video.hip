@@ -106,8 +106,6 @@ __global__ __launch_bounds__(VP_THREADS) void video_out_kernel(const uint8_t* __
   for (int c = 0; c < 3; ++c) o[c * plane] = lut[p.c[c]];
 }
 
-constexpr size_t vp_align(size_t n) { return (n + 255) & ~size_t(255); }
-
 struct VpLayout {
   size_t clips, tables, lut, sums, total;
 };
@@ -115,10 +113,10 @@ struct VpLayout {
 VpLayout vp_layout(int64_t B, int64_t T, int64_t n_table) {
   VpLayout l;
   l.clips = 0;
-  l.tables = l.clips + vp_align((size_t)B * sizeof(stlt_video_clip));
-  l.lut = l.tables + vp_align((size_t)n_table * sizeof(int32_t));
-  l.sums = l.lut + vp_align(256 * sizeof(float));
-  l.total = l.sums + vp_align((size_t)B * T * sizeof(unsigned long long));
+  l.tables = l.clips + stlt_align256((size_t)B * sizeof(stlt_video_clip));
+  l.lut = l.tables + stlt_align256((size_t)n_table * sizeof(int32_t));
+  l.sums = l.lut + stlt_align256(256 * sizeof(float));
+  l.total = l.sums + stlt_align256((size_t)B * T * sizeof(unsigned long long));
   return l;
 }
 
