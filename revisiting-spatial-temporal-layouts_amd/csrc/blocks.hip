@@ -6,6 +6,7 @@
 //   attention block:  out = LN_eps( x + drop( MHA(x, c, c; kpm, causal, prob-dropout) · Woᵀ + bo ) )      c = x for self-attention
 //   feed-forward block: out = LN_eps( x + drop( W2 · drop_inner( act(W1 x + b1) ) + b2 ) )                 act = GELU | ReLU
 // Dropout sites: site0 = attention probabilities / inner dropout, site0 + 1 = the dropout in front of the residual.
+#include <cstdlib>
 #include "ctx.h"
 
 namespace {
@@ -59,18 +60,6 @@ BlockScratch block_scratch(char* keep, char* work, int64_t rows, int64_t d, int 
   return b;
 }
 
-// The partial-row reductions of one backward call (LayerNorm parameters, bias column sums) run as one batched launch at its end.
-struct BlockDefer {
-  StltReduceDefer d;
-  BlockDefer(const BlockScratch& sc, hipStream_t s) {
-    d.s = s; d.pool = sc.red_pool; d.pool_floats = sc.red_floats * 4;
-    stlt_reduce_defer_set(sc.red_pool ? &d : nullptr);
-  }
-  ~BlockDefer() { stlt_reduce_defer_set(nullptr); }
-  float* chunk(const BlockScratch& sc) { int err = 0; return stlt_reduce_defer_chunk(sc.red_pool ? &d : nullptr, sc.red_floats, sc.red, &err); }
-  int flush() { return stlt_reduce_defer_flush(&d); }
-};
-
 // The weight-gradient products of a block are collected and run as ONE grouped stream-K launch at the end of the block's
 // backward (gemm.hip: launch_weight_grad_group) when every product contracts over a multiple of 32 rows; otherwise product
 // by product (MFMA over the 32-row multiple + the strided kernel for the rest: stlt_linear_bwd).
@@ -92,7 +81,7 @@ struct DwList {
 int flush_dw(const DwList& l, const BlockScratch& sc, hipStream_t s) {
   if (l.n == 0) return 0;
   bool group_ok = true;
-  for (int i = 0; i < l.n; ++i) group_ok = group_ok && l.it[i].rows % 32 == 0 && l.it[i].rows <= 4096;  // long contractions: separate launches are as fast (train.hip: weight_grad_all)
+  for (int i = 0; i < l.n; ++i) group_ok = group_ok && l.it[i].rows % 32 == 0 && l.it[i].rows <= STLT_DW_GROUP_MAX_ROWS;
   if (stlt_ctx* c = group_ok ? stlt_ctx_current() : nullptr) {
     std::lock_guard<std::mutex> lk(c->mu);
     if (c->dw_on && c->dw_n + l.n <= STLT_DW_DEFER_CAP) {
@@ -100,7 +89,6 @@ int flush_dw(const DwList& l, const BlockScratch& sc, hipStream_t s) {
       return 0;
     }
   }
-  StltGemmScratch lend(sc.lin, STLT_GEMM_SCRATCH_BYTES);
   if (group_ok) return launch_weight_grad_group(l.it, l.n, s);
   for (int i = 0; i < l.n; ++i)
     TRY(stlt_linear_bwd(l.it[i].x, l.it[i].g_w /* unused: dx is null */, l.it[i].dy, l.it[i].rows, l.it[i].n_out, l.it[i].k_in, nullptr, l.it[i].g_w, nullptr,
@@ -111,20 +99,84 @@ int flush_dw(const DwList& l, const BlockScratch& sc, hipStream_t s) {
 // dx (M,K) = dy·W (+ add); the weight gradient dw (N,K) += dyᵀ·x is queued on `dws`; db (N) += column sums of dy.
 // N (the contraction length of dx) is a multiple of 32 for every Linear of these blocks (d, 2d, 3d, 4d with d = 64 H).
 int linear_bwd(const float* x, const float* w, const float* dy, int64_t M, int64_t N, int64_t K, float* dx, const float* add, float* dw,
-               float* db, DwList& dws, const BlockScratch& sc, hipStream_t s, BlockDefer* defer = nullptr) {
-  if (dx && M > 0) {
-    StltGemmScratch lend(sc.lin, STLT_GEMM_SCRATCH_BYTES);
-    bool taken = false;
-    if ((size_t)(N * K) <= sc.wt_floats) TRY(launch_input_grad_bf16x3(dy, N, w, N, K, add, K, dx, K, M, sc.wt, s, &taken));
-    if (!taken) TRY(launch_input_grad_gemm16(dy, N, w, N, K, add, K, dx, K, M, s, &taken));  // few rows: whole small tiles
-    if (!taken) TRY(launch_gemm(0, 1, dy, N, w, K, nullptr, add, K, dx, K, 0, M, K, N, 1, STLT_ACT_NONE, s));
-  }
+               float* db, DwList& dws, const BlockScratch& sc, hipStream_t s) {
+  if (dx && M > 0) TRY(stlt_input_grad(dy, N, w, N, K, add, K, dx, K, M, sc.wt, sc.wt_floats, s));
   dws.add(dy, N, x, K, M, dw);
   if (db && M > 0) return launch_colsum_acc(dy, N, M, N, db, sc.red, s);
   return 0;
 }
 
 }  // namespace
+
+// ---- the training half-blocks (common.h) ----
+
+int stlt_input_grad(const float* dy, int64_t ld_dy, const float* w, int64_t n_out, int64_t k_in, const float* r, int64_t ldr, float* c, int64_t ldc,
+                    int64_t rows, float* wt, size_t wt_floats, hipStream_t s) {
+  bool taken = false;
+  if (wt && (size_t)(n_out * k_in) <= wt_floats) TRY(launch_input_grad_bf16x3(dy, ld_dy, w, n_out, k_in, r, ldr, c, ldc, rows, wt, s, &taken));
+  if (!taken) TRY(launch_input_grad_gemm16(dy, ld_dy, w, n_out, k_in, r, ldr, c, ldc, rows, s, &taken));  // under-filled launches (few rows): whole small tiles, W read as it lies
+  return taken ? 0 : launch_gemm(0, 1, dy, ld_dy, w, k_in, nullptr, r, ldr, c, ldc, 0, rows, k_in, n_out, 1, STLT_ACT_NONE, s);
+}
+
+int stlt_ffn_hidden_bwd(const float* df, const float* lin2_w, const float* u, float* du, int64_t rows, int64_t d, float* g_lin1_b, StltReduceScope& red,
+                        StltDrop dr, uint32_t site, const int* drop_rows, float* wt, size_t wt_floats, hipStream_t s) {
+  static const bool fused = [] { const char* e = getenv("STLT_FUSE_GELU_BWD"); return e ? atoi(e) != 0 : true; }();
+  const int n_part = (int)((rows + 255) / 256 * 16);
+  const bool split = wt && (size_t)(4 * d * d) <= wt_floats && stlt_split_bf16_takes(rows, 4 * d, d, d, d);
+  if (fused && g_lin1_b && (size_t)(n_part * 4 * d) <= red.red_floats && d % 32 == 0 && !split) {
+    float* part = red.chunk();
+    const StltGemmEpi epi{dr, site, drop_rows, part};
+    bool small = false;  // the temporal tower at the reference's default batch, the fusion models' blocks (~2048 rows): small tiles, same epilogue (gemm16.hip)
+    TRY(launch_input_grad_gemm16(df, d, lin2_w, d, 4 * d, u, 4 * d, du, 4 * d, rows, s, &small, 0, &epi));
+    if (!small) TRY(launch_gemm(0, 1, df, d, lin2_w, 4 * d, nullptr, u, 4 * d, du, 4 * d, 0, rows, 4 * d, d, 1, STLT_ACT_GELU_BWD, s, &epi));
+    return launch_reduce_slabs(part, 4 * d, n_part, g_lin1_b, 4 * d, 1, s);
+  }
+  TRY(stlt_input_grad(df, d, lin2_w, d, 4 * d, nullptr, 0, du, 4 * d, rows, wt, wt_floats, s));  // dh
+  if (g_lin1_b) return launch_gelu_bwd_colsum(du, u, du, rows, 4 * d, g_lin1_b, red.chunk(), s, dr, site, drop_rows);  // du; lin1_b += colsum(du)
+  return launch_gelu_bwd(du, u, du, rows * 4 * d, s, dr, site, drop_rows, 4 * d);
+}
+
+int stlt_ffn_half_fwd_train(const stlt_ffn_block_params& p, int act, const float* x, float eps, int64_t rows, int64_t d, float* u, float* h, float* f,
+                            float* out, StltDrop dr, StltDrop inner, uint32_t site, const int* drop_rows, hipStream_t s) {
+  if (act == STLT_ACT_GELU) {
+    TRY(launch_linear_gelu_keep(x, d, p.lin1_w, p.lin1_b, u, h, rows, 4 * d, d, inner, site, drop_rows, s));
+  } else {
+    TRY(launch_linear(x, d, p.lin1_w, p.lin1_b, h, 4 * d, rows, 4 * d, d, STLT_ACT_RELU, s));
+    if (inner.thr) TRY(launch_dropout(h, h, rows * 4 * d, inner, site, s));
+  }
+  TRY(launch_linear(h, 4 * d, p.lin2_w, p.lin2_b, f, d, rows, d, 4 * d, STLT_ACT_NONE, s));
+  return launch_add_layernorm(f, d, x, d, p.ln_w, p.ln_b, eps, rows, d, out, d, s, dr, site + 1, drop_rows);
+}
+
+int stlt_ffn_half_bwd_train(const stlt_ffn_block_params& p, const stlt_ffn_block_params& g, int act, const float* dy, const float* x, const float* u,
+                            const float* h, const float* f, float eps, int64_t rows, int64_t d, StltDrop dr, StltDrop inner, uint32_t site,
+                            const int* drop_rows, const StltHalfBwd& b, hipStream_t s) {
+  float* df = b.branch(dr);
+  TRY(launch_ln_bwd(dy, d, x, d, f, d, p.ln_w, eps, rows, d, b.ds, d, stlt_grad(g.ln_w), stlt_grad(g.ln_b), b.red->chunk(), s, dr, site + 1, b.dbr, 0,
+                    stlt_grad(g.lin2_b), drop_rows));                                                     // ds, df; lin2_b += colsum(df)
+  if (act == STLT_ACT_GELU) {
+    TRY(stlt_ffn_hidden_bwd(df, p.lin2_w, u, b.dh, rows, d, stlt_grad(g.lin1_b), *b.red, inner, site, drop_rows, b.wt, b.wt_floats, s));
+  } else {
+    TRY(stlt_input_grad(df, d, p.lin2_w, d, 4 * d, nullptr, 0, b.dh, 4 * d, rows, b.wt, b.wt_floats, s));  // dh = df·W2
+    if (inner.thr) TRY(launch_dropout(b.dh, b.dh, rows * 4 * d, inner, site, s));
+    TRY(stlt_relu_bwd(b.dh, h, b.dh, rows * 4 * d, (stlt_stream_t)s));  // h > 0 <=> pre-activation > 0 and kept
+    if (g.lin1_b) TRY(launch_colsum_acc(b.dh, 4 * d, rows, 4 * d, stlt_grad(g.lin1_b), b.red->chunk(), s));
+  }
+  return stlt_input_grad(b.dh, 4 * d, p.lin1_w, 4 * d, d, b.ds, d, b.dx, d, rows, b.wt, b.wt_floats, s);  // dx = du·W1 + ds
+}
+
+int stlt_attn_half_fwd_train(const stlt_attn_block_params& p, const float* ctx, const float* x, float eps, int64_t rows, int64_t d, float* a, float* out,
+                             StltDrop dr, uint32_t site, const int* drop_rows, hipStream_t s) {
+  TRY(launch_linear(ctx, d, p.out_proj_w, p.out_proj_b, a, d, rows, d, d, STLT_ACT_NONE, s));
+  return launch_add_layernorm(a, d, x, d, p.ln_w, p.ln_b, eps, rows, d, out, d, s, dr, site, drop_rows);
+}
+
+int stlt_attn_half_bwd_train(const stlt_attn_block_params& p, const stlt_attn_block_params& g, const float* dy, const float* x, const float* a, float eps,
+                             int64_t rows, int64_t d, StltDrop dr, uint32_t site, const int* drop_rows, const StltHalfBwd& b, hipStream_t s) {
+  TRY(launch_ln_bwd(dy, d, x, d, a, d, p.ln_w, eps, rows, d, b.ds, d, stlt_grad(g.ln_w), stlt_grad(g.ln_b), b.red->chunk(), s, dr, site, b.dbr, 0,
+                    stlt_grad(g.out_proj_b), drop_rows));                                                 // ds, da; out_proj_b += colsum(da)
+  return stlt_input_grad(b.branch(dr), d, p.out_proj_w, d, d, nullptr, 0, b.dx, d, rows, b.wt, b.wt_floats, s);  // dctx = da·Wo
+}
 
 extern "C" {
 
@@ -198,8 +250,7 @@ int stlt_attn_block_fwd_train(const stlt_attn_block_params* p, int64_t d, int64_
     TRY(launch_linear(c, d, p->in_proj_w + d * d, p->in_proj_b + d, kv, 2 * d, Mk, 2 * d, d, STLT_ACT_NONE, s));
     TRY(launch_attn_general(q, d, kv, kv + d, 2 * d, kpm, causal, S, Lq, Lk, H, d / H, ctx, kid, s, dr, site0));
   }
-  TRY(launch_linear(ctx, d, p->out_proj_w, p->out_proj_b, a, d, Mq, d, d, STLT_ACT_NONE, s));
-  return launch_add_layernorm(a, d, x, d, p->ln_w, p->ln_b, eps, Mq, d, out, d, s, dr, site0 + 1);
+  return stlt_attn_half_fwd_train(*p, ctx, x, eps, Mq, d, a, out, dr, site0 + 1, nullptr, s);
 }
 
 // g: gradient buffers of the block's parameters (same struct; ACCUMULATED into; null members are skipped).
@@ -220,26 +271,24 @@ int stlt_attn_block_bwd_train(const stlt_attn_block_params* p, const stlt_attn_b
   StltCtxScope scope(tctx, s);
   if (scope.error()) return scope.error();
   const StltDrop dr = stlt_drop_make(drop_p, seed);
-  auto G = [&](const float* q_) { return const_cast<float*>(q_); };
-  BlockDefer defer(sc, s);
-  // out = LN(x + drop(a)): ds = residual-path gradient, da = gradient wrt a (= ds without dropout); out_proj_b += colsum(da)
-  float* da = dr.thr ? sc.da : sc.ds;
-  TRY(launch_ln_bwd(dy, d, x, d, a, d, p->ln_w, eps, Mq, d, sc.ds, d, G(g->ln_w), G(g->ln_b), defer.chunk(sc), s, dr, site0 + 1, sc.da, 0, G(g->out_proj_b)));
-  // a = ctx·Woᵀ + bo
+  StltGemmScratch lend(sc.lin, STLT_GEMM_SCRATCH_BYTES);
+  StltReduceScope red(sc.red_pool, sc.red_floats * 4, sc.red, sc.red_floats, s);
+  // out = LN(x + drop(a)), a = ctx·Woᵀ + bo: ds = residual-path gradient, da = gradient wrt a (= ds without dropout); dctx = da·Wo
+  const StltHalfBwd hb{sc.ds, sc.da, nullptr, sc.dctx, &red, sc.wt, sc.wt_floats};
+  TRY(stlt_attn_half_bwd_train(*p, *g, dy, x, a, eps, Mq, d, dr, site0 + 1, nullptr, hb, s));
   DwList dws;
-  TRY(linear_bwd(ctx, p->out_proj_w, da, Mq, d, d, sc.dctx, nullptr, G(g->out_proj_w), nullptr, dws, sc, s));
+  dws.add(hb.branch(dr), d, ctx, d, Mq, stlt_grad(g->out_proj_w));
   if (!c) {
     // packed self-attention: dqkv (Mq, 3d); in_proj_b += its column sums (accumulated by the attention backward)
-    TRY(launch_attn_bwd(q, sc.dctx, kpm, causal, S, Lq, H, d / H, sc.dq, s, dr, site0, G(g->in_proj_b), defer.chunk(sc)));
-    TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, 3 * d, d, dx, sc.ds, G(g->in_proj_w), nullptr, dws, sc, s));  // dx = dqkv·Win + ds
-    TRY(defer.flush());
-    return flush_dw(dws, sc, s);
+    TRY(launch_attn_bwd(q, sc.dctx, kpm, causal, S, Lq, H, d / H, sc.dq, s, dr, site0, stlt_grad(g->in_proj_b), red.chunk()));
+    TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, 3 * d, d, dx, sc.ds, stlt_grad(g->in_proj_w), nullptr, dws, sc, s));  // dx = dqkv·Win + ds
+  } else {
+    TRY(stlt_attn_bwd(q, d, kv, kv + d, 2 * d, sc.dctx, kpm, causal, S, Lq, Lk, H, d / H, drop_p, seed, site0, sc.dq, d, sc.dkv, sc.dkv + d, 2 * d, stream));
+    TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, d, d, dx, sc.ds, stlt_grad(g->in_proj_w), stlt_grad(g->in_proj_b), dws, sc, s));  // dx = dq·Wq + ds
+    TRY(linear_bwd(c, p->in_proj_w + d * d, sc.dkv, Mk, 2 * d, d, dc, nullptr, g->in_proj_w ? stlt_grad(g->in_proj_w) + d * d : nullptr,
+                   g->in_proj_b ? stlt_grad(g->in_proj_b) + d : nullptr, dws, sc, s));
   }
-  TRY(stlt_attn_bwd(q, d, kv, kv + d, 2 * d, sc.dctx, kpm, causal, S, Lq, Lk, H, d / H, drop_p, seed, site0, sc.dq, d, sc.dkv, sc.dkv + d, 2 * d, stream));
-  TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, d, d, dx, sc.ds, G(g->in_proj_w), G(g->in_proj_b), dws, sc, s, &defer));  // dx = dq·Wq + ds
-  TRY(linear_bwd(c, p->in_proj_w + d * d, sc.dkv, Mk, 2 * d, d, dc, nullptr, g->in_proj_w ? G(g->in_proj_w) + d * d : nullptr,
-                 g->in_proj_b ? G(g->in_proj_b) + d : nullptr, dws, sc, s, &defer));
-  TRY(defer.flush());
+  TRY(red.flush());
   return flush_dw(dws, sc, s);
 }
 
@@ -254,14 +303,7 @@ int stlt_ffn_block_fwd_train(const stlt_ffn_block_params* p, int64_t d, float ep
   hipStream_t s = (hipStream_t)stream;
   const StltDrop dr = stlt_drop_make(drop_p, seed);
   const StltDrop inner = inner_dropout ? dr : StltDrop{0u, 1.0f, 0ull};
-  if (act == STLT_ACT_GELU) {
-    TRY(launch_linear_gelu_keep(x, d, p->lin1_w, p->lin1_b, u, h, M, 4 * d, d, inner, site0, nullptr, s));
-  } else {
-    TRY(launch_linear(x, d, p->lin1_w, p->lin1_b, h, 4 * d, M, 4 * d, d, STLT_ACT_RELU, s));
-    if (inner.thr) TRY(stlt_dropout(h, h, M * 4 * d, drop_p, seed, site0, stream));
-  }
-  TRY(launch_linear(h, 4 * d, p->lin2_w, p->lin2_b, f, d, M, d, 4 * d, STLT_ACT_NONE, s));
-  return launch_add_layernorm(f, d, x, d, p->ln_w, p->ln_b, eps, M, d, out, d, s, dr, site0 + 1);
+  return stlt_ffn_half_fwd_train(*p, act, x, eps, M, d, u, h, f, out, dr, inner, site0, nullptr, s);
 }
 
 int stlt_ffn_block_bwd_train(const stlt_ffn_block_params* p, const stlt_ffn_block_params* g, int64_t d, float eps, int act, int inner_dropout,
@@ -278,30 +320,14 @@ int stlt_ffn_block_bwd_train(const stlt_ffn_block_params* p, const stlt_ffn_bloc
   if (scope.error()) return scope.error();
   const StltDrop dr = stlt_drop_make(drop_p, seed);
   const StltDrop inner = inner_dropout ? dr : StltDrop{0u, 1.0f, 0ull};
-  auto G = [&](const float* q_) { return const_cast<float*>(q_); };
-  BlockDefer defer(sc, s);
-  float* df = dr.thr ? sc.da : sc.ds;
-  TRY(launch_ln_bwd(dy, d, x, d, f, d, p->ln_w, eps, M, d, sc.ds, d, G(g->ln_w), G(g->ln_b), defer.chunk(sc), s, dr, site0 + 1, sc.da, 0, G(g->lin2_b)));
+  StltGemmScratch lend(sc.lin, STLT_GEMM_SCRATCH_BYTES);
+  StltReduceScope red(sc.red_pool, sc.red_floats * 4, sc.red, sc.red_floats, s);
+  const StltHalfBwd hb{sc.ds, sc.da, sc.dh, dx, &red, sc.wt, sc.wt_floats};
+  TRY(stlt_ffn_half_bwd_train(*p, *g, act, dy, x, u, h, f, eps, M, d, dr, inner, site0, nullptr, hb, s));
   DwList dws;
-  bool gelu_fused = false;
-  if (act == STLT_ACT_GELU && g->lin1_b && (size_t)((M + 255) / 256 * 16 * 4 * d) <= sc.red_floats) {
-    // du = drop(df·W2) ∘ gelu'(u) in the dX product's epilogue + the bias column sums (train.hip's fused form); lin2_w += dfᵀ·h queued
-    StltGemmScratch lend(sc.lin, STLT_GEMM_SCRATCH_BYTES);
-    TRY(stlt_ffn_hidden_backward_fused(df, p->lin2_w, u, sc.dh, M, d, G(g->lin1_b), defer.chunk(sc), inner, site0, s, &gelu_fused));
-    if (gelu_fused) dws.add(df, d, h, 4 * d, M, G(g->lin2_w));
-  }
-  if (!gelu_fused) TRY(linear_bwd(h, p->lin2_w, df, M, d, 4 * d, sc.dh, nullptr, G(g->lin2_w), nullptr, dws, sc, s));  // dh = df·W2 ; lin2_w += dfᵀ·h
-  if (gelu_fused) {
-  } else if (act == STLT_ACT_GELU) {
-    if (g->lin1_b) TRY(launch_gelu_bwd_colsum(sc.dh, u, sc.dh, M, 4 * d, G(g->lin1_b), defer.chunk(sc), s, inner, site0));
-    else TRY(launch_gelu_bwd(sc.dh, u, sc.dh, M * 4 * d, s, inner, site0));
-  } else {
-    if (inner.thr) TRY(stlt_dropout(sc.dh, sc.dh, M * 4 * d, drop_p, seed, site0, stream));
-    TRY(stlt_relu_bwd(sc.dh, h, sc.dh, M * 4 * d, stream));  // h > 0 <=> pre-activation > 0 and kept
-    if (g->lin1_b) TRY(launch_colsum_acc(sc.dh, 4 * d, M, 4 * d, G(g->lin1_b), defer.chunk(sc), s));
-  }
-  TRY(linear_bwd(x, p->lin1_w, sc.dh, M, 4 * d, d, dx, sc.ds, G(g->lin1_w), nullptr, dws, sc, s));  // dx = du·W1 + ds ; lin1_w += duᵀ·x
-  TRY(defer.flush());
+  dws.add(hb.branch(dr), d, h, 4 * d, M, stlt_grad(g->lin2_w));  // lin2_w += dfᵀ·h
+  dws.add(sc.dh, 4 * d, x, d, M, stlt_grad(g->lin1_w));          // lin1_w += duᵀ·x
+  TRY(red.flush());
   return flush_dw(dws, sc, s);
 }
 

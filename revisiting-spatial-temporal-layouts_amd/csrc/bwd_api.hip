@@ -255,18 +255,22 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__
 
 }  // namespace
 
+int launch_dropout(const float* x, float* y, int64_t n, StltDrop dr, uint32_t site, hipStream_t s) {
+  if (n < 0 || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return stlt_set_error(STLT_EINVAL, "stlt_dropout: buffers must be 16-byte aligned");
+  if (n == 0) return 0;
+  int64_t blocks = (n + 1023) / 1024;
+  if (blocks > 4096) blocks = 4096;
+  StltProfScope ps(STLT_K_MISC, s);
+  hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, y, n, dr, site);
+  return stlt_check_launch("dropout_kernel");
+}
+
 extern "C" {
 
 int stlt_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint32_t site, stlt_stream_t stream) {
   if (!x || !y) return stlt_set_error(STLT_EINVAL, "stlt_dropout: null pointer");
   if (!(p >= 0.f && p < 1.f)) return stlt_set_error(STLT_EINVAL, "dropout probability must be in [0,1)");
-  if (n < 0 || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return stlt_set_error(STLT_EINVAL, "stlt_dropout: buffers must be 16-byte aligned");
-  if (n == 0) return 0;
-  int64_t blocks = (n + 1023) / 1024;
-  if (blocks > 4096) blocks = 4096;
-  StltProfScope ps(STLT_K_MISC, (hipStream_t)stream);
-  hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, y, n, stlt_drop_make(p, seed), site);
-  return stlt_check_launch("dropout_kernel");
+  return launch_dropout(x, y, n, stlt_drop_make(p, seed), site, (hipStream_t)stream);
 }
 
 int stlt_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, stlt_stream_t stream) {
@@ -296,13 +300,8 @@ int stlt_linear_bwd(const float* x, const float* w, const float* dy, int64_t M, 
   StltGemmScratch lend(scratch, STLT_GEMM_SCRATCH_BYTES);
   float* red = (float*)((char*)scratch + STLT_GEMM_SCRATCH_BYTES);
   const bool mfma_ok = N % 32 == 0 && K % 4 == 0;  // contraction lengths / leading dimensions the MFMA kernel takes
-  if (dx) {  // dx (M,K) = dy (M,N) · W (N,K)
-    bool small = false;
-    if (mfma_ok) { if (int e = launch_input_grad_gemm16(dy, N, w, N, K, nullptr, 0, dx, K, M, s, &small)) return e; }
-    if (small) {}
-    else if (mfma_ok) { if (int e = launch_gemm(0, 1, dy, N, w, K, nullptr, nullptr, 0, dx, K, 0, M, K, N, 1, STLT_ACT_NONE, s)) return e; }
-    else if (int e = launch_small_gemm(dy, N, 1, w, K, 1, dx, K, M, K, N, 0, s)) return e;
-  }
+  if (dx)  // dx (M,K) = dy (M,N) · W (N,K); never the split-bf16 form (no buffer for the transposed weight)
+    TRY(mfma_ok ? stlt_input_grad(dy, N, w, N, K, nullptr, 0, dx, K, M, nullptr, 0, s) : launch_small_gemm(dy, N, 1, w, K, 1, dx, K, M, K, N, 0, s));
   if (dw) {  // dw (N,K) += dyᵀ (N,M) · x (M,K): the MFMA kernel contracts over multiples of 32 rows, the rest goes to the strided kernel
     const int64_t Mf = (N % 4 == 0 && K % 4 == 0) ? M / 32 * 32 : 0;
     if (Mf > 0) { if (int e = launch_gemm(1, 1, dy, N, x, K, nullptr, dw, K, dw, K, 0, N, K, Mf, 1, STLT_ACT_NONE, s)) return e; }

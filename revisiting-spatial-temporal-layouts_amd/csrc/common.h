@@ -410,8 +410,6 @@ int launch_gelu_fwd(const float* u, float* h, int64_t n, hipStream_t s, StltDrop
                     const int* drop_rows = nullptr, int64_t ncols = 0);
 int launch_gelu_bwd(const float* dh, const float* u, float* du, int64_t n, hipStream_t s, StltDrop dr = StltDrop{0u, 1.0f, 0ull},
                     uint32_t site = 0, const int* drop_rows = nullptr, int64_t ncols = 0);
-int stlt_ffn_hidden_backward_fused(const float* df, const float* lin2_w, const float* u, float* du, int64_t rows, int64_t d, float* g_lin1_b,
-                                   float* cs_part, StltDrop dr, uint32_t site, hipStream_t s, bool* taken);  // train.hip
 int launch_gelu_bwd_colsum(const float* dh, const float* u, float* du, int64_t M, int64_t N, float* g_colsum, float* scratch,
                            hipStream_t s, StltDrop dr = StltDrop{0u, 1.0f, 0ull}, uint32_t site = 0, const int* drop_rows = nullptr);  // scratch >= 512*N floats
 // ragged attention backward: groups of whole segments (rows [grp_ptr[g], grp_ptr[g+1]), at most max_rows <= 64 each)
@@ -429,3 +427,60 @@ int launch_frames_bwd(const float* ds, const int64_t* frame_types, int64_t B, in
 int launch_scatter_last(const float* dh, const int64_t* lengths, int64_t B, int64_t T, int64_t d, float* dout, hipStream_t s);
 int launch_small_gemm(const float* a, int64_t sam, int64_t sak, const float* b, int64_t sbk, int64_t sbn, float* c,
                       int64_t ldc, int64_t M, int64_t N, int64_t K, int accumulate, hipStream_t s);
+
+// ---- the training half-blocks, written once (blocks.hip) for the reverse sweep (train.hip), the block-level training calls (blocks.hip)
+// and stlt_linear_bwd (bwd_api.hip).  Like the inference forms above they are plain launch sequences on the caller's buffers: they own no
+// memory, open no StltProfScope and lend no GEMM scratch; what differs between the callers is what they pass.
+inline float* stlt_grad(const float* p) { return const_cast<float*>(p); }  // a gradient buffer behind a parameter struct's const member
+constexpr int64_t STLT_DW_GROUP_MAX_ROWS = 4096;  // weight gradients contracting over more rows run as fast one launch each as grouped
+// Sets a StltReduceDefer on this thread, hands out its chunks, flushes on every exit path.  pool == nullptr: no deferral.
+struct StltReduceScope {
+  StltReduceDefer d;
+  float* red;  // the one shared buffer of red_floats floats: every chunk while nothing is deferred
+  size_t red_floats;
+  StltReduceScope(float* pool, size_t pool_floats, float* red_, size_t red_floats_, hipStream_t s) : red(red_), red_floats(red_floats_) {
+    d.s = s; d.pool = pool; d.pool_floats = pool_floats; stlt_reduce_defer_set(pool ? &d : nullptr);
+  }
+  ~StltReduceScope() { if (d.n > 0) (void)stlt_reduce_defer_flush(&d); stlt_reduce_defer_set(nullptr); }  // error exits: what the producers left is still reduced
+  StltReduceScope(const StltReduceScope&) = delete;
+  StltReduceScope& operator=(const StltReduceScope&) = delete;
+  float* chunk() { int err = 0; return stlt_reduce_defer_chunk(d.pool ? &d : nullptr, red_floats, red, &err); }  // the partial-row scratch of the next producer
+  int flush() { return stlt_reduce_defer_flush(d.pool ? &d : nullptr); }
+};
+// c (rows, k_in) = dy (rows, n_out)·W (n_out, k_in) (+ r): the input gradient of a Linear.  Split-bf16 (opt-in) if it takes the launch — W is
+// then transposed into wt (wt_floats >= n_out * k_in; nullptr: never this form) —, else the small tiles if they take it (gemm16.hip), else the
+// f32-MFMA NN product, which needs n_out % 32 == 0 and k_in % 4 == 0.
+int stlt_input_grad(const float* dy, int64_t ld_dy, const float* w, int64_t n_out, int64_t k_in, const float* r, int64_t ldr, float* c, int64_t ldc,
+                    int64_t rows, float* wt, size_t wt_floats, hipStream_t s);
+// du (rows, 4d) = drop(df·W2) ∘ gelu'(u) and g_lin1_b += column sums of du.  Fused (default): derivative, mask and column sums ride in the
+// product's epilogue / fix-up (gemm.hip: STLT_ACT_GELU_BWD) and one reduction finishes the bias gradient — when a chunk of `red` holds the
+// ceil(rows / 256) * 16 partial rows of 4d floats, d % 32 == 0 and the split-bf16 product (no such epilogue) would not take the launch with
+// `wt`; else the product + the stand-alone pass (STLT_FUSE_GELU_BWD=0: always, A/B runs; its chunk, >= 512 * 4d floats, is taken behind the product).
+int stlt_ffn_hidden_bwd(const float* df, const float* lin2_w, const float* u, float* du, int64_t rows, int64_t d, float* g_lin1_b, StltReduceScope& red,
+                        StltDrop dr, uint32_t site, const int* drop_rows, float* wt, size_t wt_floats, hipStream_t s);
+// Buffers of a half-block's reverse (rows padded as the caller's weight-gradient products need).  The gradient wrt the branch output — df / da, the
+// dY operand of the caller's weight-gradient items — is branch(dr): with dropout the masked, rescaled copy in `dbr`, without it `ds` itself.
+struct StltHalfBwd {
+  float *ds, *dbr;  // (rows,d): residual-path gradient behind the LayerNorm; gradient wrt the un-dropped branch output (may equal ds without dropout)
+  float* dh;        // (rows,4d): hidden gradient du (feed-forward half)
+  float* dx;        // (rows,d): the half's product — du·W1 + ds (feed-forward), dctx = da·Wo (out-projection)
+  StltReduceScope* red;
+  float* wt; size_t wt_floats;  // stlt_input_grad's transposed-weight buffer
+  float* branch(const StltDrop& dr) const { return dr.thr ? dbr : ds; }
+};
+// Dropout sites of the feed-forward half: `site` = the hidden's (inner), site + 1 = in front of the residual.  g: gradient buffers, ACCUMULATED
+// into, null members skipped.  drop_rows (GELU only): the rows' original positions for the masks (picked-rows form of the sweep).
+//   forward: u = x·W1ᵀ+b1 ; h = inner(act(u)) ; f = h·W2ᵀ+b2 ; out = LN_eps(x + drop(f))     (ReLU keeps no u)
+//   reverse: LN backward (lin2_b += colsum(df)) -> du (lin1_b += colsum(du)) -> b.dx = du·W1 + ds
+int stlt_ffn_half_fwd_train(const stlt_ffn_block_params& p, int act, const float* x, float eps, int64_t rows, int64_t d, float* u, float* h, float* f,
+                            float* out, StltDrop dr, StltDrop inner, uint32_t site, const int* drop_rows, hipStream_t s);
+int stlt_ffn_half_bwd_train(const stlt_ffn_block_params& p, const stlt_ffn_block_params& g, int act, const float* dy, const float* x, const float* u,
+                            const float* h, const float* f, float eps, int64_t rows, int64_t d, StltDrop dr, StltDrop inner, uint32_t site,
+                            const int* drop_rows, const StltHalfBwd& b, hipStream_t s);
+// The out-projection half behind an attention core: a = ctx·Woᵀ+bo ; out = LN_eps(x + drop(a)), dropout site `site`.
+//   reverse: LN backward (out_proj_b += colsum(da)) -> b.dx = dctx = da·Wo
+int stlt_attn_half_fwd_train(const stlt_attn_block_params& p, const float* ctx, const float* x, float eps, int64_t rows, int64_t d, float* a, float* out,
+                             StltDrop dr, uint32_t site, const int* drop_rows, hipStream_t s);
+int stlt_attn_half_bwd_train(const stlt_attn_block_params& p, const stlt_attn_block_params& g, const float* dy, const float* x, const float* a, float eps,
+                             int64_t rows, int64_t d, StltDrop dr, uint32_t site, const int* drop_rows, const StltHalfBwd& b, hipStream_t s);
+int launch_dropout(const float* x, float* y, int64_t n, StltDrop dr, uint32_t site, hipStream_t s);  // bwd_api.hip: stlt_dropout behind its probability check

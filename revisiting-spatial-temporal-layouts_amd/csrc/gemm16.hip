@@ -254,7 +254,7 @@ int launch_linear_gelu_keep(const float* x, int64_t ldx, const float* w, const f
 int launch_input_grad_gemm16(const float* dy, int64_t ld_dy, const float* w, int64_t n_out, int64_t k_in, const float* r, int64_t ldr, float* c,
                              int64_t ldc, int64_t rows, hipStream_t s, bool* taken, int force_tile, const StltGemmEpi* gelu_bwd) {
   // gelu_bwd != null: the FFN hidden gradient in the epilogue — c = drop(dy·w) ∘ gelu'(r) with r the pre-activation (not added), and the
-  // column sums of c left in gelu_bwd->cs_part (16 partial rows per 256 rows; train.hip: stlt_ffn_hidden_backward_fused)
+  // column sums of c left in gelu_bwd->cs_part (16 partial rows per 256 rows; blocks.hip: stlt_ffn_hidden_bwd)
   *taken = false;
   if (gelu_bwd && (!r || !gelu_bwd->cs_part)) return stlt_set_error(STLT_EINVAL, "gemm16 (GELU backward): the pre-activation and a column-sum buffer are required");
   // a current transposed copy of the weight (a trainer step refreshed it: wt_cache.hip): the product is a forward product dX = dY·(Wt)ᵀ on

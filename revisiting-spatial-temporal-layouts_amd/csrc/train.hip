@@ -62,12 +62,11 @@ static Tape tape_layout(char* base, int64_t B, int64_t T, int64_t N, int64_t d, 
 // a second stream beside the NEXT layer's dX chain: two sets per tower, used by alternate layers (GradBufs).
 struct GradBufs { float *B, *D, *E, *Q, *H; };
 constexpr int DW_EXTRA_SETS = 6;            // + the tower's own set + the second set = 8 layers per grouped launch
-constexpr int64_t DW_DEFER_MAX_ROWS = 4096;  // beyond this the products are long enough by themselves (weight_grad_all) and the sets large
 struct Scratch {
   float *sA, *sB, *sC, *sD, *sE, *sQKV, *sH;  // spatial: (tokp,d) x5, (tokp,3d), (tokp,4d)
   float *tA, *tB, *tC, *tD, *tE, *tQKV, *tH;  // temporal
   GradBufs s2, t2;                  // the second sets
-  GradBufs tx[DW_EXTRA_SETS];       // temporal tower, few rows (<= DW_DEFER_MAX_ROWS): more sets, so that the weight gradients of up to
+  GradBufs tx[DW_EXTRA_SETS];       // temporal tower, few rows (<= STLT_DW_GROUP_MAX_ROWS; beyond it the sets are large): more sets, so that the weight gradients of up to
   int n_tx;                         //   eight layers run as ONE grouped launch (32 products) instead of one launch per layer
   float* sk2;                       // stream-K partial tiles of the second stream's launches
   float *hA, *hB;                   // head: (bp,d) x2
@@ -77,13 +76,8 @@ struct Scratch {
   size_t slab_floats, bytes;
   float* red_pool;                  // chunks of `red_floats` for the sweep's partial rows while their reductions are deferred (StltReduceDefer)
   size_t red_floats, red_pool_floats;
-  StltReduceDefer* defer = nullptr;
+  StltReduceScope* rs = nullptr;    // the sweep's deferral holder: rs->chunk() is the partial-row scratch of the next producer
 };
-// the partial-row scratch of the next producer: a fresh chunk of the pool while reductions are deferred, else the one shared buffer
-static float* RED(const Scratch& sc) {
-  int err = 0;
-  return stlt_reduce_defer_chunk(sc.defer, sc.red_floats, sc.red, &err);
-}
 
 constexpr int MAX_SPLIT = 32;
 constexpr int AB_MAX_ROWS = 256;  // attention backward: longest sequence (backward.hip: 64 in LDS, up to 256 streamed)
@@ -115,7 +109,7 @@ static Scratch scratch_layout(char* base, int64_t B, int64_t T, int64_t N, int64
   s.red_floats = (size_t)red;
   s.sk = take((int64_t)(STLT_GEMM_SCRATCH_BYTES / sizeof(float)));
   s.t2 = GradBufs{take(btp * d), take(btp * d), take(btp * d), take(btp * 3 * d), take(btp * 4 * d)};
-  s.n_tx = btp <= DW_DEFER_MAX_ROWS ? DW_EXTRA_SETS : 0;
+  s.n_tx = btp <= STLT_DW_GROUP_MAX_ROWS ? DW_EXTRA_SETS : 0;
   for (int i = 0; i < s.n_tx; ++i) s.tx[i] = GradBufs{take(btp * d), take(btp * d), take(btp * d), take(btp * 3 * d), take(btp * 4 * d)};
   // ---- optional parts
   s.red_pool_floats = (size_t)red * 24 < ((size_t)64 << 20) ? (size_t)red * 24 : ((size_t)64 << 20);  // <= 256 MB
@@ -248,20 +242,11 @@ static int weight_grad(const float* dy, int64_t n_out, const float* x, int64_t k
   return launch_reduce_slabs(sc.slabs, n_out * k_in, split, g_w, n_out * k_in, 1, s);
 }
 
-// C (rows, k_in) = dY (rows, n_out)·W (n_out, k_in) (+ R): the input gradient of a Linear.  With the opt-in split-bf16 products
-// switched on and a launch they take, W is transposed into the (then unused) split-K slab buffer and the product runs as the
-// NT form the split-bf16 kernel has (gemm_bf16x3.hip: launch_input_grad_bf16x3); otherwise the f32-MFMA NN kernel.
+// The sweep's input-gradient products (common.h: stlt_input_grad): while stream-K scratch is lent the split-K slab buffer is unused and
+// takes the transposed weight of the opt-in split-bf16 form.
 static int dx_product(const float* dy, int64_t ld_dy, const float* w, int64_t n_out, int64_t k_in, const float* r, int64_t ldr, float* c,
                       int64_t ldc, int64_t rows, const Scratch& sc, hipStream_t s) {
-  if (sc.sk && (size_t)(n_out * k_in) <= sc.slab_floats) {
-    bool taken = false;
-    TRY(launch_input_grad_bf16x3(dy, ld_dy, w, n_out, k_in, r, ldr, c, ldc, rows, sc.slabs, s, &taken));
-    if (taken) return 0;
-  }
-  bool small = false;  // under-filled launches (few rows): whole small tiles, W read as it lies (gemm16.hip)
-  TRY(launch_input_grad_gemm16(dy, ld_dy, w, n_out, k_in, r, ldr, c, ldc, rows, s, &small));
-  if (small) return 0;
-  return launch_gemm(0, 1, dy, ld_dy, w, k_in, nullptr, r, ldr, c, ldc, 0, rows, k_in, n_out, 1, STLT_ACT_NONE, s);
+  return stlt_input_grad(dy, ld_dy, w, n_out, k_in, r, ldr, c, ldc, rows, sc.sk ? sc.slabs : nullptr, sc.slab_floats, s);
 }
 
 // The weight gradients of a layer as ONE grouped stream-K launch (gemm.hip: launch_weight_grad_group) when stream-K
@@ -272,7 +257,7 @@ static int weight_grad_all(const StltWeightGradItem* items, int n, const Scratch
   // Grouping pays where the products are launch-bound (the temporal tower at 64 clips: 54 k-steps per workgroup for all four,
   // 322 -> 266 us); with long contractions (the spatial tower: 378 k-steps per workgroup) the four separate launches are
   // slightly faster — three interleaved A/B pairs of the 64-clip step: 27.17 ms grouped everywhere, 27.07 ms with this limit
-  static const int64_t max_rows = [] { const char* e = getenv("STLT_GEMM_GROUP_DW_MAXROWS"); return e ? (int64_t)atoll(e) : (int64_t)4096; }();
+  static const int64_t max_rows = [] { const char* e = getenv("STLT_GEMM_GROUP_DW_MAXROWS"); return e ? (int64_t)atoll(e) : STLT_DW_GROUP_MAX_ROWS; }();
   int64_t rows = 0;
   for (int i = 0; i < n; ++i) if (items[i].rows > rows) rows = items[i].rows;
   if (grouped && rows <= max_rows && sc.sk && stlt_gemm_has_scratch()) return launch_weight_grad_group(items, n, s);
@@ -280,55 +265,19 @@ static int weight_grad_all(const StltWeightGradItem* items, int n, const Scratch
   return 0;
 }
 
-// dh = df·W2 followed by du = drop(dh) ∘ gelu'(u) and lin1_b += column sums of du.  Fused (default): the activation
-// derivative, the dropout mask and the column sums ride in the product's epilogue / fix-up (gemm.hip: STLT_ACT_GELU_BWD) and
-// one reduction finishes the bias gradient; STLT_FUSE_GELU_BWD=0 keeps the stand-alone pass behind the product (A/B runs).
-static int ffn_hidden_backward(const float* df, const float* lin2_w, const float* u, float* du, int64_t rows, int64_t d, float* g_lin1_b,
-                               const Scratch& sc, StltDrop dr, uint32_t site, const int* drop_rows, hipStream_t s);
-}  // namespace
-// The same for the block-level training calls (blocks.hip): du = drop(df·W2) ∘ gelu'(u) in the dX product's epilogue, lin1_b += colsum(du)
-// through `cs_part` (>= ceil(rows / 256) * 16 * 4d floats; with deferred reductions a chunk of the caller's pool).  Needs lent stream-K
-// scratch on the calling thread like every under-filled product; *taken = false when the fused form does not apply.
-int stlt_ffn_hidden_backward_fused(const float* df, const float* lin2_w, const float* u, float* du, int64_t rows, int64_t d, float* g_lin1_b,
-                                   float* cs_part, StltDrop dr, uint32_t site, hipStream_t s, bool* taken) {
-  static const bool fused = [] { const char* e = getenv("STLT_FUSE_GELU_BWD"); return e ? atoi(e) != 0 : true; }();
-  *taken = false;
-  if (!fused || !g_lin1_b || !cs_part || d % 32 != 0 || stlt_split_bf16_takes(rows, 4 * d, d, d, d)) return 0;
-  *taken = true;
-  const StltGemmEpi epi{dr, site, nullptr, cs_part};
-  bool small = false;  // under-filled launches (the fusion models' 2048 / 2112-row blocks): whole small tiles with the same epilogue (gemm16.hip)
-  if (int e = launch_input_grad_gemm16(df, d, lin2_w, d, 4 * d, u, 4 * d, du, 4 * d, rows, s, &small, 0, &epi)) return e;
-  if (!small) { if (int e = launch_gemm(0, 1, df, d, lin2_w, 4 * d, nullptr, u, 4 * d, du, 4 * d, 0, rows, 4 * d, d, 1, STLT_ACT_GELU_BWD, s, &epi)) return e; }
-  return launch_reduce_slabs(cs_part, 4 * d, (int)((rows + 255) / 256 * 16), g_lin1_b, 4 * d, 1, s);
-}
-namespace {
-static int ffn_hidden_backward(const float* df, const float* lin2_w, const float* u, float* du, int64_t rows, int64_t d, float* g_lin1_b,
-                               const Scratch& sc, StltDrop dr, uint32_t site, const int* drop_rows, hipStream_t s) {
-  static const bool fused = [] { const char* e = getenv("STLT_FUSE_GELU_BWD"); return e ? atoi(e) != 0 : true; }();
-  if (fused && g_lin1_b && d % 32 == 0 && !(sc.sk && stlt_split_bf16_takes(rows, 4 * d, d, d, d))) {  // (the split-bf16 product has no GELU-backward epilogue)
-    float* cs = RED(sc);
-    const StltGemmEpi epi{dr, site, drop_rows, cs};
-    bool small = false;  // the temporal tower at the reference's default batch (2048 rows): whole small tiles with the same epilogue (gemm16.hip)
-    TRY(launch_input_grad_gemm16(df, d, lin2_w, d, 4 * d, u, 4 * d, du, 4 * d, rows, s, &small, 0, &epi));
-    if (!small) TRY(launch_gemm(0, 1, df, d, lin2_w, 4 * d, nullptr, u, 4 * d, du, 4 * d, 0, rows, 4 * d, d, 1, STLT_ACT_GELU_BWD, s, &epi));
-    return launch_reduce_slabs(cs, 4 * d, (int)((rows + 255) / 256 * 16), g_lin1_b, 4 * d, 1, s);
-  }
-  TRY(dx_product(df, d, lin2_w, d, 4 * d, nullptr, 0, du, 4 * d, rows, sc, s));  // dh
-  if (g_lin1_b) return launch_gelu_bwd_colsum(du, u, du, rows, 4 * d, g_lin1_b, RED(sc), s, dr, site, drop_rows);  // du; lin1_b += colsum(du)
-  return launch_gelu_bwd(du, u, du, rows * 4 * d, s, dr, site, drop_rows, 4 * d);
-}
+// the two half-blocks of an encoder layer as the shared training half-blocks take them (common.h)
+static stlt_ffn_block_params ffn_half(const stlt_layer_params& l) { return {l.lin1_w, l.lin1_b, l.lin2_w, l.lin2_b, l.norm2_w, l.norm2_b}; }
+static stlt_attn_block_params attn_half(const stlt_layer_params& l) { return {l.in_proj_w, l.in_proj_b, l.out_proj_w, l.out_proj_b, l.norm1_w, l.norm1_b}; }
 
 // backward of one encoder layer.  dy: gradient wrt the layer output (M,d) in bufA; on return bufA holds the gradient
 // wrt the layer input.  bufB / bufC / bufD / bufE (M,d), bufQ (M,3d), bufH (M,4d) are scratch with zero row padding.
-// The four output gradients of the layer's Linears (df, du, da, dqkv) stay alive until the end of the layer, where their
-// weight gradients run as one grouped launch: df in bufD (dropout on: the gradient wrt the un-dropped branch output,
-// ds * mask / (1-p)) or bufB (dropout off: the residual-path gradient is the branch gradient), du in bufH, da in bufE,
-// dqkv in bufQ.
+// The four output gradients of the layer's Linears stay alive until the end of the layer, where their weight gradients run as one
+// grouped launch: df in bufD / da in bufE (dropout off: df in bufB, the residual-path gradient — StltHalfBwd::branch), du in bufH, dqkv in bufQ.
 static int layer_backward(const stlt_layer_params& lp, const stlt_layer_params* g, const LayerTape& t, int64_t d, int64_t H,
                           int64_t M, int64_t Mp, int64_t S, int64_t L, const uint8_t* kpm, int causal, float* bufA, float* bufB,
                           float* bufC, float* bufD, float* bufE, float* bufQ, float* bufH, const Scratch& sc, StltDrop dr, uint32_t site0,
                           hipStream_t s, const AttnBwdRagged* rg = nullptr, DwQueue* q = nullptr) {
-  auto G = [&](const float* stlt_layer_params::*m) -> float* { return g ? const_cast<float*>(g->*m) : nullptr; };
+  const stlt_layer_params gl = g ? *g : stlt_layer_params{};  // null members are skipped
   // with a queue, the layer takes the next set of operand buffers (waiting for the flush that still reads it, if any) and leaves its
   // four weight-gradient products with the queue
   int set_idx = 0;
@@ -338,33 +287,21 @@ static int layer_backward(const stlt_layer_params& lp, const stlt_layer_params* 
     bufB = gb.B; bufD = gb.D; bufE = gb.E; bufQ = gb.Q; bufH = gb.H;
   }
   StltGemmWgCap chain_cap(q && q->side && q->side->on ? dx_chain_wg_cap() : 0);
-  float* df = dr.thr ? bufD : bufB;   // gradient wrt f (after the dropout mask)
-  float* ds1 = dr.thr ? bufB : bufE;  // residual-path gradient behind norm1 (bufB's ds2 is dead by then when dropout is on)
-  float* da = bufE;                   // gradient wrt a
-  // y = LN2(x1 + drop(f))
-  TRY(launch_ln_bwd(bufA, d, t.x1, d, t.f, d, lp.norm2_w, 1e-5f, M, d, bufB, d, G(&stlt_layer_params::norm2_w),
-                    G(&stlt_layer_params::norm2_b), RED(sc), s, dr, site0 + 3, bufD, 0,
-                    G(&stlt_layer_params::lin2_b)));                                               // bufB = ds2, df; lin2_b += colsum(df)
-  // f = h·W2ᵀ + b2
-  // h = drop(gelu(u)): bufH = du = drop(df·W2) ∘ gelu'(u); lin1_b += colsum(du)
-  TRY(ffn_hidden_backward(df, lp.lin2_w, t.u, bufH, M, d, G(&stlt_layer_params::lin1_b), sc, dr, site0 + 2, nullptr, s));
-  // u = x1·W1ᵀ + b1
-  TRY(dx_product(bufH, 4 * d, lp.lin1_w, 4 * d, d, bufB, d, bufC, d, M, sc, s));  // bufC = dx1 = du·W1 + ds2
-  // x1 = LN1(x + drop(a))
-  TRY(launch_ln_bwd(bufC, d, t.x, d, t.a, d, lp.norm1_w, 1e-5f, M, d, ds1, d, G(&stlt_layer_params::norm1_w),
-                    G(&stlt_layer_params::norm1_b), RED(sc), s, dr, site0 + 1, bufE, 0,
-                    G(&stlt_layer_params::out_proj_b)));                                           // ds1, da; out_proj_b += colsum(da)
-  // a = ctx·Woᵀ + bo
-  TRY(dx_product(da, d, lp.out_proj_w, d, d, nullptr, 0, bufC, d, M, sc, s));  // bufC = dctx
+  // y = LN2(x1 + drop(f)), f = h·W2ᵀ + b2, h = drop(gelu(u)), u = x1·W1ᵀ + b1: bufB = ds2, df, bufH = du, bufC = dx1 = du·W1 + ds2
+  const StltHalfBwd ffn{bufB, bufD, bufH, bufC, sc.rs, sc.sk ? sc.slabs : nullptr, sc.slab_floats};
+  TRY(stlt_ffn_half_bwd_train(ffn_half(lp), ffn_half(gl), STLT_ACT_GELU, bufA, t.x1, t.u, t.h, t.f, 1e-5f, M, d, dr, dr, site0 + 2, nullptr, ffn, s));
+  // x1 = LN1(x + drop(a)), a = ctx·Woᵀ + bo: ds1 (in bufB when dropout is on: its ds2 is dead by then), da in bufE, bufC = dctx
+  const StltHalfBwd att{dr.thr ? bufB : bufE, bufE, nullptr, bufC, sc.rs, ffn.wt, ffn.wt_floats};
+  TRY(stlt_attn_half_bwd_train(attn_half(lp), attn_half(gl), bufC, t.x, t.a, 1e-5f, M, d, dr, site0 + 1, nullptr, att, s));
   // ctx = attention(qkv) with dropout on the probabilities
-  TRY(launch_attn_bwd(t.qkv, bufC, kpm, causal, S, L, H, d / H, bufQ, s, dr, site0, G(&stlt_layer_params::in_proj_b), RED(sc), rg));  // bufQ = dqkv; in_proj_b += colsum(dqkv)
+  TRY(launch_attn_bwd(t.qkv, bufC, kpm, causal, S, L, H, d / H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), rg));  // bufQ = dqkv; in_proj_b += colsum(dqkv)
   // qkv = x·Winᵀ + bin
-  TRY(dx_product(bufQ, 3 * d, lp.in_proj_w, 3 * d, d, ds1, d, bufA, d, M, sc, s));  // bufA = dx = dqkv·Win + ds1
+  TRY(dx_product(bufQ, 3 * d, lp.in_proj_w, 3 * d, d, att.ds, d, bufA, d, M, sc, s));  // bufA = dx = dqkv·Win + ds1
   // the four weight gradients (off the dX chain): one grouped launch
-  const StltWeightGradItem items[4] = {{df, d, t.h, 4 * d, Mp, G(&stlt_layer_params::lin2_w)},
-                                       {bufH, 4 * d, t.x1, d, Mp, G(&stlt_layer_params::lin1_w)},
-                                       {da, d, t.ctx, d, Mp, G(&stlt_layer_params::out_proj_w)},
-                                       {bufQ, 3 * d, t.x, d, Mp, G(&stlt_layer_params::in_proj_w)}};
+  const StltWeightGradItem items[4] = {{ffn.branch(dr), d, t.h, 4 * d, Mp, stlt_grad(gl.lin2_w)},
+                                       {bufH, 4 * d, t.x1, d, Mp, stlt_grad(gl.lin1_w)},
+                                       {att.branch(dr), d, t.ctx, d, Mp, stlt_grad(gl.out_proj_w)},
+                                       {bufQ, 3 * d, t.x, d, Mp, stlt_grad(gl.in_proj_w)}};
   if (q) {
     for (int i = 0; i < 4; ++i) q->items[q->n_items++] = items[i];
     q->chunk_sets[q->layers_in_chunk++] = set_idx;
@@ -437,12 +374,8 @@ static int layer_forward(const stlt_layer_params& lp, int64_t d, int64_t H, cons
     ctx = g_ctx;
     x = g_x;
   }
-  TRY(launch_linear(ctx, d, lp.out_proj_w, lp.out_proj_b, t.a, d, n, d, d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(t.a, d, x, d, lp.norm1_w, lp.norm1_b, 1e-5f, n, d, t.x1, d, s, dr, site0 + 1, rows));
-  TRY(launch_linear_gelu_keep(t.x1, d, lp.lin1_w, lp.lin1_b, t.u, t.h, n, 4 * d, d, dr, site0 + 2, rows, s));
-  TRY(launch_linear(t.h, 4 * d, lp.lin2_w, lp.lin2_b, t.f, d, n, d, 4 * d, STLT_ACT_NONE, s));
-  TRY(launch_add_layernorm(t.f, d, t.x1, d, lp.norm2_w, lp.norm2_b, 1e-5f, n, d, y, d, s, dr, site0 + 3, rows));
-  return 0;
+  TRY(stlt_attn_half_fwd_train(attn_half(lp), ctx, x, 1e-5f, n, d, t.a, t.x1, dr, site0 + 1, rows, s));
+  return stlt_ffn_half_fwd_train(ffn_half(lp), STLT_ACT_GELU, t.x1, 1e-5f, n, d, t.u, t.h, t.f, y, dr, dr, site0 + 2, rows, s);
 }
 
 static int zero_rows(float* buf, int64_t width, int64_t r0, int64_t r1, hipStream_t s) {
@@ -459,38 +392,32 @@ static int layer_backward_tail(const stlt_layer_params& lp, const stlt_layer_par
                                int64_t M, int64_t Mp, int64_t S, int64_t L, const uint8_t* kpm, int causal, const int* rows, int64_t n,
                                const float* dy, float* bufA, float* bufB, float* bufC, float* bufD, float* bufE, float* bufQ, float* bufH,
                                const Scratch& sc, StltDrop dr, uint32_t site0, hipStream_t s, const AttnBwdRagged* rg) {
-  auto G = [&](const float* stlt_layer_params::*m) -> float* { return g ? const_cast<float*>(g->*m) : nullptr; };
+  const stlt_layer_params gl = g ? *g : stlt_layer_params{};
   const int64_t np = up32(n);
-  float* df = dr.thr ? bufD : bufB;
-  float* ds1 = dr.thr ? bufB : bufE;
-  float* da = bufE;
   TRY(zero_rows(bufB, d, n, np, s));
   TRY(zero_rows(bufD, d, n, np, s));
   TRY(zero_rows(bufE, d, n, np, s));
   TRY(zero_rows(bufH, 4 * d, n, np, s));
-  // y = LN2(x1 + drop(f))
-  TRY(launch_ln_bwd(dy, d, t.x1, d, t.f, d, lp.norm2_w, 1e-5f, n, d, bufB, d, G(&stlt_layer_params::norm2_w),
-                    G(&stlt_layer_params::norm2_b), RED(sc), s, dr, site0 + 3, bufD, 0, G(&stlt_layer_params::lin2_b), rows));
-  TRY(ffn_hidden_backward(df, lp.lin2_w, t.u, bufH, n, d, G(&stlt_layer_params::lin1_b), sc, dr, site0 + 2, rows, s));  // bufH = du
-  TRY(dx_product(bufH, 4 * d, lp.lin1_w, 4 * d, d, bufB, d, bufC, d, n, sc, s));  // bufC = dx1 = du·W1 + ds2
+  // the feed-forward half on the picked rows: bufB = ds2, df, bufH = du, bufC = dx1 = du·W1 + ds2
+  const StltHalfBwd ffn{bufB, bufD, bufH, bufC, sc.rs, sc.sk ? sc.slabs : nullptr, sc.slab_floats};
+  TRY(stlt_ffn_half_bwd_train(ffn_half(lp), ffn_half(gl), STLT_ACT_GELU, dy, t.x1, t.u, t.h, t.f, 1e-5f, n, d, dr, dr, site0 + 2, rows, ffn, s));
   // x1 = LN1(x[rows] + drop(a)), a = ctx[rows]·Woᵀ + bo: gather the two inputs again (bufQ is free until the attention backward)
   float* g_x = bufQ;
   float* g_ctx = bufQ + np * d;
   TRY(launch_gather_rows(t.x, d, rows, n, d, g_x, s));
   TRY(launch_gather_rows(t.ctx, d, rows, n, d, g_ctx, s));
-  TRY(launch_ln_bwd(bufC, d, g_x, d, t.a, d, lp.norm1_w, 1e-5f, n, d, ds1, d, G(&stlt_layer_params::norm1_w),
-                    G(&stlt_layer_params::norm1_b), RED(sc), s, dr, site0 + 1, bufE, 0, G(&stlt_layer_params::out_proj_b), rows));  // ds1, da
-  TRY(dx_product(da, d, lp.out_proj_w, d, d, nullptr, 0, bufC, d, n, sc, s));  // bufC = dctx of the picked rows
+  const StltHalfBwd att{dr.thr ? bufB : bufE, bufE, nullptr, bufC, sc.rs, ffn.wt, ffn.wt_floats};  // ds1, da; bufC = dctx of the picked rows
+  TRY(stlt_attn_half_bwd_train(attn_half(lp), attn_half(gl), bufC, g_x, t.a, 1e-5f, n, d, dr, site0 + 1, rows, att, s));
   // the weight gradients of the three Linears that ran on the picked rows: one grouped launch, before bufH / bufQ are reused
-  const StltWeightGradItem items[3] = {{df, d, t.h, 4 * d, np, G(&stlt_layer_params::lin2_w)},
-                                       {bufH, 4 * d, t.x1, d, np, G(&stlt_layer_params::lin1_w)},
-                                       {da, d, g_ctx, d, np, G(&stlt_layer_params::out_proj_w)}};
+  const StltWeightGradItem items[3] = {{ffn.branch(dr), d, t.h, 4 * d, np, stlt_grad(gl.lin2_w)},
+                                       {bufH, 4 * d, t.x1, d, np, stlt_grad(gl.lin1_w)},
+                                       {att.branch(dr), d, g_ctx, d, np, stlt_grad(gl.out_proj_w)}};
   TRY(weight_grad_all(items, 3, sc, s));
   // the other rows' attention outputs were never read: their dctx is zero
   TRY(launch_scatter_rows(bufC, rows, n, d, bufH, M, s));                                           // bufH (as M x d) = dctx
-  TRY(launch_attn_bwd(t.qkv, bufH, kpm, causal, S, L, H, d / H, bufQ, s, dr, site0, G(&stlt_layer_params::in_proj_b), RED(sc), rg));  // bufQ = dqkv
-  TRY(weight_grad(bufQ, 3 * d, t.x, d, Mp, G(&stlt_layer_params::in_proj_w), sc, s));
-  TRY(launch_scatter_rows(ds1, rows, n, d, bufC, M, s));                                            // residual path: ds1 on the picked rows only
+  TRY(launch_attn_bwd(t.qkv, bufH, kpm, causal, S, L, H, d / H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), rg));  // bufQ = dqkv
+  TRY(weight_grad(bufQ, 3 * d, t.x, d, Mp, stlt_grad(gl.in_proj_w), sc, s));
+  TRY(launch_scatter_rows(att.ds, rows, n, d, bufC, M, s));                                            // residual path: ds1 on the picked rows only
   TRY(dx_product(bufQ, 3 * d, lp.in_proj_w, 3 * d, d, bufC, d, bufA, d, M, sc, s));  // bufA = dx = dqkv·Win + ds1
   // the 4d-wide view of bufH lost its zero rows past M to the dctx image only below M*d floats: nothing to restore
   return 0;
@@ -614,22 +541,12 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
   if (scratch_bytes < sc.bytes) return stlt_set_error(STLT_EWORKSPACE, "scratch %zu B < required %zu B", scratch_bytes, sc.bytes);
   // the sweep's ~55 partial-row reductions (LayerNorm / bias gradients) are collected and run as a few batched launches
   // (STLT_TRAIN_DEFER_REDUCE=0: one launch each, A/B runs)
-  const bool defer_on = defer_wanted();
-  StltReduceDefer defer;
-  defer.s = (hipStream_t)stream;
-  defer.pool = sc.red_pool;
-  defer.pool_floats = sc.red_pool_floats;
-  struct DeferGuard {
-    StltReduceDefer* d;
-    explicit DeferGuard(StltReduceDefer* x) : d(x) { stlt_reduce_defer_set(d); }
-    ~DeferGuard() { if (d && d->n > 0) (void)stlt_reduce_defer_flush(d); stlt_reduce_defer_set(nullptr); }  // error exits: what the producers left is still reduced
-  } defer_guard(defer_on && sc.red_pool ? &defer : nullptr);
-  if (defer_on && sc.red_pool) sc.defer = &defer;
+  StltReduceScope red(sc.red_pool, sc.red_pool_floats, sc.red, sc.red_floats, s);  // (no pool was carved while deferral is off)
+  sc.rs = &red;
   int64_t tok = B * T * N, BT = B * T;
   int64_t tokp = t.tokp, btp = t.btp;
   StltGemmScratch gemm_scratch(sc.sk, STLT_GEMM_SCRATCH_BYTES);
   const StltDrop dr = stlt_drop_make(dropout_p, dropout_seed);
-  auto W = [](const float* q) { return const_cast<float*>(q); };
   // Skip-padding: the tape holds the real rows only (same buffers, fewer rows).  The weight-gradient products
   // contract over the row count rounded up to 32, so the gradient-side operands' rows between the count and its
   // round-up are zeroed here (the padded schedule never dirties them; a ragged row count changes every step).
@@ -694,19 +611,19 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
     TRY(dwq_flush(q_tp, sc, s));
   } else if (do_upper) {
   // ---- prediction head (models.py:162-163): logits = z2·W2ᵀ+b2, z2 = LN(z1), z1 = gelu(u0), u0 = h0·W1ᵀ+b1
-  if (g->fc2_w) TRY(launch_small_gemm(dlogits, 1, K, t.z2, d, 1, W(g->fc2_w), d, K, d, B, 1, s));   // (K,d) += dlogitsᵀ·z2
-  if (g->fc2_b) TRY(launch_colsum_acc(dlogits, K, B, K, W(g->fc2_b), RED(sc), s));
+  if (g->fc2_w) TRY(launch_small_gemm(dlogits, 1, K, t.z2, d, 1, stlt_grad(g->fc2_w), d, K, d, B, 1, s));   // (K,d) += dlogitsᵀ·z2
+  if (g->fc2_b) TRY(launch_colsum_acc(dlogits, K, B, K, stlt_grad(g->fc2_b), red.chunk(), s));
   TRY(launch_small_gemm(dlogits, K, 1, p->fc2_w, d, 1, sc.hA, d, B, d, K, 0, s));                   // hA = dz2
-  TRY(launch_ln_bwd(sc.hA, d, t.z1, d, nullptr, 0, p->head_ln_w, p->ln_eps, B, d, sc.hB, d, W(g->head_ln_w), W(g->head_ln_b),
-                    RED(sc), s));                                                                    // hB = dz1
+  TRY(launch_ln_bwd(sc.hA, d, t.z1, d, nullptr, 0, p->head_ln_w, p->ln_eps, B, d, sc.hB, d, stlt_grad(g->head_ln_w), stlt_grad(g->head_ln_b),
+                    red.chunk(), s));                                                                    // hB = dz1
   TRY(launch_gelu_bwd(sc.hB, t.u0, sc.hB, B * d, s));                                               // hB = du0
   // the two d x d products of fc1 go to the MFMA kernel (it contracts over multiples of 32 clips; the strided kernel takes the rest)
   if (g->fc1_w) {                                                                                   // (d,d) += du0ᵀ·h0
     const int64_t Bf = B / 32 * 32;
-    if (Bf > 0) TRY(launch_gemm(1, 1, sc.hB, d, t.h0, d, nullptr, W(g->fc1_w), d, W(g->fc1_w), d, 0, d, d, Bf, 1, STLT_ACT_NONE, s));
-    if (B > Bf) TRY(launch_small_gemm(sc.hB + Bf * d, 1, d, t.h0 + Bf * d, d, 1, W(g->fc1_w), d, d, d, B - Bf, 1, s));
+    if (Bf > 0) TRY(launch_gemm(1, 1, sc.hB, d, t.h0, d, nullptr, stlt_grad(g->fc1_w), d, stlt_grad(g->fc1_w), d, 0, d, d, Bf, 1, STLT_ACT_NONE, s));
+    if (B > Bf) TRY(launch_small_gemm(sc.hB + Bf * d, 1, d, t.h0 + Bf * d, d, 1, stlt_grad(g->fc1_w), d, d, d, B - Bf, 1, s));
   }
-  if (g->fc1_b) TRY(launch_colsum_acc(sc.hB, d, B, d, W(g->fc1_b), RED(sc), s));
+  if (g->fc1_b) TRY(launch_colsum_acc(sc.hB, d, B, d, stlt_grad(g->fc1_b), red.chunk(), s));
   TRY(launch_gemm(0, 1, sc.hB, d, p->fc1_w, d, nullptr, nullptr, 0, sc.hA, d, 0, B, d, d, 1, STLT_ACT_NONE, s));  // hA = dh0
   // ---- temporal transformer
   int64_t l_tp = p->n_temporal - 1;
@@ -724,14 +641,14 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
                        ragged ? &rg_tp : nullptr, &q_tp));
     TRY(dwq_flush(q_tp, sc, s));
   }  // upper half: sc.tA now holds the gradient wrt the temporal tower's input
-  if (!do_lower) { TRY(stlt_reduce_defer_flush(sc.defer)); return dw_side_join(&side, s); }
+  if (!do_lower) { TRY(red.flush()); return dw_side_join(&side, s); }
   // ---- frames embeddings (models.py:98-111).  The gradient wrt the frames' CLS rows goes to tC, a chain-only buffer: the temporal
   // tower's last weight-gradient products may still be reading tB / tD / tE / tQKV / tH on the side stream.
   float* d_cls = sc.tC;
-  TRY(launch_ln_bwd(sc.tA, d, t.s_frames, d, nullptr, 0, p->frames_ln_w, p->ln_eps, BT, d, d_cls, d, W(g->frames_ln_w),
-                    W(g->frames_ln_b), RED(sc), s, dr, 0, nullptr, STLT_SITE_FRAMES));                // d_cls = gradient wrt the frames' CLS rows
+  TRY(launch_ln_bwd(sc.tA, d, t.s_frames, d, nullptr, 0, p->frames_ln_w, p->ln_eps, BT, d, d_cls, d, stlt_grad(g->frames_ln_w),
+                    stlt_grad(g->frames_ln_b), red.chunk(), s, dr, 0, nullptr, STLT_SITE_FRAMES));                // d_cls = gradient wrt the frames' CLS rows
   const bool dense_scatter = !ragged && !sp_tail;  // padded dense schedule: the CLS rows sit at stride N in the token buffer
-  TRY(launch_frames_bwd(d_cls, in->frame_types, B, T, N, d, dense_scatter ? sc.sA : nullptr, W(g->pos_emb), W(g->type_emb), RED(sc), s,
+  TRY(launch_frames_bwd(d_cls, in->frame_types, B, T, N, d, dense_scatter ? sc.sA : nullptr, stlt_grad(g->pos_emb), stlt_grad(g->type_emb), red.chunk(), s,
                         ragged ? ix.f_row_of : nullptr));
   // ---- spatial transformer
   int64_t l_sp = p->n_spatial - 1;
@@ -747,11 +664,11 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
     TRY(layer_backward(p->spatial[l], g->spatial ? &g->spatial[l] : nullptr, t.sp[l], d, H, tok, tokp, B * T, N, in->kpm_boxes, 0,
                        sc.sA, sc.sB, sc.sC, sc.sD, sc.sE, sc.sQKV, sc.sH, sc, dr, (uint32_t)(8 * (l + 1)), s, ragged ? &rg_sp : nullptr, &q_sp));
   // ---- category / box / score embeddings (models.py:29-39); sC for the same reason as tC above
-  TRY(launch_ln_bwd(sc.sA, d, t.s_embed, d, nullptr, 0, p->emb_ln_w, p->ln_eps, tok, d, sc.sC, d, W(g->emb_ln_w), W(g->emb_ln_b),
-                    RED(sc), s, dr, 0, nullptr, STLT_SITE_EMBED));
-  TRY(launch_embed_bwd(sc.sC, in->categories, in->boxes, in->scores, p->n_categories, tok, d, W(g->cat_emb), W(g->box_w),
-                       W(g->box_b), W(g->score_w), W(g->score_b), RED(sc), s, ragged ? ix.t_orig : nullptr));
-  TRY(stlt_reduce_defer_flush(sc.defer));
+  TRY(launch_ln_bwd(sc.sA, d, t.s_embed, d, nullptr, 0, p->emb_ln_w, p->ln_eps, tok, d, sc.sC, d, stlt_grad(g->emb_ln_w), stlt_grad(g->emb_ln_b),
+                    red.chunk(), s, dr, 0, nullptr, STLT_SITE_EMBED));
+  TRY(launch_embed_bwd(sc.sC, in->categories, in->boxes, in->scores, p->n_categories, tok, d, stlt_grad(g->cat_emb), stlt_grad(g->box_w),
+                       stlt_grad(g->box_b), stlt_grad(g->score_w), stlt_grad(g->score_b), red.chunk(), s, ragged ? ix.t_orig : nullptr));
+  TRY(red.flush());
   return dw_side_join(&side, s);
 }
 

@@ -154,7 +154,7 @@ def test_split_bf16_wide_dynamic_range(pkg, split):
 
 def test_split_bf16_training_forward_gives_the_same_loss_and_gradients(pkg, split):
     """cfg2 / 64 clips, dropout 0.1 (counter-based masks: the same in both runs): with the forward and
-    input-gradient products of the step on the split-bf16 kernel (train.hip: dx_product transposes the weight and runs the NT
+    input-gradient products of the step on the split-bf16 kernel (blocks.hip: stlt_input_grad transposes the weight and runs the NT
     form), the loss and every parameter gradient agree with the f32 run to rounding level; the weight-gradient products stay
     on the f32 kernel."""
     c = pkg.synth.CONFIGS["cfg2"]
