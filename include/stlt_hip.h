@@ -27,6 +27,19 @@
  *     the same device are serialised from their first fork to their join); different contexts never interact, so two
  *     training loops in one process — or a plain autograd backward of another model in the middle of a trainer's step —
  *     cannot read each other's copies or queue into each other's flush.
+ *   - extents and alignment.  A call reads and writes only the logical extent of each operand: rows of `ld` elements are touched in
+ *     their first `cols` columns only (gap columns ld - cols are neither read nor written), nothing before the base pointer or after
+ *     the last logical element — two documented exceptions: stlt_gemm rounds the contraction length of contraction-major operands up
+ *     to 32 rows, stlt_weight_grad_group takes rows_i in multiples of 32 (the extra rows are the caller's, zero-filled).  Scratch,
+ *     workspace and tape buffers are used inside exactly the bytes their *_bytes function returns.  Every pointer has the natural
+ *     alignment of its element type; each entry point below states which pointers must ALSO be 16-byte aligned (LDS-DMA of whole rows,
+ *     16-byte vector loads / stores) and what it does with one that is not: "routed" = the call runs on a path of four-byte accesses,
+ *     same result to rounding; "refused" = STLT_EINVAL, the message names the pointer, nothing is launched.  A row pitch that must be a
+ *     multiple of 4 floats is stated with the pitch.  torch allocations are 256-byte aligned; a contiguous view such as flat[1:] is not.
+ *     The whole-path, training, block, R3D and data-pipeline entry points REQUIRE 16-byte-aligned buffers throughout (parameters, inputs,
+ *     outputs) and a 256-byte-aligned workspace / tape / scratch.  The forward, training and R3D calls test the latter themselves
+ *     (STLT_EINVAL); a misaligned parameter or input there is the caller's error and is not promised a refusal by name.
+ *     tests/test_pointer_alignment_gpu.py holds every op-level rule.
  *   - plain C: this header compiles as C99 and as C++ (tests/test_host_cpu.py builds a C client against the library).
  */
 #ifndef STLT_HIP_H
@@ -70,7 +83,8 @@ int stlt_ctx_destroy(stlt_ctx* ctx);
 
 /* K1 — CategoryBoxEmbeddings.forward, src/modelling/models.py:29-39.
  * out[t,:] = LN_eps( cat_table[categories[t]] + boxes[t,0:4]·box_w^T + box_b (+ scores[t]*score_w[:,0] + score_b) )
- * scores may be NULL (key absent from the batch, models.py:33).  d % 4 == 0, d <= 2048. */
+ * scores may be NULL (key absent from the batch, models.py:33).  d % 4 == 0, d <= 2048.
+ * Alignment: boxes, cat_table, box_w, box_b, score_w, score_b, ln_w, ln_b, out 16 bytes (refused otherwise); categories 8, scores 4. */
 int stlt_embed_fwd(const int64_t* categories, const float* boxes, const float* scores,
                    const float* cat_table, int64_t n_categories,
                    const float* box_w, const float* box_b, const float* score_w, const float* score_b,
@@ -83,7 +97,10 @@ int stlt_embed_fwd(const int64_t* categories, const float* boxes, const float* s
  * M, N arbitrary.  K % 32 == 0 (every hidden size the released checkpoints use): f32-input MFMA (v_mfma_f32_32x32x2_f32), fp32
  * accumulate.  Any other K (hidden sizes like 100 or 200, which configs.py:92-111 allows): the same product and epilogues on
  * csrc/gemm_any.hip (zero-filled tiles staged through LDS by ordinary loads) — a compatibility path with the same tolerances, not a
- * tuned one. */
+ * tuned one.
+ * Alignment: none beyond 4 bytes.  x or w off a 16-byte boundary, or ldx % 4 != 0, is routed to that compatibility path (four-byte
+ * loads); y off a 16-byte boundary or ldy % 4 != 0 takes guarded scalar stores; bias is read one float at a time.  Gap columns
+ * K .. ldx-1 of x are not read, N .. ldy-1 of y not written. */
 int stlt_linear_fwd(const float* x, int64_t ldx, const float* w, const float* bias,
                     float* y, int64_t ldy, int64_t M, int64_t N, int64_t K, int act, stlt_stream_t stream);
 
@@ -94,7 +111,10 @@ int stlt_linear_fwd(const float* x, int64_t ldx, const float* w, const float* bi
  *   transB=0: b is (N,K) row-major, ldb;  transB=1: b is (K,N) row-major, ldb   (dX = dY·W)
  * r (nullable, ldr) is added in the epilogue (residual gradient).  n_split > 1 splits the contraction: split s writes
  * its partial product to c + s*slab_stride; sum them with stlt_reduce_slabs (deterministic, no atomics).
- * Rows of a contraction-major operand beyond the logical K must be zero-filled by the caller (K is rounded up). */
+ * Rows of a contraction-major operand beyond the logical K must be zero-filled by the caller (K is rounded up).
+ * Alignment, n_split == 1: none beyond 4 bytes — a or b off a 16-byte boundary (or lda / ldb no multiple of 4) is routed to the
+ * compatibility path, r / c off it (or ldr / ldc no multiple of 4) take guarded scalar accesses.  n_split > 1 exists on the LDS-DMA
+ * kernel only: a and b 16 bytes, lda % 4 == ldb % 4 == 0 (refused otherwise); c and slab_stride anywhere on 4 bytes. */
 int stlt_gemm(int transA, int transB, const float* a, int64_t lda, const float* b, int64_t ldb,
               const float* r, int64_t ldr, float* c, int64_t ldc, int64_t slab_stride,
               int64_t M, int64_t N, int64_t K, int n_split, stlt_stream_t stream);
@@ -105,7 +125,9 @@ int stlt_gemm(int transA, int transB, const float* a, int64_t lda, const float* 
  * reference's default batch of 64 clips, the fusion models' 2048 / 2112-row blocks); stlt_linear_small_choice returns the tile
  * (same encoding) that dispatch picks for (M, N, K) — 0: the product stays on the large tiles; STLT_GEMM16=0 in the environment disables the routing.
  * This entry point runs the kernel on any shape it can take (K % 32 == 0, K >= 64, N % 4 == 0, pitches % 4 == 0) with the tile
- * given (tests, A/B measurements); other shapes return STLT_EINVAL.  Same result as stlt_linear_fwd to fp32 rounding. */
+ * given (tests, A/B measurements); other shapes return STLT_EINVAL.  Same result as stlt_linear_fwd to fp32 rounding.
+ * Alignment: x, w, bias, r, y 16 bytes (refused otherwise: this entry point names the kernel).  The routing inside stlt_linear_fwd and
+ * the other callers leaves a product with such a pointer, or with ldy / ldr no multiple of 4, to the large-tile / compatibility kernels. */
 int stlt_linear_small_fwd(const float* x, int64_t ldx, const float* w, const float* bias, const float* r, int64_t ldr, float* y, int64_t ldy,
                           int64_t M, int64_t N, int64_t K, int act, int tile, stlt_stream_t stream);
 int stlt_linear_small_choice(int64_t M, int64_t N, int64_t K);
@@ -115,7 +137,9 @@ int stlt_linear_small_choice(int64_t M, int64_t N, int64_t K);
  * on that tile (columns | rows << 16), always reading w as it lies; tile == 0 routes by the estimate — STLT_EINVAL when the estimate
  * leaves the product to the large tiles (stlt_input_grad_small_choice tells beforehand) — and, when `ctx` holds a current transposed
  * copy of w (stlt_ctx_wt_refresh), runs the product as a forward product on the copy.  n_out % 32 == 0, n_out >= 64, k_in % 4 == 0.
- * Same result as stlt_gemm(0, 1, ...) to rounding.  ctx may be NULL. */
+ * Same result as stlt_gemm(0, 1, ...) to rounding.  ctx may be NULL.
+ * Alignment: dy, w, r, dx 16 bytes; ld_dx, ldr multiples of 4 (tile != 0: refused otherwise; tile == 0: such a product is not this
+ * kernel's and the call returns STLT_EINVAL like any other product the estimate leaves to the large tiles). */
 int stlt_input_grad_small(const float* dy, int64_t ld_dy, const float* w, int64_t n_out, int64_t k_in, const float* r, int64_t ldr, float* dx,
                           int64_t ld_dx, int64_t M, int tile, stlt_ctx* ctx, stlt_stream_t stream);
 int stlt_input_grad_small_choice(int64_t M, int64_t n_out, int64_t k_in);  /* the tile the routing picks for that input gradient, reading w as it lies: columns | rows << 16 (0: large tiles) */
@@ -130,7 +154,8 @@ int stlt_set_gemm_small_tiles(int mode);
  * units idle (fewer tiles than CUs, or a ragged last round) is cut into equal contiguous k-step ranges instead
  * ("stream-K"); tiles computed by more than one workgroup are summed in workgroup order by a second kernel, so results
  * stay deterministic.  The buffer must hold stlt_gemm_scratch_bytes() and may only be reused by work ordered after
- * the launch on its stream.  Pass NULL to withdraw.  The whole-path entry points lend a slice of their workspace. */
+ * the launch on its stream.  Pass NULL to withdraw.  The whole-path entry points lend a slice of their workspace.
+ * The buffer is 16-byte aligned (refused otherwise); partial tiles stay inside its first stlt_gemm_scratch_bytes() bytes. */
 size_t stlt_gemm_scratch_bytes(void);
 int stlt_gemm_set_scratch(void* scratch, size_t bytes);
 /* Weight gradients of several nn.Linear modules in ONE launch (what autograd computes product by product for
@@ -138,10 +163,13 @@ int stlt_gemm_set_scratch(void* scratch, size_t bytes);
  * dy_i (rows_i, n_out_i) and x_i (rows_i, k_in_i) row-major; rows_i a multiple of 32 (rows beyond the logical count
  * must be zero in dy or x); n_out_i, k_in_i multiples of 4; 1..32 items; items with g_w == NULL are skipped.  Needs lent
  * stream-K scratch (stlt_gemm_set_scratch).  One persistent stream-K launch over the concatenated k-step space of the
- * items + one fix-up: deterministic (fixed summation order). */
+ * items + one fix-up: deterministic (fixed summation order).
+ * Alignment: every dy_i and x_i 16 bytes (refused otherwise, the message names the item); g_w_i anywhere on 4 bytes (a g_w off a
+ * 16-byte boundary takes guarded scalar accesses). */
 typedef struct { const float* dy; int64_t n_out; const float* x; int64_t k_in; int64_t rows; float* g_w; } stlt_wgrad_item;
 int stlt_weight_grad_group(const stlt_wgrad_item* items, int n_items, stlt_stream_t stream);
-/* dst[i] = (accumulate ? dst[i] : 0) + sum_s slabs[s*stride + i], i < n */
+/* dst[i] = (accumulate ? dst[i] : 0) + sum_s slabs[s*stride + i], i < n.  Alignment: none beyond 4 bytes — slabs / dst off a 16-byte boundary
+ * or a stride that is no multiple of 4 floats are routed to the element-wise kernel (another, equally fixed, summation order; n below 2^35 there, STLT_EINVAL above). */
 int stlt_reduce_slabs(const float* slabs, int64_t stride, int n_slabs, float* dst, int64_t n, int accumulate,
                       stlt_stream_t stream);
 
@@ -151,7 +179,9 @@ int stlt_reduce_slabs(const float* slabs, int64_t stride, int n_slabs, float* ds
  * ctx[s,i,h,:] = softmax_j( q_i·k_j/sqrt(dh) + M_ij ) v_j with M_ij = -inf if kpm[s,j] or (causal and j>i).
  * Rows whose keys are all masked produce zeros.  1 <= dh <= 256: dh == 64 (every released checkpoint) runs on the MFMA kernels; any
  * other head dim the reference's configs.py:92-111 allows runs on the vector-ALU kernels of csrc/attn_any.hip (at most 1024 keys per
- * sequence in the forward, 256 tokens a side in the backward) — the same arithmetic, masks, dropout indices and tolerances. */
+ * sequence in the forward, 256 tokens a side in the backward) — the same arithmetic, masks, dropout indices and tolerances.
+ * Alignment: dh == 64: qkv and ctx 16 bytes (refused otherwise: K / V rows are staged by LDS-DMA); any other dh: none beyond 4 bytes
+ * (csrc/attn_any.hip falls back to four-byte accesses).  kpm: bytes. */
 int stlt_attn_core_fwd(const float* qkv, const uint8_t* kpm, int causal,
                        int64_t S, int64_t L, int64_t H, int64_t dh, float* ctx, stlt_stream_t stream);
 
@@ -161,7 +191,8 @@ int stlt_attn_core_fwd(const float* qkv, const uint8_t* kpm, int causal,
  * (causal mask of utils/model_utils.py:4-7 + src_key_padding_mask_frames, models.py:142-150).  Sequences of 1 <= L <= 64 tokens
  * (the reference's layouts are T = layout_num_frames + 1 = 17 / 33, datasets.py:97-113; Action Genome 64) and 64-channel heads
  * (d == 64*H); other shapes return STLT_EINVAL (callers use stlt_linear_fwd + stlt_attn_core_fwd).  Same result as that pair to
- * fp32 rounding. */
+ * fp32 rounding.
+ * Alignment (both forms): x, in_proj_w, ctx and qkv_out 16 bytes (refused otherwise); in_proj_b 4 bytes; kpm bytes. */
 int stlt_mhsa_fused_fwd(const float* x, const float* in_proj_w, const float* in_proj_b, const uint8_t* kpm, int64_t S, int64_t L,
                         int64_t H, int64_t d, float* ctx, stlt_stream_t stream);
 /* The same kernel with every option: causal = 0 is the spatial tower's form (key-padding mask only, models.py:68-71; L up to
@@ -181,7 +212,9 @@ int stlt_fused_mhsa_active(int64_t T, int64_t d, int64_t H);
 int stlt_fused_mhsa_used(int64_t S, int64_t L, int64_t d, int64_t H, int causal);
 /* Cross-attention core (CrossAttentionLayer of CAF/CACNF, models.py:362-382; also self-attention on unpacked buffers):
  * queries q (S*Lq rows, stride ldq floats) attend to keys k / values v (S*Lk rows, stride ldkv).  kpm: (S*Lk) bytes over
- * the KEY tokens (pass zeros for no padding mask).  ctx: (S*Lq, H*dh).  causal requires Lq == Lk. */
+ * the KEY tokens (pass zeros for no padding mask).  ctx: (S*Lq, H*dh).  causal requires Lq == Lk.
+ * ldq, ldkv multiples of 4; columns H*dh .. ld-1 of a row are not read.  Alignment: dh == 64: q, k, v, ctx 16 bytes (refused
+ * otherwise); any other dh: none beyond 4 bytes. */
 int stlt_attn_cross_fwd(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const uint8_t* kpm,
                         int causal, int64_t S, int64_t Lq, int64_t Lk, int64_t H, int64_t dh, float* ctx,
                         stlt_stream_t stream);
@@ -189,24 +222,30 @@ int stlt_attn_cross_fwd(const float* q, int64_t ldq, const float* k, const float
 /* K3 on a ragged layout: self-attention over M compacted rows of a packed (M, 3*H*dh) buffer cut into variable-length
  * segments (one frame's objects, one clip's frames) — what STLT_FLAG_SKIP_PADDING runs instead of the padded K3.
  * seg_start[r] / seg_end[r] (int32, device): first row / one past the last row of row r's segment; segments are
- * contiguous and cover [0, M).  ctx[r] = softmax over the keys of r's segment (only those at rows <= r when causal). */
+ * contiguous and cover [0, M).  ctx[r] = softmax over the keys of r's segment (only those at rows <= r when causal).
+ * Alignment: dh == 64: qkv and ctx 16 bytes (refused otherwise); any other dh: none beyond 4 bytes.  seg_start / seg_end: 4 bytes. */
 int stlt_attn_ragged_fwd(const float* qkv, const int32_t* seg_start, const int32_t* seg_end, int causal, int64_t M,
                          int64_t H, int64_t dh, float* ctx, stlt_stream_t stream);
 
 /* Residual + LayerNorm (norm1/norm2 of nn.TransformerEncoderLayer, eps 1e-5; ClassificationHead.layer_norm
- * models.py:159,163 with res == NULL).  out[m,:] = LN_eps( x[m*ldx + :] + res[m*ldres + :] ). */
+ * models.py:159,163 with res == NULL).  out[m,:] = LN_eps( x[m*ldx + :] + res[m*ldres + :] ).
+ * d % 4 == 0, d <= 2048; ldx, ldres, ldout multiples of 4, columns d .. ld-1 neither read nor written.  Alignment: x, res, ln_w, ln_b,
+ * out 16 bytes (refused otherwise). */
 int stlt_add_layernorm_fwd(const float* x, int64_t ldx, const float* res, int64_t ldres,
                            const float* ln_w, const float* ln_b, float eps,
                            int64_t M, int64_t d, float* out, int64_t ldout, stlt_stream_t stream);
 
 /* K7 — CLS select (models.py:79) + FramesEmbeddings.forward (models.py:98-111).
- * out[b,t,:] = LN_eps( spatial[(b*T+t)*row_stride + :] + pos_table[t] + type_table[frame_types[b,t]] ). */
+ * out[b,t,:] = LN_eps( spatial[(b*T+t)*row_stride + :] + pos_table[t] + type_table[frame_types[b,t]] ).
+ * row_stride % 4 == 0; only the first d floats of a row are read.  Alignment: spatial, pos_table, type_table, ln_w, ln_b, out 16 bytes
+ * (refused otherwise); frame_types 8. */
 int stlt_frames_embed_fwd(const float* spatial, int64_t row_stride, const int64_t* frame_types,
                           const float* pos_table, const float* type_table,
                           const float* ln_w, const float* ln_b, float eps,
                           int64_t B, int64_t T, int64_t d, float* out, stlt_stream_t stream);
 
-/* K8a — Stlt.forward gather, models.py:189-192: out[b,:] = x[b, lengths[b]-1, :] for batch-major x (B,T,d). */
+/* K8a — Stlt.forward gather, models.py:189-192: out[b,:] = x[b, lengths[b]-1, :] for batch-major x (B,T,d).
+ * Alignment: x and out 16 bytes (refused otherwise); lengths 8. */
 int stlt_gather_last_fwd(const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t d,
                          float* out, stlt_stream_t stream);
 
@@ -215,7 +254,8 @@ int stlt_gather_last_fwd(const float* x, const int64_t* lengths, int64_t B, int6
  * concatenated along the frame axis: video b owns frames [frame_offsets[b], frame_offsets[b+1]); outputs are the padded
  * (B,T,N,.) batch and both key-padding masks (uint8, 1 = padded).  Frames past a video's length carry the CLS object in
  * slot 0 (category cls_id, box [0,0,1,1], score 1) and frame type 0.  scores_ragged/scores are NULL together
- * (datasets.py:253-260 keeps scores only for action_genome). */
+ * (datasets.py:253-260 keeps scores only for action_genome).
+ * Alignment: boxes_ragged and boxes 16 bytes (refused otherwise: a box is one 16-byte access); the int64 arrays 8, scores 4, masks bytes. */
 int stlt_collate_fwd(const int64_t* categories_ragged, const float* boxes_ragged, const float* scores_ragged,
                      const int64_t* frame_types_ragged, const int64_t* frame_offsets, int64_t B, int64_t T, int64_t N,
                      int64_t cls_id, int64_t* categories, float* boxes, float* scores, int64_t* frame_types,
@@ -579,6 +619,12 @@ typedef struct {
 } stlt_opt_chunk;
 /* ---- per-kernel backward entry points (autograd of the K-row forwards above; the fusion models' training is composed
  * from these, the STLT training step uses the fixed reverse sweep of stlt_train_backward) ----
+ * Alignment: stlt_linear_bwd — dy, db and the scratch 16 bytes (refused otherwise: the column sums move 16 bytes per lane); x, w, dx, dw
+ *   none beyond 4 bytes (its three products route them as stlt_gemm does).  stlt_add_layernorm_bwd, stlt_embed_bwd, stlt_frames_embed_bwd —
+ *   every float pointer and the scratch 16 bytes (refused otherwise, the message names the pointer).  stlt_attn_core_bwd / stlt_attn_bwd
+ *   (and stlt_attn_fwd_dropout) with dh == 64 likewise (masks are bytes); with any other dh the activations and gradients none beyond 4
+ *   bytes (in_proj_b_grad and its scratch: 16).  Index arrays 8 bytes.  Every scratch is used inside
+ *   exactly the bytes its *_scratch_bytes function returns.
  * stlt_linear_bwd: y = x·Wᵀ + b (no activation).  dx (M,K) = dy·W (nullable), dw (N,K) += dyᵀ·x (nullable), db (N) +=
  *   column sums of dy (nullable).  scratch: stlt_linear_bwd_scratch_bytes(N).  ctx (nullable): dx may run on the context's transposed copy of w.
  * stlt_attn_bwd: backward of stlt_attn_cross_fwd (and, with q = qkv, k = qkv+d, v = qkv+2d, of stlt_attn_core_fwd):
@@ -610,7 +656,7 @@ int stlt_attn_bwd(const float* q, int64_t ldq, const float* k, const float* v, i
 size_t stlt_add_layernorm_bwd_scratch_bytes(int64_t d);
 int stlt_add_layernorm_bwd(const float* dy, const float* x, const float* res, const float* ln_w, float eps, int64_t M, int64_t d,
                            float* ds, float* g_w, float* g_b, void* scratch, size_t scratch_bytes, stlt_stream_t stream);
-int stlt_gelu_fwd(const float* u, float* h, int64_t n, stlt_stream_t stream);
+int stlt_gelu_fwd(const float* u, float* h, int64_t n, stlt_stream_t stream);  /* h = gelu(u) (exact erf form); n % 4 == 0; u, h 16 bytes (refused otherwise) */
 /* K1 / K7 for an op-level autograd: the forward also returns the pre-LayerNorm sum; the LayerNorm part of the backward is
  * stlt_add_layernorm_bwd on that sum (res = NULL), the rest is below: given d_pre (gradient wrt the sum) the parameter
  * gradients ACCUMULATE into g_* (nullable); the gradient wrt the K7 input rows is d_pre itself.  Row 0 of the category /
@@ -628,17 +674,21 @@ int stlt_frames_embed_fwd_train(const float* spatial, int64_t row_stride, const 
 size_t stlt_frames_embed_bwd_scratch_bytes(int64_t T, int64_t d);
 int stlt_frames_embed_bwd(const float* d_pre, const int64_t* frame_types, int64_t B, int64_t T, int64_t d, float* g_pos, float* g_type,
                           void* scratch, size_t scratch_bytes, stlt_stream_t stream);
-int stlt_gelu_bwd(const float* dh, const float* u, float* du, int64_t n, stlt_stream_t stream);
+int stlt_gelu_bwd(const float* dh, const float* u, float* du, int64_t n, stlt_stream_t stream);  /* du = dh * gelu'(u); n % 4 == 0; dh, u, du 16 bytes (refused otherwise) */
 /* Element-wise pieces of the op-level training path.  stlt_dropout: y[i] = keep(seed, site, i) ? x[i] / (1-p) : 0 with the
  * library's counter-based mask — the backward is the same call on the gradient (nn.Dropout at models.py:333-376 and inside
  * nn.TransformerEncoderLayer).  stlt_relu_bwd: dx = dy where the activation's OUTPUT y is positive (the ReLU itself runs in
- * the producing product's epilogue: stlt_linear_fwd with STLT_ACT_RELU).  Buffers 16-byte aligned; y may alias x / dx may alias dy. */
+ * the producing product's epilogue: stlt_linear_fwd with STLT_ACT_RELU).  Any n; every buffer 16-byte aligned (refused otherwise, the
+ * message names it); y may alias x / dx may alias dy. */
 int stlt_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, uint32_t site, stlt_stream_t stream);
 int stlt_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, stlt_stream_t stream);
 
 /* Criterion of the reference (utils/train_inference_utils.py:64-76) and its gradient in one pass: loss_out[0] = weight *
  * mean loss, dlogits = weight * d(mean loss)/d(logits).  CROSS_ENTROPY: labels int64 (B); BCE_WITH_LOGITS: labels float
- * (B,K) multi-hot.  `weight` = 1 / number of logit heads (the reference averages the heads' losses).  scratch: >= B floats. */
+ * (B,K) multi-hot.  `weight` = 1 / number of logit heads (the reference averages the heads' losses).  scratch: >= B floats.
+ * Alignment: none beyond the element types' (scalar accesses).  stlt_grad_norm: flat_grad 16 bytes (refused otherwise).  stlt_adamw_step:
+ * none beyond 4 bytes — a chunk whose parameter, gradient and moment pointers are all 16-byte aligned moves 16 bytes per lane, any other
+ * chunk one float at a time, same arithmetic. */
 #define STLT_LOSS_CROSS_ENTROPY 0
 #define STLT_LOSS_BCE_WITH_LOGITS 1
 int stlt_loss_fwd_bwd(const float* logits, const void* labels, int kind, int64_t B, int64_t K, float weight,
@@ -717,7 +767,9 @@ int stlt_ffn_block_bwd_train(const stlt_ffn_block_params* p, const stlt_ffn_bloc
  * (n, C) row-major float (scores = sigmoid of the logits, truths multi-hot); ap[c] = average precision of class c (NaN
  * when the class has no positive), positives[c] = its number of positives; scratch >= n bytes.  n <= stlt_eval_max_clips()
  * (a class column is sorted inside one workgroup's LDS).  Equal scores keep clip order (the reference's argsort leaves
- * ties unspecified). */
+ * ties unspecified).
+ * Alignment (all three evaluator calls): none beyond the element types' (floats 4, int64 / double 8); logits rows of `ld` floats are read
+ * in their first K / C columns only; stlt_eval_store_sigmoid writes rows [row0, row0 + B) of the tables and nothing else. */
 int stlt_eval_topk(const float* logits, int64_t ld, const int64_t* labels, int64_t B, int64_t K, int64_t* counts,
                    stlt_stream_t stream);
 int64_t stlt_eval_max_clips(void);

@@ -258,6 +258,7 @@ size_t stlt_gemm_scratch_bytes(void) { return STLT_GEMM_SCRATCH_BYTES; }
 int stlt_gemm_set_scratch(void* scratch, size_t bytes) {
   if (scratch && bytes < STLT_GEMM_SCRATCH_BYTES)
     return stlt_set_error(STLT_EWORKSPACE, "gemm scratch %zu B < required %zu B", bytes, (size_t)STLT_GEMM_SCRATCH_BYTES);
+  if ((uintptr_t)scratch & 15) return stlt_set_error(STLT_EINVAL, "stlt_gemm_set_scratch: scratch must be 16-byte aligned (partial tiles are 16-byte stores)");
   stlt_gemm_set_scratch_impl(scratch, bytes);
   return 0;
 }
@@ -445,6 +446,7 @@ static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* work
   const WsLayout w = ws_layout(B, T, N, d, p->n_classes < 0 ? 0 : p->n_classes);
   if (!workspace || workspace_bytes < w.total)
     return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
+  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
   char* base = (char*)workspace;
   StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
   float* x = (float*)(base + w.x);
@@ -586,6 +588,7 @@ int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* work
     const WsLayout w = ws_layout(in->B, in->T, in->N, p->d, p->n_classes < 0 ? 0 : p->n_classes);
     if (!workspace || workspace_bytes < w.total)
       return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
+    if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
     if (!out_btd) return stlt_set_error(STLT_EINVAL, "skip-padding backbone: out_btd is null");
     StltGemmScratch gemm_scratch((char*)workspace + w.sk, STLT_GEMM_SCRATCH_BYTES);
     return forward_ragged(p, in, workspace, w, nullptr, out_btd, s);
@@ -614,6 +617,7 @@ int stlt_forward(const stlt_params* p, const stlt_inputs* in, void* workspace, s
   const WsLayout w = ws_layout(B, T, N, d, p->n_classes);
   if (!workspace || workspace_bytes < w.total)
     return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
+  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
   char* base = (char*)workspace;
   StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
   float* bb_out = out_btd ? out_btd : (float*)(base + w.x1);  // x1 doubles as the in-place temporal buffer

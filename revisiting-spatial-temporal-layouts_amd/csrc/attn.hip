@@ -353,6 +353,8 @@ int launch_attn_general(const float* q, int64_t ldq, const float* k, const float
   if (Lq <= 0 || Lk <= 0 || Lq > 32768 || Lk > 32768 || H <= 0 || H > 65535) return stlt_set_error(STLT_EINVAL, "stlt_attn_core_fwd: bad L/H");
   if (causal && Lq != Lk) return stlt_set_error(STLT_EINVAL, "stlt_attn_core_fwd: causal masking needs Lq == Lk");
   if (ldq % 4 || ldkv % 4) return stlt_set_error(STLT_EINVAL, "stlt_attn_core_fwd: strides must be multiples of 4 floats");
+  // 64-channel heads: K / V rows are staged by LDS-DMA, q and ctx move 16 bytes per lane (the mask is bytes; other head dims: attn_any.hip tests its own pointers)
+  if (const char* off = stlt_first_unaligned16({{"q", q}, {"k", k}, {"v", v}, {"ctx", ctx}})) return stlt_set_error(STLT_EINVAL, "stlt_attn_core_fwd: %s must be 16-byte aligned", off);
   if (S == 0) return 0;
   // sequences packed per 32-token tile (short self-attention sequences only)
   const int P = (Lq == Lk && Lq <= 16) ? (int)(TILE / Lq) : 1;
@@ -408,6 +410,7 @@ int launch_attn(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int
                 float* ctx, int kid, hipStream_t s, StltDrop dr, uint32_t site) {
   if (!qkv) return stlt_set_error(STLT_EINVAL, "stlt_attn_core_fwd: null pointer");
   const int64_t d = H * dh;
+  if (dh == DH && ((uintptr_t)qkv & 15)) return stlt_set_error(STLT_EINVAL, "stlt_attn_core_fwd: qkv must be 16-byte aligned");  // named as the caller passed it
   return launch_attn_general(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, kpm, causal, S, L, L, H, dh, ctx, kid, s, dr, site);
 }
 
@@ -422,6 +425,7 @@ int launch_attn_ragged(const float* qkv, const int* seg_start, const int* seg_en
     return launch_attn_any_fwd(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, nullptr, seg_start, seg_end, causal, M, 256, 256, H, dh, ctx, s, dr, site);  // segments: frames / clips; the whole-path callers refuse layouts whose segments could exceed the kernel's 1024 keys (api.hip: forward_ragged)
   }
   if (H <= 0 || H > 65535 || M < 0 || M > 0x7fffff00LL) return stlt_set_error(STLT_EINVAL, "attn_ragged: bad M/H");
+  if (const char* off = stlt_first_unaligned16({{"qkv", qkv}, {"ctx", ctx}})) return stlt_set_error(STLT_EINVAL, "attn_ragged: %s must be 16-byte aligned", off);
   if (M == 0) return 0;
   const int64_t d = H * dh;
   AttnGeo g;

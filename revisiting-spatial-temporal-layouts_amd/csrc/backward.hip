@@ -804,6 +804,7 @@ int launch_gelu_fwd(const float* u, float* h, int64_t n, hipStream_t s, StltDrop
   stlt_prof_note("gelu_fwd n=%lld", (long long)n);
   stlt_prof_add_bytes(8.0 * (double)n);
   if (n % 4) return stlt_set_error(STLT_EINVAL, "gelu: element count must be a multiple of 4");
+  if (const char* off = stlt_first_unaligned16({{"u", u}, {"h", h}})) return stlt_set_error(STLT_EINVAL, "gelu: %s must be 16-byte aligned", off);
   if (n == 0) return 0;
   int64_t blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -833,6 +834,7 @@ int launch_gelu_bwd(const float* dh, const float* u, float* du, int64_t n, hipSt
                     int64_t ncols) {
   StltProfScope ps(STLT_K_GELU, s);
   if (n % 4) return stlt_set_error(STLT_EINVAL, "gelu: element count must be a multiple of 4");
+  if (const char* off = stlt_first_unaligned16({{"dh", dh}, {"u", u}, {"du", du}})) return stlt_set_error(STLT_EINVAL, "gelu backward: %s must be 16-byte aligned", off);
   if (n == 0) return 0;
   int64_t blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;

@@ -256,7 +256,8 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__
 }  // namespace
 
 int launch_dropout(const float* x, float* y, int64_t n, StltDrop dr, uint32_t site, hipStream_t s) {
-  if (n < 0 || ((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return stlt_set_error(STLT_EINVAL, "stlt_dropout: buffers must be 16-byte aligned");
+  if (n < 0) return stlt_set_error(STLT_EINVAL, "stlt_dropout: negative element count");
+  if (const char* off = stlt_first_unaligned16({{"x", x}, {"y", y}})) return stlt_set_error(STLT_EINVAL, "stlt_dropout: %s must be 16-byte aligned", off);
   if (n == 0) return 0;
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 4096) blocks = 4096;
@@ -275,7 +276,8 @@ int stlt_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, ui
 
 int stlt_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, stlt_stream_t stream) {
   if (!dy || !y || !dx) return stlt_set_error(STLT_EINVAL, "stlt_relu_bwd: null pointer");
-  if (n < 0 || ((uintptr_t)dy & 15) || ((uintptr_t)y & 15) || ((uintptr_t)dx & 15)) return stlt_set_error(STLT_EINVAL, "stlt_relu_bwd: buffers must be 16-byte aligned");
+  if (n < 0) return stlt_set_error(STLT_EINVAL, "stlt_relu_bwd: negative element count");
+  if (const char* off = stlt_first_unaligned16({{"dy", dy}, {"y", y}, {"dx", dx}})) return stlt_set_error(STLT_EINVAL, "stlt_relu_bwd: %s must be 16-byte aligned", off);
   if (n == 0) return 0;
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 4096) blocks = 4096;
@@ -293,6 +295,10 @@ int stlt_linear_bwd(const float* x, const float* w, const float* dy, int64_t M, 
   if (!x || !w || !dy || !scratch) return stlt_set_error(STLT_EINVAL, "stlt_linear_bwd: null pointer");
   if (M < 0 || N <= 0 || K <= 0) return stlt_set_error(STLT_EINVAL, "stlt_linear_bwd: bad shape");
   if (scratch_bytes < stlt_linear_bwd_scratch_bytes(N)) return stlt_set_error(STLT_EWORKSPACE, "stlt_linear_bwd: scratch %zu B < required %zu B", scratch_bytes, stlt_linear_bwd_scratch_bytes(N));
+  // the three products route x, w, dx and dw off a 16-byte boundary by themselves (gemm.hip: launch_gemm_impl); the column sums of dy and the
+  // lent scratch move 16 bytes per lane
+  if (const char* off = stlt_first_unaligned16({{"dy", dy}, {"db", db}, {"scratch", scratch}}))
+    return stlt_set_error(STLT_EINVAL, "stlt_linear_bwd: %s must be 16-byte aligned", off);
   if (M == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   StltCtxScope ctx_scope(ctx, s);  // dx may be served from the context's transposed copy of w
@@ -324,6 +330,10 @@ int stlt_attn_bwd(const float* q, int64_t ldq, const float* k, const float* v, i
                   float* dq, int64_t lddq, float* dk, float* dv, int64_t lddkv, stlt_stream_t stream) {
   if (!(dropout_p >= 0.f && dropout_p < 1.f)) return stlt_set_error(STLT_EINVAL, "dropout probability must be in [0,1)");
   if (!q || !k || !v || !dctx || !dq || !dk || !dv) return stlt_set_error(STLT_EINVAL, "stlt_attn_bwd: null pointer");
+  if (dh == XB_DH) {  // 64-channel heads: tiles by LDS-DMA, gradients as 16-byte stores (other head dims: attn_any.hip tests its own pointers)
+    if (const char* off = stlt_first_unaligned16({{"q", q}, {"k", k}, {"v", v}, {"dctx", dctx}, {"dq", dq}, {"dk", dk}, {"dv", dv}}))
+      return stlt_set_error(STLT_EINVAL, "stlt_attn_bwd: %s must be 16-byte aligned", off);
+  }
   if (dh != XB_DH) {  // any other head dim: attn_any.hip
     StltProfScope ps(STLT_K_ATTN_BWD, (hipStream_t)stream);
     return launch_attn_any_bwd(q, ldq, k, v, ldkv, dctx, kpm, nullptr, nullptr, nullptr, 0, causal, S, Lq, Lk, H, dh, dq, lddq, dk, dv, lddkv,
@@ -378,6 +388,10 @@ int stlt_attn_core_bwd(const float* qkv, const float* dctx, const uint8_t* kpm, 
   if (dh < 1 || dh > 256 || H <= 0 || S < 0 || L <= 0) return stlt_set_error(STLT_EINVAL, "stlt_attn_core_bwd: bad shape (head dim 1 ... 256)");
   if (!(dropout_p >= 0.f && dropout_p < 1.f)) return stlt_set_error(STLT_EINVAL, "dropout probability must be in [0,1)");
   if (in_proj_b_grad && (!scratch || scratch_bytes < stlt_attn_core_bwd_scratch_bytes(H))) return stlt_set_error(STLT_EWORKSPACE, "stlt_attn_core_bwd: scratch too small");
+  if (dh == 64) {
+    if (const char* off = stlt_first_unaligned16({{"qkv", qkv}, {"dctx", dctx}, {"dqkv", dqkv}, {"in_proj_b_grad", in_proj_b_grad}, {"scratch", in_proj_b_grad ? scratch : nullptr}}))
+      return stlt_set_error(STLT_EINVAL, "stlt_attn_core_bwd: %s must be 16-byte aligned", off);
+  }
   if (S == 0) return 0;
   return launch_attn_bwd(qkv, dctx, kpm, causal, S, L, H, dh, dqkv, (hipStream_t)stream, stlt_drop_make(dropout_p, seed), site, in_proj_b_grad,
                          (float*)scratch);
@@ -388,6 +402,8 @@ size_t stlt_add_layernorm_bwd_scratch_bytes(int64_t d) { return (size_t)ln_bwd_s
 int stlt_add_layernorm_bwd(const float* dy, const float* x, const float* res, const float* ln_w, float eps, int64_t M, int64_t d,
                            float* ds, float* g_w, float* g_b, void* scratch, size_t scratch_bytes, stlt_stream_t stream) {
   if (scratch_bytes < stlt_add_layernorm_bwd_scratch_bytes(d)) return stlt_set_error(STLT_EWORKSPACE, "stlt_add_layernorm_bwd: scratch too small");
+  if (const char* off = stlt_first_unaligned16({{"dy", dy}, {"x", x}, {"res", res}, {"ln_w", ln_w}, {"ds", ds}, {"g_w", g_w}, {"g_b", g_b}, {"scratch", scratch}}))
+    return stlt_set_error(STLT_EINVAL, "stlt_add_layernorm_bwd: %s must be 16-byte aligned", off);
   return launch_ln_bwd(dy, d, x, d, res, d, ln_w, eps, M, d, ds, d, g_w, g_b, (float*)scratch, (hipStream_t)stream);
 }
 
@@ -408,6 +424,9 @@ int stlt_embed_bwd(const float* d_pre, const int64_t* categories, const float* b
                    int64_t n_tokens, int64_t d, float* g_cat, float* g_box_w, float* g_box_b, float* g_score_w, float* g_score_b,
                    void* scratch, size_t scratch_bytes, stlt_stream_t stream) {
   if (scratch_bytes < stlt_embed_bwd_scratch_bytes(n_tokens, n_categories, d)) return stlt_set_error(STLT_EWORKSPACE, "stlt_embed_bwd: scratch too small");
+  if (const char* off = stlt_first_unaligned16({{"d_pre", d_pre}, {"boxes", boxes}, {"g_cat", g_cat}, {"g_box_w", g_box_w}, {"g_box_b", g_box_b}, {"g_score_w", g_score_w},
+                                                {"g_score_b", g_score_b}, {"scratch", scratch}}))
+    return stlt_set_error(STLT_EINVAL, "stlt_embed_bwd: %s must be 16-byte aligned", off);
   return launch_embed_bwd(d_pre, categories, boxes, scores, n_categories, n_tokens, d, g_cat, g_box_w, g_box_b, g_score_w, g_score_b,
                           (float*)scratch, (hipStream_t)stream);
 }
@@ -424,6 +443,8 @@ size_t stlt_frames_embed_bwd_scratch_bytes(int64_t T, int64_t d) { return (size_
 int stlt_frames_embed_bwd(const float* d_pre, const int64_t* frame_types, int64_t B, int64_t T, int64_t d, float* g_pos, float* g_type,
                           void* scratch, size_t scratch_bytes, stlt_stream_t stream) {
   if (scratch_bytes < stlt_frames_embed_bwd_scratch_bytes(T, d)) return stlt_set_error(STLT_EWORKSPACE, "stlt_frames_embed_bwd: scratch too small");
+  if (const char* off = stlt_first_unaligned16({{"d_pre", d_pre}, {"g_pos", g_pos}, {"g_type", g_type}, {"scratch", scratch}}))
+    return stlt_set_error(STLT_EINVAL, "stlt_frames_embed_bwd: %s must be 16-byte aligned", off);
   return launch_frames_bwd(d_pre, frame_types, B, T, 1, d, nullptr, g_pos, g_type, (float*)scratch, (hipStream_t)stream);
 }
 

@@ -135,6 +135,7 @@ extern "C" int stlt_caf_forward_flags(const stlt_caf_params* p, const stlt_input
     return stlt_set_error(STLT_EINVAL, "stlt_caf_forward: CACNF needs both unimodal heads and all four outputs");
   const CafWs w = caf_ws(B, T, N, d, C, S, K);
   if (workspace_bytes < w.total) return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
+  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
   char* base = (char*)workspace;
   StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
   auto F = [&](size_t o) { return (float*)(base + o); };

@@ -57,6 +57,8 @@ extern "C" int stlt_collate_fwd(const int64_t* categories_ragged, const float* b
   if ((scores_ragged == nullptr) != (scores == nullptr))
     return stlt_set_error(STLT_EINVAL, "stlt_collate_fwd: scores input and output must be given together");
   if (B < 0 || T <= 0 || N <= 0) return stlt_set_error(STLT_EINVAL, "stlt_collate_fwd: bad shape");
+  if (const char* off = stlt_first_unaligned16({{"boxes_ragged", boxes_ragged}, {"boxes", boxes}}))  // a box is one 16-byte load and one 16-byte store
+    return stlt_set_error(STLT_EINVAL, "stlt_collate_fwd: %s must be 16-byte aligned", off);
   if (B == 0) return 0;
   const int64_t n = B * T * N;
   hipLaunchKernelGGL(collate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, categories_ragged,

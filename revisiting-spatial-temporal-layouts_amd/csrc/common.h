@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include "stlt_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -14,6 +15,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 int stlt_set_error(int code, const char* fmt, ...);
 int stlt_check_launch(const char* what);
 #define TRY(expr) do { int _e = (expr); if (_e) return _e; } while (0)
+// The launchers' test of the base pointers a kernel moves 16 bytes at a time (LDS-DMA of whole rows, f32x4 loads / stores): the name of
+// the first non-null pointer that is off a 16-byte boundary, or nullptr.  Next to each launcher's pitch test (ld % 4).
+struct StltNamedPtr { const char* name; const void* p; };
+inline const char* stlt_first_unaligned16(std::initializer_list<StltNamedPtr> ptrs) {
+  for (const StltNamedPtr& q : ptrs) if ((uintptr_t)q.p & 15) return q.name;
+  return nullptr;
+}
 constexpr size_t stlt_align256(size_t v) { return (v + 255) / 256 * 256; }  // workspace / tape / scratch carving: every buffer starts on 256 bytes
 
 // Per-device state (api.hip).  Nothing in the library caches a property of "the first device it saw": CU counts,

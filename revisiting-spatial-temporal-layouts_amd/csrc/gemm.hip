@@ -1160,8 +1160,11 @@ static int launch_gemm_impl(int transA, int transB, const float* a, int64_t lda,
       return stlt_set_error(STLT_EINVAL, "gemm: the fused GELU backward is the dX layout with u as the add-source and a column-sum buffer");
   }
   if (M < 0 || N <= 0 || K <= 0) return stlt_set_error(STLT_EINVAL, "gemm: bad shape (M=%lld N=%lld K=%lld)", (long long)M, (long long)N, (long long)K);
-  if (K % BK != 0 || lda % 4 != 0 || ldb % 4 != 0) {  // a partial k-slab / rows that are not 16-byte aligned cannot be staged by LDS-DMA:
-    // the fallback kernel of gemm_any.hip (hidden sizes that are not multiples of 32)
+  const bool base_off = (((uintptr_t)a | (uintptr_t)b) & 15) != 0;  // an operand that starts off a 16-byte boundary: every row of it does
+  if (K % BK != 0 || lda % 4 != 0 || ldb % 4 != 0 || base_off) {  // a partial k-slab / rows that are not 16-byte aligned cannot be staged by LDS-DMA:
+    // the fallback kernel of gemm_any.hip (hidden sizes that are not multiples of 32; views such as flat[1:]: four-byte loads there)
+    if ((n_split != 1 || act == STLT_ACT_GELU_BWD) && base_off && K % BK == 0 && lda % 4 == 0 && ldb % 4 == 0)
+      return stlt_set_error(STLT_EINVAL, "gemm: a split product / the fused GELU backward needs %s 16-byte aligned", ((uintptr_t)a & 15) ? "a" : "b");
     if (n_split != 1 || act == STLT_ACT_GELU_BWD)
       return stlt_set_error(STLT_EINVAL, "gemm: a split product / the fused GELU backward needs K=%lld to be a multiple of %d and pitches that are multiples of 4", (long long)K, BK);
     return launch_gemm_any(transA, transB, a, lda, b, ldb, bias, r, ldr, c, ldc, M, N, K, act, s);
@@ -1287,6 +1290,8 @@ int launch_weight_grad_group(const StltWeightGradItem* items, int n_items, hipSt
       return stlt_set_error(STLT_EINVAL, "weight_grad_group: item %d: rows=%lld must be a multiple of %d, n_out=%lld / k_in=%lld multiples of 4", i,
                             (long long)it.rows, BK, (long long)it.n_out, (long long)it.k_in);
     if (it.n_out > 0x3fffffLL || it.k_in > 0x3fffffLL || it.rows > 0x7fffff00LL) return stlt_set_error(STLT_EINVAL, "weight_grad_group: item too large");
+    if (const char* off = stlt_first_unaligned16({{"dy", it.dy}, {"x", it.x}}))  // both operands are staged by LDS-DMA (g_w is tested tile by tile in the epilogue)
+      return stlt_set_error(STLT_EINVAL, "weight_grad_group: item %d: %s must be 16-byte aligned", i, off);
     const int64_t tm = (it.n_out + BM - 1) / BM, tn = (it.k_in + BN - 1) / BN;
     StltGemmProblem& q = grp.p[n];
     q.a = it.dy; q.lda = (int)it.n_out; q.b = it.x; q.ldb = (int)it.k_in; q.r = it.g_w; q.ldr = (int)it.k_in; q.c = it.g_w; q.ldc = (int)it.k_in;
@@ -1336,7 +1341,11 @@ int launch_reduce_slabs(const float* slabs, int64_t stride, int n_slabs, float* 
   if (!slabs || !dst || n_slabs < 1) return stlt_set_error(STLT_EINVAL, "reduce_slabs: bad arguments");
   if (n == 0) return 0;
   if (accumulate) { int err = 0; if (reduce_defer_take(slabs, stride, n_slabs, dst, nullptr, nullptr, 1, n, s, &err)) return err; }
-  if (n_slabs > 32 && n <= 16384) {
+  // reduce_slabs_kernel moves 16 bytes per lane: slabs / dst off a 16-byte boundary, or a slab stride that is no multiple of 4 floats, take the
+  // element-wise kernel (exact either way for one slab; for more the summation order differs as it does between the two kernels today)
+  const bool off16 = (((uintptr_t)slabs | (uintptr_t)dst) & 15) != 0 || (n_slabs > 1 && stride % 4 != 0);
+  if (off16 && (n + 15) / 16 > 0x7fffffffLL) return stlt_set_error(STLT_EINVAL, "reduce_slabs: n=%lld is too large for slabs / dst off a 16-byte boundary", (long long)n);
+  if ((n_slabs > 32 && n <= 16384) || off16) {
     hipLaunchKernelGGL(reduce_tall_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, slabs, stride, n_slabs, dst, n, accumulate);
     return stlt_check_launch("reduce_tall_kernel");
   }

@@ -210,6 +210,14 @@ int launch_linear_gemm16(const float* x, int64_t ldx, const float* w, int64_t ld
     return stlt_set_error(STLT_EINVAL, "gemm16: K must be a multiple of 32 (>= 64), N and the row pitches multiples of 4, tiles of 128 x 16{3,4,6,8,9,12}, 64 x 16{4,6,8,10,12,16} or 32 x 16{8,12,16}");
   if (code == 0) return 0;
   if (!x || !w || !y) return stlt_set_error(STLT_EINVAL, "gemm16: null pointer");
+  // the loaders stage x and w by LDS-DMA, bias / r / y move 16 bytes per lane: every base pointer on a 16-byte boundary.  A routed product
+  // that is not stays with gemm.hip (which sends it to the four-byte loads of gemm_any.hip); a forced tile is refused
+  if (const char* off = stlt_first_unaligned16({{"x", x}, {"w", w}, {"bias", bias}, {"r", r}, {"y", y}})) {
+    if (force_tile == 0) return 0;
+    return stlt_set_error(STLT_EINVAL, "gemm16: %s must be 16-byte aligned", off);
+  }
+  if (force_tile == 0 && ldx >= K && ldw >= K && ldy >= N && (!r || ldr >= N) && (ldy % 4 != 0 || (r && ldr % 4 != 0)))
+    return 0;  // a routed product whose output / add-source pitch is no multiple of 4: gemm.hip's guarded scalar epilogue takes it
   if (ldx < K || ldw < K || ldy < N || (r && ldr < N) || ldy % 4 != 0 || (r && ldr % 4 != 0))
     return stlt_set_error(STLT_EINVAL, "gemm16: bad leading dimension (ldx=%lld ldw=%lld ldy=%lld ldr=%lld)", (long long)ldx, (long long)ldw, (long long)ldy, (long long)ldr);
   const int rb = tile_rb(code), nt = tile_nt(code);
@@ -261,7 +269,7 @@ int launch_input_grad_gemm16(const float* dy, int64_t ld_dy, const float* w, int
   // the forward build — same add-source / GELU-backward epilogues, the forward build's cost table for the tile
   const float* wt = nullptr;
   int64_t ldwt = 0;
-  if (force_tile == 0 && dy && w && c && stlt_wt_lookup(w, n_out, k_in, &wt, &ldwt)) {
+  if (force_tile == 0 && dy && w && c && !stlt_first_unaligned16({{"dy", dy}, {"r", r}, {"dx", c}}) && ldc % 4 == 0 && (!r || ldr % 4 == 0) && stlt_wt_lookup(w, n_out, k_in, &wt, &ldwt)) {
     const int fcode = stlt_gemm16_choice(rows, k_in, n_out, ld_dy, ldwt, false);
     if (fcode != 0) {
       if (ld_dy < n_out || ldc < k_in || (r && ldr < k_in) || ldc % 4 != 0 || (r && ldr % 4 != 0)) return stlt_set_error(STLT_EINVAL, "gemm16 (input gradient): bad leading dimension");
@@ -288,6 +296,11 @@ int launch_input_grad_gemm16(const float* dy, int64_t ld_dy, const float* w, int
     return stlt_set_error(STLT_EINVAL, "gemm16 (input gradient): n_out must be a multiple of 32 (>= 64), k_in and the row pitches multiples of 4");
   if (code == 0) return 0;
   if (!dy || !w || !c) return stlt_set_error(STLT_EINVAL, "gemm16 (input gradient): null pointer");
+  if (force_tile == 0 && !gelu_bwd && ld_dy >= n_out && ldc >= k_in && (!r || ldr >= k_in) && (ldc % 4 != 0 || (r && ldr % 4 != 0))) return 0;  // as in launch_linear_gemm16
+  if (const char* off = stlt_first_unaligned16({{"dy", dy}, {"w", w}, {"r", r}, {"dx", c}})) {  // as in launch_linear_gemm16
+    if (force_tile == 0 && !gelu_bwd) return 0;
+    return stlt_set_error(STLT_EINVAL, "gemm16 (input gradient): %s must be 16-byte aligned", off);
+  }
   if (ld_dy < n_out || ldc < k_in || (r && ldr < k_in) || ldc % 4 != 0 || (r && ldr % 4 != 0)) return stlt_set_error(STLT_EINVAL, "gemm16 (input gradient): bad leading dimension");
   const int rb = tile_rb(code), nt = tile_nt(code);
   Gemm16Args a{};

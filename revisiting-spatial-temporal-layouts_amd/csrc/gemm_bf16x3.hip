@@ -436,6 +436,9 @@ int launch_linear_bf16x3(const float* x, int64_t ldx, const float* w, int64_t ld
                          int64_t ldy, int64_t M, int64_t N, int64_t K, int act, hipStream_t s, bool* taken) {
   *taken = false;
   if (!stlt_split_bf16_takes(M, N, K, ldx, ldw)) return 0;
+  // x and w are read 16 bytes at a time (the producers' buffer loads, w_planes_kernel): an operand that starts off a 16-byte boundary is not
+  // this kernel's — gemm.hip routes it to the four-byte loads of gemm_any.hip (y and r are tested tile by tile in the epilogue)
+  if ((((uintptr_t)x | (uintptr_t)w) & 15) != 0) return 0;
   if (act != STLT_ACT_NONE && act != STLT_ACT_GELU && act != STLT_ACT_RELU) return 0;
   if (r && act != STLT_ACT_NONE) return 0;
   // the argument checks launch_gemm makes for the f32 kernel: with the opt-in switch on, a bad call must still come back as
@@ -481,6 +484,7 @@ int launch_input_grad_bf16x3(const float* dy, int64_t ld_dy, const float* w, int
                              int64_t ldc, int64_t rows, float* wt_scratch, hipStream_t s, bool* taken) {
   *taken = false;
   if (!wt_scratch || !stlt_split_bf16_takes(rows, k_in, n_out, ld_dy, n_out)) return 0;
+  if ((((uintptr_t)dy | (uintptr_t)w | (uintptr_t)wt_scratch) & 15) != 0) return 0;  // as launch_linear_bf16x3: before the transpose is launched
   if (!dy || !w || !c) return stlt_set_error(STLT_EINVAL, "input gradient (split-bf16): null pointer");
   if (ld_dy < n_out || ldc < k_in || (r && ldr < k_in)) return stlt_set_error(STLT_EINVAL, "input gradient (split-bf16): bad leading dimension");
   hipLaunchKernelGGL(weight_transpose_kernel, dim3((unsigned)((k_in + 31) / 32), (unsigned)((n_out + 31) / 32)), dim3(256), 0, s, w, (int)n_out, (int)k_in, wt_scratch);

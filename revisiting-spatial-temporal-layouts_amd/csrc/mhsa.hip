@@ -570,6 +570,9 @@ int launch_mhsa_fused(const float* x, const float* w_in, const float* b_in, cons
   if (!stlt_mhsa_fused_takes(L, H, d, causal))
     return stlt_set_error(STLT_EINVAL, "mhsa_fused: sequences of 1..64 tokens and 64-channel heads (L=%lld, d=%lld, H=%lld, causal=%d)", (long long)L,
                           (long long)d, (long long)H, causal);
+  // x and in_proj_w are staged by LDS-DMA (16 bytes per lane), ctx and qkv_out leave as 16-byte stores; in_proj_b is fetched a dword per lane
+  if (const char* off = stlt_first_unaligned16({{"x", x}, {"in_proj_w", w_in}, {"ctx", ctx}, {"qkv_out", qkv_out}}))
+    return stlt_set_error(STLT_EINVAL, "mhsa_fused: %s must be 16-byte aligned", off);
   if (S <= 0) return 0;
   if (S * L * 3 * d > 0x7fffffffLL * 4 || S * L > 0x7fffff00LL || (S / (FM / L) + 1) * H > 0x3fffffffLL)
     return stlt_set_error(STLT_EINVAL, "mhsa_fused: batch too large");

@@ -92,7 +92,7 @@ extern "C" {
 
 int stlt_grad_norm(const float* flat_grad, int64_t n, float max_norm, float* scratch, float* out, stlt_stream_t stream) {
   if (!flat_grad || !scratch || !out) return stlt_set_error(STLT_EINVAL, "stlt_grad_norm: null pointer");
-  if (n < 0 || ((uintptr_t)flat_grad & 15)) return stlt_set_error(STLT_EINVAL, "stlt_grad_norm: buffer must be 16-byte aligned");
+  if (n < 0 || ((uintptr_t)flat_grad & 15)) return stlt_set_error(STLT_EINVAL, "stlt_grad_norm: flat_grad must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   StltProfScope ps(STLT_K_OPTIM, s);
   stlt_prof_note("grad_norm n=%lld", (long long)n);

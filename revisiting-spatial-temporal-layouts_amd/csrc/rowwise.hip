@@ -332,6 +332,10 @@ int launch_embed(const int64_t* categories, const float* boxes, const float* sco
   if (!categories || !boxes || !cat_table || !box_w || !box_b || !ln_w || !ln_b || !out || n_categories <= 0)
     return stlt_set_error(STLT_EINVAL, "stlt_embed_fwd: null pointer / empty table");
   if (scores && (!score_w || !score_b)) return stlt_set_error(STLT_EINVAL, "stlt_embed_fwd: scores given without score_w/score_b");
+  // rows and parameter vectors move 16 bytes per lane (scores and categories are read one element at a time)
+  if (const char* off = stlt_first_unaligned16({{"boxes", boxes}, {"cat_table", cat_table}, {"box_w", box_w}, {"box_b", box_b}, {"score_w", scores ? score_w : nullptr},
+                                                {"score_b", scores ? score_b : nullptr}, {"ln_w", ln_w}, {"ln_b", ln_b}, {"out", out}, {"pre_out", pre_out}}))
+    return stlt_set_error(STLT_EINVAL, "stlt_embed_fwd: %s must be 16-byte aligned", off);
   if (n_tokens == 0) return 0;
   StltProfScope ps(STLT_K_EMBED, s);
   stlt_prof_note("embed rows=%lld d=%lld", (long long)n_tokens, (long long)d);
@@ -363,6 +367,8 @@ int launch_add_layernorm(const float* x, int64_t ldx, const float* res, int64_t 
   if (int e = check_d(d)) return e;
   if (!x || !w || !b || !out) return stlt_set_error(STLT_EINVAL, "stlt_add_layernorm_fwd: null pointer");
   if (ldx % 4 || ldout % 4 || (res && ldres % 4)) return stlt_set_error(STLT_EINVAL, "stlt_add_layernorm_fwd: leading dims must be multiples of 4");
+  if (const char* off = stlt_first_unaligned16({{"x", x}, {"res", res}, {"ln_w", w}, {"ln_b", b}, {"out", out}}))  // 16 bytes per lane on every one of them
+    return stlt_set_error(STLT_EINVAL, "stlt_add_layernorm_fwd: %s must be 16-byte aligned", off);
   if (M == 0) return 0;
   StltProfScope ps(STLT_K_ADDLN, s);
   stlt_prof_note("add_ln rows=%lld d=%lld%s", (long long)M, (long long)d, res ? " +res" : "");
@@ -380,6 +386,9 @@ int launch_frames_embed(const float* spatial, int64_t row_stride, const int64_t*
   if (!spatial || !frame_types || !pos_table || !type_table || !ln_w || !ln_b || !out)
     return stlt_set_error(STLT_EINVAL, "stlt_frames_embed_fwd: null pointer");
   if (row_stride % 4) return stlt_set_error(STLT_EINVAL, "stlt_frames_embed_fwd: row_stride must be a multiple of 4");
+  if (const char* off = stlt_first_unaligned16({{"spatial", spatial}, {"pos_table", pos_table}, {"type_table", type_table}, {"ln_w", ln_w}, {"ln_b", ln_b}, {"out", out},
+                                                {"pre_out", pre_out}}))
+    return stlt_set_error(STLT_EINVAL, "stlt_frames_embed_fwd: %s must be 16-byte aligned", off);
   const int64_t rows = src_index ? n_rows : B * T;  // ragged mode: n_rows compacted frames
   if (rows == 0) return 0;
   StltProfScope ps(STLT_K_FRAMES, s);
@@ -396,6 +405,7 @@ int launch_gather_last(const float* x, const int64_t* lengths, int64_t B, int64_
                        hipStream_t s) {
   if (int e = check_d(d)) return e;
   if (!x || !lengths || !out) return stlt_set_error(STLT_EINVAL, "stlt_gather_last_fwd: null pointer");
+  if (const char* off = stlt_first_unaligned16({{"x", x}, {"out", out}})) return stlt_set_error(STLT_EINVAL, "stlt_gather_last_fwd: %s must be 16-byte aligned", off);
   if (B == 0) return 0;
   StltProfScope ps(STLT_K_GATHER, s);
   stlt_prof_note("gather_last rows=%lld d=%lld", (long long)B, (long long)d);

@@ -464,6 +464,7 @@ int stlt_train_forward(const stlt_params* p, const stlt_inputs* in, void* tape_m
   const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H;
   const Tape t = tape_layout((char*)tape_mem, B, T, N, d, p->n_spatial, p->n_temporal);
   if (tape_bytes < t.bytes) return stlt_set_error(STLT_EWORKSPACE, "tape %zu B < required %zu B", tape_bytes, t.bytes);
+  if ((uintptr_t)tape_mem & 255) return stlt_set_error(STLT_EINVAL, "tape must be 256-byte aligned");
   StltGemmScratch gemm_scratch(t.sk, STLT_GEMM_SCRATCH_BYTES);
   if (!(dropout_p >= 0.f && dropout_p < 1.f)) return stlt_set_error(STLT_EINVAL, "dropout probability must be in [0,1)");
   const StltDrop dr = stlt_drop_make(dropout_p, dropout_seed);
@@ -537,8 +538,10 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
   const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H, K = p->n_classes;
   const Tape t = tape_layout((char*)const_cast<void*>(tape_mem), B, T, N, d, p->n_spatial, p->n_temporal);
   if (tape_bytes < t.bytes) return stlt_set_error(STLT_EWORKSPACE, "tape %zu B < required %zu B", tape_bytes, t.bytes);
+  if ((uintptr_t)tape_mem & 255) return stlt_set_error(STLT_EINVAL, "tape must be 256-byte aligned");
   Scratch sc = scratch_layout((char*)scratch_mem, B, T, N, d, p->n_categories);
   if (scratch_bytes < sc.bytes) return stlt_set_error(STLT_EWORKSPACE, "scratch %zu B < required %zu B", scratch_bytes, sc.bytes);
+  if ((uintptr_t)scratch_mem & 255) return stlt_set_error(STLT_EINVAL, "scratch must be 256-byte aligned");
   // the sweep's ~55 partial-row reductions (LayerNorm / bias gradients) are collected and run as a few batched launches
   // (STLT_TRAIN_DEFER_REDUCE=0: one launch each, A/B runs)
   StltReduceScope red(sc.red_pool, sc.red_pool_floats, sc.red, sc.red_floats, s);  // (no pool was carved while deferral is off)
