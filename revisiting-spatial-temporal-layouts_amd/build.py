@@ -105,7 +105,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags=()) -> str:
 
 
 def variant(tag: str, flags_by_file, verbose: bool = False) -> str:
-    """Same library with extra flags for some files ({"gemm.hip": ["-DSTLT_GEMM_STAGGER=0"]}) -> build/variants/libstlt_hip_<tag>.so"""
+    """Same library with extra flags for some files ({"gemm.hip": ["-DSTLT_GEMM_ABLATE=1"]}) -> build/variants/libstlt_hip_<tag>.so"""
     d = os.path.join(ROOT, "build", "variants")
     os.makedirs(d, exist_ok=True)
     return _build_to(os.path.join(d, f"libstlt_hip_{tag}.so"), dict(flags_by_file), verbose)

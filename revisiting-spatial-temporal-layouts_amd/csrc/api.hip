@@ -351,7 +351,7 @@ size_t stlt_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t 
 // The residual adds of a post-norm layer ride in the out-proj / FFN2 epilogues and the LayerNorm passes read one tensor
 // instead of two (bit-identical logits: the accumulators start from the bias, the residual is added last).  Round 2 measured
 // it a wash (the residual tile was read inside the exposed epilogue: LayerNorm 3.06 -> 2.00 ms, GEMMs +1.0 ms); with the
-// first half of a tile's residual pieces requested during the tile's last k-step (gemm.hip: STLT_GEMM_RES_PREFETCH) the GEMMs
+// first half of a tile's residual pieces requested during the tile's last k-step (gemm.hip: RES_PF) the GEMMs
 // pay 0.4 ms and the forward gains 0.5 ms at cfg2 / 1024 clips (profiles/round3_fwd_residual_ab.txt).  STLT_FUSE_RESIDUAL=0
 // restores the separate pass (A/B runs).
 static bool fuse_residual() {

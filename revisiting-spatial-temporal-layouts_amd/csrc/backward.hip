@@ -10,9 +10,6 @@
 namespace {
 
 constexpr int RW_WAVES = 4;  // waves per 256-thread block for the row-wise kernels
-#ifndef STLT_LN_BWD_PIPE
-#define STLT_LN_BWD_PIPE 1  // 0: a row's loads issued when its turn comes (A/B builds)
-#endif
 
 // ------------------------------------------------------------------ LayerNorm backward
 // y = LN(s) * w + b with s = a (+ b2).  Given dy: ds = rstd * (g - mean(g) - xhat * mean(g*xhat)), g = dy*w;
@@ -42,7 +39,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
   }
   const float inv_d = 1.0f / (float)d;
   // The waves are persistent at 2 per SIMD (136+ registers, 512 blocks), each walking ~7 rows whose work is one dependent chain (three row
-  // loads -> four wave-wide sums -> stores): the next row's loads are issued before the current row's arithmetic (STLT_LN_BWD_PIPE), and the
+  // loads -> four wave-wide sums -> stores): the next row's loads are issued before the current row's arithmetic, and the
   // sums run on DPP / permlane swaps (wave_dpp.h: the shuffle butterfly's bits without its 24 LDS round trips per row).
   f32x4 na[NV], nb[NV], ng[NV];  // the next row as loaded: a, b2, dy
   auto load_row = [&](int64_t row) {
@@ -56,18 +53,17 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
       }
     }
   };
-  if (STLT_LN_BWD_PIPE && gw < M) load_row(gw);
+  if (gw < M) load_row(gw);
   for (int64_t row = gw; row < M; row += n_waves) {
     const uint64_t drow = (dr.thr && drop_rows) ? (uint64_t)drop_rows[row] : (uint64_t)row;  // dropout masks follow the row's original position
     f32x4 x[NV], g[NV], bcur[NV];
-    if (!STLT_LN_BWD_PIPE) load_row(row);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       x[i] = na[i];
       bcur[i] = nb[i];
       g[i] = ng[i];
     }
-    if (STLT_LN_BWD_PIPE && row + n_waves < M) load_row(row + n_waves);
+    if (row + n_waves < M) load_row(row + n_waves);
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {

@@ -84,16 +84,12 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
-#ifndef STLT_GELU_BRANCH_FREE
-#define STLT_GELU_BRANCH_FREE 1
-#endif
 // GELU of the FFN1 epilogue.  The library erff takes one of two branches per lane (|z| < 1: 8 instructions; else a
 // degree-7 polynomial + exp, ~24), so its cost in a 64-lane wave depends on the data: cheap while every lane of a wave
-// is below 1, ~38 instructions once both branches are live.  STLT_GELU_BRANCH_FREE=1 selects a fixed-cost form instead:
+// is below 1, ~38 instructions once both branches are live.  The epilogue uses a fixed-cost form instead:
 // erf(t) = 1 - 2^q(t) for t = min(|z|, 3.95) with q a degree-11 fit of log2(erfc) and one v_exp_f32; max abs error of
 // erf 1.1e-7 in fp32 (200k points), the order of erff's own rounding.
 __device__ __forceinline__ float gelu_epilogue(float x) {
-#if STLT_GELU_BRANCH_FREE
   const float z = x * 0.70710678118654752440f;
   const float t = fminf(fabsf(z), 3.95f);
   float q = 1.1830035617776957e-07f;
@@ -110,9 +106,6 @@ __device__ __forceinline__ float gelu_epilogue(float x) {
   q = fmaf(q, t, 2.831300349726007e-08f);
   const float e = copysignf(1.0f - __builtin_amdgcn_exp2f(q), z);
   return 0.5f * x * (1.0f + e);
-#else
-  return gelu_erf(x);
-#endif
 }
 
 

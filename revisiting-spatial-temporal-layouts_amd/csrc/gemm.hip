@@ -6,8 +6,8 @@
 //   v_mfma_f32_32x32x2_f32.  The k index inside an 8-wide chunk is permuted (MFMA e pairs k = 8c+e with
 //   k = 8c+4+e); a sum over k does not care, and A and B use the same permutation.
 //
-// Structure (one persistent 512-thread workgroup per CU = 8 waves as 4x2):
-//   * block tile 256x128x32, each wave 64x64 = 2x2 MFMA tiles of 32x32 (64 accumulator VGPRs).  The per-CU
+// Structure (one persistent 768-thread workgroup per CU = 8 MFMA waves as 4x2 + 4 DMA-only loader waves, see below):
+//   * block tile 256x128x32, each MFMA wave 64x64 = 2x2 MFMA tiles of 32x32 (64 accumulator VGPRs).  The per-CU
 //     fetch path (~10 B/clk measured) is co-critical with the f32 MFMA pipe: two independent 128x128 tiles per
 //     CU need 8 B/clk at full MFMA rate and queue up at VMEM issue; one 256x128 tile needs 6 B/clk;
 //   * a workgroup walks its tiles (XCD-contiguous tile order) as ONE flattened stream of k-steps, so the next
@@ -15,9 +15,9 @@
 //   * global -> LDS by LDS-DMA (global_load_lds_dwordx4): no staging registers, no ds_write.  The LDS image is
 //     lane-linear per wave instruction (8 rows x 128 B), so the bank swizzle chunk ^= (row>>1)&7 is applied
 //     to the per-lane SOURCE address and again on the fragment reads (conflict-free ds_read_b128);
-//   * three LDS stages (144 KB): step s+2's DMA is issued in thirds between the MFMA chunks of step s (into the
-//     stage retired by the previous barrier); the barrier that retires step s is preceded by a COUNTED
-//     vmcnt(6) that only waits for step s+1's data;
+//   * three LDS stages (144 KB): the loader waves issue step s+2's DMA (into the stage retired by the previous
+//     barrier) while the MFMA waves multiply step s; the barrier that retires step s is preceded, in the loader
+//     waves, by a COUNTED vmcnt(12) that only waits for step s+1's data;
 //   * fragments are read one 8-wide k-chunk ahead (ping-pong registers), and the read of the next step's first
 //     chunk sits between the barrier and the last 16 MFMAs of the current step;
 //   * the MFMA computes the TRANSPOSED tile (W fragment as the A operand, X fragment as B): a lane then owns one
@@ -27,14 +27,15 @@
 //   * the bias is the accumulators' initial value, fetched one tile ahead (read from its LDS strip straight into
 //     the accumulator registers when a tile's epilogue re-initialises them).
 //
-// Wave specialisation (template flag WS, the default for launches that are not stream-K): the workgroup has four more
-// waves (8..11, one per SIMD) that do nothing but issue the LDS-DMA, and the eight MFMA waves issue none.  The CU's
+// Wave specialisation (every launch, stream-K and grouped ones included): waves 8..11, one per SIMD, do nothing
+// but issue the LDS-DMA, and the eight MFMA waves issue none.  The CU's
 // load path delivers ~10 B/clk and a k-step needs 6: a wave that issues a DMA queues behind the other waves' pieces
 // (~130 cycles per instruction, in order, so its MFMAs wait too), and because SIMD partners alternate whole 16-MFMA
-// runs both partners reach their DMA issue together and the matrix pipe idles meanwhile.  Ablation (timing-only
-// builds, 229376x2304x768 / 229376x768x3072): no DMA issue 131 -> 144 / 136 -> 146 TFLOP/s, no fragment reads +-0, no
+// runs both partners reach their DMA issue together and the matrix pipe idles meanwhile.  Ablation of the 8-wave
+// build whose MFMA waves issued their own DMA (timing-only builds, 229376x2304x768 / 229376x768x3072): no DMA issue 131 -> 144 / 136 -> 146 TFLOP/s, no fragment reads +-0, no
 // barrier -1 %, no counted wait +-1 %, no epilogue stores +4 % / +1 %.  A loader wave parks at the barrier between
-// its bursts and costs the matrix pipe nothing.
+// its bursts and costs the matrix pipe nothing.  (profiles/round2_gemm_ablation_nonws.log; the
+// same ablation of the loader-wave build: round2_gemm_ablation_ws.log.)
 //
 // Operand layouts (template flags) for the backward pass of nn.Linear:
 //   TA=0: A stored (M, Kc) k-contiguous      TA=1: A stored (Kc, M) m-contiguous  (dW = dYᵀ·X reads dY this way)
@@ -49,15 +50,10 @@
 
 namespace {
 
-#ifndef STLT_GEMM_PRIO_MODE
-#define STLT_GEMM_PRIO_MODE 0  // 0 off (measured best: 134.4 TF); 1 static priority for waves 4-7 (134); 2 SIMD partners alternate priority per half k-step (133.7)
-#endif
-
 constexpr int BM = 256, BN = 128, BK = 32;
 constexpr int GEMM_WAVES = 8;                           // MFMA waves
-constexpr int GEMM_THREADS = 64 * GEMM_WAVES;
-constexpr int GEMM_LOADERS = 4;                         // WS: DMA-only waves 8..11
-constexpr int GEMM_THREADS_WS = 64 * (GEMM_WAVES + GEMM_LOADERS);
+constexpr int GEMM_LOADERS = 4;                         // DMA-only waves 8..11
+constexpr int GEMM_THREADS = 64 * (GEMM_WAVES + GEMM_LOADERS);
 constexpr int NSTAGE = 3;
 constexpr int STAGE_FLOATS = (BM + BN) * BK;  // 12288 floats = 48 KB per stage
 
@@ -66,19 +62,6 @@ typedef const __attribute__((address_space(1))) void* glb_void_ptr;
 
 #ifndef STLT_GEMM_ABLATE
 #define STLT_GEMM_ABLATE 0  // timing-only builds (wrong results): bit 0 no steady-state DMA, bit 3 loaders do not wait for their DMA, bit 4 no epilogue stores, bit 5 loaders re-read k-step 0 of their first tile (cache-hot source)
-#endif
-#ifndef STLT_GEMM_RES_PREFETCH
-// (requesting the second row half's pieces ahead of the first half's stores as well was tried: 8 pieces spill 72 registers at the 168 budget, 4 spill 32)
-#define STLT_GEMM_RES_PREFETCH 1  // the add-source pieces of a tile's first row half are requested at the start of the tile's last k-step (forward layout, loader-wave build, whole tiles): cfg2 / 1024 clips with the residual adds in the epilogues 107.2 -> 106.7 ms (profiles/round3_fwd_residual_ab.txt)
-#endif
-#ifndef STLT_GEMM_STORE_NT
-#define STLT_GEMM_STORE_NT 0  // 1: non-temporal epilogue stores — measured slower (cfg2 / 1024 clips: 107.3 -> 108.1 ms per forward, round 3)
-#endif
-#ifndef STLT_GEMM_GROUPED
-#define STLT_GEMM_GROUPED 1  // 1: every XCD walks a contiguous stretch of a band-major tile order (bands of 4 M-panels, N outer inside a band); 0: round-1 order
-#endif
-#ifndef STLT_GEMM_WS_DEFAULT
-#define STLT_GEMM_WS_DEFAULT 1
 #endif
 __device__ __forceinline__ float half_wave_sum(float x) {  // over the 32 lanes that share lane >> 5
   x += __shfl_xor(x, 1, 64);
@@ -98,11 +81,11 @@ struct SkPlan { int dp_rounds; int P[9]; int S[8]; };
 struct SkNone {};
 template <bool B, class T> auto karg(const T& t) { if constexpr (B) return t; else return SkNone{}; }
 
-// GROUP (with SK and WS): the launch walks the tiles of several products (StltGemmGroup, by value in the kernel arguments:
+// GROUP (with SK): the launch walks the tiles of several products (StltGemmGroup, by value in the kernel arguments:
 // a wave reads the fields of the product its current tile belongs to with scalar loads); X / W / R / Y / M / N / K of the
 // single-product form are unused.  Plain stream-K assignment over the concatenated k-step space.
-template <int ACT, bool STAMP, bool TA, bool TB, bool ADD, bool SK, bool WS, bool GROUP = false>
-__global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) void gemm_nt_kernel(const float* __restrict__ X, int64_t ldx,
+template <int ACT, bool STAMP, bool TA, bool TB, bool ADD, bool SK, bool GROUP = false>
+__global__ __launch_bounds__(GEMM_THREADS, 3) void gemm_nt_kernel(const float* __restrict__ X, int64_t ldx,
                                                                   const float* __restrict__ W, int64_t ldw,
                                                                   const float* __restrict__ bias,
                                                                   const float* __restrict__ R, int64_t ldr,
@@ -118,9 +101,8 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
   if constexpr (SK) plan = plan_in;
   if constexpr (GROUP) grp = grp_in;
   if constexpr (ACT == STLT_ACT_GELU_BWD) epi = epi_in;
-  static_assert(!GROUP || (SK && WS), "grouped launches are stream-K launches of the loader-wave build");
+  static_assert(!GROUP || SK, "grouped launches are stream-K launches");
   static_assert(ACT != STLT_ACT_GELU_BWD || (ADD && !GROUP), "the fused GELU backward reads u through the add-source");
-  constexpr int prio = STLT_GEMM_PRIO_MODE;
   constexpr int NBIAS = 2;  // bias strips, by tile parity
   __shared__ __attribute__((aligned(16))) float smem[NSTAGE * STAGE_FLOATS + NBIAS * BN];  // operand stages + bias strips
 
@@ -149,7 +131,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
   // (4 X panels + 8 W panels instead of ~2 + all of them), and the next round moves on along N inside the same band, so the
   // band's X panels stay in the XCD's L2 while its W panels stream.
   constexpr int GROUP_M = 4;
-  const bool grouped = STLT_GEMM_GROUPED && !SK && n_split == 1 && (G & 7) == 0;
+  const bool grouped = !SK && n_split == 1 && (G & 7) == 0;
   const int g_xcd = blockIdx.x & 7, g_local = blockIdx.x >> 3, g_gx = G >> 3;
   const int g_rounds = (n_tiles + G - 1) / G;
   int my_tiles, sk_first = 0, sk_kt0 = 0, sk_tail = 0;
@@ -272,7 +254,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
   //   k-contiguous operand : image [rows][32 k] (swizzled); an instruction covers 8 rows x 128 B
   //   contraction-major    : image [32 k][256 m | 128 n]; an instruction covers one 1-KB k-row (A) / two 512-B k-rows (B)
   const int drow = lane >> 3, dslot = lane & 7;
-  constexpr int NV = WS ? 2 : 1;  // a loader wave does the DMA share of MFMA waves 2j and 2j+1
+  constexpr int NV = 2;  // a loader wave does the DMA share of MFMA waves 2j and 2j+1
   // Addresses = a wave-uniform base per operand (the tile's origin: scalar registers; the k offset is added with scalar arithmetic) + a
   // per-lane 32-bit byte offset fixed for the tile, so that a k-step's DMA issue costs no vector-ALU instruction (round 5: with 64-bit
   // per-lane pointers every instruction paid a 64-bit vector add, issued beside the MFMA waves of the loader's SIMD; the small-tile
@@ -281,7 +263,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
   uint32_t vob[NV][2];
   const char* base_a = nullptr;
   const char* base_b = nullptr;
-  const int vw0 = WS ? 2 * (wave - GEMM_WAVES) : wave;  // first "virtual wave" whose DMA share this wave issues (WS: loaders only)
+  const int vw0 = 2 * (wave - GEMM_WAVES);  // first "virtual wave" whose DMA share this wave issues (loaders only)
   int64_t a_kstep = (TA ? (int64_t)BK * ldx : BK) * (int64_t)sizeof(float);  // bytes per k-step
   int64_t b_kstep = (TB ? (int64_t)BK * ldw : BK) * (int64_t)sizeof(float);
   auto dma_set_tile = [&](int it) {
@@ -334,7 +316,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
   };
   // One k-step's DMA = 6 instructions per wave, issued in three parts (A 0-1, A 2-3, B) so they can be spread
   // between the MFMA chunks of the previous step instead of queueing at the TA all at once.
-  auto issue_dma_part = [&](int part, int kt, int stage, int u = 0) {
+  auto issue_dma_part = [&](int part, int kt, int stage, int u) {
     const int vw = vw0 + u;
     float* sa = smem + stage * STAGE_FLOATS + (TA ? (vw * 4) * BM : (vw * 32) * BK);
     float* sb = smem + stage * STAGE_FLOATS + BM * BK + (TB ? (vw * 4) * BN : (vw * 16) * BK);
@@ -396,7 +378,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
   // would make hipcc drain the DMA in flight with a vmcnt(0) at its first use.)
   float* bias_lds = smem + NSTAGE * STAGE_FLOATS;
   auto dma_bias = [&](int it) {
-    if (bias && wave == (WS ? GEMM_WAVES : 0)) {
+    if (bias && wave == GEMM_WAVES) {
       int m0, n0, split;
       tile_origin(it, m0, n0, split);
       float* dst = bias_lds + (it & 1) * BN;
@@ -408,7 +390,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
       }
     }
   };
-  if (WS && wave >= GEMM_WAVES) {
+  if (wave >= GEMM_WAVES) {
     // ---- loader waves: the whole DMA stream of the workgroup, two k-steps ahead of the MFMA waves, same barriers
     int l_it = 0, l_kt = kt_begin(0), l_stage = 0;
     bool l_fresh = true;  // row pointers not yet set for the tile the stream is in (first step, possibly mid-tile)
@@ -447,7 +429,6 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
     }
     return;
   }
-  if (!WS) dma_bias(0);
   f32x16 acc[2][2];
   // accumulator (a, b), register r of lane (lr, lh) holds output element
   //   row  = wm*64 + a*32 + lr                  (TA: wm*64 + 2*lr + a, the row-interleaved tiles of the ds_read_b64 fragments)
@@ -484,28 +465,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
     }
   };
 
-  // ---- prologue: two steps in flight ------------------------------------------------------------------
-  int d_it = 0, d_kt = SK ? sk_kt0 : 0;  // DMA stream position (runs two steps ahead of the MFMAs)
-  int d_stage = 0;
-  if (!WS && SK && sk_kt0 != 0) dma_set_tile(0);  // a range that begins inside a tile
-  auto dma_part = [&](int part) {  // part 0 also moves to the next tile's row pointers when needed
-    if (WS) return;                // the loader waves own the DMA stream
-    if (part == 0 && d_kt == 0) dma_set_tile(d_it);
-    issue_dma_part(part, d_kt, d_stage);
-    if (part == 2) {
-      if (++d_kt == nk) { d_kt = 0; ++d_it; }
-      if (++d_stage == NSTAGE) d_stage = 0;
-    }
-  };
-  dma_part(0); dma_part(1); dma_part(2);
-  if (WS) {
-    // nothing of this wave's is in flight: the loaders' counted wait + this barrier publish step 0
-  } else if (total_steps > 1) {
-    dma_part(0); dma_part(1); dma_part(2);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");  // in-order counter: step 0 (and the bias strip before it) landed
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  // ---- MFMA waves: nothing of theirs is in flight, the loaders' counted wait + this barrier publish step 0 ----
   __builtin_amdgcn_s_barrier();
   init_acc(0, SK && !seg_complete(0));
   Frags fa = read_frags(0, 0), fb;  // ping-pong fragment registers: 4 chunk reads per step, so fa is "current" at every step start
@@ -513,19 +473,18 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
   int c_it = 0, c_kt = kt_begin(0);  // MFMA stream position
   if constexpr (GROUP) nk = grp.p[g_p0].nk;  // k-steps of the MFMA stream's current tile
   int stage = 0;
-  constexpr bool RES_PF = STLT_GEMM_RES_PREFETCH && ADD && WS && !SK && !TA && !TB;
+  // the add-source pieces of a tile's first row half are requested at the start of the tile's last k-step (forward layout, whole tiles): cfg2 /
+  // 1024 clips with the residual adds in the epilogues 107.2 -> 106.7 ms (profiles/round3_fwd_residual_ab.txt).  Requesting the second row
+  // half's pieces ahead of the first half's stores as well was tried: 8 pieces spill 72 registers at the 168 budget, 4 spill 32.
+  constexpr bool RES_PF = ADD && !SK && !TA && !TB;
   f32x4 rpf[RES_PF ? 8 : 1];  // add-source pieces of row half a = 0 of the current tile, in flight during its last k-step
   bool rpf_ok = false;
   unsigned long long t_acc[6] = {0, 0, 0, 0, 0, 0}, t_prev = 0;
 #define GSTAMP(k) do { if (STAMP) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_now = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); t_acc[k] += t_now - t_prev; t_prev = t_now; __builtin_amdgcn_sched_barrier(0); } } while (0)
   if (STAMP) { t_prev = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); }
-  if (prio == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);  // static: the second-dispatched half wins arbitration
+  // (wave priorities were tried and lost: none 134.4 TFLOP/s, static priority for waves 4-7 134.0, SIMD partners alternating per half k-step 133.7)
   for (int step = 0; step < total_steps; ++step) {
-    if (prio == 2) { if (wave < 4) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
     const int next_stage = stage + 1 == NSTAGE ? 0 : stage + 1;
-    const bool prefetch = (STLT_GEMM_ABLATE & 1) ? false : step + 2 < total_steps;  // step+2's operands go to the stage retired by the previous barrier
-    const bool bias_step = c_kt == nk - 1 && c_it + 1 < my_tiles;
-    if (!WS && bias_step) dma_bias(c_it + 1);  // older than this step's operand DMA: covered by the counted wait below
     if constexpr (RES_PF) {
       if (c_kt == nk - 1) {  // the epilogue is 64 MFMAs away: its first eight residual pieces travel under them
         int m0, n0, split;
@@ -538,26 +497,19 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
         }
       }
     }
-    // chunks 0..2: read the next chunk of this stage, 16 MFMAs on the current one, a third of step+2's DMA
+    // chunks 0..2: read the next chunk of this stage, 16 MFMAs on the current one
     fb = read_frags(stage, 1);
     mfma_chunk(fa);
-    if (prefetch) dma_part(0);
     fa = read_frags(stage, 2);
     mfma_chunk(fb);
-    if (prio == 2) { if (wave < 4) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
-    if (prefetch) dma_part(1);
     fb = read_frags(stage, 3);
     mfma_chunk(fa);
-    if (prefetch) dma_part(2);
     if (STAMP) asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[1][1][15]));
-    GSTAMP(0);  // chunks 0..2: 48 MFMAs + fragment reads + DMA issue
-    // chunk 3: retire this stage.  Every wave has received all its reads of `stage`, and step+1's DMA has
-    // landed.  The VMEM counter is in order: the only operations younger than step+1's DMA that may stay in
-    // flight are the 6 DMAs of step+2 (the bias strip and a previous epilogue's stores are older than those).
-    if (WS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own fragment reads only; a previous epilogue's stores may stay in flight
-    else if (prefetch) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    GSTAMP(1);  // wait for own DMA + LDS reads
+    GSTAMP(0);  // chunks 0..2: 48 MFMAs + fragment reads
+    // chunk 3: retire this stage.  Every wave has received all its reads of `stage`; the loaders' counted wait in front of the
+    // same barrier says that step+1's DMA has landed.
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own fragment reads only; a previous epilogue's stores may stay in flight
+    GSTAMP(1);  // wait for own LDS reads
     __builtin_amdgcn_s_barrier();
     GSTAMP(2);  // barrier
     GSTAMP(3);
@@ -706,8 +658,7 @@ __global__ __launch_bounds__(WS ? GEMM_THREADS_WS : GEMM_THREADS, WS ? 3 : 2) vo
               if (ACT == STLT_ACT_RELU) val[j] = fmaxf(val[j], 0.f);
             }
             if (STLT_GEMM_ABLATE & 16) asm volatile("" :: "v"(val));
-            else if (STLT_GEMM_STORE_NT) __builtin_nontemporal_store(val, reinterpret_cast<f32x4*>(yrow + t_col4(g)));
-            else *reinterpret_cast<f32x4*>(yrow + t_col4(g)) = val;
+            else *reinterpret_cast<f32x4*>(yrow + t_col4(g)) = val;  // (non-temporal stores measured slower: cfg2 / 1024 clips 107.3 -> 108.1 ms per forward, round 3)
           }
         }
       } else {
@@ -1190,7 +1141,7 @@ static int launch_gemm_impl(int transA, int transB, const float* a, int64_t lda,
   stlt_prof_add_flops(2.0 * (double)M * (double)N * (double)K);
   stlt_prof_note("gemm%s M=%lld N=%lld K=%lld act=%d%s tile=256x128 tiles=%lld", transA ? "(dW)" : (transB ? "(dX)" : (on_copy ? "(dX on the Wt copy)" : "")), (long long)M, (long long)N, (long long)K, act,
                  r ? "+R" : "", (long long)(tiles_m * tiles_n));
-  dim3 block(GEMM_THREADS);
+  const dim3 block(GEMM_THREADS);
   // Stream-K when whole tiles would leave CUs idle (fewer tiles than CUs, or a ragged last round) and the caller
   // lent scratch for the partial tiles (StltGemmScratch / stlt_gemm_set_scratch).
   const int64_t n_tiles = tiles_m * tiles_n, nk = K / BK;
@@ -1212,19 +1163,17 @@ static int launch_gemm_impl(int transA, int transB, const float* a, int64_t lda,
       dim3 grid((unsigned)G);
       float* P = t_gemm_scratch;
       stlt_prof_note("stream-K wg=%lld ksteps/wg=%d (+fix-up)", (long long)G, S);
-      static const bool ws_sk = [] { const char* e = getenv("STLT_GEMM_WS"); return e ? atoi(e) != 0 : (STLT_GEMM_WS_DEFAULT != 0); }();
-      // hybrid: whole-tile rounds in the grouped order + a stream-K tail (loader-wave build, full grid of 8 x Gx workgroups,
+      // hybrid: whole-tile rounds in the grouped order + a stream-K tail (full grid of 8 x Gx workgroups,
       // the tail at least 4 k-steps per workgroup: the last whole round joins it otherwise).  STLT_GEMM_HYBRID=0: plain stream-K.
       static const bool hybrid_on = [] { const char* e = getenv("STLT_GEMM_HYBRID"); return e ? atoi(e) != 0 : true; }();
       SkPlan plan{};
       int64_t fix_tiles = n_tiles;
-      if (hybrid_on && ws_sk && G == n_cu()) {
+      if (hybrid_on && G == n_cu()) {
         int64_t tail = 0;
         if (make_sk_plan(n_tiles, nk, G, xcd_weights(), weighted, plan, tail)) fix_tiles = tail;
         else plan = SkPlan{};
       }
-#define LAUNCH_SK1(ACTV, TAV, TBV, ADDV, WSV, BLK) hipLaunchKernelGGL((gemm_nt_kernel<ACTV, false, TAV, TBV, ADDV, true, WSV>), grid, BLK, 0, s, a, lda, b, ldb, bias, r, ldr, c, ldc, slab_stride, (int)M, (int)N, (int)K, (int)tiles_m, (int)tiles_n, 1, P, nullptr, plan, SkNone{}, karg<(ACTV) == STLT_ACT_GELU_BWD>(epi))
-#define LAUNCH_SK(ACTV, TAV, TBV, ADDV) do { if (ws_sk) LAUNCH_SK1(ACTV, TAV, TBV, ADDV, true, dim3(GEMM_THREADS_WS)); else LAUNCH_SK1(ACTV, TAV, TBV, ADDV, false, block); } while (0)
+#define LAUNCH_SK(ACTV, TAV, TBV, ADDV) hipLaunchKernelGGL((gemm_nt_kernel<ACTV, false, TAV, TBV, ADDV, true>), grid, block, 0, s, a, lda, b, ldb, bias, r, ldr, c, ldc, slab_stride, (int)M, (int)N, (int)K, (int)tiles_m, (int)tiles_n, 1, P, nullptr, plan, SkNone{}, karg<(ACTV) == STLT_ACT_GELU_BWD>(epi))
       if (transA) { if (r) LAUNCH_SK(STLT_ACT_NONE, true, true, true); else LAUNCH_SK(STLT_ACT_NONE, true, true, false); }
       else if (transB && act == STLT_ACT_GELU_BWD) LAUNCH_SK(STLT_ACT_GELU_BWD, false, true, true);
       else if (transB) { if (r) LAUNCH_SK(STLT_ACT_NONE, false, true, true); else LAUNCH_SK(STLT_ACT_NONE, false, true, false); }
@@ -1234,7 +1183,6 @@ static int launch_gemm_impl(int transA, int transB, const float* a, int64_t lda,
       else if (act == STLT_ACT_RELU) LAUNCH_SK(STLT_ACT_RELU, false, false, false);
       else LAUNCH_SK(STLT_ACT_NONE, false, false, false);
 #undef LAUNCH_SK
-#undef LAUNCH_SK1
       if (int e = stlt_check_launch("gemm_nt_kernel(stream-k)")) return e;
       dim3 fgrid((unsigned)(fix_tiles * FIXUP_CHUNKS)), fblock(256);
 #define FIX(ACTV) hipLaunchKernelGGL((gemm_fixup_kernel<ACTV>), fgrid, fblock, 0, s, P, S, (int)nk, bias, r, ldr, c, ldc, (int)M, (int)N, (int)tiles_m, (int)tiles_n, (int)G, plan, epi)
@@ -1248,11 +1196,7 @@ static int launch_gemm_impl(int transA, int transB, const float* a, int64_t lda,
   }
   dim3 grid((unsigned)n_wg);
   stlt_prof_note("wg=%lld rounds=%lld ksteps=%lld split=%d", (long long)n_wg, (long long)((tiles_m * tiles_n * n_split + n_wg - 1) / n_wg), (long long)(nk / n_split), n_split);
-  // wave-specialised build (4 DMA-only waves beside the 8 MFMA waves) unless STLT_GEMM_WS=0 (A/B measurements)
-  static const bool ws = [] { const char* e = getenv("STLT_GEMM_WS"); return e ? atoi(e) != 0 : (STLT_GEMM_WS_DEFAULT != 0); }();
-  const dim3 block_ws(GEMM_THREADS_WS);
-#define LAUNCH1(ACTV, STAMPV, TAV, TBV, ADDV, WSV, BLK) hipLaunchKernelGGL((gemm_nt_kernel<ACTV, STAMPV, TAV, TBV, ADDV, false, WSV>), grid, BLK, 0, s, a, lda, b, ldb, bias, r, ldr, c, ldc, slab_stride, (int)M, (int)N, (int)K, (int)tiles_m, (int)tiles_n, n_split, (float*)nullptr, g_stlt_debug_buf, SkNone{}, SkNone{}, karg<(ACTV) == STLT_ACT_GELU_BWD>(epi))
-#define LAUNCH(ACTV, STAMPV, TAV, TBV, ADDV) do { if (ws) LAUNCH1(ACTV, STAMPV, TAV, TBV, ADDV, true, block_ws); else LAUNCH1(ACTV, STAMPV, TAV, TBV, ADDV, false, block); } while (0)
+#define LAUNCH(ACTV, STAMPV, TAV, TBV, ADDV) hipLaunchKernelGGL((gemm_nt_kernel<ACTV, STAMPV, TAV, TBV, ADDV, false>), grid, block, 0, s, a, lda, b, ldb, bias, r, ldr, c, ldc, slab_stride, (int)M, (int)N, (int)K, (int)tiles_m, (int)tiles_n, n_split, (float*)nullptr, g_stlt_debug_buf, SkNone{}, SkNone{}, karg<(ACTV) == STLT_ACT_GELU_BWD>(epi))
   if (transA) { if (r) LAUNCH(STLT_ACT_NONE, false, true, true, true); else LAUNCH(STLT_ACT_NONE, false, true, true, false); }
   else if (transB && act == STLT_ACT_GELU_BWD) LAUNCH(STLT_ACT_GELU_BWD, false, false, true, true);
   else if (transB) { if (r) LAUNCH(STLT_ACT_NONE, false, false, true, true); else LAUNCH(STLT_ACT_NONE, false, false, true, false); }
@@ -1264,7 +1208,6 @@ static int launch_gemm_impl(int transA, int transB, const float* a, int64_t lda,
   else if (act == STLT_ACT_RELU) LAUNCH(STLT_ACT_RELU, false, false, false, false);
   else LAUNCH(STLT_ACT_NONE, false, false, false, false);
 #undef LAUNCH
-#undef LAUNCH1
   return stlt_check_launch("gemm_nt_kernel");
 }
 
@@ -1314,7 +1257,7 @@ int launch_weight_grad_group(const StltWeightGradItem* items, int n_items, hipSt
   stlt_prof_add_flops(flops);
   stlt_prof_note("gemm(dW group) products=%d tiles=%lld ksteps=%lld tile=256x128 stream-K wg=%lld ksteps/wg=%d (+fix-up)", n, (long long)tiles, (long long)steps, (long long)G, S);
   float* P = t_gemm_scratch;
-  hipLaunchKernelGGL((gemm_nt_kernel<STLT_ACT_NONE, false, true, true, true, true, true, true>), dim3((unsigned)G), dim3(GEMM_THREADS_WS), 0, s,
+  hipLaunchKernelGGL((gemm_nt_kernel<STLT_ACT_NONE, false, true, true, true, true, true>), dim3((unsigned)G), dim3(GEMM_THREADS), 0, s,
                      (const float*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, (const float*)nullptr, (const float*)nullptr, (int64_t)0,
                      (float*)nullptr, (int64_t)0, (int64_t)0, 0, 0, BK, 0, 0, 1, P, (unsigned long long*)nullptr, SkPlan{}, grp, SkNone{});
   if (int e = stlt_check_launch("gemm_nt_kernel(grouped stream-k)")) return e;

@@ -12,15 +12,6 @@
 #pragma once
 #include "common.h"
 
-#ifndef STLT_G16_SCHED
-#define STLT_G16_SCHED 0  // 1: the k-step's read / MFMA phases pinned with sched_barrier; 0: the compiler's own order (measured equal on narrow tiles, 3 - 8 % faster on 192-column ones: profiles/round5_gemm16_ablation.txt)
-#endif
-#ifndef STLT_G16_DEEP
-#define STLT_G16_DEEP 1  // 1: narrow wave tiles prefetch a whole k-step of fragments (0: the two-phase pipeline for every tile, A/B builds)
-#endif
-#ifndef STLT_G16_PRIO
-#define STLT_G16_PRIO 0  // s_setprio of the MFMA waves (the loader waves stay at 0); A/B builds
-#endif
 #ifndef STLT_G16_ABLATE
 #define STLT_G16_ABLATE 0  // timing-only builds (wrong results): bit 0 no steady-state DMA, bit 1 no steady-state fragment reads, bit 2 no steady-state barrier, bit 3 no epilogue stores, bit 4 the loaders re-read k-step 0 (cache-hot source), bit 5 the loaders run their code without the DMA instructions
 #endif
@@ -69,7 +60,7 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
   // Narrow wave tiles (<= 3 column tiles per wave: 12 MFMAs per k-chunk) cannot cover an LDS round trip with the MFMAs of one phase.  Their
   // MFMA waves keep a whole k-step of fragments in registers and request step s + 1's while multiplying step s, so the barrier that ends
   // step s must already have published step s + 2: the loaders' counted wait leaves one step fewer in flight (DEEP; needs >= 4 stages).
-  constexpr bool DEEP = STLT_G16_DEEP && NTW <= 3 && Q_NSTAGE >= 4;
+  constexpr bool DEEP = NTW <= 3 && Q_NSTAGE >= 4;
   constexpr int PUB = DEEP ? 2 : 1;  // the barrier at the end of step s publishes step s + PUB
   constexpr int NI = 2 * RB + 2 * NT;   // 8-row (1 KB) LDS-DMA instructions per k-step: the X image's 2 RB, then the W image's 2 NT
   constexpr int NL_MAX = (NI + 3) / 4;  // ... dealt round-robin to the four loaders
@@ -199,7 +190,6 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
   }
 
   // ---- MFMA waves: wave w owns rows [16 rb, 16 rb + 16) of the tile and the column tiles cg NTW .. cg NTW + NTW - 1
-  if (STLT_G16_PRIO) __builtin_amdgcn_s_setprio(STLT_G16_PRIO);
   const int rb = wave % RB, cg = wave / RB;
   const int li = lane & 15, lg = lane >> 4;
   const int sw = (li >> 1) & 7;
@@ -207,8 +197,8 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
   const int w_row = (QM + cg * NTW * 16 + li) * QK;
   // A k-step is NP phases: one k-chunk of 16 per phase with all the wave's column tiles (NTW <= 6), or half the column tiles per
   // phase (registers).  The fragments of phase p + 1 are requested behind the first MFMA group of phase p, and those of the next stage's
-  // phase 0 right behind the barrier that publishes it, in front of the last phase's MFMAs.  (STLT_G16_SCHED=1 pins that order with
-  // sched_barrier; the compiler's own placement measured equal on narrow tiles and 3 - 8 % faster on 192-column ones.)
+  // phase 0 right behind the barrier that publishes it, in front of the last phase's MFMAs.  (Pinning that order with sched_barrier was
+  // tried: the compiler's own placement measured equal on narrow tiles and 3 - 8 % faster on 192-column ones, profiles/round5_gemm16_ablation.txt.)
   constexpr bool SPLIT = NTW > 6;
   constexpr int NP = SPLIT ? 4 : 2;
   constexpr int PT = SPLIT ? (NTW + 1) / 2 : NTW;  // column tiles per phase (the second half of a split chunk has NTW - PT)
@@ -260,11 +250,6 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
       for (int t = 0; t < PT; ++t)
         if (t0 + t < NTW) acc[t0 + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.w[t][e], xf[c][e], acc[t0 + t], 0, 0, 0);
   };
-#if STLT_G16_SCHED
-#define G16_PIN() __builtin_amdgcn_sched_barrier(0)
-#else
-#define G16_PIN() ((void)0)
-#endif
 
   int c_it = 0, c_kt = 0, stage = 0;
   // epilogue of tile c_it (its last k-step's MFMAs are issued), then the next tile's accumulators
@@ -437,23 +422,17 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
       // the phase's first MFMA group goes in front of the next phase's read requests: the compiler's wait for this phase's fragments
       // is an lgkmcnt(0) (the counter is shared with scalar loads), which behind the new requests would wait for those as well
       mfma_phase(p, F[p & 1], 0, 1);
-      G16_PIN();
       if (!ablate_reads) read_phase(stage, p + 1, F[(p + 1) & 1]);
-      G16_PIN();
       mfma_phase(p, F[p & 1], 1, 4);
-      G16_PIN();
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // own fragment reads of this stage are done
     if (!(STLT_G16_ABLATE & 4)) __builtin_amdgcn_s_barrier();  // retire the stage; step+1 landed
     // the next stage's first fragments (after the last k-step of a tile: the next tile's; after the very last step: a dead read), under the last phase's MFMAs
     if (!ablate_reads) read_phase(next_stage, 0, F[0]);
-    G16_PIN();
     mfma_phase(NP - 1, F[1], 0, 4);
-    G16_PIN();
     stage = next_stage;
     if (++c_kt == nk) tile_done(step);
   }
-#undef G16_PIN
 }
 
 template <int RB, int NT, int ACT, bool ADD, bool WKN>

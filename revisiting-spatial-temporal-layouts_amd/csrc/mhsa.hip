@@ -16,23 +16,11 @@ namespace {
 #ifndef STLT_MHSA_ABLATE
 #define STLT_MHSA_ABLATE 0  // timing-only builds (wrong results): bit 0 no ctx stores (what keeping the attention output on chip for a fused out-projection could save at most); bit 2 no attention phase but its two barriers (the in-projection alone, accumulators kept alive): 5 749 against 6 077 us for 32 768 frames of 7 objects, 830 against 862 us for 1 024 clips of 32 frames (profiles/round6_mhsa_window_ab.txt)
 #endif
-#ifndef STLT_MHSA_SWAP_REDUCE
-#define STLT_MHSA_SWAP_REDUCE 1  // 0: the softmax's two cross-group reductions through ds_bpermute shuffles (A/B builds)
-#endif
-#ifndef STLT_MHSA_EARLY_RESTART
-#define STLT_MHSA_EARLY_RESTART 0  // 1 (A/B builds): the next item's bias rows and first fragments requested right behind attention barrier 2 (the q / k / v accumulators are dead there), under the softmax and PV, instead of after the phase — measured slower: 6 131 against 6 060 us (32 768 frames of 7), 866 - 877 against 860 us (1 024 clips of 32 frames), profiles/round6_mhsa_window_ab.txt
-#endif
-#ifndef STLT_MHSA_LOADER
-#define STLT_MHSA_LOADER 2
-#endif
 constexpr int FM = 128, FN = 192, FK = 32;
 constexpr int F_WAVES = 8, F_LOADERS = 4;
 constexpr int F_THREADS = 64 * (F_WAVES + F_LOADERS);
 constexpr int F_NSTAGE = 3;
 constexpr int F_STAGE = (FM + FN) * FK;        // 10240 floats = 40 KB
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef const __attribute__((address_space(1))) void* glb_void_ptr;
 
 // Any sequence length up to 64 tokens (the reference's real layouts are T = layout_num_frames + 1 = 17 / 33, datasets.py:97-113;
 // cfg4 has 64 frames), training forwards (probability dropout, packed QKV written for the tape) and — CAUSAL = false — the spatial
@@ -126,15 +114,11 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
     // addresses = a wave-uniform base (scalar registers, advanced per k-step by scalar adds) + a per-lane 32-bit byte offset fixed for
     // the item: no vector-ALU instruction in the steady state (see gemm16_kernel.h).  An instruction's 8 rows of the W image lie in one
     // of the head's q / k / v blocks (8 divides 64), so that block's first row goes into the instruction's base.
-    // STLT_MHSA_LOADER (A/B builds): 0 = round 4's 64-bit per-lane pointers + a vector add per instruction, 1 = the compiler's builtin on base + offset
-    // (it folds the X image's into the scalar-base form and keeps a vector add for the W image's), 2 = stlt_dma16 for every instruction
+    // Every instruction is a stlt_dma16: round 4's 64-bit per-lane pointers cost a vector add per instruction, and the compiler's builtin on
+    // base + offset keeps a vector add for the W image's (profiles/round5_loader_ab.txt).
     uint32_t voa[4], vob[6];
     const char* bx = nullptr;
     const char* bw = nullptr;
-#if STLT_MHSA_LOADER == 0
-    const float* pa[4];
-    const float* pb[6];
-#endif
     auto set_item = [&](int it) {
       int grp, head;
       item_of(it, grp, head);
@@ -146,17 +130,11 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
         const int r = Ld * 32 + i * 8 + drow;
         const int rr = r < M - row0 ? r : M - 1 - row0;  // rows past the batch re-read the last row; nothing of theirs is stored
         voa[i] = ((uint32_t)rr * (uint32_t)d + (uint32_t)((dslot ^ ((r >> 1) & 7)) * 4)) * 4u;
-#if STLT_MHSA_LOADER == 0
-        pa[i] = a.X + (int64_t)(row0 + rr) * d + (dslot ^ ((r >> 1) & 7)) * 4;
-#endif
       }
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
         const int r = Ld * 48 + i * 8 + drow;
         vob[i] = ((uint32_t)(r & 63) * (uint32_t)d + (uint32_t)((dslot ^ ((r >> 1) & 7)) * 4)) * 4u;
-#if STLT_MHSA_LOADER == 0
-        pb[i] = a.Win + (int64_t)((r >> 6) * d + head * 64 + (r & 63)) * d + (dslot ^ ((r >> 1) & 7)) * 4;
-#endif
       }
     };
     auto dma_bias = [&](int it) {
@@ -165,10 +143,7 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
         item_of(it, grp, head);
         float* dst = bias_lds + (it & 1) * FN;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          if (STLT_MHSA_LOADER == 2) stlt_dma4(a.bin + i * d + head * 64, (uint32_t)lane * 4u, stlt_lds_addr(dst + i * 64));
-          else __builtin_amdgcn_global_load_lds((glb_void_ptr)(a.bin + i * d + head * 64 + lane), (lds_void_ptr)(dst + i * 64), 4, 0, 0);
-        }
+        for (int i = 0; i < 3; ++i) stlt_dma4(a.bin + i * d + head * 64, (uint32_t)lane * 4u, stlt_lds_addr(dst + i * 64));
       }
     };
     int l_it = 0, l_kt = 0, l_stage = 0;
@@ -176,28 +151,17 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
       if (l_kt == 0) set_item(l_it);
       float* sa = smem + l_stage * F_STAGE + (Ld * 32) * FK;
       float* sb = smem + l_stage * F_STAGE + FM * FK + (Ld * 48) * FK;
-#if STLT_MHSA_LOADER == 0
-#pragma unroll
-      for (int i = 0; i < 4; ++i) __builtin_amdgcn_global_load_lds((glb_void_ptr)(pa[i] + l_kt * FK), (lds_void_ptr)(sa + i * 8 * FK), 16, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) __builtin_amdgcn_global_load_lds((glb_void_ptr)(pb[i] + l_kt * FK), (lds_void_ptr)(sb + i * 8 * FK), 16, 0, 0);
-#else
       const uint32_t la = stlt_lds_addr(sa), lb = stlt_lds_addr(sb);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (STLT_MHSA_LOADER == 1) __builtin_amdgcn_global_load_lds((glb_void_ptr)(bx + voa[i]), (lds_void_ptr)(sa + i * 8 * FK), 16, 0, 0);
-        else stlt_dma16(bx, voa[i], la + i * 8 * FK * 4);
-      }
+      for (int i = 0; i < 4; ++i) stlt_dma16(bx, voa[i], la + i * 8 * FK * 4);
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
         const int qkv = (Ld * 48 + i * 8) >> 6;  // wave-uniform: the q / k / v block of this instruction's 8 rows
         const char* bwi = bw + (int64_t)qkv * d * d * (int64_t)sizeof(float);
-        if (STLT_MHSA_LOADER == 1) __builtin_amdgcn_global_load_lds((glb_void_ptr)(bwi + vob[i]), (lds_void_ptr)(sb + i * 8 * FK), 16, 0, 0);
-        else stlt_dma16(bwi, vob[i], lb + i * 8 * FK * 4);
+        stlt_dma16(bwi, vob[i], lb + i * 8 * FK * 4);
       }
       bx += FK * sizeof(float);
       bw += FK * sizeof(float);
-#endif
       if (++l_kt == nk) { ++l_it; l_kt = 0; }
       if (++l_stage == F_NSTAGE) l_stage = 0;
     };
@@ -354,10 +318,6 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // attention barrier 2: the K tile is read (the loaders may refill its stage); q, k, v accumulators are dead
-    if (STLT_MHSA_EARLY_RESTART && step + 1 < total_steps) {  // next item: accumulators from its bias strip (published by the last k-step's barrier), first fragments
-      init_acc(c_it + 1);
-      read_phase(stage, 0, F[0]);
-    }
     if (STLT_MHSA_ABLATE & 4) {
 #pragma unroll
       for (int t = 0; t < 12; ++t) asm volatile("" :: "v"(acc[t]));  // the product is kept
@@ -384,12 +344,7 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
           }
         }
       }
-      if (STLT_MHSA_SWAP_REDUCE) {  // over the four 16-lane groups: permlane swaps, no LDS round trips on the phase's critical path
-        m = groups_max(m);
-      } else {
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-      }
+      m = groups_max(m);  // over the four 16-lane groups: permlane swaps, no LDS round trips on the phase's critical path
       float sum = 0.f;
 #pragma unroll
       for (int i = 0; i < NKB; ++i) {
@@ -402,12 +357,7 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
           }
         }
       }
-      if (STLT_MHSA_SWAP_REDUCE) {
-        sum = groups_sum(sum);
-      } else {
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-      }
+      sum = groups_sum(sum);
       const float inv = sum > 0.f ? 1.0f / sum : 0.f;  // fully masked row -> zeros
       // TRAIN: dropout of the probabilities, applied where a probability is consumed (attn.hip's element index:
       // ((query token * H + head) << 8) | key position; an unmasked key is in the query's sequence, so its position is its row minus
@@ -446,7 +396,10 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
     }
     ++c_it;
     c_kt = 0;
-    if (!STLT_MHSA_EARLY_RESTART && step + 1 < total_steps) {
+    // next item: accumulators from its bias strip (published by the last k-step's barrier), first fragments.  (Requesting them right behind
+    // attention barrier 2, under the softmax and PV, measured slower: 6 131 against 6 060 us for 32 768 frames of 7, 866 - 877 against 860 us
+    // for 1 024 clips of 32 frames, profiles/round6_mhsa_window_ab.txt.)
+    if (step + 1 < total_steps) {
       init_acc(c_it);
       read_phase(stage, 0, F[0]);
     }

@@ -26,14 +26,7 @@ __device__ __forceinline__ void wave_pair32(float v, float& a, float& b) {
 }
 // max / sum over the four 16-lane groups of a wave (lanes ^ 16, ^ 32): what the attention kernels' softmax needs per query column; the same
 // values, added / compared in the same pairs, as `v = op(v, __shfl_xor(v, 16)); v = op(v, __shfl_xor(v, 32))`, without the two LDS round trips
-#ifndef STLT_GROUPS_SWAP
-#define STLT_GROUPS_SWAP 1  // 0: through ds_bpermute shuffles (A/B builds)
-#endif
 __device__ __forceinline__ float groups_max(float v) {
-#if !STLT_GROUPS_SWAP
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-#endif
   float a, b;
   wave_pair16(v, a, b);
   v = fmaxf(a, b);
@@ -41,25 +34,13 @@ __device__ __forceinline__ float groups_max(float v) {
   return fmaxf(a, b);
 }
 __device__ __forceinline__ float groups_sum(float v) {
-#if !STLT_GROUPS_SWAP
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-#endif
   float a, b;
   wave_pair16(v, a, b);
   v = a + b;
   wave_pair32(v, a, b);
   return a + b;
 }
-#ifndef STLT_LN_DPP
-#define STLT_LN_DPP 1  // 0: the LayerNorm reductions through common.h's wave_sum (A/B builds)
-#endif
 __device__ __forceinline__ float wave_sum_dpp(float v) {
-#if !STLT_LN_DPP
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-#else
   float a = v, b = v;
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
   v = a + b;
@@ -72,5 +53,4 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   v += dpp_mov<0x4E>(v);   // quad_perm:[2,3,0,1]
   v += dpp_mov<0xB1>(v);   // quad_perm:[1,0,3,2]
   return v;
-#endif
 }

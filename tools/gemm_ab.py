@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """A/B of GEMM build variants in ONE process, interleaved rounds (GPU box only; build the variants on the CPU side).
 
-    python tools/gemm_ab.py --build s0:-DSTLT_GEMM_STAGGER=0 s1:-DSTLT_GEMM_STAGGER=1     # CPU: build/variants/*.so
-    python tools/gemm_ab.py --run s0 s1 [--batch 1024] [--rounds 7] [--iters 5]           # GPU: median TFLOP/s per shape
+    python tools/gemm_ab.py --build base: nodma:-DSTLT_GEMM_ABLATE=1     # CPU: build/variants/*.so
+    python tools/gemm_ab.py --run base nodma [--batch 1024] [--rounds 7] [--iters 5]           # GPU: median TFLOP/s per shape
 
 Every variant's output is compared with the first variant's (max abs difference), so a schedule change that breaks a
 tile shows up here before the test-suite run.

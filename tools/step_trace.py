@@ -14,9 +14,9 @@ rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 def short(n):
     n = re.sub(r"\(anonymous namespace\)::", "", n)
     n = re.sub(r"^void ", "", n)
-    m = re.match(r"gemm_nt_kernel<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\w+)(?:, (\w+))?>", n)
+    m = re.match(r"gemm_nt_kernel<(\d), (\w+), (\w+), (\w+), (\w+), (\w+)(?:, (\w+))?>", n)
     if m:
-        act, st, ta, tb, add, sk, ws, grp = m.groups()
+        act, st, ta, tb, add, sk, grp = m.groups()
         kind = "dW" if ta == "true" else ("dX" if tb == "true" else "fwd")
         return f"gemm[{kind}{' act' + act if act != '0' else ''}{' +R' if add == 'true' else ''}{' SK' if sk == 'true' else ''}{' GRP' if grp == 'true' else ''}]"
     return n.split("(")[0][:48]
