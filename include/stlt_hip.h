@@ -427,6 +427,34 @@ int stlt_backbone_forward(const stlt_params* p, const stlt_inputs* in, void* wor
 int stlt_forward(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes,
                  int flags, float* out_btd, float* logits, stlt_stream_t stream);
 
+/* ---- Per-prefix logits: Stlt's prediction after every number of observed frames, in one pass ----
+ * The temporal tower is causal (models.py:136-152) and the clip is read out at the extract frame the dataset appends behind the sampled
+ * frames (datasets.py:97-113, models.py:185-195), so "the logits after t observed frames" are Stlt.forward on frames 0 .. t-1 of the clip
+ * followed by the clip's own extract frame (the frame at lengths-1), lengths = t+1.  Spatial tower and frame rows of the temporal tower
+ * are shared by all prefixes of a clip; only the extract token differs.  It runs as a second stream of B*T "probe" rows: probe (b,t) is
+ * the clip's extract frame embedded at position t, which in every temporal layer attends to the frame stream's keys j < t and to itself. */
+
+/* Probe attention of one temporal layer (extends the attention of models.py:136-152 to the probe stream).  qkv_frames, qkv_probes:
+ * (S*T, 3*H*dh) packed rows [q;k;v] of the frame stream and of the probe stream (same in-projection); kpm: (S*T) bytes, 1 = frame masked
+ * as a key; ctx: (S*T, H*dh).  ctx[s,t,h,:] = softmax over { q_p[s,t]·k_f[s,j]/sqrt(dh) : j < t, kpm[s,j] == 0 } and q_p[s,t]·k_p[s,t]/sqrt(dh)
+ * of { v_f[s,j] }, v_p[s,t].  The own key is always present: no row is fully masked, ctx[s,0] = v_p[s,0].  Probes never see other probes;
+ * the queries of qkv_frames are not read.  Any T >= 1 (key tiles with an online softmax), 1 <= dh <= 256.
+ * Alignment: qkv_frames, qkv_probes, ctx 16 bytes (refused otherwise); kpm bytes. */
+int stlt_attn_prefix_probe_fwd(const float* qkv_frames, const float* qkv_probes, const uint8_t* kpm, int64_t S, int64_t T, int64_t H,
+                               int64_t dh, float* ctx, stlt_stream_t stream);
+
+/* bytes of scratch stlt_forward_prefixes needs for this shape (0 for an empty shape) */
+size_t stlt_prefix_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes);
+
+/* Stlt.forward (models.py:185-195 on the backbone of models.py:136-152) for every prefix of every clip.  logits: (B,T,n_classes);
+ * logits[b,t] for t < lengths[b] is what stlt_forward returns for the batch cut to frames 0 .. t-1 of clip b followed by its extract frame
+ * (t = 0: the extract frame alone; t = lengths[b]-1: stlt_forward's own logits); entries t >= lengths[b] are written as 0.
+ * Inference only, padded schedule.  flags: STLT_FLAG_CLS_ONLY_LAST_SPATIAL is honoured, STLT_FLAG_LAST_ROW_ONLY_TEMPORAL is ignored,
+ * STLT_FLAG_SKIP_PADDING is refused (STLT_EINVAL).  In the last temporal layer the frame stream is only projected to keys and values.
+ * No allocation, no synchronisation, capturable.  workspace: 256-byte aligned, stlt_prefix_workspace_bytes. */
+int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags, float* logits,
+                          stlt_stream_t stream);
+
 /* ---- CAF / CACNF on precomputed appearance features (reference models.py:230-271, 286-298, 328-549) ----
  * The layout branch is the StltBackbone above; the appearance branch starts from the R3D-50 feature map the reference's
  * Resnet3D.forward_features returns, (B, 2048, 2,4,4) = (B, feat_channels, app_tokens) row-major, given by the caller. */

@@ -74,3 +74,30 @@ def real_counts(batch, round_up_to: int = 1) -> dict:
         up = lambda v, cap: min(cap, (v + round_up_to - 1) // round_up_to * round_up_to)  # noqa: E731
         tokens, frames = up(tokens, B * T * N), up(frames, B * T)
     return {"num_real_tokens": tokens, "num_real_frames": frames}
+
+
+_PREFIX_KEYS = ("categories", "boxes", "scores", "frame_types", "src_key_padding_mask_boxes", "src_key_padding_mask_frames")
+
+
+def prefix_batch(batch: Dict[str, torch.Tensor], t: int) -> Dict[str, object]:
+    """The collated batch after `t` observed frames: frames 0 .. t-1 of every clip followed by the clip's own extract frame (the frame at
+    index lengths[b]-1, which the dataset appends behind the sampled frames, reference datasets.py:97-113), lengths = t+1.  `t = 0` is the
+    extract frame alone; for a clip with lengths[b]-1 == t it is the clip itself, cut to t+1 columns.  Clips shorter than that carry
+    their padding in front of the extract frame: they have no such prefix (`Stlt.forward_prefixes` marks them invalid).  Works on CPU
+    and device tensors; `scores` is carried when present, other entries (labels, video_id) are passed through."""
+    cats = batch["categories"]
+    B, T = cats.shape[0], cats.shape[1]
+    if not 0 <= t < T:
+        raise ValueError(f"prefix length {t} outside [0, {T})")
+    lengths = batch["lengths"]
+    rows = torch.arange(B, device=lengths.device)
+    ext = (lengths - 1).clamp(0, T - 1)
+    out = dict(batch)
+    for k in _PREFIX_KEYS:
+        if k in batch:
+            v = batch[k]
+            out[k] = torch.cat([v[:, :t], v[rows.to(v.device), ext.to(v.device)].unsqueeze(1)], dim=1).contiguous()
+    out["lengths"] = torch.full_like(lengths, t + 1)
+    out.pop("num_real_tokens", None)  # counted for the whole clips
+    out.pop("num_real_frames", None)
+    return out

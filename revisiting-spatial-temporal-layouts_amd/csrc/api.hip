@@ -324,8 +324,9 @@ struct WsLayout {
   size_t x, x1, qkv, ctx, tmp, hh, head, sk, ridx, total;
 };
 
-static WsLayout ws_layout(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
-  const size_t tok = (size_t)B * T * N;  // spatial tokens >= temporal tokens
+// min_slots: rows per frame the buffers hold at least (the per-prefix forward runs two temporal streams: 2 rows per frame)
+static WsLayout ws_layout(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes, int64_t min_slots = 1) {
+  const size_t tok = (size_t)B * T * (N > min_slots ? N : min_slots);  // spatial tokens >= temporal tokens
   const size_t f = sizeof(float);
   WsLayout w;
   size_t off = 0;
@@ -437,25 +438,12 @@ int stlt_head(const stlt_head_params& h, const float* x, int64_t ldx, int64_t in
   return launch_linear(h2, d, h.fc2_w, h.fc2_b, logits, K, B, K, d, STLT_ACT_NONE, s);
 }
 
-// Backbone body.  With last_rows != nullptr the final temporal layer only produces the rows the head reads
-// (Stlt.forward, models.py:189-192: out[lengths-1, arange(B)]) into last_rows (B,d): K/V/Q are projected for every
-// frame, the attention core runs as usual, but out-proj / norm1 / FFN / norm2 run on the B gathered rows only.
-static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes,
-                         int flags, float* out_btd, float* last_rows, hipStream_t s) {
+// Token embedding + spatial transformer of the backbone (models.py:29-39,57-81) on the caller's buffers (each B*T*N rows; qkv 3x, hh 4x as
+// wide).  *cls_rows / *cls_stride: where each frame's CLS row — the only row read afterwards (models.py:79) — lies: in x (stride N*d), or
+// with STLT_FLAG_CLS_ONLY_LAST_SPATIAL compact in ctx.  x1 is free afterwards.
+static int spatial_tower(const stlt_params* p, const stlt_inputs* in, int flags, float* x, float* x1, float* qkv, float* ctx, float* tmp, float* hh,
+                         const float** cls_rows_out, int64_t* cls_stride_out, hipStream_t s) {
   const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H;
-  const WsLayout w = ws_layout(B, T, N, d, p->n_classes < 0 ? 0 : p->n_classes);
-  if (!workspace || workspace_bytes < w.total)
-    return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
-  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
-  char* base = (char*)workspace;
-  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
-  float* x = (float*)(base + w.x);
-  float* x1 = (float*)(base + w.x1);
-  float* qkv = (float*)(base + w.qkv);
-  float* ctx = (float*)(base + w.ctx);
-  float* tmp = (float*)(base + w.tmp);
-  float* hh = (float*)(base + w.hh);
-
   const int64_t tok = B * T * N, BT = B * T;
   // K1
   TRY(launch_embed(in->categories, in->boxes, in->scores, p->cat_emb, p->n_categories, p->box_w, p->box_b, p->score_w,
@@ -480,6 +468,34 @@ static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* work
     cls_rows = ctx;
     cls_stride = d;
   }
+  *cls_rows_out = cls_rows;
+  *cls_stride_out = cls_stride;
+  return 0;
+}
+
+// Backbone body.  With last_rows != nullptr the final temporal layer only produces the rows the head reads
+// (Stlt.forward, models.py:189-192: out[lengths-1, arange(B)]) into last_rows (B,d): K/V/Q are projected for every
+// frame, the attention core runs as usual, but out-proj / norm1 / FFN / norm2 run on the B gathered rows only.
+static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes,
+                         int flags, float* out_btd, float* last_rows, hipStream_t s) {
+  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H;
+  const WsLayout w = ws_layout(B, T, N, d, p->n_classes < 0 ? 0 : p->n_classes);
+  if (!workspace || workspace_bytes < w.total)
+    return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
+  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
+  char* base = (char*)workspace;
+  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
+  float* x = (float*)(base + w.x);
+  float* x1 = (float*)(base + w.x1);
+  float* qkv = (float*)(base + w.qkv);
+  float* ctx = (float*)(base + w.ctx);
+  float* tmp = (float*)(base + w.tmp);
+  float* hh = (float*)(base + w.hh);
+
+  const int64_t BT = B * T;
+  const float* cls_rows = nullptr;
+  int64_t cls_stride = 0;
+  TRY(spatial_tower(p, in, flags, x, x1, qkv, ctx, tmp, hh, &cls_rows, &cls_stride, s));
   // K7: CLS select + position + frame type + LN -> (B,T,d).  x1 is free here (its last reader was the
   // final norm2 above), x / ctx still hold the CLS rows being read.
   float* tbuf = p->n_temporal > 0 ? x1 : out_btd;
@@ -635,6 +651,72 @@ int stlt_forward(const stlt_params* p, const stlt_inputs* in, void* workspace, s
   }
   const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
   return stlt_head(head, h0, d, d, B, d, p->n_classes, p->ln_eps, h1, h2, logits, s);
+}
+
+
+size_t stlt_prefix_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
+  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
+  return ws_layout(B, T, N, d, n_classes < 0 ? 0 : n_classes, 2).total;
+}
+
+int stlt_attn_prefix_probe_fwd(const float* qkv_frames, const float* qkv_probes, const uint8_t* kpm, int64_t S, int64_t T, int64_t H, int64_t dh,
+                               float* ctx, stlt_stream_t stream) {
+  return launch_attn_prefix_probe(qkv_frames, qkv_probes, kpm, S, T, H, dh, ctx, (hipStream_t)stream);
+}
+
+// Two temporal streams stacked as one (2*B*T, d) matrix: rows [0, B*T) the frames, rows [B*T, 2*B*T) the probes (probe (b,t): the clip's
+// extract frame at position t).  Every product and LayerNorm of a layer is one launch over both; the frames run the ordinary causal
+// attention, the probes launch_attn_prefix_probe.  In the last layer the frames are needed as keys and values only.
+int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags, float* logits,
+                          stlt_stream_t stream) {
+  TRY(check_params(p, in, true));
+  if (!logits) return stlt_set_error(STLT_EINVAL, "stlt_forward_prefixes: logits is null");
+  if (flags & STLT_FLAG_SKIP_PADDING)
+    return stlt_set_error(STLT_EINVAL, "stlt_forward_prefixes: STLT_FLAG_SKIP_PADDING is not supported (the per-prefix forward runs the padded schedule)");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H, BT = B * T;
+  const WsLayout w = ws_layout(B, T, N, d, p->n_classes, 2);
+  if (!workspace || workspace_bytes < w.total)
+    return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
+  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
+  char* base = (char*)workspace;
+  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
+  float* x = (float*)(base + w.x);
+  float* x1 = (float*)(base + w.x1);
+  float* qkv = (float*)(base + w.qkv);
+  float* ctx = (float*)(base + w.ctx);
+  float* tmp = (float*)(base + w.tmp);
+  float* hh = (float*)(base + w.hh);
+  const float* cls_rows = nullptr;
+  int64_t cls_stride = 0;
+  TRY(spatial_tower(p, in, flags, x, x1, qkv, ctx, tmp, hh, &cls_rows, &cls_stride, s));
+  // both streams' embeddings into x1 (free here; x / ctx still hold the CLS rows being read)
+  float* g = x1;                      // frames (BT,d)
+  float* pr = x1 + (size_t)BT * d;    // probes (BT,d)
+  TRY(launch_frames_embed(cls_rows, cls_stride, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T, d, g, s));
+  TRY(launch_probes_embed(cls_rows, cls_stride, in->frame_types, in->lengths, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T,
+                          d, pr, s));
+  float* qkv_p = qkv + (size_t)BT * 3 * d;
+  float* ctx_p = ctx + (size_t)BT * d;
+  for (int64_t l = 0; l < p->n_temporal; ++l) {
+    const stlt_layer_params& lp = p->temporal[l];
+    if (l + 1 < p->n_temporal) {
+      TRY(launch_linear(g, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, 2 * BT, 3 * d, d, STLT_ACT_NONE, s));
+      TRY(launch_attn(qkv, in->kpm_frames, 1, B, T, H, d / H, ctx, STLT_K_ATTN_TEMPORAL, s));
+      TRY(launch_attn_prefix_probe(qkv, qkv_p, in->kpm_frames, B, T, H, d / H, ctx_p, s));
+      TRY(encoder_tail(lp, d, ctx, d, g, d, 2 * BT, fuse_residual(), tmp, x, hh, g, s));  // in place, as the backbone's temporal layers
+    } else {
+      // the frames' query columns of qkv keep stale scratch: the probe attention reads their keys and values only
+      TRY(launch_linear(g, d, lp.in_proj_w + d * d, lp.in_proj_b + d, qkv + d, 3 * d, BT, 2 * d, d, STLT_ACT_NONE, s));
+      TRY(launch_linear(pr, d, lp.in_proj_w, lp.in_proj_b, qkv_p, 3 * d, BT, 3 * d, d, STLT_ACT_NONE, s));
+      TRY(launch_attn_prefix_probe(qkv, qkv_p, in->kpm_frames, B, T, H, d / H, ctx_p, s));
+      TRY(encoder_tail(lp, d, ctx_p, d, pr, d, BT, fuse_residual(), tmp, x, hh, pr, s));
+    }
+  }
+  // the head on the B*T probe rows; qkv and ctx are dead: they hold its two (BT,d) intermediates
+  const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
+  TRY(stlt_head(head, pr, d, d, BT, d, p->n_classes, p->ln_eps, qkv, ctx, logits, s));
+  return launch_prefix_zero_invalid(logits, in->lengths, B, T, p->n_classes, s);
 }
 
 }  // extern "C"

@@ -358,6 +358,15 @@ int launch_frames_embed(const float* spatial, int64_t row_stride, const int64_t*
                         const int* src_index = nullptr, int64_t n_rows = 0);
 int launch_gather_last(const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t d, float* out,
                        hipStream_t s);
+// per-prefix logits (stlt_forward_prefixes).  rowwise.hip: the probe stream's embedding — row (b,t) = LN(spatial[b, e_b] + pos[t] + type[frame_types[b, e_b]])
+// with e_b = lengths[b]-1 (the clip's extract frame, indexed as launch_gather_last does), same arithmetic as launch_frames_embed
+int launch_probes_embed(const float* spatial, int64_t row_stride, const int64_t* frame_types, const int64_t* lengths, const float* pos_table,
+                        const float* type_table, const float* ln_w, const float* ln_b, float eps, int64_t B, int64_t T, int64_t d, float* out,
+                        hipStream_t s);
+// attn_prefix.hip: the probe stream's attention (include/stlt_hip.h: stlt_attn_prefix_probe_fwd); logits[b,t,:] = 0 for t >= lengths[b]
+int launch_attn_prefix_probe(const float* qkv_frames, const float* qkv_probes, const uint8_t* kpm, int64_t S, int64_t T, int64_t H, int64_t dh,
+                             float* ctx, hipStream_t s);
+int launch_prefix_zero_invalid(float* logits, const int64_t* lengths, int64_t B, int64_t T, int64_t K, hipStream_t s);
 
 // ragged layout (ragged.hip): index of the real tokens / frames of a padded batch, see RaggedIndex
 struct RaggedIndex {

@@ -260,7 +260,9 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------- K7
-template <int NV>
+// PROBE (per-prefix logits, stlt_forward_prefixes): row (b,t) takes the spatial row and the frame type of the clip's extract frame
+// e_b = probe_lengths[b]-1 (indexed as gather_last_kernel does) and the position t — the extract frame as it is embedded behind t observed frames
+template <int NV, bool PROBE>
 __global__ __launch_bounds__(256) void frames_embed_kernel(const float* __restrict__ spatial, int64_t row_stride,
                                                            const int64_t* __restrict__ frame_types,
                                                            const float* __restrict__ pos_table,
@@ -268,12 +270,20 @@ __global__ __launch_bounds__(256) void frames_embed_kernel(const float* __restri
                                                            const float* __restrict__ w, const float* __restrict__ b,
                                                            float eps, int64_t BT, int T, int d,
                                                            float* __restrict__ out, float* __restrict__ pre_out, StltDrop dr,
-                                                           const int* __restrict__ src_index) {
+                                                           const int* __restrict__ src_index, const int64_t* __restrict__ probe_lengths) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= BT) return;
-  const int64_t src = src_index ? src_index[row] : row;  // ragged mode: output row -> frame b*T+t of the padded batch
+  int64_t src = src_index ? src_index[row] : row;  // ragged mode: output row -> frame b*T+t of the padded batch
   const int t = (int)(src % T);
+  int64_t in_row = row;  // row of `spatial` that is read
+  if (PROBE) {
+    const int64_t b = row / T;
+    int64_t e = probe_lengths[b] - 1;
+    e = e < 0 ? e + T : e;
+    e = e < 0 ? 0 : (e >= T ? T - 1 : e);
+    src = in_row = b * T + e;
+  }
   int64_t ft = frame_types[src];
   ft = ft < 0 ? 0 : (ft > 4 ? 4 : ft);  // frame_type_embedding has 5 rows (models.py:91)
   f32x4 v[NV];
@@ -281,7 +291,7 @@ __global__ __launch_bounds__(256) void frames_embed_kernel(const float* __restri
   for (int i = 0; i < NV; ++i) {
     int e = (i * 64 + lane) * 4;
     if (e < d) {
-      f32x4 a = *reinterpret_cast<const f32x4*>(spatial + row * row_stride + e);
+      f32x4 a = *reinterpret_cast<const f32x4*>(spatial + in_row * row_stride + e);
       f32x4 p = *reinterpret_cast<const f32x4*>(pos_table + (int64_t)t * d + e);
       f32x4 f = *reinterpret_cast<const f32x4*>(type_table + ft * d + e);
       v[i] = (a + p) + f;  // models.py:108 evaluation order
@@ -395,10 +405,31 @@ int launch_frames_embed(const float* spatial, int64_t row_stride, const int64_t*
   stlt_prof_note("frames_embed rows=%lld d=%lld", (long long)rows, (long long)d);
   stlt_prof_add_bytes((double)rows * (4.0 * d * (pre_out ? 3 : 2) + 9.0));
   dim3 grid((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK));
-  DISPATCH_NV(nv_for(d), hipLaunchKernelGGL((frames_embed_kernel<NV>), grid, dim3(256), 0, s, spatial, row_stride,
+  DISPATCH_NV(nv_for(d), hipLaunchKernelGGL((frames_embed_kernel<NV, false>), grid, dim3(256), 0, s, spatial, row_stride,
                                             frame_types, pos_table, type_table, ln_w, ln_b, eps, rows, (int)T, (int)d,
-                                            out, pre_out, dr, src_index));
+                                            out, pre_out, dr, src_index, (const int64_t*)nullptr));
   return stlt_check_launch("frames_embed_kernel");
+}
+
+int launch_probes_embed(const float* spatial, int64_t row_stride, const int64_t* frame_types, const int64_t* lengths, const float* pos_table,
+                        const float* type_table, const float* ln_w, const float* ln_b, float eps, int64_t B, int64_t T, int64_t d, float* out,
+                        hipStream_t s) {
+  if (int e = check_d(d)) return e;
+  if (!spatial || !frame_types || !lengths || !pos_table || !type_table || !ln_w || !ln_b || !out)
+    return stlt_set_error(STLT_EINVAL, "probes embedding: null pointer");
+  if (row_stride % 4) return stlt_set_error(STLT_EINVAL, "probes embedding: row_stride must be a multiple of 4");
+  if (const char* off = stlt_first_unaligned16({{"spatial", spatial}, {"pos_table", pos_table}, {"type_table", type_table}, {"ln_w", ln_w}, {"ln_b", ln_b}, {"out", out}}))
+    return stlt_set_error(STLT_EINVAL, "probes embedding: %s must be 16-byte aligned", off);
+  const int64_t rows = B * T;
+  if (rows <= 0) return 0;
+  StltProfScope ps(STLT_K_FRAMES, s);
+  stlt_prof_note("probes_embed rows=%lld d=%lld", (long long)rows, (long long)d);
+  stlt_prof_add_bytes((double)rows * (4.0 * d * 2 + 9.0));
+  dim3 grid((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK));
+  DISPATCH_NV(nv_for(d), hipLaunchKernelGGL((frames_embed_kernel<NV, true>), grid, dim3(256), 0, s, spatial, row_stride, frame_types, pos_table,
+                                            type_table, ln_w, ln_b, eps, rows, (int)T, (int)d, out, (float*)nullptr, StltDrop{0u, 1.0f, 0ull},
+                                            (const int*)nullptr, lengths));
+  return stlt_check_launch("frames_embed_kernel (probes)");
 }
 
 int launch_gather_last(const float* x, const int64_t* lengths, int64_t B, int64_t T, int64_t d, float* out,

@@ -71,3 +71,42 @@ def run_inference(model, batches: Iterable[Dict[str, torch.Tensor]], device, ran
     if collect_logits:
         out["logits"] = torch.cat(kept, dim=0) if kept else torch.zeros(0, 0)
     return out
+
+
+@torch.no_grad()
+def run_prefix_inference(model, batches: Iterable[Dict[str, torch.Tensor]], device, rank: int = 0, world: int = 1) -> Dict[str, torch.Tensor]:
+    """Accuracy against the number of observed frames: `model.forward_prefixes` over an iterable of collated batches (each holding `labels`),
+    every batch sharded over the ranks as in `run_inference`.  Returns {"top1", "top5", "num_clips"}: int64 tensors of length T (the longest
+    batch's), entry t counting the clips that have a prefix of t observed frames (t < lengths) and those of them whose label is among the
+    1 / 5 largest logits after t frames.  The counters stay on the device while the batches run: one `stlt_eval_topk` launch per t on the
+    strided view logits[:, t] (row pitch T * num_classes), the labels of clips without that prefix set to -1 (the kernel ignores
+    out-of-range labels); the counts are summed over the ranks at the end."""
+    from . import _lib as L
+    lib = L.load()
+    if hasattr(model, "train"):
+        model.train(False)
+    counts = torch.zeros(0, 3, dtype=torch.int64, device=device)  # per t: top1, top5, clips
+    for batch in batches:
+        mine = D.shard_batch(batch, rank, world)
+        mine = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in mine.items()}
+        T = int(batch["categories"].shape[1])
+        if T > counts.shape[0]:
+            counts = torch.cat([counts, torch.zeros(T - counts.shape[0], 3, dtype=torch.int64, device=device)])
+        if D.batch_size(mine) == 0:
+            continue
+        out = model.forward_prefixes(mine)
+        logits, valid = out["stlt"], out["valid"]
+        B, _, K = logits.shape
+        labels = torch.where(valid.t(), mine["labels"].to(torch.int64)[None, :], torch.full((), -1, dtype=torch.int64, device=device)).contiguous()  # (T,B)
+        part = torch.zeros(T, 3, dtype=torch.int64, device=device)
+        with torch.cuda.device(logits.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for t in range(T):
+                L.check(lib.stlt_eval_topk(logits.data_ptr() + 4 * t * K, T * K, labels.data_ptr() + 8 * t * B, B, K, part.data_ptr() + 24 * t, stream),
+                        "stlt_eval_topk")
+        part[:, 2] = valid.sum(0)  # the kernel's two counters of row t sit in part[t, 0:2]
+        counts[:T] += part
+    if world > 1:  # every rank sees the same batches, so the same T
+        D.all_reduce_sum_(counts, world)
+    counts = counts.cpu()
+    return {"top1": counts[:, 0].clone(), "top5": counts[:, 1].clone(), "num_clips": counts[:, 2].clone()}

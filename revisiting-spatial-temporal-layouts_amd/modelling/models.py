@@ -421,6 +421,31 @@ class Stlt(nn.Module):
         return {k: v for k, v in zip(self.logit_names, (logits,))}
 
 
+    @torch.no_grad()
+    def forward_prefixes(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The model's logits after every number of observed frames, in one pass (include/stlt_hip.h: stlt_forward_prefixes).
+        -> {"stlt": (B, T, num_classes) float32, "valid": (B, T) bool}.  `valid[b, t] = t < lengths[b]`; for valid entries `stlt[b, t]` is
+        what `forward` returns for `collate.prefix_batch(batch, t)` — frames 0 .. t-1 of the clip followed by its own extract frame — so
+        `stlt[b, lengths[b]-1]` is the ordinary forward's logits; invalid entries are 0.  Inference only, padded schedule."""
+        bb = self.backbone
+        if bb._dropout_live():
+            raise L.StltHipError("forward_prefixes is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if bb.skip_padding:
+            raise L.StltHipError("forward_prefixes runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
+        lib = L.load()
+        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
+        device = batch["categories"].device
+        p, _, _ = bb.c_params(self.prediction_head)
+        d, K = self.config.hidden_size, self.prediction_head.fc2.weight.shape[0]
+        ws = bb._ws.get(ops.prefix_workspace_bytes(B, T, N, d, K), device)
+        logits = torch.empty(B, T, K, device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            L.check(lib.stlt_forward_prefixes(C.byref(p), C.byref(inp), ws.data_ptr(), ws.numel(), bb._flags(), logits.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream), "stlt_forward_prefixes")
+            valid = torch.arange(T, device=device)[None, :] < batch["lengths"].to(device)[:, None]
+        return {"stlt": logits, "valid": valid}
+
+
 class _StltTrainFn(torch.autograd.Function):
     """Autograd shell of the native training step: forward = stlt_train_forward (records the tape), backward =
     stlt_train_backward (the reverse sweep in HIP).  The parameters are passed as inputs only so that autograd

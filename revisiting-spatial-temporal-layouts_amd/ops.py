@@ -271,6 +271,22 @@ def attn_core(qkv: torch.Tensor, kpm: torch.Tensor, causal: bool, num_heads: int
     return ctx
 
 
+def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
+    """Probe attention of the per-prefix forward (include/stlt_hip.h: stlt_attn_prefix_probe_fwd).  qkv_frames, qkv_probes: (S,T,3d) packed
+    [q;k;v] rows of the frame and of the probe stream, kpm (S,T) bool/uint8 (True = frame masked as a key).  Probe (s,t) attends to the frame
+    keys j < t that are not masked and to its own key. -> ctx (S,T,d)"""
+    lib = L.load()
+    _chk(qkv_frames, torch.float32, "qkv_frames"); _chk(qkv_probes, torch.float32, "qkv_probes")
+    kpm = _mask_u8(kpm, "kpm")
+    S, T, d3 = qkv_probes.shape
+    assert qkv_frames.shape == qkv_probes.shape and tuple(kpm.shape) == (S, T) and d3 % (3 * num_heads) == 0
+    d = d3 // 3
+    ctx = torch.empty(S, T, d, device=qkv_probes.device, dtype=torch.float32)
+    L.check(lib.stlt_attn_prefix_probe_fwd(_p(qkv_frames), _p(qkv_probes), _p(kpm), S, T, num_heads, d // num_heads, _p(ctx), _stream()),
+            "stlt_attn_prefix_probe_fwd")
+    return ctx
+
+
 def attn_cross(q: torch.Tensor, kv: torch.Tensor, kpm_k: Optional[torch.Tensor], num_heads: int, causal: bool = False):
     """Cross-attention core: q (S,Lq,d) projected queries, kv (S,Lk,2d) packed [k;v], kpm_k (S,Lk) over the keys or None."""
     lib = L.load()
@@ -345,6 +361,10 @@ def gather_last(x_btd: torch.Tensor, lengths: torch.Tensor):
 
 def workspace_bytes(B: int, T: int, N: int, d: int, n_classes: int) -> int:
     return int(L.load().stlt_workspace_bytes(B, T, N, d, n_classes))
+
+
+def prefix_workspace_bytes(B: int, T: int, N: int, d: int, n_classes: int) -> int:
+    return int(L.load().stlt_prefix_workspace_bytes(B, T, N, d, n_classes))
 
 
 def prof_enable(on: bool):
