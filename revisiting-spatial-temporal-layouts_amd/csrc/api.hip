@@ -265,6 +265,7 @@ int stlt_gemm_set_scratch(void* scratch, size_t bytes) {
 
 int stlt_reduce_slabs(const float* slabs, int64_t stride, int n_slabs, float* dst, int64_t n, int accumulate,
                       stlt_stream_t stream) {
+  StltProfScope ps(STLT_K_MISC, (hipStream_t)stream);  // a record of its own: the launcher's note (its cut) is kept
   return launch_reduce_slabs(slabs, stride, n_slabs, dst, n, accumulate, (hipStream_t)stream);
 }
 

@@ -354,6 +354,7 @@ int launch_attn_bwd16_ragged(const float* qkv, const float* dctx, const AttnBwdR
   g.cs = want_colsum ? scratch : nullptr;
   if (chunks_out) *chunks_out = (int)chunks;
   const int n_wg = (int)((chunks * H + bwaves - 1) / bwaves);
+  stlt_prof_note("bwd16 items=%d chunks=%d wg=%d", g.n_items, g.chunks, n_wg);
   int rc;
   if (nb == 2) rc = causal ? launch_bwd16_ragged<2, true>(g, n_wg, s) : launch_bwd16_ragged<2, false>(g, n_wg, s);
   else if (nb == 3) rc = causal ? launch_bwd16_ragged<3, true>(g, n_wg, s) : launch_bwd16_ragged<3, false>(g, n_wg, s);
@@ -394,6 +395,7 @@ int launch_attn_bwd16(const float* qkv, const float* dctx, const uint8_t* kpm, i
   g.cs = want_colsum ? scratch : nullptr;
   if (chunks_out) *chunks_out = (int)chunks;
   const int n_wg = (int)((chunks * H + bwaves - 1) / bwaves);
+  stlt_prof_note("bwd16 items=%d chunks=%d wg=%d", g.n_items, g.chunks, n_wg);
   int rc;
   if (L <= 16) rc = launch_bwd16<2, false, false>(g, n_wg, s);
   else if (nb == 2) rc = causal ? launch_bwd16<2, true, true>(g, n_wg, s) : launch_bwd16<2, true, false>(g, n_wg, s);

@@ -761,6 +761,7 @@ int launch_ln_bwd(const float* dy, int64_t lddy, const float* a, int64_t lda, co
   stlt_prof_add_bytes((double)M * 4.0 * d * 4.0);  // dy, the two summands (or the sum), ds
   if (nv_for(d) > 4) {  // d > 1024: accumulators in LDS (no shape of the path has such rows; kept working without scratch memory)
     const size_t lds = (size_t)RW_WAVES * 3 * d * sizeof(float);  // <= 96 KB
+    stlt_prof_note("wide lds=%zu", lds);
     static StltPerDeviceOnce lds_once;
     if (!lds_once.flag()) {
       if (hipError_t e = hipFuncSetAttribute((const void*)ln_bwd_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RW_WAVES * 3 * 2048 * (int)sizeof(float)); e != hipSuccess)
@@ -789,6 +790,7 @@ int launch_colsum_acc(const float* x, int64_t ld, int64_t M, int64_t N, float* g
   int parts = (int)((M + 15) / 16);
   if (parts > 64) parts = 64;
   const int64_t rows = (M + parts - 1) / parts;
+  stlt_prof_note("colsum rows=%lld cols=%lld parts=%d rows/part=%lld", (long long)M, (long long)N, parts, (long long)rows);
   hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)parts), dim3(256), 0, s, x, ld, M, (int)N,
                      rows, scratch);
   if (int e = stlt_check_launch("colsum_partial_kernel")) return e;
@@ -805,6 +807,7 @@ int launch_gelu_fwd(const float* u, float* h, int64_t n, hipStream_t s, StltDrop
   int64_t blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (drop_rows && (ncols <= 0 || ncols % 4)) return stlt_set_error(STLT_EINVAL, "gelu: row width must be a positive multiple of 4");
+  stlt_prof_note("blocks=%lld", (long long)blocks);
   hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, u, h, n / 4, dr, site, drop_rows, ncols / 4);
   return stlt_check_launch("gelu_fwd_kernel");
 }
@@ -820,6 +823,7 @@ int launch_gelu_bwd_colsum(const float* dh, const float* u, float* du, int64_t M
   int64_t rows = 32;
   if ((M + rows - 1) / rows > 512) rows = (M + 511) / 512;  // at most 512 partial rows (scratch >= 512*N floats)
   const int64_t parts = (M + rows - 1) / rows;
+  stlt_prof_note("parts=%lld rows/part=%lld", (long long)parts, (long long)rows);
   hipLaunchKernelGGL(gelu_bwd_colsum_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)parts), dim3(256), 0, s, dh, u, du, M, (int)N,
                      rows, scratch, dr, site, drop_rows);
   if (int e = stlt_check_launch("gelu_bwd_colsum_kernel")) return e;
@@ -835,6 +839,7 @@ int launch_gelu_bwd(const float* dh, const float* u, float* du, int64_t n, hipSt
   int64_t blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (drop_rows && (ncols <= 0 || ncols % 4)) return stlt_set_error(STLT_EINVAL, "gelu: row width must be a positive multiple of 4");
+  stlt_prof_note("gelu_bwd n=%lld blocks=%lld", (long long)n, (long long)blocks);
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dh, u, du, n / 4, dr, site, drop_rows, ncols / 4);
   return stlt_check_launch("gelu_bwd_kernel");
 }
@@ -906,6 +911,7 @@ int launch_attn_bwd(const float* qkv, const float* dctx, const uint8_t* kpm, int
   if (groups == 0) return 0;
   if (g_colsum && !scratch) return stlt_set_error(STLT_EINVAL, "attn_bwd: column sums need scratch");
   int64_t chunks = groups < 256 ? groups : 256;  // persistent blocks per head (scratch >= 256 * 3 * H * dh floats)
+  stlt_prof_note("fma groups=%lld chunks=%lld", (long long)groups, (long long)chunks);
   const size_t lds = ((size_t)4 * GL * AB_LD + (size_t)2 * GL * (L + 1) + 3 * GL) * sizeof(float);
   static StltPerDeviceOnce lds_once;  // > 64 KB of dynamic LDS (one 64-token sequence: 100 KB) needs the attribute, per device
   bool& lds_opt_in = lds_once.flag();
@@ -948,6 +954,8 @@ int launch_embed_bwd(const float* dx, const int64_t* categories, const float* bo
       lds_once.flag() = true;
     }
   }
+  stlt_prof_note("embed_bwd tokens=%lld d=%lld C=%lld blocks=%lld tok/block=%lld slices=%lld lds=%zu", (long long)n_tokens, (long long)d, (long long)C,
+                 (long long)blocks, (long long)tpb, (long long)((d + 255) / 256), lds);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)blocks, (unsigned)((d + 255) / 256)), dim3(256), lds, s, dx, categories, boxes, scores, (int)C,
                      n_tokens, (int)d, tpb, scratch, src_index);
   if (int e = stlt_check_launch("embed_bwd_kernel")) return e;
@@ -966,6 +974,7 @@ int launch_frames_bwd(const float* ds, const int64_t* frame_types, int64_t B, in
     if (int e = stlt_check_launch("frames_bwd_scatter_kernel")) return e;
   }
   const int chunks = B < 16 ? (int)B : 16;  // scratch >= 16 * (T+5) * d floats
+  stlt_prof_note("frames_bwd B=%lld T=%lld d=%lld chunks=%d clips/chunk=%lld", (long long)B, (long long)T, (long long)d, chunks, (long long)((B + chunks - 1) / chunks));
   hipLaunchKernelGGL(frames_bwd_params_kernel, dim3((unsigned)((d + 255) / 256), (unsigned)(T + 5), (unsigned)chunks), dim3(256), 0, s, ds,
                      frame_types, B, (int)T, (int)d, scratch, row_of);
   if (int e = stlt_check_launch("frames_bwd_params_kernel")) return e;

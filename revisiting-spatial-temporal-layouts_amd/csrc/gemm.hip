@@ -1289,11 +1289,13 @@ int launch_reduce_slabs(const float* slabs, int64_t stride, int n_slabs, float* 
   const bool off16 = (((uintptr_t)slabs | (uintptr_t)dst) & 15) != 0 || (n_slabs > 1 && stride % 4 != 0);
   if (off16 && (n + 15) / 16 > 0x7fffffffLL) return stlt_set_error(STLT_EINVAL, "reduce_slabs: n=%lld is too large for slabs / dst off a 16-byte boundary", (long long)n);
   if ((n_slabs > 32 && n <= 16384) || off16) {
+    stlt_prof_note("reduce n=%lld slabs=%d tall blocks=%lld", (long long)n, n_slabs, (long long)((n + 15) / 16));
     hipLaunchKernelGGL(reduce_tall_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, slabs, stride, n_slabs, dst, n, accumulate);
     return stlt_check_launch("reduce_tall_kernel");
   }
   int64_t blocks = (n + 1023) / 1024;
   if (blocks > 2048) blocks = 2048;
+  stlt_prof_note("reduce n=%lld slabs=%d blocks=%lld", (long long)n, n_slabs, (long long)blocks);
   hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slabs, stride, n_slabs, dst, n, accumulate);
   return stlt_check_launch("reduce_slabs_kernel");
 }

@@ -99,6 +99,7 @@ int stlt_grad_norm(const float* flat_grad, int64_t n, float max_norm, float* scr
   stlt_prof_add_bytes(4.0 * (double)n);
   int64_t blocks = (n / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+  stlt_prof_note("blocks=%lld tail=%lld", (long long)blocks, (long long)(n % 4));
   hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, s, flat_grad, n / 4, n, scratch);
   if (int e = stlt_check_launch("sumsq_kernel")) return e;
   hipLaunchKernelGGL(norm_finish_kernel, dim3(1), dim3(256), 0, s, scratch, (int)blocks, max_norm, out);
@@ -225,6 +226,8 @@ extern "C" int stlt_loss_fwd_bwd(const float* logits, const void* labels, int ki
   StltProfScope ps(STLT_K_OPTIM, s);
   // mean reduction: over the clips (cross entropy) or over all B*K elements (BCE)
   const float mean = kind == STLT_LOSS_CROSS_ENTROPY ? 1.0f / (float)B : 1.0f / ((float)B * (float)K);
+  stlt_prof_note("loss kind=%d B=%lld K=%lld blocks=%lld class_trips=%lld clip_trips=%lld", kind, (long long)B, (long long)K, (long long)B,
+                 (long long)((K + 255) / 256), (long long)((B + 255) / 256));
   hipLaunchKernelGGL(loss_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, logits, labels, kind, (int)K, weight * mean, scratch, dlogits);
   if (int e = stlt_check_launch("loss_rows_kernel")) return e;
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, s, scratch, B, weight * mean, loss_out,
