@@ -455,6 +455,39 @@ size_t stlt_prefix_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, i
 int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags, float* logits,
                           stlt_stream_t stream);
 
+/* ---- attention maps: what the model looked at (extends the nn.MultiheadAttention layers of models.py:46-55,118-128 by their
+ * need_weights=True output, which the reference's encoder layers discard) ---- */
+
+/* Attention probabilities of K3 (what nn.MultiheadAttention returns with need_weights=True), same arguments and masks as stlt_attn_core_fwd.
+ * per_head == 0: probs (S, L, L),    probs[s,i,j]   = (1/H) * sum_h softmax_j( q_i·k_j/sqrt(dh) + M_ij )   (average_attn_weights=True)
+ * per_head == 1: probs (S, H, L, L), probs[s,h,i,j] = softmax_j( ... ) of head h                           (average_attn_weights=False)
+ * M_ij = -inf if kpm[s,j] or (causal and j > i).  Masked entries are written as exactly 0; a query row whose keys are all masked is
+ * written as zeros (the core's rule for ctx); every element of probs is written, none is left uninitialised.  Query rows are NOT
+ * filtered by kpm: a padded token's row holds what the reference computes for it.  The head average is summed head by head in
+ * registers (no atomics): the same bits on every run.
+ * 1 <= L <= 1024, 1 <= dh <= 256; dh == 64 with L <= 64 (every released checkpoint, every layout of the reference) runs on the MFMA
+ * kernel of csrc/attn_probs.hip, everything else on its vector-ALU kernel.
+ * Alignment: dh == 64: qkv 16 bytes (refused otherwise); other dh: 4 bytes; probs 4 bytes; kpm bytes. */
+int stlt_attn_probs_fwd(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh,
+                        int per_head, float* probs, stlt_stream_t stream);
+
+/* bytes of scratch stlt_forward_attention needs for this shape (0 for an empty shape) */
+size_t stlt_attention_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes);
+
+/* Stlt.forward (models.py:185-195) on the dense padded schedule, also writing every layer's attention probabilities.
+ * attn_spatial:  (n_spatial, B, T, N, N)  [per_head: (n_spatial, B, T, H, N, N)]  or NULL
+ * attn_temporal: (n_temporal, B, T, T)    [per_head: (n_temporal, B, H, T, T)]    or NULL
+ * Layer-major: each layer's launch writes one contiguous block (stlt_attn_probs_fwd on the layer's packed QKV).  With a map requested,
+ * N (spatial) / T (temporal) is at most 1024.  logits (B, n_classes) as stlt_forward with flags == 0 — to fp32 rounding, not bit for bit:
+ * every layer here runs the unfused pair (in-projection into a packed QKV buffer, then the attention core), never the fused MHSA kernel,
+ * which has no QKV in memory; a NULL map changes neither the other outputs nor the launches that produce them.
+ * Inference only.  Every layer runs on every row: the elision flags (STLT_FLAG_CLS_ONLY_LAST_SPATIAL, STLT_FLAG_LAST_ROW_ONLY_TEMPORAL)
+ * are ignored, STLT_FLAG_SKIP_PADDING is refused (STLT_EINVAL).  A workspace smaller than stlt_attention_workspace_bytes is refused with
+ * STLT_EINVAL as well.  Nothing is launched by a refused call.
+ * No allocation, no synchronisation, capturable.  workspace: 256-byte aligned.  logits, attn_spatial, attn_temporal: 4 bytes. */
+int stlt_forward_attention(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags, int per_head,
+                           float* logits, float* attn_spatial, float* attn_temporal, stlt_stream_t stream);
+
 /* ---- CAF / CACNF on precomputed appearance features (reference models.py:230-271, 286-298, 328-549) ----
  * The layout branch is the StltBackbone above; the appearance branch starts from the R3D-50 feature map the reference's
  * Resnet3D.forward_features returns, (B, 2048, 2,4,4) = (B, feat_channels, app_tokens) row-major, given by the caller. */
@@ -824,7 +857,8 @@ int stlt_eval_average_precision(const float* scores, const float* truths, int64_
 #define STLT_K_MISC 12         /* row gathers / scatters, column sums, ragged index, the head's small products */
 #define STLT_K_MHSA_FUSED 13    /* fused in-projection + causal attention core (stlt_mhsa_fused_fwd): temporal tower */
 #define STLT_K_MHSA_FUSED_SPATIAL 14  /* the same kernel's non-causal launches (spatial tower) */
-#define STLT_K_COUNT 15
+#define STLT_K_ATTN_PROBS 15    /* attention probabilities (stlt_attn_probs_fwd; one launch per layer of stlt_forward_attention) */
+#define STLT_K_COUNT 16
 /* The switch is process-wide; the records (and both calls below) belong to the device that is CURRENT when they are made: a
  * process driving several GPUs collects once per device (with that device current) before it switches timing off, or the
  * other devices' records stay queued. */

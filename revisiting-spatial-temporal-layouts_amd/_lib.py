@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STLT_HIP_LIB") or os.path.join(HERE, "libstlt_hip.so")  # env override: A/B experiments only
 
 K_NAMES = ("embed", "gemm", "attn_spatial", "attn_temporal", "add_layernorm", "frames_embed", "gather_last", "ln_bwd", "attn_bwd",
-           "gelu", "embed_bwd", "optim", "misc", "mhsa_fused", "mhsa_fused_spatial")
+           "gelu", "embed_bwd", "optim", "misc", "mhsa_fused", "mhsa_fused_spatial", "attn_probs")
 FLAG_CLS_ONLY_LAST_SPATIAL = 1
 FLAG_LAST_ROW_ONLY_TEMPORAL = 2
 FLAG_SKIP_PADDING = 4
@@ -189,6 +189,9 @@ SIGNATURES = {
     "stlt_attn_prefix_probe_fwd": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "stlt_prefix_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "stlt_forward_prefixes": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, _vp, _vp]),
+    "stlt_attn_probs_fwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _vp, _vp]),
+    "stlt_attention_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "stlt_forward_attention": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "stlt_caf_workspace_bytes": (C.c_size_t, [C.c_int64] * 7),
     "stlt_caf_forward": (C.c_int, [C.c_void_p, C.POINTER(Inputs), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     "stlt_caf_forward_flags": (C.c_int, [C.c_void_p, C.POINTER(Inputs), _vp, _vp, C.c_size_t, C.c_int, _vp, _vp, _vp, _vp, _vp]),

@@ -720,4 +720,71 @@ int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* wor
   return launch_prefix_zero_invalid(logits, in->lengths, B, T, p->n_classes, s);
 }
 
+int stlt_attn_probs_fwd(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh, int per_head, float* probs,
+                        stlt_stream_t stream) {
+  return launch_attn_probs(qkv, kpm, causal, S, L, H, dh, per_head, probs, (hipStream_t)stream);
+}
+
+size_t stlt_attention_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
+  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
+  return ws_layout(B, T, N, d, n_classes < 0 ? 0 : n_classes).total;
+}
+
+// The dense schedule with every layer as the unfused pair: the layer's packed QKV lies in the workspace, the attention core and the
+// probabilities launch read it side by side, and the post-norm block is the one every forward shares.  Buffers as backbone_impl's.
+int stlt_forward_attention(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags, int per_head, float* logits,
+                           float* attn_spatial, float* attn_temporal, stlt_stream_t stream) {
+  TRY(check_params(p, in, true));
+  if (!logits) return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: logits is null");
+  if (flags & STLT_FLAG_SKIP_PADDING)
+    return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: STLT_FLAG_SKIP_PADDING is not supported (the attention maps are those of the padded schedule)");
+  if (per_head != 0 && per_head != 1) return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: per_head must be 0 or 1");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H, BT = B * T, tok = BT * N;
+  if ((attn_spatial && p->n_spatial > 0 && N > 1024) || (attn_temporal && p->n_temporal > 0 && T > 1024))
+    return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: a map of more than 1024 keys (N=%lld, T=%lld)", (long long)N, (long long)T);
+  if (((uintptr_t)logits | (uintptr_t)attn_spatial | (uintptr_t)attn_temporal) & 3)
+    return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: logits / attn_spatial / attn_temporal must be 4-byte aligned");
+  const WsLayout w = ws_layout(B, T, N, d, p->n_classes);
+  if (!workspace || workspace_bytes < w.total)
+    return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: workspace %zu B < required %zu B", workspace_bytes, w.total);
+  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
+  char* base = (char*)workspace;
+  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
+  float* x = (float*)(base + w.x);
+  float* x1 = (float*)(base + w.x1);
+  float* qkv = (float*)(base + w.qkv);
+  float* ctx = (float*)(base + w.ctx);
+  float* tmp = (float*)(base + w.tmp);
+  float* hh = (float*)(base + w.hh);
+  const int64_t heads_out = per_head ? H : 1;
+  TRY(launch_embed(in->categories, in->boxes, in->scores, p->cat_emb, p->n_categories, p->box_w, p->box_b, p->score_w, p->score_b, p->emb_ln_w,
+                   p->emb_ln_b, p->ln_eps, tok, d, x, s));
+  // spatial transformer: sequences = frames (B*T), tokens = objects (N), key-padding mask only
+  for (int64_t l = 0; l < p->n_spatial; ++l) {
+    const stlt_layer_params& lp = p->spatial[l];
+    TRY(launch_linear(x, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, tok, 3 * d, d, STLT_ACT_NONE, s));
+    TRY(launch_attn(qkv, in->kpm_boxes, 0, BT, N, H, d / H, ctx, STLT_K_ATTN_SPATIAL, s));
+    if (attn_spatial) TRY(launch_attn_probs(qkv, in->kpm_boxes, 0, BT, N, H, d / H, per_head, attn_spatial + (size_t)l * BT * heads_out * N * N, s));
+    TRY(encoder_tail(lp, d, ctx, d, x, d, tok, fuse_residual(), tmp, x1, hh, x, s));
+  }
+  // CLS select + position + frame type + LN -> (B,T,d) in x1 (free: its last reader was the final norm2 above)
+  float* tbuf = x1;
+  TRY(launch_frames_embed(x, N * d, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T, d, tbuf, s));
+  // temporal transformer: sequences = clips (B), tokens = frames (T), causal + key padding; in place on tbuf, x is the post-norm1 scratch
+  for (int64_t l = 0; l < p->n_temporal; ++l) {
+    const stlt_layer_params& lp = p->temporal[l];
+    TRY(launch_linear(tbuf, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, BT, 3 * d, d, STLT_ACT_NONE, s));
+    TRY(launch_attn(qkv, in->kpm_frames, 1, B, T, H, d / H, ctx, STLT_K_ATTN_TEMPORAL, s));
+    if (attn_temporal) TRY(launch_attn_probs(qkv, in->kpm_frames, 1, B, T, H, d / H, per_head, attn_temporal + (size_t)l * B * heads_out * T * T, s));
+    TRY(encoder_tail(lp, d, ctx, d, tbuf, d, BT, fuse_residual(), tmp, x, hh, tbuf, s));
+  }
+  float* h0 = (float*)(base + w.head);
+  float* h1 = h0 + (size_t)B * d;
+  float* h2 = h1 + (size_t)B * d;
+  TRY(launch_gather_last(tbuf, in->lengths, B, T, d, h0, s));  // models.py:189-192
+  const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
+  return stlt_head(head, h0, d, d, B, d, p->n_classes, p->ln_eps, h1, h2, logits, s);
+}
+
 }  // extern "C"

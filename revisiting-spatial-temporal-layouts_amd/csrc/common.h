@@ -367,6 +367,10 @@ int launch_probes_embed(const float* spatial, int64_t row_stride, const int64_t*
 int launch_attn_prefix_probe(const float* qkv_frames, const float* qkv_probes, const uint8_t* kpm, int64_t S, int64_t T, int64_t H, int64_t dh,
                              float* ctx, hipStream_t s);
 int launch_prefix_zero_invalid(float* logits, const int64_t* lengths, int64_t B, int64_t T, int64_t K, hipStream_t s);
+// attn_probs.hip: the attention probabilities of K3 on the same packed QKV buffer and masks as launch_attn (include/stlt_hip.h: stlt_attn_probs_fwd):
+// probs (S,L,L) averaged over the heads, or (S,H,L,L) with per_head; MFMA kernel for dh == 64 and L <= 64, vector ALU otherwise
+int launch_attn_probs(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh, int per_head, float* probs,
+                      hipStream_t s);
 
 // ragged layout (ragged.hip): index of the real tokens / frames of a padded batch, see RaggedIndex
 struct RaggedIndex {

@@ -446,6 +446,42 @@ class Stlt(nn.Module):
         return {"stlt": logits, "valid": valid}
 
 
+    @torch.no_grad()
+    def forward_attention(self, batch: Dict[str, torch.Tensor], per_head: bool = False) -> Dict[str, torch.Tensor]:
+        """The model's logits and every layer's attention probabilities in one pass (include/stlt_hip.h: stlt_forward_attention): what
+        the reference's nn.MultiheadAttention layers return with need_weights=True.
+        -> {"stlt": (B, num_classes), "spatial_attention": (n_spatial, B, T, N, N), "temporal_attention": (n_temporal, B, T, T)} float32,
+        averaged over the heads; with `per_head` the maps are (n_spatial, B, T, H, N, N) and (n_temporal, B, H, T, T).  Index [layer, ..., i, j]
+        is how much query i attends to key j; masked keys are exactly 0.
+        `spatial_attention[-1][:, :, 0, :]` is what each frame's CLS token attends to among the frame's objects;
+        `temporal_attention[-1][b, lengths[b]-1]` is what clip b's read-out (extract) token attends to among its frames.
+        Rows of padded tokens hold the reference's values for them: mask them with the batch's `src_key_padding_mask_boxes` /
+        `src_key_padding_mask_frames`.  Inference only, dense padded schedule: every layer runs on every row as the unfused pair, so the
+        logits equal `forward`'s to fp32 rounding, not bit for bit."""
+        bb = self.backbone
+        if bb._dropout_live():
+            raise L.StltHipError("forward_attention is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if bb.skip_padding:
+            raise L.StltHipError("forward_attention runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
+        if not batch["categories"].is_cuda:
+            raise L.StltHipError("forward_attention runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        lib = L.load()
+        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
+        device = batch["categories"].device
+        p, _, _ = bb.c_params(self.prediction_head)
+        d, K, H = self.config.hidden_size, self.prediction_head.fc2.weight.shape[0], self.config.num_attention_heads
+        n_sp, n_tp = self.config.num_spatial_layers, self.config.num_temporal_layers
+        ws = bb._ws.get(ops.attention_workspace_bytes(B, T, N, d, K), device)
+        logits = torch.empty(B, K, device=device, dtype=torch.float32)
+        spatial = torch.empty((n_sp, B, T, H, N, N) if per_head else (n_sp, B, T, N, N), device=device, dtype=torch.float32)
+        temporal = torch.empty((n_tp, B, H, T, T) if per_head else (n_tp, B, T, T), device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            L.check(lib.stlt_forward_attention(C.byref(p), C.byref(inp), ws.data_ptr(), ws.numel(), 0, int(bool(per_head)), logits.data_ptr(),
+                                               spatial.data_ptr() if n_sp else None, temporal.data_ptr() if n_tp else None,
+                                               torch.cuda.current_stream().cuda_stream), "stlt_forward_attention")
+        return {"stlt": logits, "spatial_attention": spatial, "temporal_attention": temporal}
+
+
 class _StltTrainFn(torch.autograd.Function):
     """Autograd shell of the native training step: forward = stlt_train_forward (records the tape), backward =
     stlt_train_backward (the reverse sweep in HIP).  The parameters are passed as inputs only so that autograd

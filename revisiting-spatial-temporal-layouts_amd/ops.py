@@ -271,6 +271,22 @@ def attn_core(qkv: torch.Tensor, kpm: torch.Tensor, causal: bool, num_heads: int
     return ctx
 
 
+def attn_probs(qkv: torch.Tensor, kpm: torch.Tensor, causal: bool, num_heads: int, per_head: bool = False):
+    """Attention probabilities of K3 (include/stlt_hip.h: stlt_attn_probs_fwd), what nn.MultiheadAttention returns with need_weights=True:
+    qkv (S,L,3d) packed [q;k;v], kpm (S,L) bool/uint8 (True = key masked). -> probs (S,L,L) averaged over the heads, or (S,H,L,L) with
+    per_head.  Masked entries are exactly 0; L <= 1024."""
+    lib = L.load()
+    _chk(qkv, torch.float32, "qkv")
+    kpm = _mask_u8(kpm, "kpm")
+    S, Lq, d3 = qkv.shape
+    assert tuple(kpm.shape) == (S, Lq) and d3 % (3 * num_heads) == 0
+    d = d3 // 3
+    probs = torch.empty((S, num_heads, Lq, Lq) if per_head else (S, Lq, Lq), device=qkv.device, dtype=torch.float32)
+    L.check(lib.stlt_attn_probs_fwd(_p(qkv), _p(kpm), int(bool(causal)), S, Lq, num_heads, d // num_heads, int(bool(per_head)), _p(probs), _stream()),
+            "stlt_attn_probs_fwd")
+    return probs
+
+
 def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
     """Probe attention of the per-prefix forward (include/stlt_hip.h: stlt_attn_prefix_probe_fwd).  qkv_frames, qkv_probes: (S,T,3d) packed
     [q;k;v] rows of the frame and of the probe stream, kpm (S,T) bool/uint8 (True = frame masked as a key).  Probe (s,t) attends to the frame
@@ -365,6 +381,10 @@ def workspace_bytes(B: int, T: int, N: int, d: int, n_classes: int) -> int:
 
 def prefix_workspace_bytes(B: int, T: int, N: int, d: int, n_classes: int) -> int:
     return int(L.load().stlt_prefix_workspace_bytes(B, T, N, d, n_classes))
+
+
+def attention_workspace_bytes(B: int, T: int, N: int, d: int, n_classes: int) -> int:
+    return int(L.load().stlt_attention_workspace_bytes(B, T, N, d, n_classes))
 
 
 def prof_enable(on: bool):
