@@ -1,6 +1,10 @@
 // C-ABI of libstlt_hip.so (see include/stlt_hip.h): argument checks, error string, per-kernel event
 // timing, and the whole-path orchestration (StltBackbone.forward / Stlt.forward as a fixed launch sequence
 // on the caller's stream — no allocation, no synchronisation, graph-capturable).
+// The inference schedule is written once: ws_carve (the workspace checks and the typed buffers of every entry point), spatial_tower and
+// temporal_tower (the layer loops), LayerOpts (what a forward adds per layer: stlt_forward_attention is the dense schedule with `unfused`
+// and a probabilities sink), classification_head.  Two schedules stand beside it on the same carve: forward_ragged (skip-padding) and
+// the two-stream temporal loop of stlt_forward_prefixes.
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -321,12 +325,14 @@ int stlt_gather_last_fwd(const float* x, const int64_t* lengths, int64_t B, int6
 
 // ------------------------------------------------------------------ whole path
 
+}  // extern "C"
+
 struct WsLayout {
   size_t x, x1, qkv, ctx, tmp, hh, head, sk, ridx, total;
 };
 
 // min_slots: rows per frame the buffers hold at least (the per-prefix forward runs two temporal streams: 2 rows per frame)
-static WsLayout ws_layout(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes, int64_t min_slots = 1) {
+static WsLayout ws_layout(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes, int64_t min_slots) {
   const size_t tok = (size_t)B * T * (N > min_slots ? N : min_slots);  // spatial tokens >= temporal tokens
   const size_t f = sizeof(float);
   WsLayout w;
@@ -338,16 +344,37 @@ static WsLayout ws_layout(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_
   w.ctx = take(tok * d * f);
   w.tmp = take(tok * d * f);
   w.hh = take(tok * 4 * d * f);
-  w.head = take((size_t)B * (3 * d + n_classes) * f);
+  w.head = take((size_t)B * (3 * d + (n_classes < 0 ? 0 : n_classes)) * f);
   w.sk = take(STLT_GEMM_SCRATCH_BYTES);  // stream-K partial tiles of under-filled GEMM launches
   w.ridx = take(ragged_index_bytes(B, T, N));  // STLT_FLAG_SKIP_PADDING: index of the real tokens / frames
   w.total = off;
   return w;
 }
 
-size_t stlt_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
-  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
-  return ws_layout(B, T, N, d, n_classes < 0 ? 0 : n_classes).total;
+// The one workspace size (declared in common.h: caf.hip places a backbone workspace inside its own); the exported size functions add
+// their treatment of empty shapes
+size_t stlt_ws_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes, int64_t min_slots) {
+  return ws_layout(B, T, N, d, n_classes, min_slots).total;
+}
+
+// The carved workspace: x, x1, ctx, tmp hold (tok, d) floats, qkv 3x and hh 4x as wide; head the classification head's rows; sk the
+// stream-K scratch an entry point lends to its GEMMs (StltGemmScratch); ridx the skip-padding index.
+struct WsBufs {
+  float *x, *x1, *qkv, *ctx, *tmp, *hh, *head;
+  char *sk, *ridx;
+};
+
+// The workspace checks of every whole-path entry point, then the carve.  short_code / who: what a short workspace returns and how its
+// message opens (stlt_forward_attention documents STLT_EINVAL under its own name; every other entry point STLT_EWORKSPACE, no name).
+static int ws_carve(const stlt_params* p, const stlt_inputs* in, int64_t min_slots, void* workspace, size_t workspace_bytes, int short_code,
+                    const char* who, WsBufs* b) {
+  const WsLayout w = ws_layout(in->B, in->T, in->N, p->d, p->n_classes, min_slots);
+  if (!workspace || workspace_bytes < w.total) return stlt_set_error(short_code, "%sworkspace %zu B < required %zu B", who, workspace_bytes, w.total);
+  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
+  char* base = (char*)workspace;
+  auto F = [&](size_t o) { return (float*)(base + o); };
+  *b = WsBufs{F(w.x), F(w.x1), F(w.qkv), F(w.ctx), F(w.tmp), F(w.hh), F(w.head), base + w.sk, base + w.ridx};
+  return 0;
 }
 
 // The residual adds of a post-norm layer ride in the out-proj / FFN2 epilogues and the LayerNorm passes read one tensor
@@ -361,19 +388,34 @@ static bool fuse_residual() {
   return on;
 }
 
+// What a padded layer does beyond the plain forward.  unfused: never the fused launch, the packed QKV lies in the workspace.  probs != null
+// (needs unfused): the layer's attention probabilities, (S,L,L) or per_head (S,H,L,L), written by launch_attn_probs right behind the core.
+struct LayerOpts {
+  bool unfused = false;
+  float* probs = nullptr;
+  int per_head = 0;
+};
+
 // in-projection + attention core of a layer: ctx (M,d) from x (M,d).  seg_start / seg_end != null: the M rows are compacted rows cut
 // into variable-length segments (ragged.hip) and the attention is restricted to the row's own segment (no padded keys exist; S, L and
-// kpm are not read); that form never takes the fused launch.
+// kpm are not read); that form never takes the fused launch and takes no options.
 static int qkv_attention(const stlt_layer_params& lp, int64_t d, int64_t H, const float* x, int64_t M, int64_t S, int64_t L,
                          const uint8_t* kpm, const int* seg_start, const int* seg_end, int causal, int kid, float* qkv, float* ctx,
-                         hipStream_t s) {
+                         hipStream_t s, const LayerOpts& o = {}) {
   // with the opt-in split-bf16 products on, a temporal in-projection they take is faster as its own launch (+ the attention core)
   // than inside the fused f32-MFMA kernel
-  if (!seg_start && stlt_fused_mhsa_on(causal) && stlt_mhsa_fused_pays(S, L, H, d, causal) && !stlt_split_bf16_takes(M, 3 * d, d, d, d))
+  if (!seg_start && !o.unfused && stlt_fused_mhsa_on(causal) && stlt_mhsa_fused_pays(S, L, H, d, causal) && !stlt_split_bf16_takes(M, 3 * d, d, d, d))
     return launch_mhsa_fused(x, lp.in_proj_w, lp.in_proj_b, kpm, S, L, H, d, ctx, s, causal);
   TRY(launch_linear(x, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, M, 3 * d, d, STLT_ACT_NONE, s));
   if (seg_start) return launch_attn_ragged(qkv, seg_start, seg_end, causal, M, H, d / H, ctx, kid, s);
-  return launch_attn(qkv, kpm, causal, S, L, H, d / H, ctx, kid, s);
+  TRY(launch_attn(qkv, kpm, causal, S, L, H, d / H, ctx, kid, s));
+  return o.probs ? launch_attn_probs(qkv, kpm, causal, S, L, H, d / H, o.per_head, o.probs, s) : 0;
+}
+
+// Layer l's options out of a tower's: its own (S,L,L) or (S,H,L,L) maps of the sink
+static LayerOpts layer_opts(LayerOpts o, int64_t l, int64_t S, int64_t L, int64_t H) {
+  if (o.probs) o.probs += (size_t)l * S * (o.per_head ? H : 1) * L * L;
+  return o;
 }
 
 // The part of a post-norm encoder layer (nn.TransformerEncoderLayer as configured at models.py:46-52,118-124) behind the attention
@@ -388,8 +430,8 @@ static int encoder_tail(const stlt_layer_params& lp, int64_t d, const float* ctx
 // One post-norm encoder layer on M compact rows of width d, padded layout or (seg_start / seg_end) ragged.  Aliasing as encoder_tail.
 static int encoder_layer(const stlt_layer_params& lp, int64_t d, int64_t H, const float* x, int64_t M, int64_t S, int64_t L,
                          const uint8_t* kpm, const int* seg_start, const int* seg_end, int causal, int kid, float* qkv, float* ctx,
-                         float* tmp, float* x1, float* hh, float* out, hipStream_t s) {
-  TRY(qkv_attention(lp, d, H, x, M, S, L, kpm, seg_start, seg_end, causal, kid, qkv, ctx, s));
+                         float* tmp, float* x1, float* hh, float* out, hipStream_t s, const LayerOpts& o = {}) {
+  TRY(qkv_attention(lp, d, H, x, M, S, L, kpm, seg_start, seg_end, causal, kid, qkv, ctx, s, o));
   return encoder_tail(lp, d, ctx, d, x, d, M, fuse_residual(), tmp, x1, hh, out, s);
 }
 
@@ -407,8 +449,6 @@ static int check_params(const stlt_params* p, const stlt_inputs* in, bool need_h
     return stlt_set_error(STLT_EINVAL, "prediction head parameters / lengths missing");
   return 0;
 }
-
-}  // extern "C"
 
 // ------------------------------------------------------------------ the post-norm block, written once (declared in common.h)
 // Every forward of the library ends its half-blocks and its heads here; the callers keep their projections, attention launches, gathers
@@ -439,13 +479,20 @@ int stlt_head(const stlt_head_params& h, const float* x, int64_t ldx, int64_t in
   return launch_linear(h2, d, h.fc2_w, h.fc2_b, logits, K, B, K, d, STLT_ACT_NONE, s);
 }
 
-// Token embedding + spatial transformer of the backbone (models.py:29-39,57-81) on the caller's buffers (each B*T*N rows; qkv 3x, hh 4x as
-// wide).  *cls_rows / *cls_stride: where each frame's CLS row — the only row read afterwards (models.py:79) — lies: in x (stride N*d), or
-// with STLT_FLAG_CLS_ONLY_LAST_SPATIAL compact in ctx.  x1 is free afterwards.
-static int spatial_tower(const stlt_params* p, const stlt_inputs* in, int flags, float* x, float* x1, float* qkv, float* ctx, float* tmp, float* hh,
-                         const float** cls_rows_out, int64_t* cls_stride_out, hipStream_t s) {
+// The model's own ClassificationHead on n rows of x (n,d); h1, h2: (n,d)
+static int classification_head(const stlt_params* p, const float* x, int64_t n, float* h1, float* h2, float* logits, hipStream_t s) {
+  const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
+  return stlt_head(head, x, p->d, p->d, n, p->d, p->n_classes, p->ln_eps, h1, h2, logits, s);
+}
+
+// Token embedding + spatial transformer of the backbone (models.py:29-39,57-81) in the carved workspace.  *cls_rows / *cls_stride: where
+// each frame's CLS row — the only row read afterwards (models.py:79) — lies: in x (stride N*d), or with STLT_FLAG_CLS_ONLY_LAST_SPATIAL
+// compact in ctx.  x1 is free afterwards.  `o` applies to the layers that run whole (a sink goes with flags without CLS_ONLY).
+static int spatial_tower(const stlt_params* p, const stlt_inputs* in, int flags, const WsBufs& w, const LayerOpts& o, const float** cls_rows_out,
+                         int64_t* cls_stride_out, hipStream_t s) {
   const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H;
   const int64_t tok = B * T * N, BT = B * T;
+  float *x = w.x, *qkv = w.qkv, *ctx = w.ctx;
   // K1
   TRY(launch_embed(in->categories, in->boxes, in->scores, p->cat_emb, p->n_categories, p->box_w, p->box_b, p->score_w,
                    p->score_b, p->emb_ln_w, p->emb_ln_b, p->ln_eps, tok, d, x, s));
@@ -453,7 +500,8 @@ static int spatial_tower(const stlt_params* p, const stlt_inputs* in, int flags,
   const bool cls_only = (flags & STLT_FLAG_CLS_ONLY_LAST_SPATIAL) && p->n_spatial > 0 && N > 1;
   const int64_t full_layers = cls_only ? p->n_spatial - 1 : p->n_spatial;
   for (int64_t l = 0; l < full_layers; ++l)
-    TRY(encoder_layer(p->spatial[l], d, H, x, tok, BT, N, in->kpm_boxes, nullptr, nullptr, 0, STLT_K_ATTN_SPATIAL, qkv, ctx, tmp, x1, hh, x, s));
+    TRY(encoder_layer(p->spatial[l], d, H, x, tok, BT, N, in->kpm_boxes, nullptr, nullptr, 0, STLT_K_ATTN_SPATIAL, qkv, ctx, w.tmp, w.x1, w.hh, x, s,
+                      layer_opts(o, l, BT, N, H)));
   const float* cls_rows = x;
   int64_t cls_stride = N * d;
   if (cls_only) {
@@ -465,7 +513,7 @@ static int spatial_tower(const stlt_params* p, const stlt_inputs* in, int flags,
     // non-CLS query rows of qkv hold stale scratch; each attention output row depends on its own query row
     // only, and only the CLS rows of ctx are read below.
     TRY(launch_attn(qkv, in->kpm_boxes, 0, BT, N, H, d / H, ctx, STLT_K_ATTN_SPATIAL, s));
-    TRY(encoder_tail(lp, d, ctx, N * d, x, N * d, BT, false, tmp, x1, hh, ctx, s));  // compact CLS rows land in ctx's first BT rows
+    TRY(encoder_tail(lp, d, ctx, N * d, x, N * d, BT, false, w.tmp, w.x1, w.hh, ctx, s));  // compact CLS rows land in ctx's first BT rows
     cls_rows = ctx;
     cls_stride = d;
   }
@@ -474,52 +522,42 @@ static int spatial_tower(const stlt_params* p, const stlt_inputs* in, int flags,
   return 0;
 }
 
-// Backbone body.  With last_rows != nullptr the final temporal layer only produces the rows the head reads
+// The first n_layers layers of the temporal transformer: sequences = clips (B), tokens = frames (T), causal + key padding.  Layers run in
+// place on tbuf (a layer's input is last read by its norm1), x is the post-norm1 scratch; the tower's last layer writes `out`.
+static int temporal_tower(const stlt_params* p, const stlt_inputs* in, int64_t n_layers, const WsBufs& w, const LayerOpts& o, float* tbuf, float* out,
+                          hipStream_t s) {
+  const int64_t B = in->B, T = in->T;
+  for (int64_t l = 0; l < n_layers; ++l) {
+    float* dst = (l == p->n_temporal - 1) ? out : tbuf;
+    TRY(encoder_layer(p->temporal[l], p->d, p->H, tbuf, B * T, B, T, in->kpm_frames, nullptr, nullptr, 1, STLT_K_ATTN_TEMPORAL, w.qkv, w.ctx, w.tmp,
+                      w.x, w.hh, dst, s, layer_opts(o, l, B, T, p->H)));
+  }
+  return 0;
+}
+
+// Backbone body in the carved workspace.  With last_rows != nullptr the final temporal layer only produces the rows the head reads
 // (Stlt.forward, models.py:189-192: out[lengths-1, arange(B)]) into last_rows (B,d): K/V/Q are projected for every
 // frame, the attention core runs as usual, but out-proj / norm1 / FFN / norm2 run on the B gathered rows only.
-static int backbone_impl(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes,
-                         int flags, float* out_btd, float* last_rows, hipStream_t s) {
-  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H;
-  const WsLayout w = ws_layout(B, T, N, d, p->n_classes < 0 ? 0 : p->n_classes);
-  if (!workspace || workspace_bytes < w.total)
-    return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
-  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
-  char* base = (char*)workspace;
-  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
-  float* x = (float*)(base + w.x);
-  float* x1 = (float*)(base + w.x1);
-  float* qkv = (float*)(base + w.qkv);
-  float* ctx = (float*)(base + w.ctx);
-  float* tmp = (float*)(base + w.tmp);
-  float* hh = (float*)(base + w.hh);
-
-  const int64_t BT = B * T;
+static int backbone_impl(const stlt_params* p, const stlt_inputs* in, const WsBufs& w, int flags, float* out_btd, float* last_rows, hipStream_t s) {
+  const int64_t B = in->B, T = in->T, d = p->d;
   const float* cls_rows = nullptr;
   int64_t cls_stride = 0;
-  TRY(spatial_tower(p, in, flags, x, x1, qkv, ctx, tmp, hh, &cls_rows, &cls_stride, s));
+  TRY(spatial_tower(p, in, flags, w, LayerOpts{}, &cls_rows, &cls_stride, s));
   // K7: CLS select + position + frame type + LN -> (B,T,d).  x1 is free here (its last reader was the
   // final norm2 above), x / ctx still hold the CLS rows being read.
-  float* tbuf = p->n_temporal > 0 ? x1 : out_btd;
+  float* tbuf = p->n_temporal > 0 ? w.x1 : out_btd;
   TRY(launch_frames_embed(cls_rows, cls_stride, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w,
                           p->frames_ln_b, p->ln_eps, B, T, d, tbuf, s));
-  // temporal transformer: sequences = clips (B), tokens = frames (T), causal + key padding.  Layers run in
-  // place on tbuf (a layer's input is last read by its norm1), x is the post-norm1 scratch; the last layer
-  // writes the caller's buffer.
-  const int64_t n_full = last_rows ? p->n_temporal - 1 : p->n_temporal;
-  for (int64_t l = 0; l < n_full; ++l) {
-    float* dst = (l == p->n_temporal - 1) ? out_btd : tbuf;
-    TRY(encoder_layer(p->temporal[l], d, H, tbuf, BT, B, T, in->kpm_frames, nullptr, nullptr, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, tmp,
-                      x, hh, dst, s));
-  }
+  TRY(temporal_tower(p, in, last_rows ? p->n_temporal - 1 : p->n_temporal, w, LayerOpts{}, tbuf, out_btd, s));
   if (last_rows) {
     const stlt_layer_params& lp = p->temporal[p->n_temporal - 1];
-    float* g_ctx = x;                      // (B,d) gathered attention rows
-    float* g_res = x + (size_t)B * d;      // (B,d) gathered layer-input rows (residual)
-    float* g_x1 = hh + (size_t)B * 4 * d;  // (B,d) post-norm1, behind the (B,4d) FFN hidden (T > 1 => hh holds >= 2*B*4d)
-    TRY(qkv_attention(lp, d, H, tbuf, BT, B, T, in->kpm_frames, nullptr, nullptr, 1, STLT_K_ATTN_TEMPORAL, qkv, ctx, s));
-    TRY(launch_gather_last(ctx, in->lengths, B, T, d, g_ctx, s));
+    float* g_ctx = w.x;                      // (B,d) gathered attention rows
+    float* g_res = w.x + (size_t)B * d;      // (B,d) gathered layer-input rows (residual)
+    float* g_x1 = w.hh + (size_t)B * 4 * d;  // (B,d) post-norm1, behind the (B,4d) FFN hidden (T > 1 => hh holds >= 2*B*4d)
+    TRY(qkv_attention(lp, d, p->H, tbuf, B * T, B, T, in->kpm_frames, nullptr, nullptr, 1, STLT_K_ATTN_TEMPORAL, w.qkv, w.ctx, s));
+    TRY(launch_gather_last(w.ctx, in->lengths, B, T, d, g_ctx, s));
     TRY(launch_gather_last(tbuf, in->lengths, B, T, d, g_res, s));
-    TRY(encoder_tail(lp, d, g_ctx, d, g_res, d, B, false, tmp, g_x1, hh, last_rows, s));
+    TRY(encoder_tail(lp, d, g_ctx, d, g_res, d, B, false, w.tmp, g_x1, w.hh, last_rows, s));
   }
   return 0;
 }
@@ -538,21 +576,14 @@ static int encoder_tail_rows(const stlt_layer_params& lp, int64_t d, const float
 // out_btd != null (the fusion models' layout branch): every temporal layer runs on all real frames and the result is
 // scattered into the (B,T,d) tensor, padded frames zero — those rows are only ever masked keys or queries whose outputs
 // nobody reads (models.py:403-431, 470), so the logits are the padded schedule's; h0 is not produced.
-static int forward_ragged(const stlt_params* p, const stlt_inputs* in, void* workspace, const WsLayout& w, float* h0, float* out_btd,
-                          hipStream_t s) {
+static int forward_ragged(const stlt_params* p, const stlt_inputs* in, const WsBufs& w, float* h0, float* out_btd, hipStream_t s) {
   const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H;
   // head dims other than 64 run the ragged attention on attn_any.hip, whose forward holds at most 1024 keys of a segment (a frame's N
   // slots, a clip's T frames) in LDS: longer segments are refused here instead of being truncated in the kernel
   if (d / H != 64 && (N > 1024 || T > 1024))
     return stlt_set_error(STLT_EINVAL, "skip-padding with head dim %lld (not 64) takes at most 1024 object slots / frames per segment (N=%lld, T=%lld)", (long long)(d / H), (long long)N, (long long)T);
-  char* base = (char*)workspace;
-  float* x = (float*)(base + w.x);
-  float* x1 = (float*)(base + w.x1);
-  float* qkv = (float*)(base + w.qkv);
-  float* ctx = (float*)(base + w.ctx);
-  float* tmp = (float*)(base + w.tmp);
-  float* hh = (float*)(base + w.hh);
-  const RaggedIndex ix = ragged_index_carve(base + w.ridx, B, T, N);
+  float *x = w.x, *x1 = w.x1, *qkv = w.qkv, *ctx = w.ctx, *tmp = w.tmp, *hh = w.hh;
+  const RaggedIndex ix = ragged_index_carve(w.ridx, B, T, N);
   TRY(launch_ragged_index(in->kpm_boxes, in->kpm_frames, in->lengths, B, T, N, ix, s));
   int64_t Ms = 0, Mf = 0;
   bool host_counts = false;  // the caller knows the two row counts: no read-back, no synchronisation
@@ -601,28 +632,41 @@ static int forward_ragged(const stlt_params* p, const stlt_inputs* in, void* wor
 int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags,
                          float* out_btd, hipStream_t s) {
   TRY(check_params(p, in, false));
+  WsBufs w;
+  TRY(ws_carve(p, in, 1, workspace, workspace_bytes, STLT_EWORKSPACE, "", &w));
+  StltGemmScratch gemm_scratch(w.sk, STLT_GEMM_SCRATCH_BYTES);
   if (flags & STLT_FLAG_SKIP_PADDING) {
-    const WsLayout w = ws_layout(in->B, in->T, in->N, p->d, p->n_classes < 0 ? 0 : p->n_classes);
-    if (!workspace || workspace_bytes < w.total)
-      return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
-    if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
     if (!out_btd) return stlt_set_error(STLT_EINVAL, "skip-padding backbone: out_btd is null");
-    StltGemmScratch gemm_scratch((char*)workspace + w.sk, STLT_GEMM_SCRATCH_BYTES);
-    return forward_ragged(p, in, workspace, w, nullptr, out_btd, s);
+    return forward_ragged(p, in, w, nullptr, out_btd, s);
   }
-  return backbone_impl(p, in, workspace, workspace_bytes, flags, out_btd, nullptr, s);
-}
-size_t stlt_workspace_bytes_public(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
-  return ws_layout(B, T, N, d, n_classes < 0 ? 0 : n_classes).total;
+  return backbone_impl(p, in, w, flags, out_btd, nullptr, s);
 }
 
 extern "C" {
+
+size_t stlt_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
+  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
+  return stlt_ws_bytes(B, T, N, d, n_classes, 1);
+}
+
+size_t stlt_prefix_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
+  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
+  return stlt_ws_bytes(B, T, N, d, n_classes, 2);
+}
+
+size_t stlt_attention_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
+  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
+  return stlt_ws_bytes(B, T, N, d, n_classes, 1);
+}
 
 int stlt_backbone_forward(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes,
                           int flags, float* out_btd, stlt_stream_t stream) {
   TRY(check_params(p, in, false));
   if (!out_btd) return stlt_set_error(STLT_EINVAL, "stlt_backbone_forward: out_btd is null");
-  return backbone_impl(p, in, workspace, workspace_bytes, flags, out_btd, nullptr, (hipStream_t)stream);
+  WsBufs w;
+  TRY(ws_carve(p, in, 1, workspace, workspace_bytes, STLT_EWORKSPACE, "", &w));
+  StltGemmScratch gemm_scratch(w.sk, STLT_GEMM_SCRATCH_BYTES);
+  return backbone_impl(p, in, w, flags, out_btd, nullptr, (hipStream_t)stream);
 }
 
 int stlt_forward(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags,
@@ -630,34 +674,22 @@ int stlt_forward(const stlt_params* p, const stlt_inputs* in, void* workspace, s
   TRY(check_params(p, in, true));
   if (!logits) return stlt_set_error(STLT_EINVAL, "stlt_forward: logits is null");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t B = in->B, T = in->T, N = in->N, d = p->d;
-  const WsLayout w = ws_layout(B, T, N, d, p->n_classes);
-  if (!workspace || workspace_bytes < w.total)
-    return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
-  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
-  char* base = (char*)workspace;
-  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
-  float* bb_out = out_btd ? out_btd : (float*)(base + w.x1);  // x1 doubles as the in-place temporal buffer
-  float* h0 = (float*)(base + w.head);
-  float* h1 = h0 + (size_t)B * d;
-  float* h2 = h1 + (size_t)B * d;
+  const int64_t B = in->B, T = in->T, d = p->d;
+  WsBufs w;
+  TRY(ws_carve(p, in, 1, workspace, workspace_bytes, STLT_EWORKSPACE, "", &w));
+  StltGemmScratch gemm_scratch(w.sk, STLT_GEMM_SCRATCH_BYTES);
+  float* bb_out = out_btd ? out_btd : w.x1;  // x1 doubles as the in-place temporal buffer
+  float* h0 = w.head;
   const bool last_only = (flags & STLT_FLAG_LAST_ROW_ONLY_TEMPORAL) && !out_btd && p->n_temporal > 0 && in->T > 1;
   if ((flags & STLT_FLAG_SKIP_PADDING) && !out_btd) {  // padded rows are never computed, so there is no (B,T,d) output to hand back
-    TRY(forward_ragged(p, in, workspace, w, h0, nullptr, s));
+    TRY(forward_ragged(p, in, w, h0, nullptr, s));
   } else if (last_only) {  // the caller does not want the (B,T,d) backbone output: produce only the rows the head reads
-    TRY(backbone_impl(p, in, workspace, workspace_bytes, flags, bb_out, h0, s));
+    TRY(backbone_impl(p, in, w, flags, bb_out, h0, s));
   } else {
-    TRY(backbone_impl(p, in, workspace, workspace_bytes, flags, bb_out, nullptr, s));
+    TRY(backbone_impl(p, in, w, flags, bb_out, nullptr, s));
     TRY(launch_gather_last(bb_out, in->lengths, B, T, d, h0, s));                                 // models.py:189-192
   }
-  const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
-  return stlt_head(head, h0, d, d, B, d, p->n_classes, p->ln_eps, h1, h2, logits, s);
-}
-
-
-size_t stlt_prefix_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
-  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
-  return ws_layout(B, T, N, d, n_classes < 0 ? 0 : n_classes, 2).total;
+  return classification_head(p, h0, B, h0 + (size_t)B * d, h0 + (size_t)2 * B * d, logits, s);
 }
 
 int stlt_attn_prefix_probe_fwd(const float* qkv_frames, const float* qkv_probes, const uint8_t* kpm, int64_t S, int64_t T, int64_t H, int64_t dh,
@@ -675,25 +707,17 @@ int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* wor
   if (flags & STLT_FLAG_SKIP_PADDING)
     return stlt_set_error(STLT_EINVAL, "stlt_forward_prefixes: STLT_FLAG_SKIP_PADDING is not supported (the per-prefix forward runs the padded schedule)");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H, BT = B * T;
-  const WsLayout w = ws_layout(B, T, N, d, p->n_classes, 2);
-  if (!workspace || workspace_bytes < w.total)
-    return stlt_set_error(STLT_EWORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, w.total);
-  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
-  char* base = (char*)workspace;
-  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
-  float* x = (float*)(base + w.x);
-  float* x1 = (float*)(base + w.x1);
-  float* qkv = (float*)(base + w.qkv);
-  float* ctx = (float*)(base + w.ctx);
-  float* tmp = (float*)(base + w.tmp);
-  float* hh = (float*)(base + w.hh);
+  const int64_t B = in->B, T = in->T, d = p->d, H = p->H, BT = B * T;
+  WsBufs w;
+  TRY(ws_carve(p, in, 2, workspace, workspace_bytes, STLT_EWORKSPACE, "", &w));
+  StltGemmScratch gemm_scratch(w.sk, STLT_GEMM_SCRATCH_BYTES);
+  float *x = w.x, *qkv = w.qkv, *ctx = w.ctx, *tmp = w.tmp, *hh = w.hh;
   const float* cls_rows = nullptr;
   int64_t cls_stride = 0;
-  TRY(spatial_tower(p, in, flags, x, x1, qkv, ctx, tmp, hh, &cls_rows, &cls_stride, s));
+  TRY(spatial_tower(p, in, flags, w, LayerOpts{}, &cls_rows, &cls_stride, s));
   // both streams' embeddings into x1 (free here; x / ctx still hold the CLS rows being read)
-  float* g = x1;                      // frames (BT,d)
-  float* pr = x1 + (size_t)BT * d;    // probes (BT,d)
+  float* g = w.x1;                      // frames (BT,d)
+  float* pr = w.x1 + (size_t)BT * d;    // probes (BT,d)
   TRY(launch_frames_embed(cls_rows, cls_stride, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T, d, g, s));
   TRY(launch_probes_embed(cls_rows, cls_stride, in->frame_types, in->lengths, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T,
                           d, pr, s));
@@ -715,8 +739,7 @@ int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* wor
     }
   }
   // the head on the B*T probe rows; qkv and ctx are dead: they hold its two (BT,d) intermediates
-  const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
-  TRY(stlt_head(head, pr, d, d, BT, d, p->n_classes, p->ln_eps, qkv, ctx, logits, s));
+  TRY(classification_head(p, pr, BT, qkv, ctx, logits, s));
   return launch_prefix_zero_invalid(logits, in->lengths, B, T, p->n_classes, s);
 }
 
@@ -725,13 +748,8 @@ int stlt_attn_probs_fwd(const float* qkv, const uint8_t* kpm, int causal, int64_
   return launch_attn_probs(qkv, kpm, causal, S, L, H, dh, per_head, probs, (hipStream_t)stream);
 }
 
-size_t stlt_attention_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
-  if (B <= 0 || T <= 0 || N <= 0 || d <= 0) return 0;
-  return ws_layout(B, T, N, d, n_classes < 0 ? 0 : n_classes).total;
-}
-
-// The dense schedule with every layer as the unfused pair: the layer's packed QKV lies in the workspace, the attention core and the
-// probabilities launch read it side by side, and the post-norm block is the one every forward shares.  Buffers as backbone_impl's.
+// The dense schedule with every layer as the unfused pair, maps or no maps: the layer's packed QKV lies in the workspace, and the attention
+// core and the probabilities launch read it side by side.
 int stlt_forward_attention(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags, int per_head, float* logits,
                            float* attn_spatial, float* attn_temporal, stlt_stream_t stream) {
   TRY(check_params(p, in, true));
@@ -740,51 +758,23 @@ int stlt_forward_attention(const stlt_params* p, const stlt_inputs* in, void* wo
     return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: STLT_FLAG_SKIP_PADDING is not supported (the attention maps are those of the padded schedule)");
   if (per_head != 0 && per_head != 1) return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: per_head must be 0 or 1");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H, BT = B * T, tok = BT * N;
+  const int64_t B = in->B, T = in->T, N = in->N, d = p->d;
   if ((attn_spatial && p->n_spatial > 0 && N > 1024) || (attn_temporal && p->n_temporal > 0 && T > 1024))
     return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: a map of more than 1024 keys (N=%lld, T=%lld)", (long long)N, (long long)T);
   if (((uintptr_t)logits | (uintptr_t)attn_spatial | (uintptr_t)attn_temporal) & 3)
     return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: logits / attn_spatial / attn_temporal must be 4-byte aligned");
-  const WsLayout w = ws_layout(B, T, N, d, p->n_classes);
-  if (!workspace || workspace_bytes < w.total)
-    return stlt_set_error(STLT_EINVAL, "stlt_forward_attention: workspace %zu B < required %zu B", workspace_bytes, w.total);
-  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "workspace must be 256-byte aligned");
-  char* base = (char*)workspace;
-  StltGemmScratch gemm_scratch(base + w.sk, STLT_GEMM_SCRATCH_BYTES);
-  float* x = (float*)(base + w.x);
-  float* x1 = (float*)(base + w.x1);
-  float* qkv = (float*)(base + w.qkv);
-  float* ctx = (float*)(base + w.ctx);
-  float* tmp = (float*)(base + w.tmp);
-  float* hh = (float*)(base + w.hh);
-  const int64_t heads_out = per_head ? H : 1;
-  TRY(launch_embed(in->categories, in->boxes, in->scores, p->cat_emb, p->n_categories, p->box_w, p->box_b, p->score_w, p->score_b, p->emb_ln_w,
-                   p->emb_ln_b, p->ln_eps, tok, d, x, s));
-  // spatial transformer: sequences = frames (B*T), tokens = objects (N), key-padding mask only
-  for (int64_t l = 0; l < p->n_spatial; ++l) {
-    const stlt_layer_params& lp = p->spatial[l];
-    TRY(launch_linear(x, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, tok, 3 * d, d, STLT_ACT_NONE, s));
-    TRY(launch_attn(qkv, in->kpm_boxes, 0, BT, N, H, d / H, ctx, STLT_K_ATTN_SPATIAL, s));
-    if (attn_spatial) TRY(launch_attn_probs(qkv, in->kpm_boxes, 0, BT, N, H, d / H, per_head, attn_spatial + (size_t)l * BT * heads_out * N * N, s));
-    TRY(encoder_tail(lp, d, ctx, d, x, d, tok, fuse_residual(), tmp, x1, hh, x, s));
-  }
-  // CLS select + position + frame type + LN -> (B,T,d) in x1 (free: its last reader was the final norm2 above)
-  float* tbuf = x1;
-  TRY(launch_frames_embed(x, N * d, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T, d, tbuf, s));
-  // temporal transformer: sequences = clips (B), tokens = frames (T), causal + key padding; in place on tbuf, x is the post-norm1 scratch
-  for (int64_t l = 0; l < p->n_temporal; ++l) {
-    const stlt_layer_params& lp = p->temporal[l];
-    TRY(launch_linear(tbuf, d, lp.in_proj_w, lp.in_proj_b, qkv, 3 * d, BT, 3 * d, d, STLT_ACT_NONE, s));
-    TRY(launch_attn(qkv, in->kpm_frames, 1, B, T, H, d / H, ctx, STLT_K_ATTN_TEMPORAL, s));
-    if (attn_temporal) TRY(launch_attn_probs(qkv, in->kpm_frames, 1, B, T, H, d / H, per_head, attn_temporal + (size_t)l * B * heads_out * T * T, s));
-    TRY(encoder_tail(lp, d, ctx, d, tbuf, d, BT, fuse_residual(), tmp, x, hh, tbuf, s));
-  }
-  float* h0 = (float*)(base + w.head);
-  float* h1 = h0 + (size_t)B * d;
-  float* h2 = h1 + (size_t)B * d;
+  WsBufs w;
+  TRY(ws_carve(p, in, 1, workspace, workspace_bytes, STLT_EINVAL, "stlt_forward_attention: ", &w));
+  StltGemmScratch gemm_scratch(w.sk, STLT_GEMM_SCRATCH_BYTES);
+  const float* cls_rows = nullptr;
+  int64_t cls_stride = 0;
+  TRY(spatial_tower(p, in, 0, w, LayerOpts{true, attn_spatial, per_head}, &cls_rows, &cls_stride, s));  // the elision flags do not apply: every row of every map is asked for
+  float* tbuf = w.x1;  // free: its last reader was the final norm2 above
+  TRY(launch_frames_embed(cls_rows, cls_stride, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T, d, tbuf, s));
+  TRY(temporal_tower(p, in, p->n_temporal, w, LayerOpts{true, attn_temporal, per_head}, tbuf, tbuf, s));
+  float* h0 = w.head;
   TRY(launch_gather_last(tbuf, in->lengths, B, T, d, h0, s));  // models.py:189-192
-  const stlt_head_params head{p->fc1_w, p->fc1_b, p->head_ln_w, p->head_ln_b, p->fc2_w, p->fc2_b};
-  return stlt_head(head, h0, d, d, B, d, p->n_classes, p->ln_eps, h1, h2, logits, s);
+  return classification_head(p, h0, B, h0 + (size_t)B * d, h0 + (size_t)2 * B * d, logits, s);
 }
 
 }  // extern "C"

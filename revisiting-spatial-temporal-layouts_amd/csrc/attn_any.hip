@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <initializer_list>
 #include "common.h"
+#include "attn_vec.h"
 
 namespace {
 
@@ -36,35 +37,6 @@ struct AnyFwd {
   int Lq, Lk, H, dh, causal;
   float scale;
 };
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-  return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-// LDS traffic of one wave is in order; this keeps the compiler from moving accesses across and drains the counters
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// dot product of a row in LDS with a row in global memory (VEC: both 16-byte aligned, n % 4 == 0)
-template <bool VEC>
-__device__ __forceinline__ float dot_row(const float* __restrict__ s, const float* __restrict__ g, int n) {
-  float acc = 0.f;
-  if (VEC) {
-    for (int c = 0; c < n; c += 4) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(s + c);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(g + c);
-      acc += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-    }
-  } else {
-    for (int c = 0; c < n; ++c) acc += s[c] * g[c];
-  }
-  return acc;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(64 * ANY_WAVES) void attn_any_fwd_kernel(const AnyFwd a, int64_t n_items, StltDrop dr, uint32_t site) {

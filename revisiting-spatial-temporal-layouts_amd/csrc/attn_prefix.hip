@@ -34,19 +34,6 @@ struct ProbeArgs {
   float scale;
 };
 
-__device__ __forceinline__ float wave_max_dpp(float v) {  // wave_sum_dpp's steps with max
-  float a, b;
-  wave_pair32(v, a, b);
-  v = fmaxf(a, b);
-  wave_pair16(v, a, b);
-  v = fmaxf(a, b);
-  v = fmaxf(v, dpp_mov<0x128>(v));  // row_ror:8
-  v = fmaxf(v, dpp_mov<0x124>(v));  // row_ror:4
-  v = fmaxf(v, dpp_mov<0x4E>(v));   // quad_perm:[2,3,0,1]
-  v = fmaxf(v, dpp_mov<0xB1>(v));   // quad_perm:[1,0,3,2]
-  return v;
-}
-
 // rows [0, n_rows) of `src` (row pitch ld, dh floats each) -> LDS rows of pitch `pitch`
 template <bool VEC>
 __device__ __forceinline__ void stage_rows(const float* __restrict__ src, int64_t ld, int n_rows, int dh, float* dst, int pitch, int tid) {

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdint>
 #include "common.h"
+#include "attn_vec.h"
 #include "wave_dpp.h"
 
 namespace {
@@ -167,27 +168,6 @@ __global__ __launch_bounds__(64 * PB_WAVES) void attn_probs16_kernel(const Probs
   if (!geo.per_head) store(out_row, acc);
 }
 
-// dot product of a row in LDS with a row in global memory (VEC: both 16-byte aligned, n % 4 == 0)
-template <bool VEC>
-__device__ __forceinline__ float probs_dot(const float* __restrict__ s, const float* __restrict__ g, int n) {
-  float acc = 0.f;
-  if (VEC) {
-    for (int c = 0; c < n; c += 4) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(s + c);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(g + c);
-      acc += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-    }
-  } else {
-    for (int c = 0; c < n; ++c) acc += s[c] * g[c];
-  }
-  return acc;
-}
-__device__ __forceinline__ float probs_wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
-  return x;
-}
-
 // one wave per (sequence, query row): keys lane, lane + 64, ... in registers, the head loop inside
 template <bool VEC>
 __global__ __launch_bounds__(64 * PB_WAVES) void attn_probs_any_kernel(const ProbsGeo geo) {
@@ -214,20 +194,20 @@ __global__ __launch_bounds__(64 * PB_WAVES) void attn_probs_any_kernel(const Pro
   float* const out_row = geo.probs + (geo.per_head ? seq * H : seq) * map + (int64_t)i * L;
   for (int head = 0; head < H; ++head) {
     const float* qrow = geo.qkv + row * ld + (int64_t)head * dh;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous head's reads of qs are done (LDS traffic of one wave is in order)
+    wave_lds_sync();  // the previous head's reads of qs are done
     for (int c = lane; c < dh; c += 64) qs[c] = qrow[c];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_sync();
     float sc[PB_KEYS_PER_LANE];
     float mx = -1e30f;
 #pragma unroll
     for (int t = 0; t < PB_KEYS_PER_LANE; ++t) {
       sc[t] = -1e30f;
       if (64 * t < L) {  // wave-uniform
-        if (ok[t]) sc[t] = probs_dot<VEC>(qs, geo.qkv + (k_base + lane + 64 * t) * ld + d + (int64_t)head * dh, dh) * geo.scale;
+        if (ok[t]) sc[t] = dot_row<VEC>(qs, geo.qkv + (k_base + lane + 64 * t) * ld + d + (int64_t)head * dh, dh) * geo.scale;
         mx = fmaxf(mx, sc[t]);
       }
     }
-    mx = probs_wave_max(mx);
+    mx = wave_max(mx);
     float sum = 0.f;
 #pragma unroll
     for (int t = 0; t < PB_KEYS_PER_LANE; ++t) {

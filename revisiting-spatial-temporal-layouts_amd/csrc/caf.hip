@@ -60,7 +60,7 @@ CafWs caf_ws(int64_t B, int64_t T, int64_t N, int64_t d, int64_t C, int64_t S, i
   const size_t rows = (size_t)B * (T > S + 1 ? T : S + 1);
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = stlt_align256(off + bytes); return o; };
-  w.bb = take(stlt_workspace_bytes_public(B, T, N, d, K));
+  w.bb = take(stlt_ws_bytes(B, T, N, d, K, 1));
   w.lh = take((size_t)B * T * d * f);
   w.ah = take((size_t)B * (S + 1) * d * f);
   w.la = take(rows * d * f);
@@ -146,7 +146,7 @@ extern "C" int stlt_caf_forward_flags(const stlt_caf_params* p, const stlt_input
 
   // ---- layout branch: full (B,T,d) backbone output (models.py:451); STLT_FLAG_SKIP_PADDING computes it on the real
   // tokens / frames only and leaves the padded frames' rows zero (they are masked keys everywhere downstream)
-  TRY(backbone_impl_public(&lp, in, base + w.bb, stlt_workspace_bytes_public(B, T, N, d, K),
+  TRY(backbone_impl_public(&lp, in, base + w.bb, stlt_ws_bytes(B, T, N, d, K, 1),
                            STLT_FLAG_CLS_ONLY_LAST_SPATIAL | (flags & STLT_FLAG_SKIP_PADDING), Lh, s));
   // ---- appearance branch from the feature map (models.py:253-271)
   hipLaunchKernelGGL(feat_transpose_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((S + 31) / 32), (unsigned)B), dim3(256), 0, s, feats,

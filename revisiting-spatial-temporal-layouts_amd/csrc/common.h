@@ -348,10 +348,11 @@ int stlt_ffn_norm(const float* x, int64_t ldx, const float* w1, const float* b1,
 // logits (B,K) = fc2(LN_eps(gelu(fc1(x)))), x: B rows of in_dim values, stride ldx (ClassificationHead: in_dim = d; FusionHead: 2d); h1, h2: (B,d)
 int stlt_head(const stlt_head_params& h, const float* x, int64_t ldx, int64_t in_dim, int64_t B, int64_t d, int64_t K, float eps,
               float* h1, float* h2, float* logits, hipStream_t s);
-// api.hip, for the fusion models (caf.hip): the StltBackbone forward into out_btd (B,T,d) with its argument checks, and its workspace size
+// api.hip, for the fusion models (caf.hip): the StltBackbone forward into out_btd (B,T,d) with its argument checks, and the one size of the
+// whole-path workspace (min_slots: rows per frame it holds at least; 1, or 2 for the per-prefix forward)
 int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags,
                          float* out_btd, hipStream_t s);
-size_t stlt_workspace_bytes_public(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes);
+size_t stlt_ws_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes, int64_t min_slots);
 int launch_frames_embed(const float* spatial, int64_t row_stride, const int64_t* frame_types, const float* pos_table,
                         const float* type_table, const float* ln_w, const float* ln_b, float eps, int64_t B, int64_t T,
                         int64_t d, float* out, hipStream_t s, float* pre_out = nullptr, StltDrop dr = StltDrop{0u, 1.0f, 0ull},

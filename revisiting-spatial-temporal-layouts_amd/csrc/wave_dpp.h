@@ -1,4 +1,4 @@
-// Wave-wide sums on the DPP / permlane data paths of gfx950 (included by rowwise.hip, backward.hip, mhsa.hip, the attention kernels and tools/wave_sum_check.hip).
+// Wave-wide sums and maxima on the DPP / permlane data paths of gfx950 (included by rowwise.hip, backward.hip, mhsa.hip, the attention kernels and tools/wave_sum_check.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,5 +52,17 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   v += dpp_mov<0x124>(v);  // row_ror:4
   v += dpp_mov<0x4E>(v);   // quad_perm:[2,3,0,1]
   v += dpp_mov<0xB1>(v);   // quad_perm:[1,0,3,2]
+  return v;
+}
+__device__ __forceinline__ float wave_max_dpp(float v) {  // wave_sum_dpp's steps with max
+  float a, b;
+  wave_pair32(v, a, b);
+  v = fmaxf(a, b);
+  wave_pair16(v, a, b);
+  v = fmaxf(a, b);
+  v = fmaxf(v, dpp_mov<0x128>(v));  // row_ror:8
+  v = fmaxf(v, dpp_mov<0x124>(v));  // row_ror:4
+  v = fmaxf(v, dpp_mov<0x4E>(v));   // quad_perm:[2,3,0,1]
+  v = fmaxf(v, dpp_mov<0xB1>(v));   // quad_perm:[1,0,3,2]
   return v;
 }

@@ -340,19 +340,26 @@ class StltBackbone(nn.Module):
         """HIP forward, batch-major (B,T,d) result (the layout the kernels compute in)."""
         if (torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())) or self._dropout_live():
             return self.forward_train(batch)  # under no_grad the op-level Functions just run their forward kernels
-        lib = L.load()
-        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=False)
-        device = batch["categories"].device
-        p, _, _ = self.c_params()
-        d = self.config.hidden_size
-        nbytes = ops.workspace_bytes(B, T, N, d, 0)
-        ws = self._ws.get(nbytes, device)
-        out = torch.empty(B, T, d, device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            L.check(lib.stlt_backbone_forward(C.byref(p), C.byref(inp), ws.data_ptr(), ws.numel(), self._flags(),
-                                              out.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                    "stlt_backbone_forward")
+        out, = self._whole_path("stlt_backbone_forward", batch, None, ops.workspace_bytes, self._flags(),
+                                lambda B, T, N, K, new: (new(B, T, self.config.hidden_size),))
         return out
+
+    def _whole_path(self, entry: str, batch: Dict[str, torch.Tensor], head: Optional["ClassificationHead"], size_fn, flags: int, make_outputs, before=()):
+        """Marshal a batch and make one whole-path native call: `entry`(params, inputs, workspace, bytes, flags, *before, *outputs, stream).
+        `make_outputs(B, T, N, K, new)` allocates the call's float32 outputs with `new(*shape)`; they are returned as a tuple (an empty one
+        — a tower without layers — reaches the library as NULL).  `head`: the prediction head whose logits the call produces (None: the
+        backbone alone, which needs no lengths)."""
+        lib = L.load()
+        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=head is not None)
+        device = batch["categories"].device
+        p, _, _ = self.c_params(head)
+        K = head.fc2.weight.shape[0] if head is not None else 0
+        ws = self._ws.get(size_fn(B, T, N, self.config.hidden_size, K), device)
+        outs = make_outputs(B, T, N, K, lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32))
+        with torch.cuda.device(device):
+            L.check(getattr(lib, entry)(C.byref(p), C.byref(inp), ws.data_ptr(), ws.numel(), flags, *before,
+                                        *(o.data_ptr() if o.numel() else None for o in outs), torch.cuda.current_stream().cuda_stream), entry)
+        return outs
 
     def forward(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         # [Num. frames, Batch size, Hidden size] like the reference (a transposed view of the batch-major result)
@@ -407,18 +414,9 @@ class Stlt(nn.Module):
             params = tuple(self.parameters())
             logits = _StltTrainFn.apply(self, batch, *params)
             return {k: v for k, v in zip(self.logit_names, (logits,))}
-        lib = L.load()
-        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
-        device = batch["categories"].device
-        p, _, _ = bb.c_params(self.prediction_head)
-        d, K = self.config.hidden_size, self.prediction_head.fc2.weight.shape[0]
-        nbytes = ops.workspace_bytes(B, T, N, d, K)
-        ws = bb._ws.get(nbytes, device)
-        logits = torch.empty(B, K, device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            L.check(lib.stlt_forward(C.byref(p), C.byref(inp), ws.data_ptr(), ws.numel(), bb._flags(), None,
-                                     logits.data_ptr(), torch.cuda.current_stream().cuda_stream), "stlt_forward")
-        return {k: v for k, v in zip(self.logit_names, (logits,))}
+        logits = bb._whole_path("stlt_forward", batch, self.prediction_head, ops.workspace_bytes, bb._flags(),
+                                lambda B, T, N, K, new: (new(B, K),), before=(None,))  # no (B,T,d) backbone output
+        return {k: v for k, v in zip(self.logit_names, logits)}
 
 
     @torch.no_grad()
@@ -432,17 +430,9 @@ class Stlt(nn.Module):
             raise L.StltHipError("forward_prefixes is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
         if bb.skip_padding:
             raise L.StltHipError("forward_prefixes runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
-        lib = L.load()
-        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
-        device = batch["categories"].device
-        p, _, _ = bb.c_params(self.prediction_head)
-        d, K = self.config.hidden_size, self.prediction_head.fc2.weight.shape[0]
-        ws = bb._ws.get(ops.prefix_workspace_bytes(B, T, N, d, K), device)
-        logits = torch.empty(B, T, K, device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            L.check(lib.stlt_forward_prefixes(C.byref(p), C.byref(inp), ws.data_ptr(), ws.numel(), bb._flags(), logits.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream), "stlt_forward_prefixes")
-            valid = torch.arange(T, device=device)[None, :] < batch["lengths"].to(device)[:, None]
+        logits, = bb._whole_path("stlt_forward_prefixes", batch, self.prediction_head, ops.prefix_workspace_bytes, bb._flags(),
+                                 lambda B, T, N, K, new: (new(B, T, K),))
+        valid = torch.arange(logits.shape[1], device=logits.device)[None, :] < batch["lengths"].to(logits.device)[:, None]
         return {"stlt": logits, "valid": valid}
 
 
@@ -465,21 +455,11 @@ class Stlt(nn.Module):
             raise L.StltHipError("forward_attention runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
         if not batch["categories"].is_cuda:
             raise L.StltHipError("forward_attention runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
-        lib = L.load()
-        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
-        device = batch["categories"].device
-        p, _, _ = bb.c_params(self.prediction_head)
-        d, K, H = self.config.hidden_size, self.prediction_head.fc2.weight.shape[0], self.config.num_attention_heads
-        n_sp, n_tp = self.config.num_spatial_layers, self.config.num_temporal_layers
-        ws = bb._ws.get(ops.attention_workspace_bytes(B, T, N, d, K), device)
-        logits = torch.empty(B, K, device=device, dtype=torch.float32)
-        spatial = torch.empty((n_sp, B, T, H, N, N) if per_head else (n_sp, B, T, N, N), device=device, dtype=torch.float32)
-        temporal = torch.empty((n_tp, B, H, T, T) if per_head else (n_tp, B, T, T), device=device, dtype=torch.float32)
-        with torch.cuda.device(device):
-            L.check(lib.stlt_forward_attention(C.byref(p), C.byref(inp), ws.data_ptr(), ws.numel(), 0, int(bool(per_head)), logits.data_ptr(),
-                                               spatial.data_ptr() if n_sp else None, temporal.data_ptr() if n_tp else None,
-                                               torch.cuda.current_stream().cuda_stream), "stlt_forward_attention")
-        return {"stlt": logits, "spatial_attention": spatial, "temporal_attention": temporal}
+        H, n_sp, n_tp = self.config.num_attention_heads, self.config.num_spatial_layers, self.config.num_temporal_layers
+        def maps(B, T, N, K, new):
+            return (new(B, K), new((n_sp, B, T, H, N, N) if per_head else (n_sp, B, T, N, N)), new((n_tp, B, H, T, T) if per_head else (n_tp, B, T, T)))
+        outs = bb._whole_path("stlt_forward_attention", batch, self.prediction_head, ops.attention_workspace_bytes, 0, maps, before=(int(bool(per_head)),))
+        return dict(zip(("stlt", "spatial_attention", "temporal_attention"), outs))
 
 
 class _StltTrainFn(torch.autograd.Function):

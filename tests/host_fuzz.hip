@@ -76,7 +76,9 @@ void fuzz_bytes() {
   (void)stlt_gemm_scratch_bytes();
   (void)stlt_debug_buffer_bytes();
   (void)stlt_eval_max_clips();
-  g_calls += 14;
+  (void)stlt_prefix_workspace_bytes(B, T, N, d, K);
+  (void)stlt_attention_workspace_bytes(B, T, N, d, K);
+  g_calls += 16;
 }
 
 void fuzz_estimates() {
@@ -165,6 +167,9 @@ void fuzz_rowwise_and_attention() {
   tally(stlt_eval_topk(F<float>(1), dim(174, 1 << 20), F<int64_t>(2), B, dim(174, 1 << 20), F<int64_t>(3), s));
   tally(stlt_eval_store_sigmoid(F<float>(1), dim(157, 1 << 20), F<float>(2), B, dim(157, 1 << 20), F<double>(3), F<double>(4), dim(1000, 1ll << 40), s));
   tally(stlt_eval_average_precision(F<float>(1), F<float>(2), dim(2000, 1ll << 31), dim(157, 1 << 20), F<double>(3), F<double>(4), F<uint8_t>(5), s));
+  // the attention-map and per-prefix kernels: head dim 64 (the MFMA path of the probabilities) and not 64, both values of per_head and bad ones
+  tally(stlt_attn_probs_fwd(F<float>(1), F<uint8_t>(2), (int)uni(0, 1), S, L, H, dh, coin(8) ? (int)uni(-1, 2) : (int)uni(0, 1), F<float>(3), s));
+  tally(stlt_attn_prefix_probe_fwd(F<float>(1), F<float>(2), F<uint8_t>(3), S, coin(2) ? T : L, H, dh, F<float>(4), s));
 }
 
 struct Model {
@@ -215,6 +220,12 @@ void fuzz_whole_path() {
   const int flags = coin(3) ? (int)uni(-1, 64) : (int)uni(0, 7);
   tally(stlt_forward(coin(40) ? nullptr : &m.p, coin(40) ? nullptr : &m.in, F<char>(120), ws, flags, coin(2) ? nullptr : FA<float>(121), F<float>(122), s));
   tally(stlt_backbone_forward(&m.p, &m.in, F<char>(120), ws, flags, F<float>(121), s));
+  // per-prefix logits and attention maps: sizes of their own, sometimes short; either map absent; per_head 0, 1 and bad
+  const size_t pws = coin(4) ? (size_t)uni(0, 1 << 24) : stlt_prefix_workspace_bytes(m.in.B, m.in.T, m.in.N, m.p.d, m.p.n_classes);
+  tally(stlt_forward_prefixes(coin(40) ? nullptr : &m.p, coin(40) ? nullptr : &m.in, F<char>(120), pws, flags, F<float>(122), s));
+  const size_t aws = coin(4) ? (size_t)uni(0, 1 << 24) : stlt_attention_workspace_bytes(m.in.B, m.in.T, m.in.N, m.p.d, m.p.n_classes);
+  tally(stlt_forward_attention(coin(40) ? nullptr : &m.p, coin(40) ? nullptr : &m.in, F<char>(120), aws, flags, coin(8) ? (int)uni(-1, 2) : (int)uni(0, 1), F<float>(122),
+                               coin(3) ? nullptr : F<float>(127), coin(3) ? nullptr : F<float>(128), s));
   const size_t tape = coin(4) ? (size_t)uni(0, 1 << 24) : stlt_train_tape_bytes(m.in.B, m.in.T, m.in.N, m.p.d, m.p.n_spatial, m.p.n_temporal);
   const size_t scr = coin(4) ? (size_t)uni(0, 1 << 24) : stlt_train_scratch_bytes(m.in.B, m.in.T, m.in.N, m.p.d, m.p.n_categories);
   const int tflags = coin(3) ? (int)uni(0, 63) : (coin(2) ? 0 : 32);
