@@ -664,6 +664,19 @@ int stlt_train_forward(const stlt_params* p, const stlt_inputs* in, void* tape, 
 int stlt_train_backward(const stlt_params* p, const stlt_params* grads, const stlt_inputs* in, const void* tape,
                         size_t tape_bytes, void* scratch, size_t scratch_bytes, const float* dlogits,
                         float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, stlt_stream_t stream);
+/* Layout gradients (reference models.py:29-39: batch["boxes"] / batch["scores"] are ordinary autograd leaves there, so a backward on its Stlt
+ * gives boxes.grad).  stlt_train_backward_inputs is stlt_train_backward — same arguments, same sweep, stlt_train_backward IS this call with two
+ * NULLs — carried one step further: d_boxes (B*T*N*4) and d_scores (B*T*N; NULL, and it must be NULL when the inputs carry no scores) receive
+ * the gradient wrt the two inputs.  They are OVERWRITTEN, not accumulated; padded object slots and padded frames hold exactly 0 on both
+ * schedules (with STLT_FLAG_SKIP_PADDING every token that is no real row is cleared on the stream).  Both 16-byte aligned; d_scores only with
+ * d_boxes.  Works with STLT_FLAG_SKIP_PADDING, STLT_FLAG_TRAIN_BACKBONE and STLT_FLAG_TRAIN_LOWER_ONLY; STLT_EINVAL with
+ * STLT_FLAG_TRAIN_UPPER_ONLY (that half never reaches the embedding).  When EVERY member of `grads` is NULL (an input-only sweep: saliency, a
+ * frozen model) the sweep enqueues no weight-gradient product, no bias / LayerNorm / embedding-table reduction, and opens no side stream:
+ * what is left is the dX chain — the input-gradient products, the LayerNorm / GELU / attention backward — and the kernel below. */
+int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* grads, const stlt_inputs* in, const void* tape,
+                               size_t tape_bytes, void* scratch, size_t scratch_bytes, const float* dlogits,
+                               float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, float* d_boxes, float* d_scores,
+                               stlt_stream_t stream);
 
 /* ---- optimiser step of the training loop (reference train.py:128-131 with utils/train_inference_utils.py:37-54) ----
  * The reverse sweep writes all parameter gradients into ONE flat fp32 buffer (what a data-parallel run all-reduces).
@@ -729,6 +742,13 @@ size_t stlt_embed_bwd_scratch_bytes(int64_t n_tokens, int64_t n_categories, int6
 int stlt_embed_bwd(const float* d_pre, const int64_t* categories, const float* boxes, const float* scores, int64_t n_categories,
                    int64_t n_tokens, int64_t d, float* g_cat, float* g_box_w, float* g_box_b, float* g_score_w, float* g_score_b,
                    void* scratch, size_t scratch_bytes, stlt_stream_t stream);
+/* K1's gradient wrt its inputs (models.py:29-39: the sum is category row + box_embedding(boxes) + score_embeddings(scores)): given d_pre
+ * (n_tokens, d), d_boxes[t][j] = sum_c d_pre[t][c] * box_w[c][j] (box_w (d,4) as nn.Linear(4, d) stores it) and d_scores[t] = sum_c
+ * d_pre[t][c] * score_w[c] (score_w (d,1)).  Outputs are overwritten; the summation order is fixed (two calls are bit-identical).
+ * d_scores and score_w are NULL together.  STLT_EINVAL before any launch: a NULL required pointer, d % 4 != 0 (or d > 2048), n_tokens < 0,
+ * any pointer off a 16-byte boundary. */
+int stlt_embed_bwd_inputs(const float* d_pre, const float* box_w, const float* score_w, int64_t n_tokens, int64_t d, float* d_boxes,
+                          float* d_scores, stlt_stream_t stream);
 int stlt_frames_embed_fwd_train(const float* spatial, int64_t row_stride, const int64_t* frame_types, const float* pos_table,
                                 const float* type_table, const float* ln_w, const float* ln_b, float eps, int64_t B, int64_t T, int64_t d,
                                 float* pre_out, float* out, stlt_stream_t stream);
@@ -754,6 +774,10 @@ int stlt_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, stlt_st
 #define STLT_LOSS_BCE_WITH_LOGITS 1
 int stlt_loss_fwd_bwd(const float* logits, const void* labels, int kind, int64_t B, int64_t K, float weight,
                       float* scratch, float* loss_out, float* dlogits, stlt_stream_t stream);
+/* Seed of a saliency pass (the gradient of one raw logit per clip, what `logits[b, k].backward()` starts from on the reference's Stlt,
+ * models.py:166-195): dlogits (B,K) row b = e_k with k = target[b] (int64), or, with target == NULL, the argmax of logits row b (lowest
+ * index on ties).  An out-of-range target makes the row NaN, the convention of stlt_loss_fwd_bwd.  logits may be NULL when target is given. */
+int stlt_saliency_seed(const float* logits, const int64_t* target, int64_t B, int64_t K, float* dlogits, stlt_stream_t stream);
 int stlt_grad_norm(const float* flat_grad, int64_t n, float max_norm, float* scratch, float* out, stlt_stream_t stream);
 int stlt_adamw_step(const stlt_opt_chunk* chunks_dev, int64_t n_chunks, const float* flat_grad, float* exp_avg, float* exp_avg_sq,
                     const float* norm_and_clip, float lr, float beta1, float beta2, float eps, int64_t step, stlt_stream_t stream);

@@ -200,6 +200,10 @@ SIGNATURES = {
     "stlt_train_forward": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, _vp, C.c_float, C.c_uint64, C.c_int, _vp]),
     "stlt_train_backward": (C.c_int, [C.POINTER(Params), C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, _vp,
                                       C.c_size_t, _vp, C.c_float, C.c_uint64, C.c_int, _vp, _vp]),
+    "stlt_train_backward_inputs": (C.c_int, [C.POINTER(Params), C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, _vp,
+                                             C.c_size_t, _vp, C.c_float, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp]),
+    "stlt_embed_bwd_inputs": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "stlt_saliency_seed": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "stlt_linear_bwd_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "stlt_linear_bwd": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "stlt_attn_fwd_dropout": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,

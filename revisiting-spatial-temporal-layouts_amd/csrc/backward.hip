@@ -637,6 +637,85 @@ __global__ __launch_bounds__(256) void embed_bwd_finalize_kernel(const float* __
   else { if (has_scores && g_score_b) g_score_b[c] += acc; }
 }
 
+// ------------------------------------------------------------------ K1 backward (input gradients)
+// The gradient wrt the layout itself (models.py:29-39: the sum is category row + box_embedding(boxes) + score_embeddings(scores), so
+// d_boxes[tok][j] = sum_c d_pre[row][c] * box_w[c][j] and d_scores[tok] = sum_c d_pre[row][c] * score_w[c]).  Row-wise like the forward
+// embedding: GROUP lanes own a token (a wave, or 16 lanes — four tokens per wave — for d <= 64), each lane keeps the five weight columns
+// of its channels in registers across the tokens of its persistent loop, the five sums run on the DPP paths (wave_dpp.h) and lane 0 of
+// the group writes the token's four box gradients as one 16-byte store.  The next row is loaded before the current one is reduced.
+// A token's sum has one fixed order whatever the grid: two calls are bit-identical.  Outputs are overwritten.
+template <int GROUP>
+__device__ __forceinline__ float group_sum_dpp(float v) {
+  if (GROUP == 64) return wave_sum_dpp(v);
+  v += dpp_mov<0x128>(v);  // row_ror:8
+  v += dpp_mov<0x124>(v);  // row_ror:4
+  v += dpp_mov<0x4E>(v);   // quad_perm:[2,3,0,1]
+  v += dpp_mov<0xB1>(v);   // quad_perm:[1,0,3,2]
+  return v;
+}
+
+template <int NV, int GROUP>
+__global__ __launch_bounds__(256) void embed_bwd_inputs_kernel(const float* __restrict__ d_pre, const float* __restrict__ box_w,
+                                                               const float* __restrict__ score_w, int64_t rows, int d,
+                                                               float* __restrict__ d_boxes, float* __restrict__ d_scores,
+                                                               const int* __restrict__ src_index) {
+  constexpr int TPW = 64 / GROUP;  // tokens per wave and trip
+  const int lane = threadIdx.x & 63, gl = lane & (GROUP - 1);
+  const int64_t first = ((int64_t)blockIdx.x * RW_WAVES + (threadIdx.x >> 6)) * TPW + lane / GROUP;
+  const int64_t step = (int64_t)gridDim.x * RW_WAVES * TPW;
+  f32x4 wr[NV][4], ws[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int e = (i * GROUP + gl) * 4;
+    ws[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wr[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (e < d) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) wr[i][c] = *reinterpret_cast<const f32x4*>(box_w + (int64_t)(e + c) * 4);  // box_w is (d,4)
+      if (score_w) ws[i] = *reinterpret_cast<const f32x4*>(score_w + e);                                      // (d,1)
+    }
+  }
+  f32x4 nx[NV];  // the next row as loaded
+  auto load_row = [&](int64_t row) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int e = (i * GROUP + gl) * 4;
+      nx[i] = e < d ? *reinterpret_cast<const f32x4*>(d_pre + row * d + e) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  if (first < rows) load_row(first);
+  for (int64_t row = first; row < rows; row += step) {
+    f32x4 x[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) x[i] = nx[i];
+    if (row + step < rows) load_row(row + step);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float g = x[i][c];
+        s0 = fmaf(g, wr[i][c].x, s0);
+        s1 = fmaf(g, wr[i][c].y, s1);
+        s2 = fmaf(g, wr[i][c].z, s2);
+        s3 = fmaf(g, wr[i][c].w, s3);
+        s4 = fmaf(g, ws[i][c], s4);
+      }
+    }
+    s0 = group_sum_dpp<GROUP>(s0);
+    s1 = group_sum_dpp<GROUP>(s1);
+    s2 = group_sum_dpp<GROUP>(s2);
+    s3 = group_sum_dpp<GROUP>(s3);
+    if (d_scores) s4 = group_sum_dpp<GROUP>(s4);
+    if (gl == 0) {
+      const int64_t tok = src_index ? src_index[row] : row;  // ragged: gradient row -> token of the padded batch
+      *reinterpret_cast<f32x4*>(d_boxes + tok * 4) = f32x4{s0, s1, s2, s3};
+      if (d_scores) d_scores[tok] = s4;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ K7 backward
 // ds (B*T, d) = gradient wrt the pre-LayerNorm frames sum.  d_pos[t] = sum_b ds[b,t]; d_type[ft] = sum ds (row 0 =
 // padding_idx gets none, models.py:91); the CLS rows of the spatial gradient receive ds, the other rows zero.
@@ -964,8 +1043,44 @@ int launch_embed_bwd(const float* dx, const int64_t* categories, const float* bo
   return stlt_check_launch("embed_bwd_finalize_kernel");
 }
 
+// d_boxes (n_tokens,4) / d_scores (n_tokens; with score_w, else both null) from d_pre (rows,d).  src_index == nullptr: row = token and
+// rows == n_tokens; else token = src_index[row] (the ragged schedule's ix.t_orig) and the tokens that are no row are cleared first.
+int launch_embed_bwd_inputs(const float* d_pre, const float* box_w, const float* score_w, int64_t rows, int64_t d, float* d_boxes,
+                            float* d_scores, int64_t n_tokens, hipStream_t s, const int* src_index) {
+  StltProfScope ps(STLT_K_EMBED_BWD, s);
+  if (!d_pre || !box_w || !d_boxes) return stlt_set_error(STLT_EINVAL, "embed_bwd_inputs: null pointer");
+  if ((score_w == nullptr) != (d_scores == nullptr)) return stlt_set_error(STLT_EINVAL, "embed_bwd_inputs: score_w and d_scores come together");
+  if (d <= 0 || d % 4 != 0 || d > 2048) return stlt_set_error(STLT_EINVAL, "embed_bwd_inputs: d=%lld must be a multiple of 4 in [4,2048]", (long long)d);
+  if (rows < 0 || n_tokens < rows || n_tokens > 0x7fffffff || (!src_index && rows != n_tokens))
+    return stlt_set_error(STLT_EINVAL, "embed_bwd_inputs: bad row / token count (%lld / %lld)", (long long)rows, (long long)n_tokens);
+  if (const char* off = stlt_first_unaligned16({{"d_pre", d_pre}, {"box_w", box_w}, {"score_w", score_w}, {"d_boxes", d_boxes}, {"d_scores", d_scores}}))
+    return stlt_set_error(STLT_EINVAL, "embed_bwd_inputs: %s must be 16-byte aligned", off);
+  if (n_tokens == 0) return 0;
+  if (src_index) {
+    if (hipError_t e = hipMemsetAsync(d_boxes, 0, (size_t)n_tokens * 4 * sizeof(float), s); e != hipSuccess)
+      return stlt_set_error((int)e, "embed_bwd_inputs: memset: %s", hipGetErrorString(e));
+    if (d_scores)
+      if (hipError_t e = hipMemsetAsync(d_scores, 0, (size_t)n_tokens * sizeof(float), s); e != hipSuccess)
+        return stlt_set_error((int)e, "embed_bwd_inputs: memset: %s", hipGetErrorString(e));
+  }
+  if (rows == 0) return 0;
+  const int tpw = d <= 64 ? 4 : 1;  // tokens per wave and trip
+  int64_t blocks = (rows + RW_WAVES * tpw - 1) / (RW_WAVES * tpw);
+  if (blocks > 2048) blocks = 2048;  // persistent waves beyond that: the weight columns are loaded once per wave
+  stlt_prof_note("embed_bwd_inputs rows=%lld d=%lld blocks=%lld tokens/wave=%d", (long long)rows, (long long)d, (long long)blocks, tpw);
+  stlt_prof_add_bytes((double)rows * (4.0 * d + 20.0));
+  if (tpw == 4) {
+    hipLaunchKernelGGL((embed_bwd_inputs_kernel<1, 16>), dim3((unsigned)blocks), dim3(256), 0, s, d_pre, box_w, score_w, rows, (int)d, d_boxes, d_scores,
+                       src_index);
+  } else {
+    DISPATCH_NV(nv_for(d), hipLaunchKernelGGL((embed_bwd_inputs_kernel<NV, 64>), dim3((unsigned)blocks), dim3(256), 0, s, d_pre, box_w, score_w, rows,
+                                              (int)d, d_boxes, d_scores, src_index));
+  }
+  return stlt_check_launch("embed_bwd_inputs_kernel");
+}
+
 int launch_frames_bwd(const float* ds, const int64_t* frame_types, int64_t B, int64_t T, int64_t N, int64_t d,
-                      float* dx_spatial, float* g_pos, float* g_type, float* scratch, hipStream_t s, const int* row_of) {
+                      float* dx_spatial, float* g_pos, float* g_type, float* scratch, hipStream_t s, const int* row_of, bool want_params) {
   StltProfScope ps(STLT_K_EMBED_BWD, s);
   if (!ds || !frame_types || !scratch) return stlt_set_error(STLT_EINVAL, "frames_bwd: null pointer");
   if (B * T == 0) return 0;
@@ -973,6 +1088,7 @@ int launch_frames_bwd(const float* ds, const int64_t* frame_types, int64_t B, in
     hipLaunchKernelGGL(frames_bwd_scatter_kernel, dim3((unsigned)(B * T)), dim3(256), 0, s, ds, B * T, (int)N, (int)d, dx_spatial);
     if (int e = stlt_check_launch("frames_bwd_scatter_kernel")) return e;
   }
+  if (!want_params) return 0;  // input-only sweep: no table takes a gradient, so no partial sums either
   const int chunks = B < 16 ? (int)B : 16;  // scratch >= 16 * (T+5) * d floats
   stlt_prof_note("frames_bwd B=%lld T=%lld d=%lld chunks=%d clips/chunk=%lld", (long long)B, (long long)T, (long long)d, chunks, (long long)((B + chunks - 1) / chunks));
   hipLaunchKernelGGL(frames_bwd_params_kernel, dim3((unsigned)((d + 255) / 256), (unsigned)(T + 5), (unsigned)chunks), dim3(256), 0, s, ds,

@@ -431,6 +431,13 @@ int stlt_embed_bwd(const float* d_pre, const int64_t* categories, const float* b
                           (float*)scratch, (hipStream_t)stream);
 }
 
+// the layout's own gradient behind K1 (models.py:29-39: boxes and scores enter the sum through box_embedding / score_embeddings)
+int stlt_embed_bwd_inputs(const float* d_pre, const float* box_w, const float* score_w, int64_t n_tokens, int64_t d, float* d_boxes,
+                          float* d_scores, stlt_stream_t stream) {
+  if (n_tokens < 0) return stlt_set_error(STLT_EINVAL, "stlt_embed_bwd_inputs: n_tokens=%lld is negative", (long long)n_tokens);
+  return launch_embed_bwd_inputs(d_pre, box_w, score_w, n_tokens, d, d_boxes, d_scores, n_tokens, (hipStream_t)stream);
+}
+
 int stlt_frames_embed_fwd_train(const float* spatial, int64_t row_stride, const int64_t* frame_types, const float* pos_table,
                                 const float* type_table, const float* ln_w, const float* ln_b, float eps, int64_t B, int64_t T, int64_t d,
                                 float* pre_out, float* out, stlt_stream_t stream) {

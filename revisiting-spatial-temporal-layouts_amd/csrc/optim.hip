@@ -234,3 +234,63 @@ extern "C" int stlt_loss_fwd_bwd(const float* logits, const void* labels, int ki
                      kind == STLT_LOSS_CROSS_ENTROPY ? static_cast<const int64_t*>(labels) : nullptr, (int)K, dlogits);
   return stlt_check_launch("loss_finish_kernel");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Seed of a saliency pass: the gradient of ONE raw logit per clip wrt the logits, dlogits[b] = e_k — what autograd starts from for
+// `logits[b, k].backward()` on the reference's Stlt (models.py:166-195).  k = target[b], or the row's argmax (lowest index on ties, NaN
+// logits never win) when no target is given; an out-of-range target makes the row NaN, as stlt_loss_fwd_bwd does with a bad label.
+namespace {
+
+__global__ __launch_bounds__(256) void saliency_seed_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int K,
+                                                            float* __restrict__ dlogits) {
+  __shared__ float best_v[256];
+  __shared__ int best_k[256];
+  const int64_t b = blockIdx.x;
+  const float* x = logits + b * K;
+  float* dx = dlogits + b * K;
+  int64_t k_sel;
+  if (target) {
+    k_sel = target[b];
+  } else {
+    float v = -INFINITY;
+    int kk = 0x7fffffff;  // no finite-or-infinite candidate yet
+    for (int k = threadIdx.x; k < K; k += 256) {
+      const float c = x[k];
+      if (kk == 0x7fffffff ? c == c : c > v) { v = c; kk = k; }  // strictly greater: the thread keeps its lowest index
+    }
+    best_v[threadIdx.x] = v;
+    best_k[threadIdx.x] = kk;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (threadIdx.x < o) {
+        const float v2 = best_v[threadIdx.x + o];
+        const int k2 = best_k[threadIdx.x + o];
+        const float v1 = best_v[threadIdx.x];
+        const int k1 = best_k[threadIdx.x];
+        const bool take = k2 != 0x7fffffff && (k1 == 0x7fffffff || v2 > v1 || (v2 == v1 && k2 < k1));
+        if (take) { best_v[threadIdx.x] = v2; best_k[threadIdx.x] = k2; }
+      }
+      __syncthreads();
+    }
+    k_sel = best_k[0] == 0x7fffffff ? 0 : best_k[0];  // a row of NaNs: class 0 (its gradients are NaN whatever the seed)
+  }
+  if (k_sel < 0 || k_sel >= K) {
+    const float nan = __builtin_nanf("");
+    for (int k = threadIdx.x; k < K; k += 256) dx[k] = nan;
+    return;
+  }
+  for (int k = threadIdx.x; k < K; k += 256) dx[k] = k == k_sel ? 1.0f : 0.0f;
+}
+
+}  // namespace
+
+extern "C" int stlt_saliency_seed(const float* logits, const int64_t* target, int64_t B, int64_t K, float* dlogits, stlt_stream_t stream) {
+  if (!dlogits || (!logits && !target)) return stlt_set_error(STLT_EINVAL, "stlt_saliency_seed: null pointer");
+  if (B < 0 || K <= 0 || K > 0x7fffffffLL || B > 0x7fffffffLL) return stlt_set_error(STLT_EINVAL, "stlt_saliency_seed: bad shape");
+  if (B == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  StltProfScope ps(STLT_K_OPTIM, s);
+  stlt_prof_note("saliency_seed B=%lld K=%lld %s", (long long)B, (long long)K, target ? "target" : "argmax");
+  hipLaunchKernelGGL(saliency_seed_kernel, dim3((unsigned)B), dim3(256), 0, s, logits, target, (int)K, dlogits);
+  return stlt_check_launch("saliency_seed_kernel");
+}

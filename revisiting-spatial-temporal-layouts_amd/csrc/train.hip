@@ -437,6 +437,21 @@ static int check_train(const stlt_params* p, const stlt_inputs* in, bool need_he
   return 0;
 }
 
+// An input-only sweep (stlt_train_backward_inputs with a table of NULLs: saliency, a frozen model whose layout requires grad) names no
+// parameter gradient at all: then there is no weight-gradient product to fork a stream for and no operand row padding to clear.
+static bool layer_table_empty(const stlt_layer_params& l) {
+  return !l.in_proj_w && !l.in_proj_b && !l.out_proj_w && !l.out_proj_b && !l.lin1_w && !l.lin1_b && !l.lin2_w && !l.lin2_b && !l.norm1_w && !l.norm1_b &&
+         !l.norm2_w && !l.norm2_b;
+}
+static bool grad_table_empty(const stlt_params* p, const stlt_params* g) {
+  if (g->cat_emb || g->box_w || g->box_b || g->score_w || g->score_b || g->emb_ln_w || g->emb_ln_b || g->pos_emb || g->type_emb || g->frames_ln_w ||
+      g->frames_ln_b || g->fc1_w || g->fc1_b || g->head_ln_w || g->head_ln_b || g->fc2_w || g->fc2_b)
+    return false;
+  for (int64_t l = 0; g->spatial && l < p->n_spatial; ++l) if (!layer_table_empty(g->spatial[l])) return false;
+  for (int64_t l = 0; g->temporal && l < p->n_temporal; ++l) if (!layer_table_empty(g->temporal[l])) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -528,10 +543,27 @@ int stlt_train_forward(const stlt_params* p, const stlt_inputs* in, void* tape_m
 int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_inputs* in, const void* tape_mem,
                         size_t tape_bytes, void* scratch_mem, size_t scratch_bytes, const float* dlogits,
                         float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, stlt_stream_t stream) {
+  return stlt_train_backward_inputs(p, g, in, tape_mem, tape_bytes, scratch_mem, scratch_bytes, dlogits, dropout_p, dropout_seed, flags, ctx, nullptr,
+                                    nullptr, stream);
+}
+
+// The same sweep, carried one step further: from the gradient wrt the pre-LayerNorm embedding sum to the gradient wrt the layout itself
+// (what autograd gives the reference for batch["boxes"] / batch["scores"] as leaves, models.py:29-39).  Both outputs NULL: stlt_train_backward.
+int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const stlt_inputs* in, const void* tape_mem,
+                               size_t tape_bytes, void* scratch_mem, size_t scratch_bytes, const float* dlogits,
+                               float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, float* d_boxes, float* d_scores,
+                               stlt_stream_t stream) {
   const bool backbone_only = (flags & STLT_FLAG_TRAIN_BACKBONE) != 0;  // `dlogits` is then the gradient of the (B*T, d) backbone output
   TRY(check_train(p, in, !backbone_only));
   if (backbone_only && (flags & STLT_FLAG_SKIP_PADDING)) return stlt_set_error(STLT_EINVAL, "STLT_FLAG_TRAIN_BACKBONE excludes STLT_FLAG_SKIP_PADDING");
   if (!g || !dlogits || !tape_mem || !scratch_mem) return stlt_set_error(STLT_EINVAL, "stlt_train_backward: null argument");
+  if (d_scores && !d_boxes) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_inputs: d_scores comes with d_boxes");
+  if (d_scores && !in->scores) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_inputs: d_scores given but the inputs carry no scores");
+  if (d_boxes && (flags & STLT_FLAG_TRAIN_UPPER_ONLY))
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_inputs: STLT_FLAG_TRAIN_UPPER_ONLY never reaches the embedding");
+  if (const char* off = stlt_first_unaligned16({{"d_boxes", d_boxes}, {"d_scores", d_scores}}))
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_inputs: %s must be 16-byte aligned", off);
+  const bool no_param_grads = grad_table_empty(p, g);
   hipStream_t s = (hipStream_t)stream;
   StltCtxScope ctx_scope(ctx, s);  // the sweep's input-gradient products may read the context's transposed weight copies
   if (ctx_scope.error()) return ctx_scope.error();
@@ -574,7 +606,7 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
   // cleared every step: at most 31 rows per buffer.
   // (the fusion models' layout branch — STLT_FLAG_TRAIN_BACKBONE — keeps one stream: measured 43.75 against 44.1 ms per CACNF step at 64
   // clips; the block-level calls around the sweep are single-stream and the side launches only delay their small kernels)
-  DwSide side = backbone_only ? DwSide{} : dw_side_open(sc, ctx);
+  DwSide side = backbone_only || no_param_grads ? DwSide{} : dw_side_open(sc, ctx);
   DwSideHold side_hold(&side, s);
   // weight-gradient queues: the spatial tower flushes per layer over two sets; the temporal tower, when it has few rows, collects up to
   // eight layers (32 products) per grouped launch over eight sets (STLT_TRAIN_DW_GROUP_LAYERS=1: per layer, A/B runs)
@@ -588,14 +620,14 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
     q_tp.n_sets = 2 + sc.n_tx;
     q_tp.group_layers = group_env < q_tp.n_sets ? group_env : q_tp.n_sets;
   }
-  if (do_lower) {
+  if (do_lower && !no_param_grads) {
     for (int k = 0; k < q_sp.n_sets; ++k) {
       for (float* b : {q_sp.sets[k].B, q_sp.sets[k].D, q_sp.sets[k].E}) TRY(zero_rows(b, d, tok, tokp, s));
       TRY(zero_rows(q_sp.sets[k].Q, 3 * d, tok, tokp, s));
       TRY(zero_rows(q_sp.sets[k].H, 4 * d, tok, tokp, s));
     }
   }
-  if (do_upper) {
+  if (do_upper && !no_param_grads) {
     for (int k = 0; k < q_tp.n_sets; ++k) {
       for (float* b : {q_tp.sets[k].B, q_tp.sets[k].D, q_tp.sets[k].E}) TRY(zero_rows(b, d, BT, btp, s));
       TRY(zero_rows(q_tp.sets[k].Q, 3 * d, BT, btp, s));
@@ -652,7 +684,7 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
                     stlt_grad(g->frames_ln_b), red.chunk(), s, dr, 0, nullptr, STLT_SITE_FRAMES));                // d_cls = gradient wrt the frames' CLS rows
   const bool dense_scatter = !ragged && !sp_tail;  // padded dense schedule: the CLS rows sit at stride N in the token buffer
   TRY(launch_frames_bwd(d_cls, in->frame_types, B, T, N, d, dense_scatter ? sc.sA : nullptr, stlt_grad(g->pos_emb), stlt_grad(g->type_emb), red.chunk(), s,
-                        ragged ? ix.f_row_of : nullptr));
+                        ragged ? ix.f_row_of : nullptr, !no_param_grads));
   // ---- spatial transformer
   int64_t l_sp = p->n_spatial - 1;
   if (sp_tail) {
@@ -669,8 +701,11 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
   // ---- category / box / score embeddings (models.py:29-39); sC for the same reason as tC above
   TRY(launch_ln_bwd(sc.sA, d, t.s_embed, d, nullptr, 0, p->emb_ln_w, p->ln_eps, tok, d, sc.sC, d, stlt_grad(g->emb_ln_w), stlt_grad(g->emb_ln_b),
                     red.chunk(), s, dr, 0, nullptr, STLT_SITE_EMBED));
-  TRY(launch_embed_bwd(sc.sC, in->categories, in->boxes, in->scores, p->n_categories, tok, d, stlt_grad(g->cat_emb), stlt_grad(g->box_w),
-                       stlt_grad(g->box_b), stlt_grad(g->score_w), stlt_grad(g->score_b), red.chunk(), s, ragged ? ix.t_orig : nullptr));
+  if (!no_param_grads)
+    TRY(launch_embed_bwd(sc.sC, in->categories, in->boxes, in->scores, p->n_categories, tok, d, stlt_grad(g->cat_emb), stlt_grad(g->box_w),
+                         stlt_grad(g->box_b), stlt_grad(g->score_w), stlt_grad(g->score_b), red.chunk(), s, ragged ? ix.t_orig : nullptr));
+  if (d_boxes)
+    TRY(launch_embed_bwd_inputs(sc.sC, p->box_w, d_scores ? p->score_w : nullptr, tok, d, d_boxes, d_scores, B * T * N, s, ragged ? ix.t_orig : nullptr));
   TRY(red.flush());
   return dw_side_join(&side, s);
 }

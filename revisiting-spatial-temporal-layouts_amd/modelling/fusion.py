@@ -29,7 +29,8 @@ from torch import nn
 from .. import _lib as L
 from .. import ops
 from .configs import MultimodalModelConfig
-from .models import ClassificationHead, StltBackbone, _dev_ptr, _EncoderLayerParams, _EncoderStack, _prep_inputs, _SelfAttnParams, _Workspace
+from .models import (ClassificationHead, StltBackbone, _dev_ptr, _EncoderLayerParams, _EncoderStack, _layout_requires_grad, _prep_inputs, _SelfAttnParams,
+                     _Workspace)
 from .resnet3d import Resnet3D
 
 
@@ -207,8 +208,8 @@ class CrossAttentionFusionBackbone(nn.Module):
     def run_train(self, batch: Dict[str, torch.Tensor], fusion_head, layout_head=None, appearance_head=None):
         """Differentiable forward (see the module docstring).  -> same tuple as run()."""
         feats = self._features(batch)
-        if any(q.requires_grad for q in self.layout_branch.parameters()):
-            Lh = self.layout_branch.forward_train(batch)  # (B,T,d) with its autograd graph (op-level composition)
+        if any(q.requires_grad for q in self.layout_branch.parameters()) or _layout_requires_grad(batch):
+            Lh = self.layout_branch.forward_train(batch)  # (B,T,d) with its autograd graph (op-level composition); boxes / scores get their gradients here
         else:  # frozen (load_backbone_path + freeze_backbone): one native call, no tape
             was_training = self.layout_branch.training
             self.layout_branch.train(False)

@@ -184,6 +184,23 @@ def _prep_inputs(batch: Dict[str, torch.Tensor], need_lengths: bool):
     return inp, keep, (B, T, N)
 
 
+def _layout_requires_grad(batch: Dict[str, torch.Tensor]) -> bool:
+    """The batch's boxes or scores are autograd leaves (or results) that want a gradient, as they may be in the reference."""
+    return any(isinstance(batch.get(k), torch.Tensor) and batch[k].requires_grad for k in ("boxes", "scores"))
+
+
+def _layout_grad_buffers(ctx_needs, batch, shape, device):
+    """(d_boxes, d_scores) output buffers of stlt_train_backward_inputs for the gradients autograd asks for, (None, None) when it asks for
+    neither.  The native call writes d_scores only beside d_boxes, so a scores-only request still allocates both."""
+    B, T, N = shape
+    want_b, want_s = bool(ctx_needs[0]), bool(ctx_needs[1]) and "scores" in batch
+    if not (want_b or want_s):
+        return None, None
+    d_boxes = torch.empty(B, T, N, 4, device=device, dtype=torch.float32)
+    d_scores = torch.empty(B, T, N, device=device, dtype=torch.float32) if want_s else None
+    return d_boxes, d_scores
+
+
 class StltBackbone(nn.Module):
     """Drop-in for reference ``StltBackbone`` (models.py:114-152): ``forward(batch) -> (T, B, d)``."""
 
@@ -313,7 +330,7 @@ class StltBackbone(nn.Module):
         if not self.skip_padding and "lengths" in batch:
             # one native tape forward / reverse sweep (csrc/train.hip with STLT_FLAG_TRAIN_BACKBONE): the last spatial layer
             # runs its out-proj / norms / FFN on the CLS rows only, weight gradients go out layer by layer in grouped launches
-            return _BackboneTrainFn.apply(self, batch, *tuple(self.parameters()))
+            return _BackboneTrainFn.apply(self, batch, batch["boxes"], batch.get("scores"), *tuple(self.parameters()))
         fe = self.frames_embeddings
         le = fe.layout_embedding
         cbe = le.category_box_embeddings
@@ -338,7 +355,7 @@ class StltBackbone(nn.Module):
 
     def forward_batch_major(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         """HIP forward, batch-major (B,T,d) result (the layout the kernels compute in)."""
-        if (torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())) or self._dropout_live():
+        if (torch.is_grad_enabled() and (any(q.requires_grad for q in self.parameters()) or _layout_requires_grad(batch))) or self._dropout_live():
             return self.forward_train(batch)  # under no_grad the op-level Functions just run their forward kernels
         out, = self._whole_path("stlt_backbone_forward", batch, None, ops.workspace_bytes, self._flags(),
                                 lambda B, T, N, K, new: (new(B, T, self.config.hidden_size),))
@@ -407,12 +424,12 @@ class Stlt(nn.Module):
 
     def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         bb = self.backbone
-        grad_path = torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters())
+        grad_path = torch.is_grad_enabled() and (any(q.requires_grad for q in self.parameters()) or _layout_requires_grad(batch))
         if grad_path or bb._dropout_live():
             # train mode without grad (a validation pass that forgot model.train(False), MC-dropout): the reference still
             # applies its dropouts, so the training forward runs here too — same kernels, the tape is just not kept
             params = tuple(self.parameters())
-            logits = _StltTrainFn.apply(self, batch, *params)
+            logits = _StltTrainFn.apply(self, batch, batch["boxes"], batch.get("scores"), *params)
             return {k: v for k, v in zip(self.logit_names, (logits,))}
         logits = bb._whole_path("stlt_forward", batch, self.prediction_head, ops.workspace_bytes, bb._flags(),
                                 lambda B, T, N, K, new: (new(B, K),), before=(None,))  # no (B,T,d) backbone output
@@ -461,14 +478,79 @@ class Stlt(nn.Module):
         outs = bb._whole_path("stlt_forward_attention", batch, self.prediction_head, ops.attention_workspace_bytes, 0, maps, before=(int(bool(per_head)),))
         return dict(zip(("stlt", "spatial_attention", "temporal_attention"), outs))
 
+    @torch.no_grad()
+    def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None) -> Dict[str, torch.Tensor]:
+        """The model's logits and the gradient of one raw logit per clip with respect to the layout, in one pass: which object's
+        position (and detection score) the prediction depends on.  What the reference gives for `boxes.requires_grad_()` followed by
+        `logits[b, target[b]].backward()` (models.py:29-39, 166-195), without autograd: stlt_train_forward with dropout 0,
+        stlt_saliency_seed, then stlt_train_backward_inputs with a gradient table of NULLs — the input-only sweep (no weight-gradient
+        product, no parameter reduction, no side stream).
+        -> {"stlt": (B, num_classes) float32 logits, "target": the selected classes, "boxes_grad": (B, T, N, 4) float32,
+            "scores_grad": (B, T, N) float32 — only when the batch has scores}.
+        `target`: None — each clip's top-1 class ("target" is then the (B,) int64 device tensor of those classes); an int64 (B,) tensor —
+        that class per clip; a float (B, num_classes) tensor — used as the seed d(objective)/d(logits) itself (a multi-hot row for Action
+        Genome, or any weighting), returned as given.  The gradients are of the raw logit, not of a loss.  Entries of padded object slots
+        and of padded frames are exactly 0.  Works with `backbone.skip_padding` on and off; reads nothing back from the device (with
+        skip_padding: when the batch carries num_real_tokens / num_real_frames).  Inference only: touches no parameter's .grad.  It runs
+        on the backbone's one activation tape, so an autograd backward still pending from an earlier forward refuses to run afterwards."""
+        bb = self.backbone
+        if bb._dropout_live():
+            raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if not batch["categories"].is_cuda:
+            raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        lib = L.load()
+        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
+        device = batch["categories"].device
+        head = self.prediction_head
+        p, _, _ = bb.c_params(head)
+        d, K = self.config.hidden_size, head.fc2.weight.shape[0]
+        tgt = None
+        if isinstance(target, torch.Tensor) and target.is_floating_point():
+            if tuple(target.shape) != (B, K) or target.device != device:
+                raise L.StltHipError(f"forward_saliency: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
+            seed = target.detach().to(torch.float32).contiguous()
+        elif target is not None:
+            if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
+                raise L.StltHipError(f"forward_saliency: target is None, an int64 ({B},) tensor or a float ({B}, {K}) tensor on the batch's device")
+            tgt = target.contiguous()
+            seed = None
+        else:
+            seed = None
+        tape = bb._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
+        scratch = bb._train_buf("scratch", int(lib.stlt_train_scratch_bytes(B, T, N, d, p.n_categories)), device)
+        bb._tape_gen = getattr(bb, "_tape_gen", 0) + 1  # the tape is overwritten: a pending backward of an earlier forward must refuse
+        g, gsp, gtp = bb._build_struct(head, lambda t: None)
+        new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)  # noqa: E731
+        logits, d_boxes = new(B, K), new(B, T, N, 4)
+        d_scores = new(B, T, N) if "scores" in batch else None
+        flags = L.FLAG_SKIP_PADDING if bb.skip_padding else 0
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream().cuda_stream
+            L.check(lib.stlt_train_forward(C.byref(p), C.byref(inp), tape.data_ptr(), tape.numel(), logits.data_ptr(), 0.0, 0, flags, stream),
+                    "stlt_train_forward")
+            if seed is None:
+                seed = new(B, K)
+                L.check(lib.stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), B, K, seed.data_ptr(), stream),
+                        "stlt_saliency_seed")
+            L.check(lib.stlt_train_backward_inputs(C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(), scratch.data_ptr(),
+                                                   scratch.numel(), seed.data_ptr(), 0.0, 0, flags, None, d_boxes.data_ptr(),
+                                                   None if d_scores is None else d_scores.data_ptr(), stream), "stlt_train_backward_inputs")
+        if target is None:
+            target = seed.argmax(dim=1)  # the one-hot row's only 1: the class the kernel picked (lowest index on ties), still on the device
+        out = {"stlt": logits, "target": target, "boxes_grad": d_boxes}
+        if d_scores is not None:
+            out["scores_grad"] = d_scores
+        return out
+
 
 class _StltTrainFn(torch.autograd.Function):
     """Autograd shell of the native training step: forward = stlt_train_forward (records the tape), backward =
     stlt_train_backward (the reverse sweep in HIP).  The parameters are passed as inputs only so that autograd
-    routes their gradients; all arithmetic happens behind the C-ABI."""
+    routes their gradients, and so are the batch's boxes and scores (the reference's layout inputs are ordinary autograd leaves; the
+    sweep produces their gradients through stlt_train_backward_inputs when they are asked for); all arithmetic happens behind the C-ABI."""
 
     @staticmethod
-    def forward(ctx, model, batch, *params):
+    def forward(ctx, model, batch, boxes, scores, *params):
         lib = L.load()
         bb = model.backbone
         inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
@@ -537,11 +619,16 @@ class _StltTrainFn(torch.autograd.Function):
         # the training context the sweep names: the trainer's while its step runs this backward (its transposed weight copies, its side
         # stream), else one the module owns for the side stream of plain autograd backwards
         tctx = getattr(model, "_train_context", None) or model._own_context()
+        d_boxes, d_scores = _layout_grad_buffers(ctx.needs_input_grad[2:4], batch, (B, T, N), device)
 
         def run(extra_flags):
-            L.check(lib.stlt_train_backward(C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(),
-                                            scratch.data_ptr(), scratch.numel(), dl.data_ptr(), ctx.drop[0], ctx.drop[1],
-                                            ctx.drop[2] | extra_flags, tctx.handle, torch.cuda.current_stream().cuda_stream), "stlt_train_backward")
+            args = (C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(), dl.data_ptr(),
+                    ctx.drop[0], ctx.drop[1], ctx.drop[2] | extra_flags, tctx.handle)
+            if d_boxes is None or extra_flags == L.FLAG_TRAIN_UPPER_ONLY:  # the upper half never reaches the embedding
+                L.check(lib.stlt_train_backward(*args, torch.cuda.current_stream().cuda_stream), "stlt_train_backward")
+            else:
+                L.check(lib.stlt_train_backward_inputs(*args, d_boxes.data_ptr(), None if d_scores is None else d_scores.data_ptr(),
+                                                       torch.cuda.current_stream().cuda_stream), "stlt_train_backward_inputs")
 
         sync = getattr(model, "_grad_sync", None)  # data-parallel hook: sync(flat, lo, hi) may start reducing flat[lo:hi]
         with torch.cuda.device(device):
@@ -559,9 +646,10 @@ class _StltTrainFn(torch.autograd.Function):
                 sync(flat, 0, split)
         model._last_flat_grad = flat  # one contiguous buffer: what a data-parallel wrapper all-reduces
         model._flat_layout = layout
+        d_boxes_out = d_boxes if ctx.needs_input_grad[2] else None
         if getattr(model, "_flat_grads_only", False):  # train.FusedAdamW reads the flat buffer: skip the per-parameter .grad copies
-            return (None, None) + tuple(None for _ in ctx.params)
-        return (None, None) + tuple(views.get(id(prm)) for prm in ctx.params)
+            return (None, None, d_boxes_out, d_scores) + tuple(None for _ in ctx.params)
+        return (None, None, d_boxes_out, d_scores) + tuple(views.get(id(prm)) for prm in ctx.params)
 
 
 class _BackboneTrainFn(torch.autograd.Function):
@@ -570,7 +658,7 @@ class _BackboneTrainFn(torch.autograd.Function):
     prediction head, every temporal layer on every frame, the (B,T,d) output's gradient as the sweep's seed."""
 
     @staticmethod
-    def forward(ctx, bb, batch, *params):
+    def forward(ctx, bb, batch, boxes, scores, *params):
         lib = L.load()
         inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
         device = batch["categories"].device
@@ -638,11 +726,16 @@ class _BackboneTrainFn(torch.autograd.Function):
         tape = bb._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
         scratch = bb._train_buf("scratch", int(lib.stlt_train_scratch_bytes(B, T, N, d, p.n_categories)), device)
         dl = dout.contiguous().float()
+        d_boxes, d_scores = _layout_grad_buffers(ctx.needs_input_grad[2:4], batch, (B, T, N), device)
+        args = (C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(), dl.data_ptr(), ctx.drop[0],
+                ctx.drop[1], L.FLAG_TRAIN_BACKBONE, ops._ctx_handle(ops.context_of(ctx.params)))
         with torch.cuda.device(device):
-            L.check(lib.stlt_train_backward(C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(),
-                                            dl.data_ptr(), ctx.drop[0], ctx.drop[1], L.FLAG_TRAIN_BACKBONE, ops._ctx_handle(ops.context_of(ctx.params)),
-                                            torch.cuda.current_stream().cuda_stream), "stlt_train_backward")
-        return (None, None) + tuple(views.get(id(prm)) for prm in ctx.params)
+            if d_boxes is None:
+                L.check(lib.stlt_train_backward(*args, torch.cuda.current_stream().cuda_stream), "stlt_train_backward")
+            else:
+                L.check(lib.stlt_train_backward_inputs(*args, d_boxes.data_ptr(), None if d_scores is None else d_scores.data_ptr(),
+                                                       torch.cuda.current_stream().cuda_stream), "stlt_train_backward_inputs")
+        return (None, None, d_boxes if ctx.needs_input_grad[2] else None, d_scores) + tuple(views.get(id(prm)) for prm in ctx.params)
 
 
 models_factory = {"stlt": Stlt}  # "caf" / "cacnf" are added by modelling/fusion.py at package import

@@ -387,6 +387,21 @@ def attention_workspace_bytes(B: int, T: int, N: int, d: int, n_classes: int) ->
     return int(L.load().stlt_attention_workspace_bytes(B, T, N, d, n_classes))
 
 
+def embed_bwd_inputs(d_pre, box_w, score_w=None):
+    """K1's gradient wrt its inputs (stlt_embed_bwd_inputs; reference models.py:29-39): d_pre (..., d) -> (d_boxes (..., 4), d_scores (...) or
+    None without score_w)."""
+    lib = L.load()
+    _chk(d_pre, torch.float32, "d_pre"); _chk(box_w, torch.float32, "box_w")
+    if score_w is not None:
+        _chk(score_w, torch.float32, "score_w")
+    d = d_pre.shape[-1]
+    tok = d_pre.numel() // d
+    d_boxes = torch.empty(*d_pre.shape[:-1], 4, device=d_pre.device, dtype=torch.float32)
+    d_scores = torch.empty(*d_pre.shape[:-1], device=d_pre.device, dtype=torch.float32) if score_w is not None else None
+    L.check(lib.stlt_embed_bwd_inputs(_p(d_pre), _p(box_w), _p(score_w), tok, d, _p(d_boxes), _p(d_scores), _stream()), "stlt_embed_bwd_inputs")
+    return d_boxes, d_scores
+
+
 def prof_enable(on: bool):
     L.load().stlt_prof_enable(int(on))
 
@@ -879,7 +894,8 @@ class FfnBlockFn(torch.autograd.Function):
 
 
 class EmbedFn(torch.autograd.Function):
-    """K1 (CategoryBoxEmbeddings, models.py:29-39) under autograd: native forward keeping the pre-LayerNorm sum, native backward."""
+    """K1 (CategoryBoxEmbeddings, models.py:29-39) under autograd: native forward keeping the pre-LayerNorm sum, native backward —
+    parameter gradients, and the gradients wrt `boxes` / `scores` when they require grad (stlt_embed_bwd_inputs)."""
 
     @staticmethod
     def forward(ctx, categories, boxes, scores, cat_w, box_w, box_b, score_w, score_b, ln_w, ln_b, eps):
@@ -913,7 +929,16 @@ class EmbedFn(torch.autograd.Function):
         g_sb = torch.zeros(d, device=pre.device, dtype=torch.float32) if scores is not None else None
         L.check(lib.stlt_embed_bwd(_p(d_pre), _p(categories), _p(boxes), _p(scores), Cn, tok, d, _p(g_cat), _p(g_box_w), _p(g_box_b), _p(g_sw),
                                    _p(g_sb), sc.data_ptr(), sc.numel(), _stream()), "stlt_embed_bwd")
-        return None, None, None, g_cat, g_box_w, g_box_b, g_sw, g_sb, g_ln_w, g_ln_b, None
+        d_boxes = d_scores = None
+        want_scores = scores is not None and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_scores:
+            d_boxes = torch.empty_like(boxes)
+            d_scores = torch.empty_like(scores) if want_scores else None
+            L.check(lib.stlt_embed_bwd_inputs(_p(d_pre), _p(box_w), _p(score_w) if want_scores else None, tok, d, _p(d_boxes), _p(d_scores), _stream()),
+                    "stlt_embed_bwd_inputs")
+            if not ctx.needs_input_grad[1]:
+                d_boxes = None
+        return None, d_boxes, d_scores, g_cat, g_box_w, g_box_b, g_sw, g_sb, g_ln_w, g_ln_b, None
 
 
 class FramesEmbedFn(torch.autograd.Function):
