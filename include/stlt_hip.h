@@ -471,6 +471,20 @@ int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* wor
 int stlt_attn_probs_fwd(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh,
                         int per_head, float* probs, stlt_stream_t stream);
 
+/* The same for queries and keys that lie in different buffers and differ in number: stlt_attn_cross_fwd without its value half — what the
+ * nn.MultiheadAttention of the fusion models' CrossAttentionLayer (models.py:362-382, called at 411-419) returns with need_weights=True.
+ * q rows are ldq floats apart ((S*Lq) rows), k rows ldk floats apart ((S*Lk) rows); only the first H*dh columns of either are read.
+ * per_head == 0: probs (S, Lq, Lk);  per_head == 1: probs (S, H, Lq, Lk);  probs[s,(h,)i,j] = softmax_j( q_i·k_j/sqrt(dh) + M_ij ),
+ * M_ij = -inf if kpm[s*Lk + j] or (causal and j > i).  kpm: (S*Lk) bytes over the key tokens, never NULL (zeros for no mask); causal
+ * requires Lq == Lk.  Masked entries are written as exactly 0, a query row whose keys are all masked as zeros, every element of probs is
+ * written; query rows are not filtered by any mask.  The head average is summed head by head in registers in a fixed order (no atomics):
+ * the same bits on every run.
+ * 1 <= Lq, Lk <= 1024, 1 <= dh <= 256.  dh == 64 with Lk <= 64 (any Lq) runs on the MFMA kernel of csrc/attn_probs_cross.hip and needs q
+ * and k 16-byte aligned and ldq, ldk multiples of 4 (refused otherwise); everything else on its vector-ALU kernel, pointers and strides
+ * 4 bytes.  probs 4 bytes; kpm bytes.  Every bad argument is STLT_EINVAL and launches nothing. */
+int stlt_attn_probs_cross_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const uint8_t* kpm, int causal, int64_t S, int64_t Lq,
+                              int64_t Lk, int64_t H, int64_t dh, int per_head, float* probs, stlt_stream_t stream);
+
 /* bytes of scratch stlt_forward_attention needs for this shape (0 for an empty shape) */
 size_t stlt_attention_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes);
 
@@ -532,6 +546,37 @@ int stlt_caf_forward(const stlt_caf_params* p, const stlt_inputs* in, const floa
 int stlt_caf_forward_flags(const stlt_caf_params* p, const stlt_inputs* in, const float* appearance_features, void* workspace,
                            size_t workspace_bytes, int flags, float* logits_caf, float* logits_stlt, float* logits_resnet3d,
                            float* logits_ensemble, stlt_stream_t stream);
+
+/* ---- attention maps of the fusion models: the need_weights=True output of every nn.MultiheadAttention the forward above runs, which the
+ * reference's SelfAttentionLayer / CrossAttentionLayer discard with [0] (models.py:353-388), beside the layout branch's (models.py:46-55,
+ * 118-128) and the appearance encoder's (models.py:239-246).  A = app_tokens + 1 ---- */
+typedef struct {            /* every pointer nullable; head-averaged shapes, per_head inserts H before the last two dims */
+  float *spatial;              /* (n_spatial, B, T, N, N)   per_head: (n_spatial, B, T, H, N, N) — layout branch, as stlt_forward_attention */
+  float *temporal;             /* (n_temporal, B, T, T)     — layout branch, causal + frame padding */
+  float *appearance;           /* (n_app_layers, B, A, A)   — appearance encoder, no mask */
+  float *layout_to_appearance; /* (n_fusion, B, T, A)       cross_attn, queries = layout frames (models.py:411-414), no mask */
+  float *appearance_to_layout; /* (n_fusion, B, A, T)       cross_attn, queries = appearance tokens, keys masked by kpm_frames (415-419) */
+  float *fusion_layout;        /* (n_fusion, B, T, T)       layout_attn: causal + kpm_frames (421-425) */
+  float *fusion_appearance;    /* (n_fusion, 2, B, A, A)    [.,0] appearance_attn, [.,1] appearance_ffn (a SelfAttentionLayer, models.py:401) */
+} stlt_caf_attention_maps;
+/* bytes of scratch stlt_caf_forward_attention needs (the buffers of stlt_caf_forward: every block's Q and K already lie in them) */
+size_t stlt_caf_attention_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t feat_channels, int64_t app_tokens,
+                                          int64_t n_classes);
+/* stlt_caf_forward (models.py:446-483, 486-498, 520-549; LCF with n_fusion == 0: models.py:296-322) also writing the attention
+ * probabilities of every layer whose sink in `maps` is not NULL (maps == NULL: none).  One launch sequence serves both entry points: behind
+ * each attention core one stlt_attn_probs_fwd (self-attention: the layer's packed QKV) or stlt_attn_probs_cross_fwd (the two cross blocks:
+ * the projected queries, ldq = d, and the packed K/V, ldk = 2d, with the key-side mask the block uses) on the core's own buffers; a NULL
+ * sink skips that launch and changes nothing else.  Layer-major, each launch writes one contiguous block.  Masked entries are exactly 0;
+ * rows of padded frames hold what the reference computes for them.
+ * The layout branch runs the dense unfused schedule of stlt_forward_attention (the elision flags are ignored), so the logits equal
+ * stlt_caf_forward's to fp32 rounding, not bit for bit.  STLT_FLAG_SKIP_PADDING is refused (the maps are those of the padded schedule);
+ * so are per_head outside {0, 1}, a workspace below stlt_caf_attention_workspace_bytes, a requested map with more than 1024 keys and an
+ * output that is not 4-byte aligned — all STLT_EINVAL, nothing is launched by a refused call.
+ * Inference only.  No allocation, no synchronisation; every node of a capture is a kernel (replay: profiles/fusion_attention_bench.md §4).
+ * workspace: 256-byte aligned. */
+int stlt_caf_forward_attention(const stlt_caf_params* p, const stlt_inputs* in, const float* appearance_features, void* workspace,
+                               size_t workspace_bytes, int flags, int per_head, float* logits_caf, float* logits_stlt,
+                               float* logits_resnet3d, float* logits_ensemble, const stlt_caf_attention_maps* maps, stlt_stream_t stream);
 
 /* ---- R3D-50 video trunk (reference src/modelling/resnets3d.py:93-214, generate_model(50) minus avgpool / fc; models.py:198-228) ----
  * Internal activations are channels-last (NDHWC).  A Conv3d is an implicit GEMM on the f32 MFMA (csrc/r3d.hip): M = B·To·Ho·Wo
@@ -881,7 +926,7 @@ int stlt_eval_average_precision(const float* scores, const float* truths, int64_
 #define STLT_K_MISC 12         /* row gathers / scatters, column sums, ragged index, the head's small products */
 #define STLT_K_MHSA_FUSED 13    /* fused in-projection + causal attention core (stlt_mhsa_fused_fwd): temporal tower */
 #define STLT_K_MHSA_FUSED_SPATIAL 14  /* the same kernel's non-causal launches (spatial tower) */
-#define STLT_K_ATTN_PROBS 15    /* attention probabilities (stlt_attn_probs_fwd; one launch per layer of stlt_forward_attention) */
+#define STLT_K_ATTN_PROBS 15    /* attention probabilities (stlt_attn_probs_fwd, stlt_attn_probs_cross_fwd; one launch per layer of stlt_forward_attention / stlt_caf_forward_attention) */
 #define STLT_K_COUNT 16
 /* The switch is process-wide; the records (and both calls below) belong to the device that is CURRENT when they are made: a
  * process driving several GPUs collects once per device (with that device current) before it switches timing off, or the

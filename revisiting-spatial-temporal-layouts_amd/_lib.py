@@ -82,6 +82,12 @@ class CafParams(C.Structure):
                 ("layout_head", HeadParams), ("appearance_head", HeadParams)]
 
 
+class CafAttentionMaps(C.Structure):
+    """stlt_caf_attention_maps: one nullable sink per family of attention maps"""
+    _fields_ = [(n, _vp) for n in ("spatial", "temporal", "appearance", "layout_to_appearance", "appearance_to_layout", "fusion_layout",
+                                   "fusion_appearance")]
+
+
 class Inputs(C.Structure):
     _fields_ = [("B", C.c_int64), ("T", C.c_int64), ("N", C.c_int64)] + [
         (n, _vp) for n in ("categories", "boxes", "scores", "kpm_boxes", "frame_types", "kpm_frames", "lengths")] + [
@@ -192,6 +198,11 @@ SIGNATURES = {
     "stlt_attn_probs_fwd": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _vp, _vp]),
     "stlt_attention_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "stlt_forward_attention": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "stlt_attn_probs_cross_fwd": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                            _vp, _vp]),
+    "stlt_caf_attention_workspace_bytes": (C.c_size_t, [C.c_int64] * 7),
+    "stlt_caf_forward_attention": (C.c_int, [C.c_void_p, C.POINTER(Inputs), _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                             C.POINTER(CafAttentionMaps), _vp]),
     "stlt_caf_workspace_bytes": (C.c_size_t, [C.c_int64] * 7),
     "stlt_caf_forward": (C.c_int, [C.c_void_p, C.POINTER(Inputs), _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
     "stlt_caf_forward_flags": (C.c_int, [C.c_void_p, C.POINTER(Inputs), _vp, _vp, C.c_size_t, C.c_int, _vp, _vp, _vp, _vp, _vp]),

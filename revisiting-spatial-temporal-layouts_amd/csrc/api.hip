@@ -642,6 +642,23 @@ int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* work
   return backbone_impl(p, in, w, flags, out_btd, nullptr, s);
 }
 
+// for caf.hip (declared in common.h): the towers of stlt_forward_attention, the (B,T,d) state instead of the head
+int backbone_attention_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int per_head,
+                              float* attn_spatial, float* attn_temporal, float* out_btd, hipStream_t s) {
+  TRY(check_params(p, in, false));
+  if (!out_btd) return stlt_set_error(STLT_EINVAL, "attention backbone: out_btd is null");
+  WsBufs w;
+  TRY(ws_carve(p, in, 1, workspace, workspace_bytes, STLT_EWORKSPACE, "", &w));
+  StltGemmScratch gemm_scratch(w.sk, STLT_GEMM_SCRATCH_BYTES);
+  const float* cls_rows = nullptr;
+  int64_t cls_stride = 0;
+  TRY(spatial_tower(p, in, 0, w, LayerOpts{true, attn_spatial, per_head}, &cls_rows, &cls_stride, s));
+  float* tbuf = p->n_temporal > 0 ? w.x1 : out_btd;  // x1 is free: its last reader was the final norm2 above
+  TRY(launch_frames_embed(cls_rows, cls_stride, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, in->B, in->T, p->d,
+                          tbuf, s));
+  return temporal_tower(p, in, p->n_temporal, w, LayerOpts{true, attn_temporal, per_head}, tbuf, out_btd, s);
+}
+
 extern "C" {
 
 size_t stlt_workspace_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes) {
@@ -746,6 +763,11 @@ int stlt_forward_prefixes(const stlt_params* p, const stlt_inputs* in, void* wor
 int stlt_attn_probs_fwd(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh, int per_head, float* probs,
                         stlt_stream_t stream) {
   return launch_attn_probs(qkv, kpm, causal, S, L, H, dh, per_head, probs, (hipStream_t)stream);
+}
+
+int stlt_attn_probs_cross_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const uint8_t* kpm, int causal, int64_t S, int64_t Lq,
+                              int64_t Lk, int64_t H, int64_t dh, int per_head, float* probs, stlt_stream_t stream) {
+  return launch_attn_probs_cross(q, ldq, k, ldk, kpm, causal, S, Lq, Lk, H, dh, per_head, probs, (hipStream_t)stream);
 }
 
 // The dense schedule with every layer as the unfused pair, maps or no maps: the layer's packed QKV lies in the workspace, and the attention

@@ -352,6 +352,10 @@ int stlt_head(const stlt_head_params& h, const float* x, int64_t ldx, int64_t in
 // whole-path workspace (min_slots: rows per frame it holds at least; 1, or 2 for the per-prefix forward)
 int backbone_impl_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int flags,
                          float* out_btd, hipStream_t s);
+// ... and the dense unfused schedule of stlt_forward_attention into out_btd (B,T,d): every layer runs whole as the pair (in-projection,
+// attention core), attn_spatial / attn_temporal (either may be null) receive the layers' probabilities as that entry point lays them out
+int backbone_attention_public(const stlt_params* p, const stlt_inputs* in, void* workspace, size_t workspace_bytes, int per_head,
+                              float* attn_spatial, float* attn_temporal, float* out_btd, hipStream_t s);
 size_t stlt_ws_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int64_t n_classes, int64_t min_slots);
 int launch_frames_embed(const float* spatial, int64_t row_stride, const int64_t* frame_types, const float* pos_table,
                         const float* type_table, const float* ln_w, const float* ln_b, float eps, int64_t B, int64_t T,
@@ -372,6 +376,10 @@ int launch_prefix_zero_invalid(float* logits, const int64_t* lengths, int64_t B,
 // probs (S,L,L) averaged over the heads, or (S,H,L,L) with per_head; MFMA kernel for dh == 64 and L <= 64, vector ALU otherwise
 int launch_attn_probs(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh, int per_head, float* probs,
                       hipStream_t s);
+// attn_probs_cross.hip: the same for queries and keys in different buffers (include/stlt_hip.h: stlt_attn_probs_cross_fwd) — launch_attn_general's
+// probabilities: q rows ldq floats apart, k rows ldk floats apart, kpm (S*Lk) over the keys; probs (S,Lq,Lk), or (S,H,Lq,Lk) with per_head
+int launch_attn_probs_cross(const float* q, int64_t ldq, const float* k, int64_t ldk, const uint8_t* kpm, int causal, int64_t S, int64_t Lq,
+                            int64_t Lk, int64_t H, int64_t dh, int per_head, float* probs, hipStream_t s);
 
 // ragged layout (ragged.hip): index of the real tokens / frames of a padded batch, see RaggedIndex
 struct RaggedIndex {

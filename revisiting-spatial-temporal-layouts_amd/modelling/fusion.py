@@ -254,6 +254,22 @@ class CrossAttentionFusionBackbone(nn.Module):
             # composition runs (its Functions just execute their forward kernels under no_grad)
             return self.run_train(batch, fusion_head, layout_head, appearance_head)
         lib = L.load()
+        p, inp, keep, feats, (B, T, N, Cc, S, K) = self._native_args(batch, fusion_head, layout_head, appearance_head)
+        device = feats.device
+        nbytes = int(lib.stlt_caf_workspace_bytes(B, T, N, self.config.hidden_size, Cc, S, K))
+        ws = self._ws.get(nbytes, device)
+        outs = [torch.empty(B, K, device=device, dtype=torch.float32) for _ in range(4 if layout_head is not None else 1)]
+        ptrs = [o.data_ptr() for o in outs] + [None] * (4 - len(outs))
+        with torch.cuda.device(device):
+            # layout_branch.skip_padding (as on a stand-alone StltBackbone): the layout branch on the real tokens / frames only
+            flags = L.FLAG_SKIP_PADDING if self.layout_branch.skip_padding else 0
+            L.check(lib.stlt_caf_forward_flags(C.byref(p), C.byref(inp), feats.data_ptr(), ws.data_ptr(), ws.numel(), flags, ptrs[0],
+                                               ptrs[1], ptrs[2], ptrs[3], torch.cuda.current_stream().cuda_stream), "stlt_caf_forward")
+        return outs
+
+    def _native_args(self, batch, fusion_head, layout_head, appearance_head):
+        """Marshal a batch and the parameters for the whole-path native calls (stlt_caf_forward_flags, stlt_caf_forward_attention):
+        -> (stlt_caf_params, stlt_inputs, keep-alive, feature map, (B, T, N, feature channels, appearance tokens, classes))"""
         inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
         feats = self._features(batch)
         ab = self.appearance_branch
@@ -261,8 +277,6 @@ class CrossAttentionFusionBackbone(nn.Module):
         S = ab.pos_embed.shape[0] - 1
         if feats.shape[0] != B or feats.shape[1] != Cc or feats[0, 0].numel() != S:
             raise L.StltHipError(f"appearance_features must be (B, {Cc}, ...{S} positions), got {tuple(feats.shape)}")
-        device = feats.device
-        cfg = self.config
         K = fusion_head.fc2.weight.shape[0]
         lay, sp, tp = self.layout_branch._build_struct(None, _dev_ptr)
         lay.n_classes = K
@@ -276,16 +290,40 @@ class CrossAttentionFusionBackbone(nn.Module):
         p.n_app_layers, p.app_layers = len(ab.transformer.layers), app
         p.n_fusion, p.fusion = len(self.mm_fusion), fus
         p.fusion_head, p.layout_head, p.appearance_head = _head_struct(fusion_head), _head_struct(layout_head), _head_struct(appearance_head)
-        nbytes = int(lib.stlt_caf_workspace_bytes(B, T, N, cfg.hidden_size, Cc, S, K))
-        ws = self._ws.get(nbytes, device)
+        return p, inp, (keep, sp, tp, app, fus), feats, (B, T, N, Cc, S, K)
+
+    MAP_NAMES = ("spatial_attention", "temporal_attention", "appearance_attention", "layout_to_appearance", "appearance_to_layout",
+                 "fusion_layout_attention", "fusion_appearance_attention")
+
+    def run_attention(self, batch: Dict[str, torch.Tensor], per_head: bool, fusion_head, layout_head=None, appearance_head=None):
+        """The native forward with every attention map (include/stlt_hip.h: stlt_caf_forward_attention), beside run().
+        -> (logits as run() returns them, {map name: tensor} in the order of MAP_NAMES).  Inference only, dense padded schedule."""
+        if self.training and self.config.hidden_dropout_prob > 0:
+            raise L.StltHipError("forward_attention is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if self.layout_branch.skip_padding:
+            raise L.StltHipError("forward_attention runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set layout_branch.skip_padding = False")
+        if not batch["categories"].is_cuda:
+            raise L.StltHipError("forward_attention runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        lib = L.load()
+        p, inp, keep, feats, (B, T, N, Cc, S, K) = self._native_args(batch, fusion_head, layout_head, appearance_head)
+        device = feats.device
+        cfg = self.config
+        H, A = cfg.num_attention_heads, S + 1
+        n_sp, n_tp = len(self.layout_branch.frames_embeddings.layout_embedding.transformer.layers), len(self.layout_branch.transformer.layers)
+        n_app, n_fu = len(self.appearance_branch.transformer.layers), len(self.mm_fusion)
+        hs = (H,) if per_head else ()
+        shapes = ((n_sp, B, T, *hs, N, N), (n_tp, B, *hs, T, T), (n_app, B, *hs, A, A), (n_fu, B, *hs, T, A), (n_fu, B, *hs, A, T),
+                  (n_fu, B, *hs, T, T), (n_fu, 2, B, *hs, A, A))
+        maps = [torch.empty(sh, device=device, dtype=torch.float32) for sh in shapes]
+        sinks = L.CafAttentionMaps(*[(m.data_ptr() if m.numel() else None) for m in maps])
+        ws = self._ws.get(int(lib.stlt_caf_attention_workspace_bytes(B, T, N, cfg.hidden_size, Cc, S, K)), device)
         outs = [torch.empty(B, K, device=device, dtype=torch.float32) for _ in range(4 if layout_head is not None else 1)]
         ptrs = [o.data_ptr() for o in outs] + [None] * (4 - len(outs))
         with torch.cuda.device(device):
-            # layout_branch.skip_padding (as on a stand-alone StltBackbone): the layout branch on the real tokens / frames only
-            flags = L.FLAG_SKIP_PADDING if self.layout_branch.skip_padding else 0
-            L.check(lib.stlt_caf_forward_flags(C.byref(p), C.byref(inp), feats.data_ptr(), ws.data_ptr(), ws.numel(), flags, ptrs[0],
-                                               ptrs[1], ptrs[2], ptrs[3], torch.cuda.current_stream().cuda_stream), "stlt_caf_forward")
-        return outs
+            L.check(lib.stlt_caf_forward_attention(C.byref(p), C.byref(inp), feats.data_ptr(), ws.data_ptr(), ws.numel(), 0, int(bool(per_head)), ptrs[0],
+                                                   ptrs[1], ptrs[2], ptrs[3], C.byref(sinks), torch.cuda.current_stream().cuda_stream),
+                    "stlt_caf_forward_attention")
+        return outs, dict(zip(self.MAP_NAMES, maps))
 
 
 class CrossAttentionFusion(nn.Module):
@@ -300,6 +338,23 @@ class CrossAttentionFusion(nn.Module):
     def forward(self, batch: Dict[str, torch.Tensor]):
         (caf,) = self.caf_backbone.run(batch, self.classifier)
         return {"caf": caf}
+
+    @torch.no_grad()
+    def forward_attention(self, batch: Dict[str, torch.Tensor], per_head: bool = False) -> Dict[str, torch.Tensor]:
+        """The model's logits and the attention probabilities of every attention layer in one native pass (include/stlt_hip.h:
+        stlt_caf_forward_attention): what the reference's nn.MultiheadAttention modules return with need_weights=True and its layers throw away.
+        -> the logits under `logit_names`, and float32 maps averaged over the heads (A = appearance tokens + 1, token 0 the CLS token):
+          spatial_attention (n_spatial,B,T,N,N), temporal_attention (n_temporal,B,T,T): the layout branch, as Stlt.forward_attention;
+          appearance_attention (n_appearance,B,A,A): the appearance encoder;
+          layout_to_appearance (n_fusion,B,T,A): which appearance token each layout frame attends to (models.py:411-414);
+          appearance_to_layout (n_fusion,B,A,T): which layout frame each appearance token attends to, padded frames masked (415-419);
+          fusion_layout_attention (n_fusion,B,T,T): layout_attn, causal + padding; fusion_appearance_attention (n_fusion,2,B,A,A):
+          [:, 0] appearance_attn, [:, 1] appearance_ffn (a self-attention layer in the reference).
+        With `per_head` the head axis H is inserted before the last two dimensions.  Index [..., i, j] is how much query i attends to key j;
+        masked keys are exactly 0.  `layout_to_appearance[-1][b, lengths[b]-1]` is what clip b's read-out frame attends to in the video.
+        Inference only, dense padded schedule: the logits equal `forward`'s to fp32 rounding, not bit for bit."""
+        (caf,), maps = self.caf_backbone.run_attention(batch, per_head, self.classifier)
+        return {"caf": caf, **maps}
 
 
 class CrossAttentionCentralNetFusion(nn.Module):
@@ -317,6 +372,12 @@ class CrossAttentionCentralNetFusion(nn.Module):
     def forward(self, batch: Dict[str, torch.Tensor]):
         caf, stlt, res, ens = self.backbone.run(batch, self.fusion_classifier, self.layout_classifier, self.appearance_classifier)
         return {"stlt": stlt, "resnet3d": res, "caf": caf, "ensemble": ens}
+
+    @torch.no_grad()
+    def forward_attention(self, batch: Dict[str, torch.Tensor], per_head: bool = False) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_attention, with this model's four logits (include/stlt_hip.h: stlt_caf_forward_attention)."""
+        (caf, stlt, res, ens), maps = self.backbone.run_attention(batch, per_head, self.fusion_classifier, self.layout_classifier, self.appearance_classifier)
+        return {"stlt": stlt, "resnet3d": res, "caf": caf, "ensemble": ens, **maps}
 
 
 class LateConcatenationFusion(nn.Module):
@@ -362,6 +423,12 @@ class LateConcatenationFusion(nn.Module):
     def forward(self, batch: Dict[str, torch.Tensor]):
         (lcf,) = self._runner.run(batch, self.classifier)
         return {"lcf": lcf}
+
+    @torch.no_grad()
+    def forward_attention(self, batch: Dict[str, torch.Tensor], per_head: bool = False) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_attention; LCF has no cross-modal layers, so its four fusion maps have a leading dimension of 0."""
+        (lcf,), maps = self._runner.run_attention(batch, per_head, self.classifier)
+        return {"lcf": lcf, **maps}
 
 
 from .models import models_factory  # noqa: E402

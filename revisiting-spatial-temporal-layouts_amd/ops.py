@@ -287,6 +287,39 @@ def attn_probs(qkv: torch.Tensor, kpm: torch.Tensor, causal: bool, num_heads: in
     return probs
 
 
+def _rows_view(t: torch.Tensor, name: str):
+    """(S, L, d) float32 GPU tensor whose rows may be strided (a column slice of a wider packed buffer): -> its row stride in floats"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise L.StltHipError(f"{name}: expected a GPU tensor (the STLT hot path has no CPU fallback), got {getattr(t, 'device', type(t))}")
+    if t.dtype != torch.float32 or t.dim() != 3:
+        raise L.StltHipError(f"{name}: expected a float32 (S, L, d) tensor, got {t.dtype} {tuple(t.shape)}")
+    S, Ln, d = t.shape
+    ld = t.stride(1) if Ln > 1 else (t.stride(0) if S > 1 else d)
+    if t.stride(2) != 1 or ld < d or (Ln > 1 and S > 1 and t.stride(0) != Ln * ld):
+        raise L.StltHipError(f"{name}: rows must be unit-stride in the last dimension and evenly spaced (strides {t.stride()})")
+    return ld
+
+
+def attn_probs_cross(q: torch.Tensor, k: torch.Tensor, kpm: Optional[torch.Tensor], causal: bool, num_heads: int, per_head: bool = False):
+    """Attention probabilities of the cross-attention core (include/stlt_hip.h: stlt_attn_probs_cross_fwd): q (S,Lq,d) projected queries,
+    k (S,Lk,d) projected keys — either may be a view with a row stride, e.g. `kv[..., :d]` of a packed (S,Lk,2d) buffer — kpm (S,Lk)
+    bool/uint8 over the keys (True = masked) or None.  -> probs (S,Lq,Lk) averaged over the heads, or (S,H,Lq,Lk) with per_head.  Masked
+    entries are exactly 0; causal needs Lq == Lk; Lq, Lk <= 1024."""
+    lib = L.load()
+    ldq, ldk = _rows_view(q, "q"), _rows_view(k, "k")
+    S, Lq, d = q.shape
+    Lk = k.shape[1]
+    assert k.shape[0] == S and k.shape[2] == d and d % num_heads == 0
+    if kpm is None:
+        kpm = torch.zeros(S, Lk, dtype=torch.uint8, device=q.device)
+    kpm = _mask_u8(kpm, "kpm")
+    assert tuple(kpm.shape) == (S, Lk)
+    probs = torch.empty((S, num_heads, Lq, Lk) if per_head else (S, Lq, Lk), device=q.device, dtype=torch.float32)
+    L.check(lib.stlt_attn_probs_cross_fwd(_p(q), ldq, _p(k), ldk, _p(kpm), int(bool(causal)), S, Lq, Lk, num_heads, d // num_heads, int(bool(per_head)),
+                                          _p(probs), _stream()), "stlt_attn_probs_cross_fwd")
+    return probs
+
+
 def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
     """Probe attention of the per-prefix forward (include/stlt_hip.h: stlt_attn_prefix_probe_fwd).  qkv_frames, qkv_probes: (S,T,3d) packed
     [q;k;v] rows of the frame and of the probe stream, kpm (S,T) bool/uint8 (True = frame masked as a key).  Probe (s,t) attends to the frame

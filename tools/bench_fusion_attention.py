@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""Fusion-model attention-map benchmark (profiles/fusion_attention_bench.md).  Seeded synthetic inputs, closed-form weights; one JSON line
+per case.
+
+  --build   (no GPU needed) build the A/B variant of the library whose cross-probabilities launcher sends every shape to the vector-ALU
+            kernel (csrc/attn_probs_cross.hip with -DSTLT_PROBS_CROSS_NO_MFMA) into build/variants/; run it before the measurement.
+
+1. The cross-probabilities launch (stlt_attn_probs_cross_fwd, ops.attn_probs_cross) against the cross-attention core (stlt_attn_cross_fwd,
+   ops.attn_cross) on the same buffers — queries (S,Lq,d), packed keys / values (S,Lk,2d), 12 heads of 64 channels, about 30 % of the
+   keys masked — at the fusion models' shapes in both directions, (Lq, Lk) = (32,33), (33,32), (17,33), (33,17), (64,33), (33,64), at 64
+   and 1024 clips:
+
+  core_us, probs_us (head-averaged), probs_ph_us (per head), probs_over_core, units (single-wave work items of the MFMA launch),
+  probs_hbm_frac (q and k read, probs written, the mask, at 8 TB/s over probs_us),
+  generic_us / generic_ph_us: the same launch from the variant library (vector-ALU kernel), when it has been built; mfma_over_generic.
+
+2. forward_attention against the model's ordinary forward, CACNF at cfg2's layout shapes (d = 768, 12 heads, T = 32, N = 7, 33 appearance
+   tokens, 4 + 4 appearance / fusion layers), 64 and 1024 clips: forward_ms, attention_ms, ratio, attention_per_head_ms.
+
+Every figure is the median over --repeats windows of device-event time around --iters back-to-back calls, after --warmup calls of the same
+shape; the windows of the sides of a comparison alternate.  Needs a GPU: there is no fallback."""
+import argparse
+import ctypes as C
+import importlib
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "revisiting-spatial-temporal-layouts_amd"
+HBM_BYTES_PER_S = 8e12
+SHAPES = ((32, 33), (33, 32), (17, 33), (33, 17), (64, 33), (33, 64))
+CLIPS = (64, 1024)
+VARIANT = os.path.join(ROOT, "build", "variants", "libstlt_hip_probs_cross_generic.so")
+
+
+def alternating_ms(fns, torch, warmup, iters, repeats):
+    """{name: median ms per call}: the windows of the functions alternate, so drift of the machine hits them alike"""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            out[k].append(e0.elapsed_time(e1) / iters)
+    return {k: statistics.median(v) for k, v in out.items()}, {k: [round(min(v), 4), round(max(v), 4)] for k, v in out.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--build", action="store_true")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--skip-model", action="store_true")
+    a = ap.parse_args()
+    if a.build:
+        builder = importlib.import_module(PKG + ".build")
+        print(builder.variant("probs_cross_generic", {"attn_probs_cross.hip": ["-DSTLT_PROBS_CROSS_NO_MFMA=1"]}))
+        return
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_fusion_attention.py needs a GPU")
+    pkg = importlib.import_module(PKG)
+    generic = None
+    if os.path.exists(VARIANT):
+        generic = C.CDLL(VARIANT).stlt_attn_probs_cross_fwd
+        generic.restype, generic.argtypes = pkg._lib.SIGNATURES["stlt_attn_probs_cross_fwd"]
+    H, dh = 12, 64
+    d = H * dh
+    for Lq, Lk in SHAPES:
+        for S in CLIPS:
+            g = torch.Generator().manual_seed(1)
+            q = ((torch.rand(S, Lq, d, generator=g) * 2 - 1) * 1.5).to("cuda")
+            kv = ((torch.rand(S, Lk, 2 * d, generator=g) * 2 - 1) * 1.5).to("cuda")
+            kpm = torch.rand(S, Lk, generator=g) < 0.3
+            kpm[:, 0] = False
+            kpm = kpm.to(torch.uint8).to("cuda")
+            k = kv[..., :d]
+            fns = {"core": lambda: pkg.ops.attn_cross(q, kv, kpm, H), "probs": lambda: pkg.ops.attn_probs_cross(q, k, kpm, False, H),
+                   "probs_ph": lambda: pkg.ops.attn_probs_cross(q, k, kpm, False, H, per_head=True)}
+            if generic is not None:
+                out = {ph: torch.empty((S, H, Lq, Lk) if ph else (S, Lq, Lk), device="cuda") for ph in (0, 1)}
+
+                def gen(ph):
+                    rc = generic(q.data_ptr(), d, kv.data_ptr(), 2 * d, kpm.data_ptr(), 0, S, Lq, Lk, H, dh, ph, out[ph].data_ptr(), torch.cuda.current_stream().cuda_stream)
+                    assert rc == 0
+
+                fns["generic"], fns["generic_ph"] = (lambda: gen(0)), (lambda: gen(1))
+            med, rng = alternating_ms(fns, torch, a.warmup, a.iters, a.repeats)
+            agree = None
+            if generic is not None:  # the two kernels on the same data
+                gen(0)
+                agree = (out[0] - pkg.ops.attn_probs_cross(q, k, kpm, False, H)).abs().max().item()
+            qk = 4.0 * S * (Lq + Lk) * d + S * Lk
+            bytes_avg, bytes_ph = qk + 4.0 * S * Lq * Lk, qk + 4.0 * S * Lq * Lk * H
+            rec = dict(part="kernel", Lq=Lq, Lk=Lk, clips=S, H=H, dh=dh, units=S * ((Lq + 15) // 16), key_blocks=(Lk + 15) // 16,
+                       core_us=round(med["core"] * 1e3, 2), probs_us=round(med["probs"] * 1e3, 2), probs_ph_us=round(med["probs_ph"] * 1e3, 2),
+                       probs_over_core=round(med["probs"] / med["core"], 3), probs_ph_over_core=round(med["probs_ph"] / med["core"], 3),
+                       probs_bytes=int(bytes_avg), probs_hbm_frac=round(bytes_avg / HBM_BYTES_PER_S * 1e3 / med["probs"], 3),
+                       probs_ph_bytes=int(bytes_ph), probs_ph_hbm_frac=round(bytes_ph / HBM_BYTES_PER_S * 1e3 / med["probs_ph"], 3))
+            if generic is not None:
+                rec.update(generic_us=round(med["generic"] * 1e3, 2), generic_ph_us=round(med["generic_ph"] * 1e3, 2),
+                           mfma_over_generic=round(med["probs"] / med["generic"], 3), mfma_over_generic_ph=round(med["probs_ph"] / med["generic_ph"], 3),
+                           mfma_vs_generic_max_abs=agree)
+            rec.update(ranges_ms=rng, device=torch.cuda.get_device_name(0))
+            print(json.dumps(rec), flush=True)
+            del q, kv, kpm, k
+    if a.skip_model:
+        return
+    c = pkg.synth.CONFIGS["cfg2"]
+    m = pkg.CrossAttentionCentralNetFusion(pkg.MultimodalModelConfig(**dict(pkg.synth.model_kwargs("cfg2"), appearance_num_frames=32)))
+    m.load_state_dict(pkg.synth.make_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed=1234))
+    m = m.train(False).to("cuda")
+    for B in CLIPS:
+        batch = pkg.synth.make_batch(B, c["T"], c["N"], dataset=c["dataset"], seed=3)
+        batch["appearance_features"] = pkg.synth.make_appearance_features(B, seed=4)
+        batch = {k: v.to("cuda") for k, v in batch.items()}
+        with torch.no_grad():
+            fns = {"forward": lambda: m(batch), "attention": lambda: m.forward_attention(batch), "attention_ph": lambda: m.forward_attention(batch, per_head=True)}
+            med, rng = alternating_ms(fns, torch, max(2, a.warmup // 2), max(2, a.iters // (5 if B == 64 else 25)), a.repeats)
+            out, ref = m.forward_attention(batch), m(batch)
+            err = max((out[k] - ref[k]).abs().max().item() for k in ref)
+        print(json.dumps(dict(part="model", model="cacnf", config="cfg2", clips=B, forward_ms=round(med["forward"], 4), attention_ms=round(med["attention"], 4),
+                              ratio=round(med["attention"] / med["forward"], 3), attention_per_head_ms=round(med["attention_ph"], 4),
+                              ratio_per_head=round(med["attention_ph"] / med["forward"], 3), ranges_ms=rng, logits_vs_forward_max_abs=err,
+                              device=torch.cuda.get_device_name(0))), flush=True)
+        del batch
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
