@@ -60,19 +60,17 @@ static Tape tape_layout(char* base, int64_t B, int64_t T, int64_t N, int64_t d, 
 // rows) so that each one's row padding stays zero; split-K slabs; reduction scratch.
 // The output gradients of a layer's four Linears (df, du, da, dqkv) are the operands of its weight-gradient products, which run on
 // a second stream beside the NEXT layer's dX chain: two sets per tower, used by alternate layers (GradBufs).
-struct GradBufs { float *B, *D, *E, *Q, *H; };
+struct GradBufs { float *B, *D, *E, *Q, *H; };  // (rows,d) x3, (rows,3d), (rows,4d)
 constexpr int DW_EXTRA_SETS = 6;            // + the tower's own set + the second set = 8 layers per grouped launch
+// One tower's buffers: A carries the gradient down the dX chain, C is chain-only scratch (both (rows,d)), sets[0..n_sets-1] are its operand sets.
+// The temporal tower with few rows (<= STLT_DW_GROUP_MAX_ROWS; beyond it the sets are large) has eight, so that the weight gradients of up to
+// eight layers run as ONE grouped launch (32 products) instead of one launch per layer.
+struct TowerScratch { float *A, *C; GradBufs sets[2 + DW_EXTRA_SETS]; int n_sets; };
 struct Scratch {
-  float *sA, *sB, *sC, *sD, *sE, *sQKV, *sH;  // spatial: (tokp,d) x5, (tokp,3d), (tokp,4d)
-  float *tA, *tB, *tC, *tD, *tE, *tQKV, *tH;  // temporal
-  GradBufs s2, t2;                  // the second sets
-  GradBufs tx[DW_EXTRA_SETS];       // temporal tower, few rows (<= STLT_DW_GROUP_MAX_ROWS; beyond it the sets are large): more sets, so that the weight gradients of up to
-  int n_tx;                         //   eight layers run as ONE grouped launch (32 products) instead of one launch per layer
+  TowerScratch sp, tp;              // spatial (tokp rows), temporal (btp rows)
   float* sk2;                       // stream-K partial tiles of the second stream's launches
   float *hA, *hB;                   // head: (bp,d) x2
-  float* slabs;
-  float* red;
-  float* sk;
+  float *slabs, *red, *sk;
   size_t slab_floats, bytes;
   float* red_pool;                  // chunks of `red_floats` for the sweep's partial rows while their reductions are deferred (StltReduceDefer)
   size_t red_floats, red_pool_floats;
@@ -94,8 +92,13 @@ static Scratch scratch_layout(char* base, int64_t B, int64_t T, int64_t N, int64
   const int64_t tokp = up32(B * T * N), btp = up32(B * T), bp = up32(B);
   size_t off = 0;
   auto take = [&](int64_t floats) { float* p = base ? (float*)(base + off) : nullptr; off = stlt_align256(off + (size_t)floats * sizeof(float)); return p; };
-  s.sA = take(tokp * d); s.sB = take(tokp * d); s.sC = take(tokp * d); s.sD = take(tokp * d); s.sE = take(tokp * d); s.sQKV = take(tokp * 3 * d); s.sH = take(tokp * 4 * d);
-  s.tA = take(btp * d); s.tB = take(btp * d); s.tC = take(btp * d); s.tD = take(btp * d); s.tE = take(btp * d); s.tQKV = take(btp * 3 * d); s.tH = take(btp * 4 * d);
+  auto take_set = [&](int64_t rows) { return GradBufs{take(rows * d), take(rows * d), take(rows * d), take(rows * 3 * d), take(rows * 4 * d)}; };
+  for (TowerScratch* t : {&s.sp, &s.tp}) {  // A, B, C, D, E, Q, H
+    const int64_t rows = t == &s.sp ? tokp : btp;
+    GradBufs& g = t->sets[0];
+    t->A = take(rows * d); g.B = take(rows * d); t->C = take(rows * d); g.D = take(rows * d); g.E = take(rows * d); g.Q = take(rows * 3 * d); g.H = take(rows * 4 * d);
+    t->n_sets = 1;
+  }
   s.hA = take(bp * d); s.hB = take(bp * d);
   s.slab_floats = (size_t)MAX_SPLIT * 4 * d * d;
   s.slabs = take((int64_t)s.slab_floats);
@@ -108,15 +111,14 @@ static Scratch scratch_layout(char* base, int64_t B, int64_t T, int64_t N, int64
   s.red = take(red);
   s.red_floats = (size_t)red;
   s.sk = take((int64_t)(STLT_GEMM_SCRATCH_BYTES / sizeof(float)));
-  s.t2 = GradBufs{take(btp * d), take(btp * d), take(btp * d), take(btp * 3 * d), take(btp * 4 * d)};
-  s.n_tx = btp <= STLT_DW_GROUP_MAX_ROWS ? DW_EXTRA_SETS : 0;
-  for (int i = 0; i < s.n_tx; ++i) s.tx[i] = GradBufs{take(btp * d), take(btp * d), take(btp * d), take(btp * 3 * d), take(btp * 4 * d)};
+  s.tp.n_sets = btp <= STLT_DW_GROUP_MAX_ROWS ? 2 + DW_EXTRA_SETS : 2;
+  for (int i = 1; i < s.tp.n_sets; ++i) s.tp.sets[i] = take_set(btp);
   // ---- optional parts
   s.red_pool_floats = (size_t)red * 24 < ((size_t)64 << 20) ? (size_t)red * 24 : ((size_t)64 << 20);  // <= 256 MB
   if (s.red_pool_floats < (size_t)red || !defer_wanted()) s.red_pool_floats = 0;  // a chunk would not fit, or no deferral
   s.red_pool = s.red_pool_floats ? take((int64_t)s.red_pool_floats) : nullptr;
-  const bool side = dw_side_wanted();
-  s.s2 = side ? GradBufs{take(tokp * d), take(tokp * d), take(tokp * d), take(tokp * 3 * d), take(tokp * 4 * d)} : GradBufs{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const bool side = dw_side_wanted();  // one stream: a layer's products are flushed before the next layer rewrites the set
+  if (side) s.sp.sets[s.sp.n_sets++] = take_set(tokp);
   s.sk2 = side ? take((int64_t)(STLT_GEMM_SCRATCH_BYTES / sizeof(float))) : nullptr;
   s.bytes = off;
   return s;
@@ -198,16 +200,22 @@ struct DwSideHold {
 
 // The weight-gradient launches of one tower.  Layers take the operand-buffer sets in turn; the products of `group_layers` consecutive
 // layers are collected and flushed as one grouped launch — on the side stream when it is on (behind an event of the chain), else on the
-// caller's stream.  A set is rewritten only after the flush that read it has finished.
+// caller's stream.  A set is rewritten only after the flush that read it has finished.  With two sets a tower flushes per layer; with the temporal
+// tower's eight it collects up to eight layers (32 products) per grouped launch (STLT_TRAIN_DW_GROUP_LAYERS=1: two sets, per layer — A/B runs).
 struct DwQueue {
-  DwSide* side = nullptr;
-  GradBufs sets[2 + DW_EXTRA_SETS];
-  int n_sets = 1, group_layers = 1;
+  DwSide* side;
+  const GradBufs* sets;  // the tower's (TowerScratch)
+  int n_sets, group_layers = 1;
   StltWeightGradItem items[STLT_GEMM_GROUP_MAX];
   int n_items = 0, layers_in_chunk = 0, layer_no = 0;
   int set_flush[2 + DW_EXTRA_SETS];  // parity of the side-stream flush still reading the set, -1 = none
   int chunk_sets[2 + DW_EXTRA_SETS];  // sets of the layers collected since the last flush
-  DwQueue() { for (int& f : set_flush) f = -1; }
+  DwQueue(DwSide* sd, const TowerScratch& ts) : side(sd), sets(ts.sets), n_sets(ts.n_sets) {
+    static const int group_env = [] { const char* e = getenv("STLT_TRAIN_DW_GROUP_LAYERS"); return e ? atoi(e) : 8; }();
+    if (n_sets > 2 && group_env > 1) group_layers = group_env < n_sets ? group_env : n_sets;
+    else if (n_sets > 2) n_sets = 2;
+    for (int& f : set_flush) f = -1;
+  }
 };
 static int dwq_wait_parity(DwQueue& q, int par, hipStream_t s) {
   TRY(dw_side_wait(q.side, par, s));
@@ -220,7 +228,6 @@ static int dwq_begin_layer(DwQueue& q, hipStream_t s, GradBufs& out, int& set_id
   out = q.sets[set_idx];
   return 0;
 }
-static int dwq_flush(DwQueue& q, const Scratch& sc, hipStream_t s);
 
 static int n_cu_cached() { return stlt_device_cus(); }
 
@@ -265,52 +272,6 @@ static int weight_grad_all(const StltWeightGradItem* items, int n, const Scratch
   return 0;
 }
 
-// the two half-blocks of an encoder layer as the shared training half-blocks take them (common.h)
-static stlt_ffn_block_params ffn_half(const stlt_layer_params& l) { return {l.lin1_w, l.lin1_b, l.lin2_w, l.lin2_b, l.norm2_w, l.norm2_b}; }
-static stlt_attn_block_params attn_half(const stlt_layer_params& l) { return {l.in_proj_w, l.in_proj_b, l.out_proj_w, l.out_proj_b, l.norm1_w, l.norm1_b}; }
-
-// backward of one encoder layer.  dy: gradient wrt the layer output (M,d) in bufA; on return bufA holds the gradient
-// wrt the layer input.  bufB / bufC / bufD / bufE (M,d), bufQ (M,3d), bufH (M,4d) are scratch with zero row padding.
-// The four output gradients of the layer's Linears stay alive until the end of the layer, where their weight gradients run as one
-// grouped launch: df in bufD / da in bufE (dropout off: df in bufB, the residual-path gradient — StltHalfBwd::branch), du in bufH, dqkv in bufQ.
-static int layer_backward(const stlt_layer_params& lp, const stlt_layer_params* g, const LayerTape& t, int64_t d, int64_t H,
-                          int64_t M, int64_t Mp, int64_t S, int64_t L, const uint8_t* kpm, int causal, float* bufA, float* bufB,
-                          float* bufC, float* bufD, float* bufE, float* bufQ, float* bufH, const Scratch& sc, StltDrop dr, uint32_t site0,
-                          hipStream_t s, const AttnBwdRagged* rg = nullptr, DwQueue* q = nullptr) {
-  const stlt_layer_params gl = g ? *g : stlt_layer_params{};  // null members are skipped
-  // with a queue, the layer takes the next set of operand buffers (waiting for the flush that still reads it, if any) and leaves its
-  // four weight-gradient products with the queue
-  int set_idx = 0;
-  if (q) {
-    GradBufs gb;
-    TRY(dwq_begin_layer(*q, s, gb, set_idx));
-    bufB = gb.B; bufD = gb.D; bufE = gb.E; bufQ = gb.Q; bufH = gb.H;
-  }
-  StltGemmWgCap chain_cap(q && q->side && q->side->on ? dx_chain_wg_cap() : 0);
-  // y = LN2(x1 + drop(f)), f = h·W2ᵀ + b2, h = drop(gelu(u)), u = x1·W1ᵀ + b1: bufB = ds2, df, bufH = du, bufC = dx1 = du·W1 + ds2
-  const StltHalfBwd ffn{bufB, bufD, bufH, bufC, sc.rs, sc.sk ? sc.slabs : nullptr, sc.slab_floats};
-  TRY(stlt_ffn_half_bwd_train(ffn_half(lp), ffn_half(gl), STLT_ACT_GELU, bufA, t.x1, t.u, t.h, t.f, 1e-5f, M, d, dr, dr, site0 + 2, nullptr, ffn, s));
-  // x1 = LN1(x + drop(a)), a = ctx·Woᵀ + bo: ds1 (in bufB when dropout is on: its ds2 is dead by then), da in bufE, bufC = dctx
-  const StltHalfBwd att{dr.thr ? bufB : bufE, bufE, nullptr, bufC, sc.rs, ffn.wt, ffn.wt_floats};
-  TRY(stlt_attn_half_bwd_train(attn_half(lp), attn_half(gl), bufC, t.x, t.a, 1e-5f, M, d, dr, site0 + 1, nullptr, att, s));
-  // ctx = attention(qkv) with dropout on the probabilities
-  TRY(launch_attn_bwd(t.qkv, bufC, kpm, causal, S, L, H, d / H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), rg));  // bufQ = dqkv; in_proj_b += colsum(dqkv)
-  // qkv = x·Winᵀ + bin
-  TRY(dx_product(bufQ, 3 * d, lp.in_proj_w, 3 * d, d, att.ds, d, bufA, d, M, sc, s));  // bufA = dx = dqkv·Win + ds1
-  // the four weight gradients (off the dX chain): one grouped launch
-  const StltWeightGradItem items[4] = {{ffn.branch(dr), d, t.h, 4 * d, Mp, stlt_grad(gl.lin2_w)},
-                                       {bufH, 4 * d, t.x1, d, Mp, stlt_grad(gl.lin1_w)},
-                                       {att.branch(dr), d, t.ctx, d, Mp, stlt_grad(gl.out_proj_w)},
-                                       {bufQ, 3 * d, t.x, d, Mp, stlt_grad(gl.in_proj_w)}};
-  if (q) {
-    for (int i = 0; i < 4; ++i) q->items[q->n_items++] = items[i];
-    q->chunk_sets[q->layers_in_chunk++] = set_idx;
-    if (q->layers_in_chunk >= q->group_layers || q->n_items + 4 > STLT_GEMM_GROUP_MAX) return dwq_flush(*q, sc, s);
-    return 0;
-  }
-  return weight_grad_all(items, 4, sc, s);
-}
-
 // launch what the queue has collected: one grouped launch (weight_grad_all groups products of <= 4096 rows) on the side stream behind
 // the chain's event, or on the caller's stream
 static int dwq_flush(DwQueue& q, const Scratch& sc, hipStream_t s) {
@@ -340,32 +301,90 @@ static int dwq_flush(DwQueue& q, const Scratch& sc, hipStream_t s) {
   return 0;
 }
 
+// the two half-blocks of an encoder layer as the shared training half-blocks take them (common.h)
+static stlt_ffn_block_params ffn_half(const stlt_layer_params& l) { return {l.lin1_w, l.lin1_b, l.lin2_w, l.lin2_b, l.norm2_w, l.norm2_b}; }
+static stlt_attn_block_params attn_half(const stlt_layer_params& l) { return {l.in_proj_w, l.in_proj_b, l.out_proj_w, l.out_proj_b, l.norm1_w, l.norm1_b}; }
+
+// One tower of a call, as the forward and the reverse sweep both see it (built once per call: plan_rows).
+struct Tower {
+  int64_t d, H;
+  const stlt_layer_params* layers; const LayerTape* tape; int64_t n_layers;
+  int64_t M, Mp, S, L;           // rows (the real ones under skip-padding), M rounded up to 32, sequences, longest sequence
+  const uint8_t* kpm; int causal, kid;
+  bool ragged; AttnBwdRagged rg;  // skip-padding: the segments of the rows (seg_start / seg_end: the forward's too) and their backward groups
+  const int* rows; int64_t n;    // the only output rows that are read afterwards: the CLS row of every frame / frame lengths-1 of every clip
+  bool tail;                     // the last layer produces just those rows (layer_forward with picked rows, layer_backward_tail)
+  uint32_t site0;
+  uint32_t site(int64_t l) const { return site0 + (uint32_t)(8 * l); }  // dropout sites of layer l: site, site + 1, site + 2
+  const AttnBwdRagged* rgp() const { return ragged ? &rg : nullptr; }
+};
+
+// backward of layer l of a tower.  dy: gradient wrt the layer output (M,d) in ts.A; on return ts.A holds the gradient wrt the layer
+// input.  The layer takes the queue's next set of operand buffers — bufB / bufD / bufE (M,d), bufQ (M,3d), bufH (M,4d), scratch with zero
+// row padding — waiting for the flush that still reads it, if any; ts.C (M,d) is chain-only scratch.
+// The four output gradients of the layer's Linears stay alive until the end of the layer, where their weight-gradient products are left with the
+// queue: df in bufD / da in bufE (dropout off: df in bufB, the residual-path gradient — StltHalfBwd::branch), du in bufH, dqkv in bufQ.
+static int layer_backward(const Tower& tw, int64_t l, const stlt_layer_params* g, const TowerScratch& ts, const Scratch& sc, StltDrop dr,
+                          hipStream_t s, DwQueue& q) {
+  const stlt_layer_params& lp = tw.layers[l];
+  const stlt_layer_params gl = g ? *g : stlt_layer_params{};  // null members are skipped
+  const LayerTape& t = tw.tape[l];
+  const int64_t d = tw.d, M = tw.M;
+  const uint32_t site0 = tw.site(l);
+  int set_idx = 0;
+  GradBufs gb;
+  TRY(dwq_begin_layer(q, s, gb, set_idx));
+  float *bufA = ts.A, *bufC = ts.C, *bufB = gb.B, *bufD = gb.D, *bufE = gb.E, *bufQ = gb.Q, *bufH = gb.H;
+  StltGemmWgCap chain_cap(q.side && q.side->on ? dx_chain_wg_cap() : 0);
+  // y = LN2(x1 + drop(f)), f = h·W2ᵀ + b2, h = drop(gelu(u)), u = x1·W1ᵀ + b1: bufB = ds2, df, bufH = du, bufC = dx1 = du·W1 + ds2
+  const StltHalfBwd ffn{bufB, bufD, bufH, bufC, sc.rs, sc.sk ? sc.slabs : nullptr, sc.slab_floats};
+  TRY(stlt_ffn_half_bwd_train(ffn_half(lp), ffn_half(gl), STLT_ACT_GELU, bufA, t.x1, t.u, t.h, t.f, 1e-5f, M, d, dr, dr, site0 + 2, nullptr, ffn, s));
+  // x1 = LN1(x + drop(a)), a = ctx·Woᵀ + bo: ds1 (in bufB when dropout is on: its ds2 is dead by then), da in bufE, bufC = dctx
+  const StltHalfBwd att{dr.thr ? bufB : bufE, bufE, nullptr, bufC, sc.rs, ffn.wt, ffn.wt_floats};
+  TRY(stlt_attn_half_bwd_train(attn_half(lp), attn_half(gl), bufC, t.x, t.a, 1e-5f, M, d, dr, site0 + 1, nullptr, att, s));
+  // ctx = attention(qkv) with dropout on the probabilities
+  TRY(launch_attn_bwd(t.qkv, bufC, tw.kpm, tw.causal, tw.S, tw.L, tw.H, d / tw.H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), tw.rgp()));  // bufQ = dqkv; in_proj_b += colsum(dqkv)
+  // qkv = x·Winᵀ + bin
+  TRY(dx_product(bufQ, 3 * d, lp.in_proj_w, 3 * d, d, att.ds, d, bufA, d, M, sc, s));  // bufA = dx = dqkv·Win + ds1
+  // the four weight gradients (off the dX chain): one grouped launch
+  const StltWeightGradItem items[4] = {{ffn.branch(dr), d, t.h, 4 * d, tw.Mp, stlt_grad(gl.lin2_w)},
+                                       {bufH, 4 * d, t.x1, d, tw.Mp, stlt_grad(gl.lin1_w)},
+                                       {att.branch(dr), d, t.ctx, d, tw.Mp, stlt_grad(gl.out_proj_w)},
+                                       {bufQ, 3 * d, t.x, d, tw.Mp, stlt_grad(gl.in_proj_w)}};
+  for (int i = 0; i < 4; ++i) q.items[q.n_items++] = items[i];
+  q.chunk_sets[q.layers_in_chunk++] = set_idx;
+  if (q.layers_in_chunk >= q.group_layers || q.n_items + 4 > STLT_GEMM_GROUP_MAX) return dwq_flush(q, sc, s);
+  return 0;
+}
+
 // in-projection + attention core of a training forward: the packed projections stay in the tape (t.qkv) for the reverse sweep.
 // Padded layout, sequences of <= 64 tokens: one fused launch (mhsa.hip, TRAIN build: dropout of the probabilities from the
 // counter mask, q / k / v written from the accumulators); ragged layout and other shapes: product + attention core.
-static int qkv_attention_train(const stlt_layer_params& lp, int64_t d, int64_t H, const LayerTape& t, int64_t M, int64_t S, int64_t L,
-                               const uint8_t* kpm, int causal, int kid, StltDrop dr, uint32_t site0, hipStream_t s, const int* seg_start,
-                               const int* seg_end) {
-  if (!seg_start && stlt_fused_mhsa_on(causal) && stlt_mhsa_fused_pays(S, L, H, d, causal) && !stlt_split_bf16_takes(M, 3 * d, d, d, d))
-    return launch_mhsa_fused(t.x, lp.in_proj_w, lp.in_proj_b, kpm, S, L, H, d, t.ctx, s, causal, t.qkv, dr, site0);
-  TRY(launch_linear(t.x, d, lp.in_proj_w, lp.in_proj_b, t.qkv, 3 * d, M, 3 * d, d, STLT_ACT_NONE, s));
-  if (seg_start) return launch_attn_ragged(t.qkv, seg_start, seg_end, causal, M, H, d / H, t.ctx, kid, s, dr, site0);
-  return launch_attn(t.qkv, kpm, causal, S, L, H, d / H, t.ctx, kid, s, dr, site0);
+static int qkv_attention_train(const Tower& tw, const stlt_layer_params& lp, const LayerTape& t, StltDrop dr, uint32_t site0, hipStream_t s) {
+  const int64_t d = tw.d, H = tw.H;
+  if (!tw.ragged && stlt_fused_mhsa_on(tw.causal) && stlt_mhsa_fused_pays(tw.S, tw.L, H, d, tw.causal) && !stlt_split_bf16_takes(tw.M, 3 * d, d, d, d))
+    return launch_mhsa_fused(t.x, lp.in_proj_w, lp.in_proj_b, tw.kpm, tw.S, tw.L, H, d, t.ctx, s, tw.causal, t.qkv, dr, site0);
+  TRY(launch_linear(t.x, d, lp.in_proj_w, lp.in_proj_b, t.qkv, 3 * d, tw.M, 3 * d, d, STLT_ACT_NONE, s));
+  if (tw.ragged) return launch_attn_ragged(t.qkv, tw.rg.seg_start, tw.rg.seg_end, tw.causal, tw.M, H, d / H, t.ctx, tw.kid, s, dr, site0);
+  return launch_attn(t.qkv, tw.kpm, tw.causal, tw.S, tw.L, H, d / H, t.ctx, tw.kid, s, dr, site0);
 }
 
-// One layer of the training forward.  rows == nullptr: every row (n = M; t.ctx / t.x are read in place, no gathers).
-// rows != nullptr: the last layer of a tower when only n of its M output rows are read afterwards (the CLS row of every frame after
+// Layer l of a tower's training forward, output to y.  Every layer but a tail: every row (n = M; t.ctx / t.x are read in place, no gathers).
+// The tail (tw.tail): the last layer of a tower when only n of its M output rows are read afterwards (the CLS row of every frame after
 // the spatial tower, models.py:79; frame lengths-1 of every clip after the temporal tower, models.py:189-192): the
 // in-projection and the attention run on all rows (every row is a key / value), out-proj, norms and FFN on the picked
 // rows only.  Tape: x, qkv, ctx hold M rows; a, x1, u, h, f hold n rows; the gathered ctx / x rows are parked in the
-// unused upper part of a / x1 (rows n..2n-1, hence the 2n <= M condition at the call sites) and re-gathered by the
+// unused upper part of a / x1 (rows n..2n-1, hence the 2n <= M condition of plan_rows) and re-gathered by the
 // reverse sweep.  Dropout masks keep the indices of the rows' original positions.
-static int layer_forward(const stlt_layer_params& lp, int64_t d, int64_t H, const LayerTape& t, int64_t M, int64_t S, int64_t L,
-                         const uint8_t* kpm, int causal, int kid, const int* seg_start, const int* seg_end, const int* rows, int64_t n,
-                         float* y, StltDrop dr, uint32_t site0, hipStream_t s) {
-  TRY(qkv_attention_train(lp, d, H, t, M, S, L, kpm, causal, kid, dr, site0, s, seg_start, seg_end));
-  const float* ctx = t.ctx;
-  const float* x = t.x;
+static int layer_forward(const Tower& tw, int64_t l, float* y, StltDrop dr, hipStream_t s) {
+  const stlt_layer_params& lp = tw.layers[l];
+  const LayerTape& t = tw.tape[l];
+  const bool tail = tw.tail && l == tw.n_layers - 1;
+  const int* rows = tail ? tw.rows : nullptr;
+  const int64_t d = tw.d, n = tail ? tw.n : tw.M;
+  const uint32_t site0 = tw.site(l);
+  TRY(qkv_attention_train(tw, lp, t, dr, site0, s));
+  const float *ctx = t.ctx, *x = t.x;
   if (rows) {
     float* g_ctx = t.a + n * d;
     float* g_x = t.x1 + n * d;
@@ -385,18 +404,20 @@ static int zero_rows(float* buf, int64_t width, int64_t r0, int64_t r1, hipStrea
   return 0;
 }
 
-// Reverse of layer_forward's picked-rows form.  dy: gradient wrt the n output rows; on return bufA holds the gradient wrt all M
-// input rows.  Scratch roles as in layer_backward; the gradient-side operands of the weight-gradient products are
+// Reverse of layer_forward's tail form.  dy: gradient wrt the n output rows; on return ts.A holds the gradient wrt all M
+// input rows.  Scratch roles as in layer_backward, on the tower's own set; the gradient-side operands of the weight-gradient products are
 // zeroed between n and its round-up to 32 first (those rows belong to other layers' data in the shared buffers).
-static int layer_backward_tail(const stlt_layer_params& lp, const stlt_layer_params* g, const LayerTape& t, int64_t d, int64_t H,
-                               int64_t M, int64_t Mp, int64_t S, int64_t L, const uint8_t* kpm, int causal, const int* rows, int64_t n,
-                               const float* dy, float* bufA, float* bufB, float* bufC, float* bufD, float* bufE, float* bufQ, float* bufH,
-                               const Scratch& sc, StltDrop dr, uint32_t site0, hipStream_t s, const AttnBwdRagged* rg) {
+static int layer_backward_tail(const Tower& tw, int64_t l, const stlt_layer_params* g, const float* dy, const TowerScratch& ts, const Scratch& sc,
+                               StltDrop dr, hipStream_t s) {
+  const stlt_layer_params& lp = tw.layers[l];
   const stlt_layer_params gl = g ? *g : stlt_layer_params{};
-  const int64_t np = up32(n);
-  TRY(zero_rows(bufB, d, n, np, s));
-  TRY(zero_rows(bufD, d, n, np, s));
-  TRY(zero_rows(bufE, d, n, np, s));
+  const LayerTape& t = tw.tape[l];
+  const int64_t d = tw.d, M = tw.M, n = tw.n, np = up32(n);
+  const int* rows = tw.rows;
+  const uint32_t site0 = tw.site(l);
+  const GradBufs& gb = ts.sets[0];
+  float *bufA = ts.A, *bufC = ts.C, *bufB = gb.B, *bufD = gb.D, *bufE = gb.E, *bufQ = gb.Q, *bufH = gb.H;
+  for (float* b : {bufB, bufD, bufE}) TRY(zero_rows(b, d, n, np, s));
   TRY(zero_rows(bufH, 4 * d, n, np, s));
   // the feed-forward half on the picked rows: bufB = ds2, df, bufH = du, bufC = dx1 = du·W1 + ds2
   const StltHalfBwd ffn{bufB, bufD, bufH, bufC, sc.rs, sc.sk ? sc.slabs : nullptr, sc.slab_floats};
@@ -415,15 +436,43 @@ static int layer_backward_tail(const stlt_layer_params& lp, const stlt_layer_par
   TRY(weight_grad_all(items, 3, sc, s));
   // the other rows' attention outputs were never read: their dctx is zero
   TRY(launch_scatter_rows(bufC, rows, n, d, bufH, M, s));                                           // bufH (as M x d) = dctx
-  TRY(launch_attn_bwd(t.qkv, bufH, kpm, causal, S, L, H, d / H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), rg));  // bufQ = dqkv
-  TRY(weight_grad(bufQ, 3 * d, t.x, d, Mp, stlt_grad(gl.in_proj_w), sc, s));
+  TRY(launch_attn_bwd(t.qkv, bufH, tw.kpm, tw.causal, tw.S, tw.L, tw.H, d / tw.H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), tw.rgp()));  // bufQ = dqkv
+  TRY(weight_grad(bufQ, 3 * d, t.x, d, tw.Mp, stlt_grad(gl.in_proj_w), sc, s));
   TRY(launch_scatter_rows(att.ds, rows, n, d, bufC, M, s));                                            // residual path: ds1 on the picked rows only
   TRY(dx_product(bufQ, 3 * d, lp.in_proj_w, 3 * d, d, bufC, d, bufA, d, M, sc, s));  // bufA = dx = dqkv·Win + ds1
   // the 4d-wide view of bufH lost its zero rows past M to the dctx image only below M*d floats: nothing to restore
   return 0;
 }
 
-static int check_train(const stlt_params* p, const stlt_inputs* in, bool need_head = true) {
+// Reverse of a whole tower: on return ts.A holds the gradient wrt the tower's input rows.  dy: the gradient wrt the tw.n output rows that were
+// read (the tail layer takes it as it is, a tower without one scatters it over zeros); nullptr: ts.A already holds the gradient wrt every output row.
+// g: the tower's gradient table, or nullptr.  The closing flush launches what a grouping queue still holds (nothing when it flushes per layer).
+static int tower_backward(const Tower& tw, const stlt_layer_params* g, const float* dy, const TowerScratch& ts, const Scratch& sc, StltDrop dr,
+                          hipStream_t s, DwQueue& q) {
+  int64_t l = tw.n_layers - 1;
+  if (tw.tail) {
+    TRY(layer_backward_tail(tw, l, g ? &g[l] : nullptr, dy, ts, sc, dr, s));
+    --l;
+  } else if (dy) {
+    TRY(launch_scatter_rows(dy, tw.rows, tw.n, tw.d, ts.A, tw.Mp, s));
+  }
+  for (; l >= 0; --l) TRY(layer_backward(tw, l, g ? &g[l] : nullptr, ts, sc, dr, s, q));
+  return dwq_flush(q, sc, s);
+}
+
+// The weight-gradient products contract over the row count rounded up to 32: the rows of a queue's operand sets between the count and its
+// round-up are cleared (at most 31 rows per buffer).
+static int clear_operand_padding(const DwQueue& q, const Tower& tw, hipStream_t s) {
+  for (int k = 0; k < q.n_sets; ++k) {
+    for (float* b : {q.sets[k].B, q.sets[k].D, q.sets[k].E}) TRY(zero_rows(b, tw.d, tw.M, tw.Mp, s));
+    TRY(zero_rows(q.sets[k].Q, 3 * tw.d, tw.M, tw.Mp, s));
+    TRY(zero_rows(q.sets[k].H, 4 * tw.d, tw.M, tw.Mp, s));
+  }
+  return 0;
+}
+
+static int check_train(const stlt_params* p, const stlt_inputs* in, int flags) {
+  const bool need_head = !(flags & STLT_FLAG_TRAIN_BACKBONE);
   if (!p || !in) return stlt_set_error(STLT_EINVAL, "null params/inputs");
   if (!stlt_heads_ok(p->d, p->H))
     return stlt_set_error(STLT_EINVAL, "hidden_size %lld / heads %lld: need hidden_size %% heads == 0, a head dim of at most 256 and hidden_size %% 4 == 0", (long long)p->d, (long long)p->H);
@@ -434,6 +483,7 @@ static int check_train(const stlt_params* p, const stlt_inputs* in, bool need_he
   if (need_head && (!p->fc1_w || !p->fc2_w || p->n_classes <= 0)) return stlt_set_error(STLT_EINVAL, "prediction head missing");
   if (p->n_categories > STLT_TRAIN_MAX_CATEGORIES)  // the embedding-gradient kernel keeps per-category sums in LDS (backward.hip: embed_bwd_kernel)
     return stlt_set_error(STLT_EINVAL, "training supports at most %d object categories (got %lld)", STLT_TRAIN_MAX_CATEGORIES, (long long)p->n_categories);
+  if (!need_head && (flags & STLT_FLAG_SKIP_PADDING)) return stlt_set_error(STLT_EINVAL, "STLT_FLAG_TRAIN_BACKBONE excludes STLT_FLAG_SKIP_PADDING");
   return 0;
 }
 
@@ -450,6 +500,46 @@ static bool grad_table_empty(const stlt_params* p, const stlt_params* g) {
   for (int64_t l = 0; g->spatial && l < p->n_spatial; ++l) if (!layer_table_empty(g->spatial[l])) return false;
   for (int64_t l = 0; g->temporal && l < p->n_temporal; ++l) if (!layer_table_empty(g->temporal[l])) return false;
   return true;
+}
+
+// What the forward and the reverse sweep of one call must agree on, computed in one place for both: the opened tape, the schedule (padded /
+// skip-padding), the row counts, which towers end in a tail layer, and each tower's descriptor with its dropout sites.  Two steps, because the
+// argument checks that sit between them come in a fixed order (tests/host_fuzz.hip tallies which one a bad call reports).
+struct Plan {
+  bool backbone_only, ragged, host_counts = false;  // backbone_only (STLT_FLAG_TRAIN_BACKBONE): no head, `logits` / `dlogits` are the (B*T, d) backbone output / its gradient
+  Tape t;
+  RaggedIndex ix;  // the ragged index (skip-padding), or the padded layout's picked rows: built by the forward, read again by the backward
+  int64_t tok, BT;
+  int fpg;         // skip-padding: whole frames per attention-backward group of the spatial tower
+  Tower sp, tp;    // (they point into t: a Plan is filled in place and never copied)
+};
+static int plan_open(Plan& pl, const stlt_params* p, const stlt_inputs* in, const void* tape_mem, size_t tape_bytes, int flags) {
+  pl.backbone_only = (flags & STLT_FLAG_TRAIN_BACKBONE) != 0;
+  // Padded schedule: every (clip, frame, slot) row, masks applied inside the attention.  Skip-padding: the same launches over the real rows
+  // only (ragged.hip): the tape holds those alone (same buffers, fewer rows) and dropout masks are drawn per compacted row.
+  pl.ragged = (flags & STLT_FLAG_SKIP_PADDING) != 0;
+  pl.t = tape_layout((char*)const_cast<void*>(tape_mem), in->B, in->T, in->N, p->d, p->n_spatial, p->n_temporal);
+  if (tape_bytes < pl.t.bytes) return stlt_set_error(STLT_EWORKSPACE, "tape %zu B < required %zu B", tape_bytes, pl.t.bytes);
+  if ((uintptr_t)tape_mem & 255) return stlt_set_error(STLT_EINVAL, "tape must be 256-byte aligned");
+  pl.ix = ragged_index_carve(pl.t.ridx, in->B, in->T, in->N);
+  return 0;
+}
+// the row counts (skip-padding: the caller's, or read back from the index — the forward, `pad`, has just built it) and what follows from them
+static int plan_rows(Plan& pl, const stlt_params* p, const stlt_inputs* in, bool pad, hipStream_t s) {
+  const int64_t B = in->B, T = in->T, N = in->N;
+  const RaggedIndex& ix = pl.ix;
+  pl.tok = B * T * N; pl.BT = B * T;
+  if (pl.ragged) TRY(read_ragged_counts(ix, in, pad, pl.tok, pl.BT, &pl.host_counts, s));
+  const int64_t tok = pl.tok, BT = pl.BT;
+  pl.fpg = N <= 32 ? (int)(32 / N) : 1;
+  // the last layer of each tower only has to produce the rows that are read afterwards
+  pl.sp = Tower{p->d, p->H, p->spatial, pl.t.sp, p->n_spatial, tok, up32(tok), B * T, N, in->kpm_boxes, 0, STLT_K_ATTN_SPATIAL, pl.ragged,
+                AttnBwdRagged{ix.sp_grp_ptr, ix.t_seg_start, ix.t_seg_end, (BT + pl.fpg - 1) / pl.fpg, tok, (int)(pl.fpg * N)},
+                ix.f_cls_row, BT, p->n_spatial > 0 && 2 * BT <= tok, 8u};
+  pl.tp = Tower{p->d, p->H, p->temporal, pl.t.tp, p->n_temporal, BT, up32(BT), B, T, in->kpm_frames, 1, STLT_K_ATTN_TEMPORAL, pl.ragged,
+                AttnBwdRagged{ix.clip_frm_off, ix.f_seg_start, ix.f_seg_end, B, BT, (int)T},
+                ix.last_row, B, !pl.backbone_only && p->n_temporal > 0 && 2 * B <= BT, (uint32_t)(8 * (p->n_spatial + 1))};
+  return 0;
 }
 
 }  // namespace
@@ -471,73 +561,49 @@ size_t stlt_train_scratch_bytes(int64_t B, int64_t T, int64_t N, int64_t d, int6
 
 int stlt_train_forward(const stlt_params* p, const stlt_inputs* in, void* tape_mem, size_t tape_bytes, float* logits,
                        float dropout_p, uint64_t dropout_seed, int flags, stlt_stream_t stream) {
-  const bool backbone_only = (flags & STLT_FLAG_TRAIN_BACKBONE) != 0;  // `logits` is then the (B*T, d) backbone output
-  TRY(check_train(p, in, !backbone_only));
-  if (backbone_only && (flags & STLT_FLAG_SKIP_PADDING)) return stlt_set_error(STLT_EINVAL, "STLT_FLAG_TRAIN_BACKBONE excludes STLT_FLAG_SKIP_PADDING");
+  TRY(check_train(p, in, flags));
   if (!logits || !tape_mem) return stlt_set_error(STLT_EINVAL, "stlt_train_forward: null logits/tape");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H;
-  const Tape t = tape_layout((char*)tape_mem, B, T, N, d, p->n_spatial, p->n_temporal);
-  if (tape_bytes < t.bytes) return stlt_set_error(STLT_EWORKSPACE, "tape %zu B < required %zu B", tape_bytes, t.bytes);
-  if ((uintptr_t)tape_mem & 255) return stlt_set_error(STLT_EINVAL, "tape must be 256-byte aligned");
+  const int64_t B = in->B, T = in->T, N = in->N, d = p->d;
+  Plan pl;
+  TRY(plan_open(pl, p, in, tape_mem, tape_bytes, flags));
+  const Tape& t = pl.t; const RaggedIndex& ix = pl.ix; const bool ragged = pl.ragged, backbone_only = pl.backbone_only;
   StltGemmScratch gemm_scratch(t.sk, STLT_GEMM_SCRATCH_BYTES);
   if (!(dropout_p >= 0.f && dropout_p < 1.f)) return stlt_set_error(STLT_EINVAL, "dropout probability must be in [0,1)");
   const StltDrop dr = stlt_drop_make(dropout_p, dropout_seed);
-  // Padded schedule: every (clip, frame, slot) row, masks applied inside the attention.  Skip-padding: the same
-  // launches over the real rows only (ragged.hip); dropout masks are then drawn per compacted row.
-  const bool ragged = (flags & STLT_FLAG_SKIP_PADDING) != 0;
-  int64_t tok = B * T * N, BT = B * T;
-  bool host_counts = false;
-  const RaggedIndex ix = ragged_index_carve(t.ridx, B, T, N);
   if (ragged) {
     if (N > AB_MAX_ROWS || T > AB_MAX_ROWS)  // the reverse sweep would refuse the tape anyway; head dims other than 64 hold a segment's keys in LDS
       return stlt_set_error(STLT_EINVAL, "skip-padding training supports sequences of at most %d tokens (N=%lld, T=%lld)", AB_MAX_ROWS, (long long)N, (long long)T);
     TRY(launch_ragged_index(in->kpm_boxes, in->kpm_frames, in->lengths, B, T, N, ix, s));
-    TRY(read_ragged_counts(ix, in, true, tok, BT, &host_counts, s));
   } else {
     TRY(launch_padded_rows(in->lengths, B, T, N, ix, s));  // rows the tail layers pick: f*N and b*T + lengths-1
   }
-  // the last layer of each tower only has to produce the rows that are read afterwards (layer_forward with picked rows)
-  const bool sp_tail = p->n_spatial > 0 && 2 * BT <= tok, tp_tail = !backbone_only && p->n_temporal > 0 && 2 * B <= BT;
+  TRY(plan_rows(pl, p, in, true, s));
+  const int64_t tok = pl.tok, BT = pl.BT;
   float* x0 = p->n_spatial > 0 ? t.sp[0].x : t.sp_out;
   TRY(launch_embed(in->categories, in->boxes, in->scores, p->cat_emb, p->n_categories, p->box_w, p->box_b, p->score_w,
                    p->score_b, p->emb_ln_w, p->emb_ln_b, p->ln_eps, tok, d, x0, s, t.s_embed, dr, ragged ? ix.t_orig : nullptr));
-  for (int64_t l = 0; l < p->n_spatial; ++l) {
-    const uint32_t site = (uint32_t)(8 * (l + 1));
-    const bool tail = l == p->n_spatial - 1 && sp_tail;
-    float* y = l + 1 < p->n_spatial ? t.sp[l + 1].x : t.sp_out;
-    TRY(layer_forward(p->spatial[l], d, H, t.sp[l], tok, B * T, N, in->kpm_boxes, 0, STLT_K_ATTN_SPATIAL, ragged ? ix.t_seg_start : nullptr,
-                      ragged ? ix.t_seg_end : nullptr, tail ? ix.f_cls_row : nullptr, tail ? BT : tok, y, dr, site, s));
-  }
+  for (int64_t l = 0; l < p->n_spatial; ++l) TRY(layer_forward(pl.sp, l, l + 1 < p->n_spatial ? t.sp[l + 1].x : t.sp_out, dr, s));
   float* tp_dst = backbone_only ? logits : t.tp_out;  // where the temporal tower's output rows land
   float* g0 = p->n_temporal > 0 ? t.tp[0].x : tp_dst;
-  const float* cls = t.sp_out;  // (frames, d) when the tail layer ran, else the CLS rows inside the token buffer
-  int64_t cls_stride = d;
-  if (!sp_tail) {
-    if (ragged) {  // CLS rows are not evenly strided: gather them (tp_out is free until the last temporal layer writes it)
-      TRY(launch_gather_rows(t.sp_out, d, ix.f_cls_row, BT, d, t.tp_out, s));
-      cls = t.tp_out;
-    } else {
-      cls_stride = N * d;
-    }
+  const float* cls = t.sp_out;  // (frames, d) when the tail layer ran, else the CLS rows inside the token buffer: at stride N when padded
+  const int64_t cls_stride = pl.sp.tail || ragged ? d : N * d;
+  if (!pl.sp.tail && ragged) {  // CLS rows are not evenly strided: gather them (tp_out is free until the last temporal layer writes it)
+    TRY(launch_gather_rows(t.sp_out, d, ix.f_cls_row, BT, d, t.tp_out, s));
+    cls = t.tp_out;
   }
   TRY(launch_frames_embed(cls, cls_stride, in->frame_types, p->pos_emb, p->type_emb, p->frames_ln_w, p->frames_ln_b, p->ln_eps, B, T,
                           d, g0, s, t.s_frames, dr, ragged ? ix.f_orig : nullptr, BT));
-  for (int64_t l = 0; l < p->n_temporal; ++l) {
-    const uint32_t site = (uint32_t)(8 * (p->n_spatial + l + 1));
-    const bool tail = l == p->n_temporal - 1 && tp_tail;
-    float* y = tail ? t.h0 : l + 1 < p->n_temporal ? t.tp[l + 1].x : tp_dst;
-    TRY(layer_forward(p->temporal[l], d, H, t.tp[l], BT, B, T, in->kpm_frames, 1, STLT_K_ATTN_TEMPORAL, ragged ? ix.f_seg_start : nullptr,
-                      ragged ? ix.f_seg_end : nullptr, tail ? ix.last_row : nullptr, tail ? B : BT, y, dr, site, s));
-  }
+  for (int64_t l = 0; l < p->n_temporal; ++l)
+    TRY(layer_forward(pl.tp, l, l + 1 < p->n_temporal ? t.tp[l + 1].x : pl.tp.tail ? t.h0 : tp_dst, dr, s));
   if (backbone_only) return 0;
-  if (!tp_tail) TRY(launch_gather_rows(t.tp_out, d, ix.last_row, B, d, t.h0, s));                    // models.py:189-192
+  if (!pl.tp.tail) TRY(launch_gather_rows(t.tp_out, d, ix.last_row, B, d, t.h0, s));                    // models.py:189-192
   TRY(launch_linear(t.h0, d, p->fc1_w, p->fc1_b, t.u0, d, B, d, d, STLT_ACT_NONE, s));
   TRY(launch_gelu_fwd(t.u0, t.z1, B * d, s));
   TRY(launch_add_layernorm(t.z1, d, nullptr, 0, p->head_ln_w, p->head_ln_b, p->ln_eps, B, d, t.z2, d, s));
   TRY(launch_linear(t.z2, d, p->fc2_w, p->fc2_b, logits, p->n_classes, B, p->n_classes, d, STLT_ACT_NONE, s));
   // the caller's row counts were taken on trust: NaN logits (hence a NaN loss) when they are not the index's or the masks break the contract
-  return host_counts ? launch_ragged_poison(ix, tok, BT, false, logits, B * p->n_classes, s) : 0;
+  return pl.host_counts ? launch_ragged_poison(ix, tok, BT, false, logits, B * p->n_classes, s) : 0;
 }
 
 int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_inputs* in, const void* tape_mem,
@@ -553,9 +619,7 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
                                size_t tape_bytes, void* scratch_mem, size_t scratch_bytes, const float* dlogits,
                                float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, float* d_boxes, float* d_scores,
                                stlt_stream_t stream) {
-  const bool backbone_only = (flags & STLT_FLAG_TRAIN_BACKBONE) != 0;  // `dlogits` is then the gradient of the (B*T, d) backbone output
-  TRY(check_train(p, in, !backbone_only));
-  if (backbone_only && (flags & STLT_FLAG_SKIP_PADDING)) return stlt_set_error(STLT_EINVAL, "STLT_FLAG_TRAIN_BACKBONE excludes STLT_FLAG_SKIP_PADDING");
+  TRY(check_train(p, in, flags));
   if (!g || !dlogits || !tape_mem || !scratch_mem) return stlt_set_error(STLT_EINVAL, "stlt_train_backward: null argument");
   if (d_scores && !d_boxes) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_inputs: d_scores comes with d_boxes");
   if (d_scores && !in->scores) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_inputs: d_scores given but the inputs carry no scores");
@@ -567,10 +631,10 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
   hipStream_t s = (hipStream_t)stream;
   StltCtxScope ctx_scope(ctx, s);  // the sweep's input-gradient products may read the context's transposed weight copies
   if (ctx_scope.error()) return ctx_scope.error();
-  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, H = p->H, K = p->n_classes;
-  const Tape t = tape_layout((char*)const_cast<void*>(tape_mem), B, T, N, d, p->n_spatial, p->n_temporal);
-  if (tape_bytes < t.bytes) return stlt_set_error(STLT_EWORKSPACE, "tape %zu B < required %zu B", tape_bytes, t.bytes);
-  if ((uintptr_t)tape_mem & 255) return stlt_set_error(STLT_EINVAL, "tape must be 256-byte aligned");
+  const int64_t B = in->B, T = in->T, N = in->N, d = p->d, K = p->n_classes;
+  Plan pl;
+  TRY(plan_open(pl, p, in, tape_mem, tape_bytes, flags));
+  const Tape& t = pl.t; const RaggedIndex& ix = pl.ix; const bool ragged = pl.ragged, backbone_only = pl.backbone_only;
   Scratch sc = scratch_layout((char*)scratch_mem, B, T, N, d, p->n_categories);
   if (scratch_bytes < sc.bytes) return stlt_set_error(STLT_EWORKSPACE, "scratch %zu B < required %zu B", scratch_bytes, sc.bytes);
   if ((uintptr_t)scratch_mem & 255) return stlt_set_error(STLT_EINVAL, "scratch must be 256-byte aligned");
@@ -578,72 +642,31 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
   // (STLT_TRAIN_DEFER_REDUCE=0: one launch each, A/B runs)
   StltReduceScope red(sc.red_pool, sc.red_pool_floats, sc.red, sc.red_floats, s);  // (no pool was carved while deferral is off)
   sc.rs = &red;
-  int64_t tok = B * T * N, BT = B * T;
-  int64_t tokp = t.tokp, btp = t.btp;
   StltGemmScratch gemm_scratch(sc.sk, STLT_GEMM_SCRATCH_BYTES);
   const StltDrop dr = stlt_drop_make(dropout_p, dropout_seed);
-  // Skip-padding: the tape holds the real rows only (same buffers, fewer rows).  The weight-gradient products
-  // contract over the row count rounded up to 32, so the gradient-side operands' rows between the count and its
-  // round-up are zeroed here (the padded schedule never dirties them; a ragged row count changes every step).
-  const bool ragged = (flags & STLT_FLAG_SKIP_PADDING) != 0;
   const bool do_upper = !(flags & STLT_FLAG_TRAIN_LOWER_ONLY), do_lower = !(flags & STLT_FLAG_TRAIN_UPPER_ONLY);
   if (!do_upper && !do_lower) return stlt_set_error(STLT_EINVAL, "stlt_train_backward: UPPER_ONLY and LOWER_ONLY exclude each other");
-  const RaggedIndex ix = ragged_index_carve(t.ridx, B, T, N);  // filled by the forward (ragged index, or the padded layout's picked rows)
-  AttnBwdRagged rg_sp{}, rg_tp{};
+  TRY(plan_rows(pl, p, in, false, s));
+  const int64_t tok = pl.tok, BT = pl.BT;
   if (ragged) {
-    bool host_counts = false;
-    TRY(read_ragged_counts(ix, in, false, tok, BT, &host_counts, s));
-    tokp = up32(tok);
-    btp = up32(BT);
     if (N > AB_MAX_ROWS || T > AB_MAX_ROWS) return stlt_set_error(STLT_EINVAL, "attention backward supports sequences of at most %d tokens", AB_MAX_ROWS);
-    const int fpg = N <= 32 ? (int)(32 / N) : 1;  // whole frames per attention-backward group
-    TRY(launch_ragged_groups(ix, tok, BT, fpg, s));
-    rg_sp = AttnBwdRagged{ix.sp_grp_ptr, ix.t_seg_start, ix.t_seg_end, (BT + fpg - 1) / fpg, tok, (int)(fpg * N)};
-    rg_tp = AttnBwdRagged{ix.clip_frm_off, ix.f_seg_start, ix.f_seg_end, B, BT, (int)T};
+    TRY(launch_ragged_groups(ix, tok, BT, pl.fpg, s));
   }
-  // Both schedules: the caller may hand in scratch that an earlier step with another (B,T,N) left dirty (two shapes
-  // can round to the same byte count), so the rows the weight-gradient products read beyond the row count are
-  // cleared every step: at most 31 rows per buffer.
   // (the fusion models' layout branch — STLT_FLAG_TRAIN_BACKBONE — keeps one stream: measured 43.75 against 44.1 ms per CACNF step at 64
   // clips; the block-level calls around the sweep are single-stream and the side launches only delay their small kernels)
   DwSide side = backbone_only || no_param_grads ? DwSide{} : dw_side_open(sc, ctx);
   DwSideHold side_hold(&side, s);
-  // weight-gradient queues: the spatial tower flushes per layer over two sets; the temporal tower, when it has few rows, collects up to
-  // eight layers (32 products) per grouped launch over eight sets (STLT_TRAIN_DW_GROUP_LAYERS=1: per layer, A/B runs)
-  static const int group_env = [] { const char* e = getenv("STLT_TRAIN_DW_GROUP_LAYERS"); return e ? atoi(e) : 8; }();
-  DwQueue q_sp, q_tp;
-  q_sp.side = q_tp.side = &side;
-  q_sp.sets[0] = GradBufs{sc.sB, sc.sD, sc.sE, sc.sQKV, sc.sH}; q_sp.sets[1] = sc.s2; q_sp.n_sets = sc.s2.B ? 2 : 1;  // one stream: a layer's products are flushed before the next layer rewrites the set
-  q_tp.sets[0] = GradBufs{sc.tB, sc.tD, sc.tE, sc.tQKV, sc.tH}; q_tp.sets[1] = sc.t2; q_tp.n_sets = 2;
-  if (sc.n_tx > 0 && group_env > 1 && sc.sk) {
-    for (int i = 0; i < sc.n_tx; ++i) q_tp.sets[2 + i] = sc.tx[i];
-    q_tp.n_sets = 2 + sc.n_tx;
-    q_tp.group_layers = group_env < q_tp.n_sets ? group_env : q_tp.n_sets;
-  }
-  if (do_lower && !no_param_grads) {
-    for (int k = 0; k < q_sp.n_sets; ++k) {
-      for (float* b : {q_sp.sets[k].B, q_sp.sets[k].D, q_sp.sets[k].E}) TRY(zero_rows(b, d, tok, tokp, s));
-      TRY(zero_rows(q_sp.sets[k].Q, 3 * d, tok, tokp, s));
-      TRY(zero_rows(q_sp.sets[k].H, 4 * d, tok, tokp, s));
-    }
-  }
-  if (do_upper && !no_param_grads) {
-    for (int k = 0; k < q_tp.n_sets; ++k) {
-      for (float* b : {q_tp.sets[k].B, q_tp.sets[k].D, q_tp.sets[k].E}) TRY(zero_rows(b, d, BT, btp, s));
-      TRY(zero_rows(q_tp.sets[k].Q, 3 * d, BT, btp, s));
-      TRY(zero_rows(q_tp.sets[k].H, 4 * d, BT, btp, s));
-    }
-  }
-  const bool sp_tail = p->n_spatial > 0 && 2 * BT <= tok, tp_tail = !backbone_only && p->n_temporal > 0 && 2 * B <= BT;  // as the forward decided
+  DwQueue q_sp(&side, sc.sp), q_tp(&side, sc.tp);
+  // Both schedules: the caller may hand in scratch that an earlier step with another (B,T,N) left dirty (two shapes can round to the same byte
+  // count) and a ragged row count changes every step, so the operand rows beyond the row count are cleared every step.
+  if (do_lower && !no_param_grads) TRY(clear_operand_padding(q_sp, pl.sp, s));
+  if (do_upper && !no_param_grads) TRY(clear_operand_padding(q_tp, pl.tp, s));
   if (do_upper && backbone_only) {
     // the gradient of every row of the temporal tower's output arrives from the fusion layers: no head, no row gather
-    if (hipError_t e = hipMemcpyAsync(sc.tA, dlogits, (size_t)BT * d * sizeof(float), hipMemcpyDeviceToDevice, s); e != hipSuccess)
+    if (hipError_t e = hipMemcpyAsync(sc.tp.A, dlogits, (size_t)BT * d * sizeof(float), hipMemcpyDeviceToDevice, s); e != hipSuccess)
       return stlt_set_error((int)e, "train_backward: copy: %s", hipGetErrorString(e));
-    TRY(zero_rows(sc.tA, d, BT, btp, s));
-    for (int64_t l = p->n_temporal - 1; l >= 0; --l)
-      TRY(layer_backward(p->temporal[l], g->temporal ? &g->temporal[l] : nullptr, t.tp[l], d, H, BT, btp, B, T, in->kpm_frames, 1,
-                         sc.tA, sc.tB, sc.tC, sc.tD, sc.tE, sc.tQKV, sc.tH, sc, dr, (uint32_t)(8 * (p->n_spatial + l + 1)), s, nullptr, &q_tp));
-    TRY(dwq_flush(q_tp, sc, s));
+    TRY(zero_rows(sc.tp.A, d, BT, pl.tp.Mp, s));
+    TRY(tower_backward(pl.tp, g->temporal, nullptr, sc.tp, sc, dr, s, q_tp));
   } else if (do_upper) {
   // ---- prediction head (models.py:162-163): logits = z2·W2ᵀ+b2, z2 = LN(z1), z1 = gelu(u0), u0 = h0·W1ᵀ+b1
   if (g->fc2_w) TRY(launch_small_gemm(dlogits, 1, K, t.z2, d, 1, stlt_grad(g->fc2_w), d, K, d, B, 1, s));   // (K,d) += dlogitsᵀ·z2
@@ -660,52 +683,28 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
   }
   if (g->fc1_b) TRY(launch_colsum_acc(sc.hB, d, B, d, stlt_grad(g->fc1_b), red.chunk(), s));
   TRY(launch_gemm(0, 1, sc.hB, d, p->fc1_w, d, nullptr, nullptr, 0, sc.hA, d, 0, B, d, d, 1, STLT_ACT_NONE, s));  // hA = dh0
-  // ---- temporal transformer
-  int64_t l_tp = p->n_temporal - 1;
-  if (tp_tail) {
-    TRY(layer_backward_tail(p->temporal[l_tp], g->temporal ? &g->temporal[l_tp] : nullptr, t.tp[l_tp], d, H, BT, btp, B, T, in->kpm_frames, 1,
-                            ix.last_row, B, sc.hA, sc.tA, sc.tB, sc.tC, sc.tD, sc.tE, sc.tQKV, sc.tH, sc, dr,
-                            (uint32_t)(8 * (p->n_spatial + l_tp + 1)), s, ragged ? &rg_tp : nullptr));
-    --l_tp;
-  } else {
-    TRY(launch_scatter_rows(sc.hA, ix.last_row, B, d, sc.tA, btp, s));                              // tA = d(backbone out)
-  }
-  for (int64_t l = l_tp; l >= 0; --l)
-    TRY(layer_backward(p->temporal[l], g->temporal ? &g->temporal[l] : nullptr, t.tp[l], d, H, BT, btp, B, T, in->kpm_frames, 1,
-                       sc.tA, sc.tB, sc.tC, sc.tD, sc.tE, sc.tQKV, sc.tH, sc, dr, (uint32_t)(8 * (p->n_spatial + l + 1)), s,
-                       ragged ? &rg_tp : nullptr, &q_tp));
-    TRY(dwq_flush(q_tp, sc, s));
-  }  // upper half: sc.tA now holds the gradient wrt the temporal tower's input
+  // ---- temporal transformer: hA is the gradient wrt the last frame's row of every clip (models.py:189-192)
+  TRY(tower_backward(pl.tp, g->temporal, sc.hA, sc.tp, sc, dr, s, q_tp));
+  }  // upper half: sc.tp.A now holds the gradient wrt the temporal tower's input
   if (!do_lower) { TRY(red.flush()); return dw_side_join(&side, s); }
-  // ---- frames embeddings (models.py:98-111).  The gradient wrt the frames' CLS rows goes to tC, a chain-only buffer: the temporal
-  // tower's last weight-gradient products may still be reading tB / tD / tE / tQKV / tH on the side stream.
-  float* d_cls = sc.tC;
-  TRY(launch_ln_bwd(sc.tA, d, t.s_frames, d, nullptr, 0, p->frames_ln_w, p->ln_eps, BT, d, d_cls, d, stlt_grad(g->frames_ln_w),
+  // ---- frames embeddings (models.py:98-111).  The gradient wrt the frames' CLS rows goes to tp.C, a chain-only buffer: the temporal
+  // tower's last weight-gradient products may still be reading its operand sets on the side stream.
+  float* d_cls = sc.tp.C;
+  TRY(launch_ln_bwd(sc.tp.A, d, t.s_frames, d, nullptr, 0, p->frames_ln_w, p->ln_eps, BT, d, d_cls, d, stlt_grad(g->frames_ln_w),
                     stlt_grad(g->frames_ln_b), red.chunk(), s, dr, 0, nullptr, STLT_SITE_FRAMES));                // d_cls = gradient wrt the frames' CLS rows
-  const bool dense_scatter = !ragged && !sp_tail;  // padded dense schedule: the CLS rows sit at stride N in the token buffer
-  TRY(launch_frames_bwd(d_cls, in->frame_types, B, T, N, d, dense_scatter ? sc.sA : nullptr, stlt_grad(g->pos_emb), stlt_grad(g->type_emb), red.chunk(), s,
+  const bool dense_scatter = !ragged && !pl.sp.tail;  // padded dense schedule: the CLS rows sit at stride N in the token buffer
+  TRY(launch_frames_bwd(d_cls, in->frame_types, B, T, N, d, dense_scatter ? sc.sp.A : nullptr, stlt_grad(g->pos_emb), stlt_grad(g->type_emb), red.chunk(), s,
                         ragged ? ix.f_row_of : nullptr, !no_param_grads));
-  // ---- spatial transformer
-  int64_t l_sp = p->n_spatial - 1;
-  if (sp_tail) {
-    TRY(layer_backward_tail(p->spatial[l_sp], g->spatial ? &g->spatial[l_sp] : nullptr, t.sp[l_sp], d, H, tok, tokp, B * T, N, in->kpm_boxes, 0,
-                            ix.f_cls_row, BT, d_cls, sc.sA, sc.sB, sc.sC, sc.sD, sc.sE, sc.sQKV, sc.sH, sc, dr, (uint32_t)(8 * (l_sp + 1)), s,
-                            ragged ? &rg_sp : nullptr));
-    --l_sp;
-  } else if (ragged) {
-    TRY(launch_scatter_rows(d_cls, ix.f_cls_row, BT, d, sc.sA, tokp, s));                            // sA = d(spatial out), CLS rows only
-  }
-  for (int64_t l = l_sp; l >= 0; --l)
-    TRY(layer_backward(p->spatial[l], g->spatial ? &g->spatial[l] : nullptr, t.sp[l], d, H, tok, tokp, B * T, N, in->kpm_boxes, 0,
-                       sc.sA, sc.sB, sc.sC, sc.sD, sc.sE, sc.sQKV, sc.sH, sc, dr, (uint32_t)(8 * (l + 1)), s, ragged ? &rg_sp : nullptr, &q_sp));
-  // ---- category / box / score embeddings (models.py:29-39); sC for the same reason as tC above
-  TRY(launch_ln_bwd(sc.sA, d, t.s_embed, d, nullptr, 0, p->emb_ln_w, p->ln_eps, tok, d, sc.sC, d, stlt_grad(g->emb_ln_w), stlt_grad(g->emb_ln_b),
+  // ---- spatial transformer (its queue flushes per layer)
+  TRY(tower_backward(pl.sp, g->spatial, dense_scatter ? nullptr : d_cls, sc.sp, sc, dr, s, q_sp));
+  // ---- category / box / score embeddings (models.py:29-39); sp.C for the same reason as tp.C above
+  TRY(launch_ln_bwd(sc.sp.A, d, t.s_embed, d, nullptr, 0, p->emb_ln_w, p->ln_eps, tok, d, sc.sp.C, d, stlt_grad(g->emb_ln_w), stlt_grad(g->emb_ln_b),
                     red.chunk(), s, dr, 0, nullptr, STLT_SITE_EMBED));
   if (!no_param_grads)
-    TRY(launch_embed_bwd(sc.sC, in->categories, in->boxes, in->scores, p->n_categories, tok, d, stlt_grad(g->cat_emb), stlt_grad(g->box_w),
+    TRY(launch_embed_bwd(sc.sp.C, in->categories, in->boxes, in->scores, p->n_categories, tok, d, stlt_grad(g->cat_emb), stlt_grad(g->box_w),
                          stlt_grad(g->box_b), stlt_grad(g->score_w), stlt_grad(g->score_b), red.chunk(), s, ragged ? ix.t_orig : nullptr));
   if (d_boxes)
-    TRY(launch_embed_bwd_inputs(sc.sC, p->box_w, d_scores ? p->score_w : nullptr, tok, d, d_boxes, d_scores, B * T * N, s, ragged ? ix.t_orig : nullptr));
+    TRY(launch_embed_bwd_inputs(sc.sp.C, p->box_w, d_scores ? p->score_w : nullptr, tok, d, d_boxes, d_scores, B * T * N, s, ragged ? ix.t_orig : nullptr));
   TRY(red.flush());
   return dw_side_join(&side, s);
 }

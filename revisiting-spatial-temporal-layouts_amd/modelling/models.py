@@ -201,6 +201,16 @@ def _layout_grad_buffers(ctx_needs, batch, shape, device):
     return d_boxes, d_scores
 
 
+def _flat_grad_layout(params):
+    """[(parameter, offset, numel)] of one flat fp32 gradient buffer and its length: offsets rounded up to 4 floats so each tensor stays
+    16-byte aligned (the gaps stay zero)."""
+    layout, off = [], 0
+    for q in params:
+        layout.append((q, off, q.numel()))
+        off += (q.numel() + 3) // 4 * 4
+    return layout, off
+
+
 class StltBackbone(nn.Module):
     """Drop-in for reference ``StltBackbone`` (models.py:114-152): ``forward(batch) -> (T, B, d)``."""
 
@@ -300,6 +310,62 @@ class StltBackbone(nn.Module):
         if cur is None or cur.device != device or cur.numel() != nbytes:
             bufs[name] = cur = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         return cur
+
+    def _unused_param_ids(self, has_scores: bool):
+        """ids of the parameters the forward never uses (they get no gradient, like in the reference: the dead `encoder_layer` copy, and
+        `score_embeddings` when the batch has no scores — SURVEY.md §5)."""
+        le = self.frames_embeddings.layout_embedding
+        skip = {id(q) for q in le.encoder_layer.parameters()}
+        if not has_scores:
+            skip |= {id(q) for q in le.category_box_embeddings.score_embeddings.parameters()}
+        return skip
+
+    # ---- the native training step (csrc/train.hip), its two halves: what _StltTrainFn, _BackboneTrainFn and forward_saliency run ----
+    def _train_forward(self, batch, head: Optional["ClassificationHead"], flags: int, seed_override=None, stale: str = ""):
+        """stlt_train_forward into the backbone's one tape -> (output, step): the (B, num_classes) logits with a head, the (B,T,d) backbone
+        output without one (flags: FLAG_TRAIN_BACKBONE); `step` is what `_train_backward` needs to run on that tape.  `stale`: what the
+        backward says when a later forward has overwritten the tape."""
+        lib = L.load()
+        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
+        device = batch["categories"].device
+        p, _, _ = self.c_params(head)
+        d = self.config.hidden_size
+        tape = self._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
+        # one tape per backbone: every forward overwrites it and takes a new generation number, and the backward refuses to run on a
+        # tape that is no longer its own
+        self._tape_gen = gen = getattr(self, "_tape_gen", 0) + 1
+        out = torch.empty((B, T, d) if head is None else (B, head.fc2.weight.shape[0]), device=device, dtype=torch.float32)
+        # train-mode dropout (reference default hidden_dropout_prob = 0.1): counter-based masks from one seed per
+        # forward, drawn from torch's CPU generator (so torch.manual_seed makes runs repeatable)
+        drop_p = float(self.config.hidden_dropout_prob) if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0 else 0
+        seed = seed_override or seed
+        with torch.cuda.device(device):
+            L.check(lib.stlt_train_forward(C.byref(p), C.byref(inp), tape.data_ptr(), tape.numel(), out.data_ptr(), drop_p, seed, flags,
+                                           torch.cuda.current_stream().cuda_stream), "stlt_train_forward")
+        # (the input table and the tensors it points into stay with the step, for the backward)
+        return out, dict(gen=gen, stale=stale, inp=inp, keep=keep, shape=(B, T, N), device=device, head=head, drop=(drop_p, seed), flags=flags)
+
+    def _check_tape(self, step):
+        if getattr(self, "_tape_gen", 0) != step["gen"]:
+            raise L.StltHipError(step["stale"])
+
+    def _train_backward(self, step, g, dout, ctx_handle, d_boxes=None, d_scores=None, extra_flags: int = 0):
+        """The reverse sweep of `step` from the seed `dout` into the gradient table `g` (and the layout gradients, when given):
+        stlt_train_backward_inputs, which with neither layout gradient is stlt_train_backward.  (The autograd backwards also call
+        `_check_tape` first thing, so that a refused backward has not touched a gradient buffer.)"""
+        self._check_tape(step)
+        lib = L.load()
+        (B, T, N), device, d = step["shape"], step["device"], self.config.hidden_size
+        p, _, _ = self.c_params(step["head"])
+        tape = self._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
+        scratch = self._train_buf("scratch", int(lib.stlt_train_scratch_bytes(B, T, N, d, p.n_categories)), device)
+        dl = dout.contiguous().float()
+        with torch.cuda.device(device):
+            L.check(lib.stlt_train_backward_inputs(
+                C.byref(p), C.byref(g), C.byref(step["inp"]), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(), dl.data_ptr(),
+                step["drop"][0], step["drop"][1], step["flags"] | extra_flags, ctx_handle, None if d_boxes is None else d_boxes.data_ptr(),
+                None if d_scores is None else d_scores.data_ptr(), torch.cuda.current_stream().cuda_stream), "stlt_train_backward_inputs")
 
     def _flags(self) -> int:
         return ((L.FLAG_CLS_ONLY_LAST_SPATIAL if self.cls_only_last_spatial else 0)
@@ -414,13 +480,8 @@ class Stlt(nn.Module):
         return self  # the reference returns None here; returning self is a superset
 
     def _grad_params(self, has_scores: bool):
-        """ids of the parameters the forward actually uses (the others get no gradient, like in the reference: the
-        dead `encoder_layer` copy, and `score_embeddings` when the batch has no scores — SURVEY.md §5)."""
-        le = self.backbone.frames_embeddings.layout_embedding
-        skip = {id(q) for q in le.encoder_layer.parameters()}
-        if not has_scores:
-            skip |= {id(q) for q in le.category_box_embeddings.score_embeddings.parameters()}
-        return {id(q) for q in self.parameters()} - skip
+        """ids of the parameters the forward actually uses (StltBackbone._unused_param_ids names the others)."""
+        return {id(q) for q in self.parameters()} - self.backbone._unused_param_ids(has_scores)
 
     def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         bb = self.backbone
@@ -499,12 +560,10 @@ class Stlt(nn.Module):
         if not batch["categories"].is_cuda:
             raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
         lib = L.load()
-        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
         device = batch["categories"].device
         head = self.prediction_head
-        p, _, _ = bb.c_params(head)
-        d, K = self.config.hidden_size, head.fc2.weight.shape[0]
-        tgt = None
+        B, K = batch["categories"].shape[0], head.fc2.weight.shape[0]
+        tgt = seed = None
         if isinstance(target, torch.Tensor) and target.is_floating_point():
             if tuple(target.shape) != (B, K) or target.device != device:
                 raise L.StltHipError(f"forward_saliency: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
@@ -513,28 +572,19 @@ class Stlt(nn.Module):
             if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
                 raise L.StltHipError(f"forward_saliency: target is None, an int64 ({B},) tensor or a float ({B}, {K}) tensor on the batch's device")
             tgt = target.contiguous()
-            seed = None
-        else:
-            seed = None
-        tape = bb._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
-        scratch = bb._train_buf("scratch", int(lib.stlt_train_scratch_bytes(B, T, N, d, p.n_categories)), device)
-        bb._tape_gen = getattr(bb, "_tape_gen", 0) + 1  # the tape is overwritten: a pending backward of an earlier forward must refuse
+        # (dropout is off here, so the forward draws no seed; the tape is overwritten: a pending backward of an earlier forward will refuse)
+        logits, step = bb._train_forward(batch, head, L.FLAG_SKIP_PADDING if bb.skip_padding else 0)
+        _, T, N = step["shape"]
         g, gsp, gtp = bb._build_struct(head, lambda t: None)
         new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)  # noqa: E731
-        logits, d_boxes = new(B, K), new(B, T, N, 4)
+        d_boxes = new(B, T, N, 4)
         d_scores = new(B, T, N) if "scores" in batch else None
-        flags = L.FLAG_SKIP_PADDING if bb.skip_padding else 0
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream().cuda_stream
-            L.check(lib.stlt_train_forward(C.byref(p), C.byref(inp), tape.data_ptr(), tape.numel(), logits.data_ptr(), 0.0, 0, flags, stream),
-                    "stlt_train_forward")
-            if seed is None:
-                seed = new(B, K)
-                L.check(lib.stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), B, K, seed.data_ptr(), stream),
-                        "stlt_saliency_seed")
-            L.check(lib.stlt_train_backward_inputs(C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(), scratch.data_ptr(),
-                                                   scratch.numel(), seed.data_ptr(), 0.0, 0, flags, None, d_boxes.data_ptr(),
-                                                   None if d_scores is None else d_scores.data_ptr(), stream), "stlt_train_backward_inputs")
+        if seed is None:
+            seed = new(B, K)
+            with torch.cuda.device(device):
+                L.check(lib.stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), B, K, seed.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream), "stlt_saliency_seed")
+        bb._train_backward(step, g, seed, None, d_boxes, d_scores)
         if target is None:
             target = seed.argmax(dim=1)  # the one-hot row's only 1: the class the kernel picked (lowest index on ties), still on the device
         out = {"stlt": logits, "target": target, "boxes_grad": d_boxes}
@@ -551,52 +601,25 @@ class _StltTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, batch, boxes, scores, *params):
-        lib = L.load()
         bb = model.backbone
-        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
-        device = batch["categories"].device
-        p, _, _ = bb.c_params(model.prediction_head)
-        cfg = model.config
-        d, K = cfg.hidden_size, model.prediction_head.fc2.weight.shape[0]
-        n_sp, n_tp = p.n_spatial, p.n_temporal
-        tape = bb._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, n_sp, n_tp)), device)
-        # one tape per backbone: a second grad-enabled forward overwrites it, so every forward takes a new generation
-        # number and the backward refuses to run on a tape that is no longer its own
-        bb._tape_gen = ctx.tape_gen = getattr(bb, "_tape_gen", 0) + 1
-        logits = torch.empty(B, K, device=device, dtype=torch.float32)
-        # train-mode dropout (reference default hidden_dropout_prob = 0.1): counter-based masks from one seed per
-        # forward, drawn from torch's CPU generator (so torch.manual_seed makes runs repeatable)
-        drop_p = float(cfg.hidden_dropout_prob) if bb.training else 0.0
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0 else 0
-        seed = getattr(model, "_dropout_seed_override", None) or seed
         flags = L.FLAG_SKIP_PADDING if bb.skip_padding else 0  # the other two flags are inference-only elisions
-        with torch.cuda.device(device):
-            L.check(lib.stlt_train_forward(C.byref(p), C.byref(inp), tape.data_ptr(), tape.numel(), logits.data_ptr(),
-                                           drop_p, seed, flags, torch.cuda.current_stream().cuda_stream), "stlt_train_forward")
-        ctx.model, ctx.batch, ctx.shape, ctx.params, ctx.drop = model, batch, (B, T, N, d), params, (drop_p, seed, flags)
+        logits, ctx.step = bb._train_forward(
+            batch, model.prediction_head, flags, getattr(model, "_dropout_seed_override", None),
+            "Stlt backward: the activation tape was overwritten by a later grad-enabled forward of the same "
+            "model (one tape per backbone): run each forward's backward before the next forward, or wrap "
+            "forwards that need no gradient in torch.no_grad()")
+        ctx.model, ctx.batch, ctx.params = model, batch, params
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        lib = L.load()
         model, batch = ctx.model, ctx.batch
         bb = model.backbone
-        B, T, N, d = ctx.shape
+        bb._check_tape(ctx.step)
         device = dlogits.device
-        if getattr(bb, "_tape_gen", 0) != ctx.tape_gen:
-            raise L.StltHipError("Stlt backward: the activation tape was overwritten by a later grad-enabled forward of the same "
-                                 "model (one tape per backbone): run each forward's backward before the next forward, or wrap "
-                                 "forwards that need no gradient in torch.no_grad()")
-        inp, keep, _ = _prep_inputs(batch, need_lengths=True)
-        p, _, _ = bb.c_params(model.prediction_head)
         used = model._grad_params("scores" in batch)
-        want = [prm for prm in ctx.params if prm.requires_grad and id(prm) in used]
-        # every gradient lives in one flat buffer (offsets rounded up to 4 floats so each tensor stays 16-byte aligned;
-        # the gaps stay zero): what a data-parallel run all-reduces and what train.FusedAdamW consumes
-        layout, off = [], 0
-        for q in want:
-            layout.append((q, off, q.numel()))
-            off += (q.numel() + 3) // 4 * 4
+        # every gradient lives in one flat buffer: what a data-parallel run all-reduces and what train.FusedAdamW consumes
+        layout, off = _flat_grad_layout(prm for prm in ctx.params if prm.requires_grad and id(prm) in used)
         # The fused trainer consumes the buffer before the next backward, so it is kept per backbone and cleared, not
         # re-allocated (344 MB at d = 768).  Otherwise the views below become the parameters' .grad tensors and outlive
         # this call: a fresh buffer every time.
@@ -610,25 +633,16 @@ class _StltTrainFn(torch.autograd.Function):
                 bb.__dict__["_flat_grad_buf"] = flat
         views = {id(q): flat[o: o + n].view_as(q) for q, o, n in layout}
         g, gsp, gtp = bb._build_struct(model.prediction_head, lambda t: views[id(t)].data_ptr() if id(t) in views else None)
-        tape = bb._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
-        scratch = bb._train_buf("scratch", int(lib.stlt_train_scratch_bytes(B, T, N, d, p.n_categories)), device)
-        dl = dlogits.contiguous().float()
-        model._last_flat_grad = flat
+        model._last_flat_grad = flat  # one contiguous buffer: what a data-parallel wrapper all-reduces
         model._flat_layout = layout
-
         # the training context the sweep names: the trainer's while its step runs this backward (its transposed weight copies, its side
         # stream), else one the module owns for the side stream of plain autograd backwards
         tctx = getattr(model, "_train_context", None) or model._own_context()
-        d_boxes, d_scores = _layout_grad_buffers(ctx.needs_input_grad[2:4], batch, (B, T, N), device)
+        d_boxes, d_scores = _layout_grad_buffers(ctx.needs_input_grad[2:4], batch, ctx.step["shape"], device)
 
         def run(extra_flags):
-            args = (C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(), dl.data_ptr(),
-                    ctx.drop[0], ctx.drop[1], ctx.drop[2] | extra_flags, tctx.handle)
-            if d_boxes is None or extra_flags == L.FLAG_TRAIN_UPPER_ONLY:  # the upper half never reaches the embedding
-                L.check(lib.stlt_train_backward(*args, torch.cuda.current_stream().cuda_stream), "stlt_train_backward")
-            else:
-                L.check(lib.stlt_train_backward_inputs(*args, d_boxes.data_ptr(), None if d_scores is None else d_scores.data_ptr(),
-                                                       torch.cuda.current_stream().cuda_stream), "stlt_train_backward_inputs")
+            lower = extra_flags != L.FLAG_TRAIN_UPPER_ONLY  # the upper half never reaches the embedding
+            bb._train_backward(ctx.step, g, dlogits, tctx.handle, d_boxes if lower else None, d_scores if lower else None, extra_flags)
 
         sync = getattr(model, "_grad_sync", None)  # data-parallel hook: sync(flat, lo, hi) may start reducing flat[lo:hi]
         with torch.cuda.device(device):
@@ -644,10 +658,8 @@ class _StltTrainFn(torch.autograd.Function):
                 sync(flat, split, off)
                 run(L.FLAG_TRAIN_LOWER_ONLY)
                 sync(flat, 0, split)
-        model._last_flat_grad = flat  # one contiguous buffer: what a data-parallel wrapper all-reduces
-        model._flat_layout = layout
         d_boxes_out = d_boxes if ctx.needs_input_grad[2] else None
-        if getattr(model, "_flat_grads_only", False):  # train.FusedAdamW reads the flat buffer: skip the per-parameter .grad copies
+        if reuse:  # train.FusedAdamW reads the flat buffer: skip the per-parameter .grad copies
             return (None, None, d_boxes_out, d_scores) + tuple(None for _ in ctx.params)
         return (None, None, d_boxes_out, d_scores) + tuple(views.get(id(prm)) for prm in ctx.params)
 
@@ -659,35 +671,18 @@ class _BackboneTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, bb, batch, boxes, scores, *params):
-        lib = L.load()
-        inp, keep, (B, T, N) = _prep_inputs(batch, need_lengths=True)
-        device = batch["categories"].device
-        p, _, _ = bb.c_params(None)
-        cfg = bb.config
-        d = cfg.hidden_size
-        tape = bb._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
-        bb._tape_gen = ctx.tape_gen = getattr(bb, "_tape_gen", 0) + 1
-        out = torch.empty(B, T, d, device=device, dtype=torch.float32)
-        drop_p = float(cfg.hidden_dropout_prob) if bb.training else 0.0
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0 else 0
-        with torch.cuda.device(device):
-            L.check(lib.stlt_train_forward(C.byref(p), C.byref(inp), tape.data_ptr(), tape.numel(), out.data_ptr(), drop_p, seed,
-                                           L.FLAG_TRAIN_BACKBONE, torch.cuda.current_stream().cuda_stream), "stlt_train_forward")
-        ctx.bb, ctx.batch, ctx.shape, ctx.params, ctx.drop = bb, batch, (B, T, N, d), params, (drop_p, seed)
-        ctx.inp = (inp, keep)  # the input table and the tensors it points into, for the backward
+        out, ctx.step = bb._train_forward(
+            batch, None, L.FLAG_TRAIN_BACKBONE, None,
+            "StltBackbone backward: the activation tape was overwritten by a later grad-enabled forward of the same "
+            "backbone (one tape per backbone): run each forward's backward before the next forward")
+        ctx.bb, ctx.batch, ctx.params = bb, batch, params
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = L.load()
         bb, batch = ctx.bb, ctx.batch
-        B, T, N, d = ctx.shape
+        bb._check_tape(ctx.step)
         device = dout.device
-        if getattr(bb, "_tape_gen", 0) != ctx.tape_gen:
-            raise L.StltHipError("StltBackbone backward: the activation tape was overwritten by a later grad-enabled forward of the same "
-                                 "backbone (one tape per backbone): run each forward's backward before the next forward")
-        inp, keep = ctx.inp
-        p, _, _ = bb.c_params(None)
         # inside a Trainer step, parameters whose .grad is bound to the trainer's flat buffer are accumulated into in place (no
         # temporary, autograd gets None for them); the others — and every parameter outside a Trainer step, e.g. under
         # torch.autograd.grad() — get views of a fresh zero buffer that autograd accumulates / returns.  The gradient table of a
@@ -700,10 +695,7 @@ class _BackboneTrainFn(torch.autograd.Function):
             g, gsp, gtp, touched = cached[2]
             b0._touched.update(touched)
         else:
-            le = bb.frames_embeddings.layout_embedding
-            skip = {id(q) for q in le.encoder_layer.parameters()}
-            if "scores" not in batch:
-                skip |= {id(q) for q in le.category_box_embeddings.score_embeddings.parameters()}
+            skip = bb._unused_param_ids("scores" in batch)
             want = [prm for prm in ctx.params if prm.requires_grad and id(prm) not in skip]
             direct = {}
             for q in want:
@@ -712,29 +704,15 @@ class _BackboneTrainFn(torch.autograd.Function):
                 if view is not None:
                     bound.touch(q)
                     direct[id(q)] = view
-            layout, off = [], 0
-            for q in want:
-                if id(q) not in direct:
-                    layout.append((q, off, q.numel()))
-                    off += (q.numel() + 3) // 4 * 4
+            layout, off = _flat_grad_layout(q for q in want if id(q) not in direct)
             flat = torch.zeros(off, device=device, dtype=torch.float32) if off else None
             views = {id(q): flat[o: o + n].view_as(q) for q, o, n in layout}
             target = lambda t: direct[id(t)].data_ptr() if id(t) in direct else (views[id(t)].data_ptr() if id(t) in views else None)  # noqa: E731
             g, gsp, gtp = bb._build_struct(None, target)
             if key is not None and not layout and all(getattr(q, "_stlt_bound", None) is b0 for q in want):
                 bb.__dict__["_grad_table"] = (key, b0, (g, gsp, gtp, frozenset(direct)))
-        tape = bb._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
-        scratch = bb._train_buf("scratch", int(lib.stlt_train_scratch_bytes(B, T, N, d, p.n_categories)), device)
-        dl = dout.contiguous().float()
-        d_boxes, d_scores = _layout_grad_buffers(ctx.needs_input_grad[2:4], batch, (B, T, N), device)
-        args = (C.byref(p), C.byref(g), C.byref(inp), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(), dl.data_ptr(), ctx.drop[0],
-                ctx.drop[1], L.FLAG_TRAIN_BACKBONE, ops._ctx_handle(ops.context_of(ctx.params)))
-        with torch.cuda.device(device):
-            if d_boxes is None:
-                L.check(lib.stlt_train_backward(*args, torch.cuda.current_stream().cuda_stream), "stlt_train_backward")
-            else:
-                L.check(lib.stlt_train_backward_inputs(*args, d_boxes.data_ptr(), None if d_scores is None else d_scores.data_ptr(),
-                                                       torch.cuda.current_stream().cuda_stream), "stlt_train_backward_inputs")
+        d_boxes, d_scores = _layout_grad_buffers(ctx.needs_input_grad[2:4], batch, ctx.step["shape"], device)
+        bb._train_backward(ctx.step, g, dout, ops._ctx_handle(ops.context_of(ctx.params)), d_boxes, d_scores)
         return (None, None, d_boxes if ctx.needs_input_grad[2] else None, d_scores) + tuple(views.get(id(prm)) for prm in ctx.params)
 
 

@@ -36,7 +36,16 @@ def test_gradients_match_oracle_autograd_other_layouts(pkg, T, N, B):
     _check_gradients(pkg, "cfg1", B, False, False, T=T, N=N)
 
 
-def _check_gradients(pkg, name, B, with_scores, skip_padding, T=None, N=None):
+@pytest.mark.parametrize("skip_padding", [False, True])
+@pytest.mark.parametrize("B,T,N,min_len", [(3, 1, 3, 1), (3, 5, 1, 2), (4, 1, 1, 1)])
+def test_gradients_match_oracle_autograd_without_tail_layers(pkg, B, T, N, min_len, skip_padding):
+    """Layouts whose towers have no tail layer (csrc/train.hip: a tail needs twice as many rows as it picks): one frame per clip (no
+    temporal tail: the clips' last rows are scattered), one object slot per frame (no spatial tail: the strided CLS scatter of the
+    padded schedule, the CLS gather / scatter of skip-padding), and both.  cfg1's widths (head dim 64), scores given."""
+    _check_gradients(pkg, "cfg1", B, True, skip_padding, T=T, N=N, min_len=min_len)
+
+
+def _check_gradients(pkg, name, B, with_scores, skip_padding, T=None, N=None, min_len=None):
     c = dict(pkg.synth.CONFIGS[name])
     if T is not None:
         c["T"], c["N"] = T, N
@@ -47,7 +56,7 @@ def _check_gradients(pkg, name, B, with_scores, skip_padding, T=None, N=None):
     m.train(True)  # hidden_dropout_prob = 0 in model_kwargs
     m.to(DEV)
     m.backbone.skip_padding = skip_padding  # forward + reverse sweep on the real tokens / frames only
-    batch = pkg.synth.make_batch(B, c["T"], c["N"], dataset=c["dataset"], seed=77, with_scores=with_scores)
+    batch = pkg.synth.make_batch(B, c["T"], c["N"], dataset=c["dataset"], seed=77, with_scores=with_scores, min_len=min_len)
     labels = torch.randint(0, c["num_classes"], (B,), generator=torch.Generator().manual_seed(5))
     ref_loss, ref_logits, ref_g = _oracle_grads(sd, batch, H, labels)
 
