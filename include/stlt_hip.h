@@ -663,7 +663,8 @@ int stlt_maxpool3d_ndhwc_bwd(const float* dy, const uint8_t* argmax, int64_t B, 
  * (stlt_r3d_tape_bytes, pure host arithmetic; 256-byte aligned).
  * stlt_r3d_backward: from the tape and exactly one of dfeatures (B, 2048, To, Ho, Wo) NCDHW or dpooled (B, 2048), writes (accumulate 0)
  * or adds (accumulate != 0) the 53 weight gradients dweight[i] in the torch layout (c_out, c_in, kt, kh, kw).  dgrad_w[i] are the
- * copies of stlt_r3d_repack_all.  The video gets no gradient.  Workspace: stlt_r3d_backward_workspace_bytes. */
+ * copies of stlt_r3d_repack_all.  This entry point stops at the stem's weight gradient; the video's gradient comes from
+ * stlt_r3d_backward_inputs below.  Workspace: stlt_r3d_backward_workspace_bytes. */
 size_t stlt_r3d_tape_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
 size_t stlt_r3d_backward_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
 int stlt_r3d_repack_all(const float* const* weights, const stlt_r3d_params* p, float* const* fwd, float* const* dgrad, stlt_stream_t stream);
@@ -672,6 +673,36 @@ int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t
 int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H, int64_t W,
                       const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, void* workspace, size_t workspace_bytes,
                       stlt_stream_t stream);
+
+/* ---- Pixel gradients: the data gradient of a thin-input convolution (the stem) and the trunk's sweep down to the video ----
+ * For the forward conv x (B, T, H, W, 4) NDHWC (c_in <= 4 real channels) -> y (B, To, Ho, Wo, c_out) with kernel 7x7x7, stride
+ * (1, 2, 2), padding 3 — the only geometry these entry points take; any other kernel, padding or stride (3 included) and c_in > 4
+ * are refused with STLT_EINVAL — one dedicated kernel on v_mfma_f32_16x16x4_f32 (exact f32) writes
+ *   dx[b, t, h, w, ci] = Σ_{co, taps} dy · w.
+ * A 2x2 block of input positions (h = 2i + a, w = 2j + b) reads one dy window (to in t-3..t+3, ho in i-1..i+2, wo in j-1..j+2), so the
+ * 4 (a, b) classes x 4 channels are the 16 columns of the matrix tile and the contraction is 7·4·4·c_out long.
+ *   stlt_conv3d_repack_dgrad_thin: torch weight (c_out, c_in <= 4, 7, 7, 7) -> the thin data-gradient copy, times scale[co] (NULL: 1):
+ *     [jt 7][jh 4][jw 4][c_out / 4][column 16][4] floats (stlt_conv3d_repack_dgrad_thin_floats(d) = 1792 · c_out; 0 for a refused
+ *     descriptor), entry (jt, jh, jw, co / 4, column = (2a + b)·4 + ci, co % 4) = scale[co] · w[co][ci][6 - jt][a + 5 - 2·jh][b + 5 - 2·jw],
+ *     and 0 where that tap does not exist (jh = 3 / jw = 3 of the even classes) or ci >= c_in.
+ *   stlt_conv3d_bwd_data_thin: dx from dy (16-byte aligned, c_out a multiple of 4) and the thin copy (16-byte aligned).  dx_layout
+ *     STLT_DX_NDHWC: (B, T, H, W, 4), the padded channels ci >= c_in STORED as exactly 0; STLT_DX_NCDHW: (B, c_in, T, H, W), the padded
+ *     channels not stored at all.  The real channels are the same bits in both.  Taps outside dy read as zero.  Every dx element is
+ *     written by one thread in one fixed summation order (no atomics, no workspace): bit-identical from run to run.
+ * stlt_r3d_backward_inputs: stlt_r3d_backward with two differences.  dweight == NULL runs the input-only sweep (no weight-gradient
+ * launch is enqueued).  dvideo (B, 3, T, H, W) NCDHW, when not NULL, receives the stem's data gradient (stlt_conv3d_bwd_data_thin
+ * over the gradient at the stem's output; dgrad_w[0] is the stem's thin copy, made by stlt_conv3d_repack_dgrad_thin with the
+ * stem's BN scale γ/sqrt(var + eps)).  dweight and dvideo may not both be NULL.  With dweight given the 53 weight gradients are
+ * bit-identical to stlt_r3d_backward's.  Workspace: stlt_r3d_backward_inputs_workspace_bytes (pure host arithmetic; 0 for B <= 0). */
+#define STLT_DX_NDHWC 0
+#define STLT_DX_NCDHW 1
+size_t stlt_conv3d_repack_dgrad_thin_floats(const stlt_conv3d_desc* d);
+int stlt_conv3d_repack_dgrad_thin(const float* w, const stlt_conv3d_desc* d, const float* scale, float* out, stlt_stream_t stream);
+int stlt_conv3d_bwd_data_thin(const stlt_conv3d_desc* d, const float* dy, const float* w_dgrad_thin, float* dx, int dx_layout, stlt_stream_t stream);
+size_t stlt_r3d_backward_inputs_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
+int stlt_r3d_backward_inputs(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H,
+                             int64_t W, const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, float* dvideo,
+                             void* workspace, size_t workspace_bytes, stlt_stream_t stream);
 
 /* ---- training step (reference src/train.py:119-135: forward, loss.backward(); optimiser step further below) ----
  * stlt_train_forward runs every layer on every row — except that the last layer of each tower runs its out-proj /
@@ -927,7 +958,8 @@ int stlt_eval_average_precision(const float* scores, const float* truths, int64_
 #define STLT_K_MHSA_FUSED 13    /* fused in-projection + causal attention core (stlt_mhsa_fused_fwd): temporal tower */
 #define STLT_K_MHSA_FUSED_SPATIAL 14  /* the same kernel's non-causal launches (spatial tower) */
 #define STLT_K_ATTN_PROBS 15    /* attention probabilities (stlt_attn_probs_fwd, stlt_attn_probs_cross_fwd; one launch per layer of stlt_forward_attention / stlt_caf_forward_attention) */
-#define STLT_K_COUNT 16
+#define STLT_K_CONV_DGRAD_THIN 16  /* the thin-input data gradient (stlt_conv3d_bwd_data_thin; once per stlt_r3d_backward_inputs with dvideo) */
+#define STLT_K_COUNT 17
 /* The switch is process-wide; the records (and both calls below) belong to the device that is CURRENT when they are made: a
  * process driving several GPUs collects once per device (with that device current) before it switches timing off, or the
  * other devices' records stay queued. */

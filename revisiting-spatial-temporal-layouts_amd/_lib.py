@@ -9,7 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STLT_HIP_LIB") or os.path.join(HERE, "libstlt_hip.so")  # env override: A/B experiments only
 
 K_NAMES = ("embed", "gemm", "attn_spatial", "attn_temporal", "add_layernorm", "frames_embed", "gather_last", "ln_bwd", "attn_bwd",
-           "gelu", "embed_bwd", "optim", "misc", "mhsa_fused", "mhsa_fused_spatial", "attn_probs")
+           "gelu", "embed_bwd", "optim", "misc", "mhsa_fused", "mhsa_fused_spatial", "attn_probs", "conv_dgrad_thin")
+DX_NDHWC, DX_NCDHW = 0, 1
 FLAG_CLS_ONLY_LAST_SPATIAL = 1
 FLAG_LAST_ROW_ONLY_TEMPORAL = 2
 FLAG_SKIP_PADDING = 4
@@ -283,6 +284,12 @@ SIGNATURES = {
                                          _vp]),
     "stlt_r3d_backward": (C.c_int, [C.POINTER(R3dParams), _vp, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, _vp,
                                     C.c_size_t, _vp]),
+    "stlt_conv3d_repack_dgrad_thin_floats": (C.c_size_t, [C.POINTER(Conv3dDesc)]),
+    "stlt_conv3d_repack_dgrad_thin": (C.c_int, [_vp, C.POINTER(Conv3dDesc), _vp, _vp, _vp]),
+    "stlt_conv3d_bwd_data_thin": (C.c_int, [C.POINTER(Conv3dDesc), _vp, _vp, _vp, C.c_int, _vp]),
+    "stlt_r3d_backward_inputs_workspace_bytes": (C.c_size_t, [C.c_int64] * 4),
+    "stlt_r3d_backward_inputs": (C.c_int, [C.POINTER(R3dParams), _vp, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int,
+                                           _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib = None

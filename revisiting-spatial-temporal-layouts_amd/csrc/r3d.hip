@@ -956,6 +956,179 @@ __global__ __launch_bounds__(256) void r3d_grad_in_kernel(const float* __restric
   g[idx] = y[idx] > 0.f ? v : 0.f;
 }
 
+// ---- thin-input data gradient: the stem (c_in <= 4 stored as 4, 7x7x7, stride (1, 2, 2), pad 3) ----
+// Forward: y[b, to, ho, wo, co] = Σ x[b, to + dt - 3, 2·ho + dh - 3, 2·wo + dw - 3, ci] · w[co, ci, dt, dh, dw].  For the input position
+// (t, h = 2i + a, w = 2j + b) the taps with 2 | (a + 3 - dh) and 2 | (b + 3 - dw) reach dy at to = t - 3 + jt (jt = 6 - dt, 0..6),
+// ho = i - 1 + jh (dh = a + 5 - 2·jh, jh 0..3) and wo = j - 1 + jw (dw = b + 5 - 2·jw): the four (a, b) classes of a 2x2 block read the
+// SAME 7x4x4 dy window.  So one row of the matrix tile is a block (b, t, i, j), its 16 columns are (a, b, ci), and the contraction
+// k = (jt, jh, jw, co) is 112·c_out long; taps a class does not have (dh = -1: jh = 3 of a = 0; likewise jw = 3 of b = 0) and the
+// padded channel are zeros in the repacked weight ([jt][jh][jw][co / 4][column][co % 4], 1792·c_out floats).
+// A workgroup (4 waves) owns TH_TI x TH_TJ = 8 x 16 blocks of one (b, t): wave v the rows il = 2v, 2v + 1, one 16 x 16 MFMA block each
+// (its 16 rows are the 16 consecutive j).  Per temporal tap the dy window (11 x 19 positions x up to 64 channels) is staged ONCE into
+// LDS — positions outside dy as zeros — and the MFMA A operand is read straight from it at ((il + jh), (jl + jw)): no im2col copy.  The
+// weight streams through LDS by (jt, jh) (4 jw x 64 co x 16 columns = 16 KB).  76.6 KB of LDS: two workgroups per CU, one staging
+// while the other multiplies.  Pitch 72 floats: row li's 16-byte slot is 18·li + lg (mod 16: 2·li + lg), distinct over each
+// ds_read_b128 lane group; the weight's slot is 16·(4g + lg) + li, distinct as well.  c_out above 64 runs in channel chunks of 64
+// (the last one short, zero-filled to a multiple of 16), in order: one thread, one fixed summation order per dx element.
+constexpr int TH_TI = 8, TH_TJ = 16;
+constexpr int TH_WI = TH_TI + 3, TH_WJ = TH_TJ + 3;
+constexpr int TH_CB = 64;               // channels of dy per chunk
+constexpr int TH_P = TH_CB + 8;         // window pitch (floats)
+constexpr int TH_WIN = TH_WI * TH_WJ * TH_P;          // floats
+constexpr int TH_WS = 4 * (TH_CB / 4) * 16 * 4;       // floats: [jw][co quad][column][4]
+constexpr int TH_LDS_BYTES = (TH_WIN + TH_WS) * (int)sizeof(float);
+
+struct ThinGeom {
+  int B, T, H, W;          // dx
+  int To, Ho, Wo, N;       // dy (B, To, Ho, Wo, N), N = c_out
+  int c_in;                // real channels (<= 4)
+  int tiles_i, tiles_j;
+};
+
+template <bool NCDHW>
+__global__ __launch_bounds__(256, 2) void conv3d_dgrad_thin_kernel(const float* __restrict__ dy, const float* __restrict__ wt, ThinGeom g,
+                                                                   float* __restrict__ dx) {
+  extern __shared__ __attribute__((aligned(16))) float th_lds[];
+  float* win = th_lds;
+  float* wS = th_lds + TH_WIN;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  int q = blockIdx.x;
+  const int tj = q % g.tiles_j; q /= g.tiles_j;
+  const int ti = q % g.tiles_i; q /= g.tiles_i;
+  const int t = q % g.T;
+  const int b = q / g.T;
+  const int i0 = ti * TH_TI, j0 = tj * TH_TJ;
+  const int nq_all = g.N / 4;  // channel quads of dy
+
+  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  for (int co0 = 0; co0 < g.N; co0 += TH_CB) {
+    const int cb = min(TH_CB, g.N - co0);         // real channels of this chunk (a multiple of 4)
+    const int cbq = cb / 4, cbq_pad = (cb + 15) / 16 * 4;  // quads staged: zero-filled up to a multiple of 16 channels
+    for (int jt = 0; jt < 7; ++jt) {
+      const int to = t - 3 + jt;
+      if ((unsigned)to >= (unsigned)g.To) continue;  // the whole temporal tap lies outside dy (uniform over the workgroup)
+      __syncthreads();  // the previous tap's reads of the window are done
+      for (int idx = tid; idx < TH_WI * TH_WJ * cbq_pad; idx += 256) {
+        const int cq = idx % cbq_pad, pos = idx / cbq_pad;
+        const int wj = pos % TH_WJ, wi = pos / TH_WJ;
+        const int ho = i0 - 1 + wi, wo = j0 - 1 + wj;
+        f32x4 v{0.f, 0.f, 0.f, 0.f};
+        if (cq < cbq && (unsigned)ho < (unsigned)g.Ho && (unsigned)wo < (unsigned)g.Wo)
+          v = *reinterpret_cast<const f32x4*>(dy + ((((int64_t)b * g.To + to) * g.Ho + ho) * g.Wo + wo) * g.N + co0 + 4 * cq);
+        *reinterpret_cast<f32x4*>(win + pos * TH_P + 4 * cq) = v;
+      }
+      for (int jh = 0; jh < 4; ++jh) {
+        if (jh) __syncthreads();  // the previous (jt, jh)'s reads of the weight are done (jh = 0: the barrier above)
+        for (int idx = tid; idx < 4 * cbq_pad * 16; idx += 256) {
+          const int col = idx & 15, cq = (idx >> 4) % cbq_pad, jw = (idx >> 4) / cbq_pad;
+          f32x4 v{0.f, 0.f, 0.f, 0.f};
+          if (cq < cbq) v = *reinterpret_cast<const f32x4*>(wt + ((((int64_t)(jt * 4 + jh) * 4 + jw) * nq_all + co0 / 4 + cq) * 16 + col) * 4);
+          *reinterpret_cast<f32x4*>(wS + ((jw * (TH_CB / 4) + cq) * 16 + col) * 4) = v;
+        }
+        __syncthreads();
+        const float* a0 = win + ((2 * wave + jh) * TH_WJ + li) * TH_P + 4 * lg;
+        const float* a1 = a0 + TH_WJ * TH_P;
+        const float* bp = wS + (lg * 16 + li) * 4;
+        for (int jw = 0; jw < 4; ++jw)
+          for (int gq = 0; gq < cbq_pad / 4; ++gq) {
+            const f32x4 va = *reinterpret_cast<const f32x4*>(a0 + jw * TH_P + 16 * gq);
+            const f32x4 vb = *reinterpret_cast<const f32x4*>(a1 + jw * TH_P + 16 * gq);
+            const f32x4 vw = *reinterpret_cast<const f32x4*>(bp + (jw * (TH_CB / 4) + 4 * gq) * 64);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+              acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[s], vw[s], acc[0], 0, 0, 0);
+              acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vb[s], vw[s], acc[1], 0, 0, 0);
+            }
+          }
+      }
+    }
+  }
+
+  // lane (li, lg), register e: row jl = 4·lg + e of the wave's block r, column li = (2a + b)·4 + ci
+  const int ci = li & 3, pb = (li >> 2) & 1, pa = li >> 3;
+  if (NCDHW && ci >= g.c_in) return;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int h = 2 * (i0 + 2 * wave + r) + pa;
+    if (h >= g.H) continue;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int w = 2 * (j0 + 4 * lg + e) + pb;
+      if (w >= g.W) continue;
+      if (NCDHW)
+        dx[((((int64_t)b * g.c_in + ci) * g.T + t) * g.H + h) * g.W + w] = acc[r][e];
+      else
+        dx[((((int64_t)b * g.T + t) * g.H + h) * g.W + w) * 4 + ci] = ci < g.c_in ? acc[r][e] : 0.f;
+    }
+  }
+}
+
+// the thin copy, walked in destination order ([jt][jh][jw][co / 4][column][co % 4])
+__global__ __launch_bounds__(256) void conv3d_repack_dgrad_thin_kernel(const float* __restrict__ w, int Cout, int Cin, const float* __restrict__ scale,
+                                                                       float* __restrict__ out) {
+  const int n = 1792 * Cout;
+  for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
+    int q = idx;
+    const int e = q & 3; q >>= 2;
+    const int col = q & 15; q >>= 4;
+    const int cq = q % (Cout / 4); q /= Cout / 4;
+    const int jw = q & 3; q >>= 2;
+    const int jh = q & 3;
+    const int jt = q >> 2;
+    const int co = 4 * cq + e, ci = col & 3, pb = (col >> 2) & 1, pa = col >> 3;
+    const int dt = 6 - jt, dh = pa + 5 - 2 * jh, dw = pb + 5 - 2 * jw;
+    float v = 0.f;
+    if (ci < Cin && dh >= 0 && dw >= 0) v = (scale ? scale[co] : 1.f) * w[(((int64_t)co * Cin + ci) * 7 + dt) * 49 + dh * 7 + dw];
+    out[idx] = v;
+  }
+}
+
+// the one geometry of the thin data gradient; c_in is the forward conv's REAL channel count (<= 4)
+int check_thin_desc(const stlt_conv3d_desc* d, const char* who, ThinGeom* g) {
+  if (!d) return stlt_set_error(STLT_EINVAL, "%s: null descriptor", who);
+  if (d->B <= 0 || d->T <= 0 || d->H <= 0 || d->W <= 0 || d->c_out <= 0 || d->c_in <= 0 || d->T > (1 << 24) || d->H > (1 << 24) || d->W > (1 << 24) ||
+      d->c_out > (1 << 16))
+    return stlt_set_error(STLT_EINVAL, "%s: sizes must be positive (c_out at most 65536)", who);
+  if (d->c_in > 4) return stlt_set_error(STLT_EINVAL, "%s: the thin data gradient takes at most 4 input channels, got %lld (stlt_conv3d_bwd_data serves wider inputs)", who, (long long)d->c_in);
+  if (d->st != 1 || d->sh != 2 || d->sw != 2)
+    return stlt_set_error(STLT_EINVAL, "%s: the thin data gradient is built for stride (1, 2, 2) only, got (%lld, %lld, %lld)", who, (long long)d->st,
+                          (long long)d->sh, (long long)d->sw);
+  if (d->kt != 7 || d->kh != 7 || d->kw != 7 || d->pt != 3 || d->ph != 3 || d->pw != 3)
+    return stlt_set_error(STLT_EINVAL, "%s: the thin data gradient is built for kernel 7x7x7 with padding 3 only", who);
+  if (d->c_out % 4) return stlt_set_error(STLT_EINVAL, "%s: c_out must be a multiple of 4 (dy's rows are read as 16-byte quads), got %lld", who, (long long)d->c_out);
+  const int64_t To = d->T, Ho = (d->H - 1) / 2 + 1, Wo = (d->W - 1) / 2 + 1;
+  const int64_t tiles_i = cdiv(Ho, TH_TI), tiles_j = cdiv(Wo, TH_TJ);
+  if (d->B * d->T * tiles_i * tiles_j > 0x7fffff00LL || d->B * d->T * d->H * d->W * 4 > (1LL << 40) || d->B * To * Ho * Wo * d->c_out > (1LL << 40))
+    return stlt_set_error(STLT_EINVAL, "%s: shape too large", who);
+  if (g) *g = ThinGeom{(int)d->B, (int)d->T, (int)d->H, (int)d->W, (int)To, (int)Ho, (int)Wo, (int)d->c_out, (int)d->c_in, (int)tiles_i, (int)tiles_j};
+  return 0;
+}
+
+int launch_dgrad_thin(const ThinGeom& g, const float* dy, const float* wt, float* dx, int ncdhw, hipStream_t s) {
+  StltProfScope ps(STLT_K_CONV_DGRAD_THIN, s);
+  static StltPerDeviceInt attr_set;
+  int& set = attr_set.ref();
+  if (!set) {
+    if (hipError_t e = hipFuncSetAttribute((const void*)conv3d_dgrad_thin_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TH_LDS_BYTES); e != hipSuccess)
+      return stlt_set_error((int)e, "conv3d_dgrad_thin: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (hipError_t e = hipFuncSetAttribute((const void*)conv3d_dgrad_thin_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TH_LDS_BYTES); e != hipSuccess)
+      return stlt_set_error((int)e, "conv3d_dgrad_thin: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    set = 1;
+  }
+  const int64_t wgs = (int64_t)g.B * g.T * g.tiles_i * g.tiles_j;
+  // the formulation's FLOPs, zero taps and the padded channel included: rows (2x2 blocks, whole tiles) x 16 columns x 112·c_out
+  const double flops = 2.0 * (double)wgs * (TH_TI * TH_TJ) * 16.0 * 112.0 * g.N;
+  stlt_prof_note("dgrad_thin B=%d T=%d H=%d W=%d c_out=%d %s wgs=%lld", g.B, g.T, g.H, g.W, g.N, ncdhw ? "ncdhw" : "ndhwc", (long long)wgs);
+  stlt_prof_note_flops(flops);
+  const dim3 grid((unsigned)wgs), block(256);
+  if (ncdhw)
+    hipLaunchKernelGGL(conv3d_dgrad_thin_kernel<true>, grid, block, TH_LDS_BYTES, s, dy, wt, g, dx);
+  else
+    hipLaunchKernelGGL(conv3d_dgrad_thin_kernel<false>, grid, block, TH_LDS_BYTES, s, dy, wt, g, dx);
+  return stlt_check_launch("conv3d_dgrad_thin_kernel");
+}
+
 // ---- host plans ----
 struct SubConv { ConvGeom g; DgEpi e; int64_t w_off; };
 
@@ -1340,23 +1513,28 @@ int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t
   return 0;
 }
 
-int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H, int64_t W,
-                      const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, void* workspace, size_t workspace_bytes,
-                      stlt_stream_t stream) {
-  if (int e = check_r3d_params(p, "stlt_r3d_backward")) return e;
-  if (!dgrad_w || !tape || !dweight) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: null pointer");
-  if ((dfeatures == nullptr) == (dpooled == nullptr)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: pass exactly one of dfeatures and dpooled");
+}  // extern "C"
+
+// the trunk's reverse sweep, written once: stlt_r3d_backward (dweight, no dvideo) and stlt_r3d_backward_inputs (either or both)
+static int r3d_backward_sweep(const char* who, const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B,
+                              int64_t T, int64_t H, int64_t W, const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate,
+                              float* dvideo, void* workspace, size_t workspace_bytes, stlt_stream_t stream) {
+  if (int e = check_r3d_params(p, who)) return e;
+  if (!dgrad_w || !tape) return stlt_set_error(STLT_EINVAL, "%s: null pointer", who);
+  if ((dfeatures == nullptr) == (dpooled == nullptr)) return stlt_set_error(STLT_EINVAL, "%s: pass exactly one of dfeatures and dpooled", who);
   for (int i = 0; i < STLT_R3D_CONVS; ++i) {
-    if (!dweight[i]) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: weight gradient %d is null", i);
-    if (i > 0 && (!dgrad_w[i] || ((uintptr_t)dgrad_w[i] & 15))) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: dgrad copy %d is null or not 16-byte aligned", i);
+    if (dweight && !dweight[i]) return stlt_set_error(STLT_EINVAL, "%s: weight gradient %d is null", who, i);
+    if (i > 0 && (!dgrad_w[i] || ((uintptr_t)dgrad_w[i] & 15))) return stlt_set_error(STLT_EINVAL, "%s: dgrad copy %d is null or not 16-byte aligned", who, i);
   }
+  if (dvideo && (!dgrad_w[0] || ((uintptr_t)dgrad_w[0] & 15)))
+    return stlt_set_error(STLT_EINVAL, "%s: the stem's thin dgrad copy (dgrad_w[0], stlt_conv3d_repack_dgrad_thin) is null or not 16-byte aligned", who);
   TrunkPlan P;
-  if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: bad video shape or too small for the trunk");
-  if (tape_bytes < (size_t)P.tape_bytes) return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_backward: tape of %zu bytes, %lld needed", tape_bytes, (long long)P.tape_bytes);
+  if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "%s: bad video shape or too small for the trunk", who);
+  if (tape_bytes < (size_t)P.tape_bytes) return stlt_set_error(STLT_EWORKSPACE, "%s: tape of %zu bytes, %lld needed", who, tape_bytes, (long long)P.tape_bytes);
   const int64_t need = r3d_bwd_ws_bytes(P);
   if (!workspace || workspace_bytes < (size_t)need)
-    return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_backward: workspace of %zu bytes, %lld needed", workspace_bytes, (long long)need);
-  if (((uintptr_t)workspace & 255) || ((uintptr_t)tape & 255)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: workspace and tape must be 256-byte aligned");
+    return stlt_set_error(STLT_EWORKSPACE, "%s: workspace of %zu bytes, %lld needed", who, workspace_bytes, (long long)need);
+  if (((uintptr_t)workspace & 255) || ((uintptr_t)tape & 255)) return stlt_set_error(STLT_EINVAL, "%s: workspace and tape must be 256-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   const char* tp = (const char*)tape;
   const int64_t f = sizeof(float);
@@ -1368,7 +1546,8 @@ int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, con
   float* GS = (float*)base; base += stlt_align256(P.stem_elems * f);  // at the stem's output
   float* part = (float*)base;
   const float eps = p->bn_eps;
-  auto wgrad = [&](int i, const float* x, const float* g) {
+  auto wgrad = [&](int i, const float* x, const float* g) -> int {
+    if (!dweight) return 0;  // the input-only sweep: no weight-gradient product
     const ConvGeom& c = P.g[i];
     const int cin_w = i == 0 ? 3 : c.C;
     return launch_wgrad(c, x, g, cin_w, nullptr, p->conv[i].bn_w, p->conv[i].bn_var, eps, accumulate, dweight[i], wgrad_plan_splits(c), part, s);
@@ -1415,7 +1594,62 @@ int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, con
   const ConvGeom& s0 = P.g[0];
   const float* stem = (const float*)(tp + P.stem);
   if (int e = stlt_maxpool3d_ndhwc_bwd(G3, (const uint8_t*)(tp + P.argmax), B, s0.To, s0.Ho, s0.Wo, 64, stem, GS, stream)) return e;
-  return wgrad(0, (const float*)(tp + P.xin), GS);
+  if (int e = wgrad(0, (const float*)(tp + P.xin), GS)) return e;
+  if (!dvideo) return 0;
+  // the stem's data gradient, straight into video_frames' layout (the BN scale is folded into the thin copy)
+  const ThinGeom tg{(int)B, (int)T, (int)H, (int)W, s0.To, s0.Ho, s0.Wo, 64, 3, (int)cdiv(s0.Ho, TH_TI), (int)cdiv(s0.Wo, TH_TJ)};
+  return launch_dgrad_thin(tg, GS, dgrad_w[0], dvideo, 1, s);
+}
+
+extern "C" {
+
+int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H, int64_t W,
+                      const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, void* workspace, size_t workspace_bytes,
+                      stlt_stream_t stream) {
+  if (!dweight) {  // this entry point always writes the weight gradients
+    if (int e = check_r3d_params(p, "stlt_r3d_backward")) return e;
+    return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward: null pointer");
+  }
+  return r3d_backward_sweep("stlt_r3d_backward", p, dgrad_w, tape, tape_bytes, B, T, H, W, dfeatures, dpooled, dweight, accumulate, nullptr, workspace,
+                            workspace_bytes, stream);
+}
+
+size_t stlt_r3d_backward_inputs_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
+  return stlt_r3d_backward_workspace_bytes(B, T, H, W);  // the thin data gradient needs no scratch of its own
+}
+
+int stlt_r3d_backward_inputs(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H,
+                             int64_t W, const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, float* dvideo,
+                             void* workspace, size_t workspace_bytes, stlt_stream_t stream) {
+  if (!dweight && !dvideo) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward_inputs: dweight and dvideo are both null: nothing to compute");
+  return r3d_backward_sweep("stlt_r3d_backward_inputs", p, dgrad_w, tape, tape_bytes, B, T, H, W, dfeatures, dpooled, dweight, accumulate, dvideo, workspace,
+                            workspace_bytes, stream);
+}
+
+size_t stlt_conv3d_repack_dgrad_thin_floats(const stlt_conv3d_desc* d) {
+  if (check_thin_desc(d, "stlt_conv3d_repack_dgrad_thin_floats", nullptr)) return 0;
+  return (size_t)(1792 * d->c_out);
+}
+
+int stlt_conv3d_repack_dgrad_thin(const float* w, const stlt_conv3d_desc* d, const float* scale, float* out, stlt_stream_t stream) {
+  ThinGeom g;
+  if (int e = check_thin_desc(d, "stlt_conv3d_repack_dgrad_thin", &g)) return e;
+  if (!w || !out) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_repack_dgrad_thin: null pointer");
+  const int64_t n = 1792 * (int64_t)g.N;
+  hipLaunchKernelGGL(conv3d_repack_dgrad_thin_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 4096)), dim3(256), 0, (hipStream_t)stream, w, g.N, g.c_in,
+                     scale, out);
+  return stlt_check_launch("conv3d_repack_dgrad_thin_kernel");
+}
+
+int stlt_conv3d_bwd_data_thin(const stlt_conv3d_desc* d, const float* dy, const float* w_dgrad_thin, float* dx, int dx_layout, stlt_stream_t stream) {
+  ThinGeom g;
+  if (int e = check_thin_desc(d, "stlt_conv3d_bwd_data_thin", &g)) return e;
+  if (!dy || !w_dgrad_thin || !dx) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data_thin: null pointer");
+  if (dx_layout != STLT_DX_NDHWC && dx_layout != STLT_DX_NCDHW)
+    return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data_thin: dx_layout must be STLT_DX_NDHWC or STLT_DX_NCDHW, got %d", dx_layout);
+  if (((uintptr_t)dy & 15) || ((uintptr_t)w_dgrad_thin & 15))
+    return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data_thin: dy and w_dgrad_thin must be 16-byte aligned");
+  return launch_dgrad_thin(g, dy, w_dgrad_thin, dx, dx_layout == STLT_DX_NCDHW, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,9 @@ Differences from the reference, by design of the scope (SURVEY §2 row 17, §8f 
     adds the trunk (``modelling/resnet3d.py``) with the reference's 320 ``…resnet.*`` keys in their place (reference checkpoints then load
     with ``strict=True``); a batch with ``video_frames`` and no ``appearance_features`` runs it natively.  A frozen trunk runs without a
     tape and feeds the training composition below; a trainable one under autograd needs ``train_trunk=True`` (then its conv weights
-    train through ``resnet3d.R3dTrunkFn``), else it is an error;
+    train through ``resnet3d.R3dTrunkFn``), else it is an error.  A batch whose ``video_frames`` (or ``appearance_features``) requires
+    grad takes the differentiable composition as well, frozen model or not, and gets its gradient (the trunk through its tape path);
+    ``forward_saliency`` is that composition as an inference call with the inputs as the only gradient targets;
   * inference is one native call (``stlt_caf_forward``).  Training — with autograd enabled and trainable parameters —
     composes the same arithmetic from the op-level autograd Functions of ``ops.py`` (native forward AND backward kernels
     per op: linear, attention, add+LayerNorm, GELU, the two embedding kernels); a frozen layout branch runs through the
@@ -31,7 +33,7 @@ from .. import ops
 from .configs import MultimodalModelConfig
 from .models import (ClassificationHead, StltBackbone, _dev_ptr, _EncoderLayerParams, _EncoderStack, _layout_requires_grad, _prep_inputs, _SelfAttnParams,
                      _Workspace)
-from .resnet3d import Resnet3D
+from .resnet3d import Resnet3D, inputs_only, saliency_seed, video_saliency
 
 
 class _AttnBlock(nn.Module):
@@ -106,6 +108,11 @@ def _appearance_tokens(ab, feats, H: int, p: float):
     return x
 
 
+def _appearance_requires_grad(batch: Dict[str, torch.Tensor]) -> bool:
+    """The batch's video_frames or appearance_features are autograd leaves (or results) that want a gradient."""
+    return any(isinstance(batch.get(k), torch.Tensor) and batch[k].requires_grad for k in ("video_frames", "appearance_features"))
+
+
 def _trunk_path(owner: nn.Module, trunk: nn.Module) -> str:
     """the attribute path of the trunk's parameters for the error message (e.g. ``model.backbone.appearance_branch.resnet.resnet``)"""
     for name, m in owner.named_modules():
@@ -139,6 +146,14 @@ class TransformerResnet(nn.Module):
         feats = self.resnet._runner.run(self.resnet.resnet, batch["video_frames"], name="….resnet.resnet")[0]
         x = _appearance_tokens(self, feats, self.config.num_attention_heads, 0.1 if self.training else 0.0)
         return {"resnet3d": ops.LinearFn.apply(x[:, 0].contiguous(), self.classifier.weight, self.classifier.bias)}
+
+    def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None) -> Dict[str, torch.Tensor]:
+        """As Resnet3D.forward_saliency: {"resnet3d": logits, "target", "video_frames_grad": (B, 3, T, H, W)} from the input-only sweep of
+        the op-level Functions and the trunk (no weight-gradient product, no parameter's ``.grad`` touched).  Inference call: training mode
+        keeps the appearance encoder's dropout live and is refused."""
+        if self.training:
+            raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        return video_saliency(self, batch, target, "resnet3d")
 
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
@@ -249,6 +264,8 @@ class CrossAttentionFusionBackbone(nn.Module):
         heads = [h for h in (fusion_head, layout_head, appearance_head) if h is not None]
         if torch.is_grad_enabled() and any(q.requires_grad for mod in [self] + heads for q in mod.parameters()):
             return self.run_train(batch, fusion_head, layout_head, appearance_head)
+        if torch.is_grad_enabled() and _appearance_requires_grad(batch):  # pixel (or feature) gradients of a frozen model
+            return self.run_train(batch, fusion_head, layout_head, appearance_head)
         if self.training and self.config.hidden_dropout_prob > 0:
             # train mode without grad: nn.Dropout is still live in the reference (models.py:334,351,376): the training
             # composition runs (its Functions just execute their forward kernels under no_grad)
@@ -266,6 +283,33 @@ class CrossAttentionFusionBackbone(nn.Module):
             L.check(lib.stlt_caf_forward_flags(C.byref(p), C.byref(inp), feats.data_ptr(), ws.data_ptr(), ws.numel(), flags, ptrs[0],
                                                ptrs[1], ptrs[2], ptrs[3], torch.cuda.current_stream().cuda_stream), "stlt_caf_forward")
         return outs
+
+    def run_saliency(self, owner: nn.Module, names, batch: Dict[str, torch.Tensor], target, head, fusion_head, layout_head=None, appearance_head=None):
+        """forward_saliency of the fusion models: run_train on private leaves of the batch's inputs — boxes, scores (when present) and
+        video_frames or appearance_features — with every parameter of ``owner`` frozen (``inputs_only``), then one backward from the seeded
+        head ``head`` of ``names`` to those leaves.  -> the dict forward_saliency returns."""
+        if self.training and (self.config.hidden_dropout_prob > 0 or len(self.appearance_branch.transformer.layers) > 0):
+            raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if not batch["categories"].is_cuda:
+            raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        head = names[-1] if head is None else head
+        if head not in names:
+            raise L.StltHipError(f"forward_saliency: head must be one of {names}, got {head!r}")
+        app = "appearance_features" if "appearance_features" in batch else "video_frames"
+        if app not in batch:
+            raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))")
+        keys = ["boxes"] + (["scores"] if "scores" in batch else []) + [app]
+        leaves = {k: batch[k].detach().requires_grad_(True) for k in keys}
+        with inputs_only(owner), torch.enable_grad():
+            outs = self.run_train(dict(batch, **leaves), fusion_head, layout_head, appearance_head)
+            logits = dict(zip(names, (outs[1], outs[2], outs[0], outs[3]) if layout_head is not None else outs))
+            seed, target = saliency_seed(logits[head], target)
+            grads = torch.autograd.grad(logits[head], [leaves[k] for k in keys], seed, allow_unused=True)
+        out = {k: v.detach() for k, v in logits.items()}
+        out["target"] = target
+        for k, g in zip(keys, grads):
+            out[k + "_grad"] = g if g is not None else torch.zeros_like(leaves[k])  # a head that does not read the input (CACNF's "stlt" and the video)
+        return out
 
     def _native_args(self, batch, fusion_head, layout_head, appearance_head):
         """Marshal a batch and the parameters for the whole-path native calls (stlt_caf_forward_flags, stlt_caf_forward_attention):
@@ -356,6 +400,15 @@ class CrossAttentionFusion(nn.Module):
         (caf,), maps = self.caf_backbone.run_attention(batch, per_head, self.classifier)
         return {"caf": caf, **maps}
 
+    def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None, head=None) -> Dict[str, torch.Tensor]:
+        """The model's logits and the gradient of one raw logit per clip of head ``head`` (one of ``logit_names``; default the last) with
+        respect to every input, in one pass: -> the logits under ``logit_names``, "target", "boxes_grad" (B, T, N, 4), "scores_grad"
+        (B, T, N) when the batch has scores, and "video_frames_grad" (B, 3, T, H, W) (``appearance_trunk=True`` and ``video_frames``) or
+        "appearance_features_grad" (the batch carries precomputed features; no trunk launch).  ``target`` as in Stlt.forward_saliency.
+        Built on the op-level Functions with the inputs as the only gradient targets: no weight-gradient product, no parameter's
+        ``.grad`` touched.  Inference call: training mode with live dropout is refused."""
+        return self.caf_backbone.run_saliency(self, self.logit_names, batch, target, head, self.classifier)
+
 
 class CrossAttentionCentralNetFusion(nn.Module):
     """CACNF (models.py:501-549): ``forward(batch) -> {"stlt", "resnet3d", "caf", "ensemble"}``."""
@@ -378,6 +431,11 @@ class CrossAttentionCentralNetFusion(nn.Module):
         """As CrossAttentionFusion.forward_attention, with this model's four logits (include/stlt_hip.h: stlt_caf_forward_attention)."""
         (caf, stlt, res, ens), maps = self.backbone.run_attention(batch, per_head, self.fusion_classifier, self.layout_classifier, self.appearance_classifier)
         return {"stlt": stlt, "resnet3d": res, "caf": caf, "ensemble": ens, **maps}
+
+    def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None, head=None) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_saliency with this model's four heads; an input the chosen head does not read gets zeros."""
+        return self.backbone.run_saliency(self, self.logit_names, batch, target, head, self.fusion_classifier, self.layout_classifier,
+                                          self.appearance_classifier)
 
 
 class LateConcatenationFusion(nn.Module):
@@ -429,6 +487,10 @@ class LateConcatenationFusion(nn.Module):
         """As CrossAttentionFusion.forward_attention; LCF has no cross-modal layers, so its four fusion maps have a leading dimension of 0."""
         (lcf,), maps = self._runner.run_attention(batch, per_head, self.classifier)
         return {"lcf": lcf, **maps}
+
+    def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None, head=None) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_saliency."""
+        return self._runner.run_saliency(self, self.logit_names, batch, target, head, self.classifier)
 
 
 from .models import models_factory  # noqa: E402

@@ -14,9 +14,15 @@ parameter's storage or ``_version`` moved, or the fused optimiser (which writes 
 stepped since (``ops.raw_param_writes``).  With it off (the default) nothing changes: with autograd on, a
 trainable trunk parameter is an error that names the fix (``….resnet.requires_grad_(False)``); a frozen trunk runs without a tape and
 its consumers train on its output.
+
+Pixel gradients: a grad-enabled forward whose ``video_frames`` requires grad takes the tape path as well, with a trainable trunk
+(``train_trunk``) and with a frozen one, and ``R3dTrunkFn.backward`` returns ``video_frames.grad`` from ``stlt_r3d_backward_inputs`` (the
+stem's thin data gradient, written in the video's own layout); with no conv weight to train the sweep is input-only (no weight-gradient
+launch).  ``forward_saliency`` is that sweep as an inference call: the logits and ∂ logit / ∂ video_frames in one pass.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, List, Tuple
 
@@ -107,7 +113,8 @@ class TrunkRunner:
     """Launch state of one trunk: packed weight copies (re-made when a parameter's storage or ``_version`` changes) and the workspace.
     Held outside the module's parameters and buffers, so it never reaches a state dict; copies and pickles start empty.
     ``train_trunk``: a trainable trunk under autograd runs R3dTrunkFn; its forward and dgrad copies are re-made by one batched launch
-    whenever the weights may have changed (``_weights_key``)."""
+    whenever the weights may have changed (``_weights_key``).  A video that requires grad runs R3dTrunkFn too, frozen trunk or not: the
+    same copies, plus the stem's thin data-gradient copy (``stlt_conv3d_repack_dgrad_thin``) under the same key."""
 
     def __init__(self, train_trunk: bool = False):
         self.packed: Dict[int, Tuple[Tuple, torch.Tensor]] = {}
@@ -116,6 +123,7 @@ class TrunkRunner:
         self.train_trunk = train_trunk
         self.copies = None  # (device, forward copies, dgrad copies) of the trainable trunk: stlt_r3d_repack_all's destinations
         self.copies_key = None  # _weights_key of the weights the copies were made from
+        self.thin_key = None  # ... and of those the stem's thin copy (dgrad copies [0]) was made from; made only when a video wants its gradient
 
     @staticmethod
     def _weights_key(pairs, device):
@@ -123,9 +131,9 @@ class TrunkRunner:
         return (device, ops.raw_param_writes(),
                 tuple((t.data_ptr(), t._version) for conv, bn in pairs for t in (conv.weight, bn.weight, bn.running_var)))
 
-    def _refresh(self, trunk: nn.Sequential, p, device) -> None:
+    def _refresh(self, trunk: nn.Sequential, p, device, thin: bool = False) -> None:
         """Point p at the forward copies, re-made first (stlt_r3d_repack_all: every forward copy and every BN-scaled dgrad copy, one
-        launch) when the weights may have changed since they were made."""
+        launch) when the weights may have changed since they were made.  ``thin``: also the stem's thin data-gradient copy."""
         pairs = trunk_convs(trunk)
         key = self._weights_key(pairs, device)
         if self.copies is None or self.copies[0] != device:
@@ -133,9 +141,9 @@ class TrunkRunner:
             for i, (conv, _) in enumerate(pairs):
                 co, ci, kt, kh, kw = conv.weight.shape
                 fwd.append(torch.empty(co, kt, kh, kw, (ci + 3) // 4 * 4, device=device, dtype=torch.float32))
-                dgr.append(torch.empty(conv.weight.numel() if i else 4, device=device, dtype=torch.float32))
+                dgr.append(torch.empty(conv.weight.numel() if i else THIN_FLOATS, device=device, dtype=torch.float32))
             self.copies = (device, fwd, dgr)
-            self.copies_key = None
+            self.copies_key = self.thin_key = None
         _, fwd, dgr = self.copies
         if key != self.copies_key:
             ws = L.R3dPointers(*[_dev_ptr(conv.weight) for conv, _ in pairs])
@@ -144,6 +152,12 @@ class TrunkRunner:
                     "stlt_r3d_repack_all")
             self.copies_key = key
             self.packed.clear()  # the per-conv cache would be stale after an in-place optimiser step
+        if thin and key != self.thin_key:
+            conv, bn = pairs[0]
+            scale = (bn.weight.detach() / torch.sqrt(bn.running_var + BN_EPS)).contiguous()  # the stem's BN scale, folded into the copy
+            L.check(L.load().stlt_conv3d_repack_dgrad_thin(_dev_ptr(conv.weight), C.byref(stem_desc(1, 1, 1, 1)), scale.data_ptr(), dgr[0].data_ptr(),
+                                                           torch.cuda.current_stream().cuda_stream), "stlt_conv3d_repack_dgrad_thin")
+            self.thin_key = key
         for i, t in enumerate(fwd):
             p.conv[i].w = t.data_ptr()
 
@@ -161,10 +175,12 @@ class TrunkRunner:
         return out
 
     def run(self, trunk: nn.Sequential, video: torch.Tensor, features: bool = True, pooled: bool = False, name: str = "resnet"):
-        """-> (features (B, 2048, To, Ho, Wo) | None, pooled (B, 2048) | None); an autograd tape only with ``train_trunk`` on."""
+        """-> (features (B, 2048, To, Ho, Wo) | None, pooled (B, 2048) | None); an autograd tape with ``train_trunk`` on and a trainable
+        trunk, or whenever the video requires grad."""
         trainable = any(p.requires_grad for p in trunk.parameters())
-        with_grad = torch.is_grad_enabled() and trainable
-        if with_grad and not self.train_trunk:
+        video_grad = torch.is_grad_enabled() and isinstance(video, torch.Tensor) and video.requires_grad
+        with_grad = (torch.is_grad_enabled() and trainable) or video_grad
+        if torch.is_grad_enabled() and trainable and not self.train_trunk:
             raise L.StltHipError(
                 f"the R3D-50 trunk ({name}) has trainable parameters, but Conv3d backward is not built: freeze it with "
                 f"`{name}.requires_grad_(False)` (training then goes on through the layers after it), or run under torch.no_grad() "
@@ -181,14 +197,14 @@ class TrunkRunner:
         p.bn_eps = BN_EPS
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream().cuda_stream
-            refresh = self.train_trunk and trainable
+            refresh = (self.train_trunk and trainable) or video_grad  # the tape path reads the batched copies (the dgrad ones among them)
             for i, (conv, bn) in enumerate(trunk_convs(trunk)):
                 if abs(bn.eps - BN_EPS) > 0:
                     raise L.StltHipError(f"BatchNorm3d eps must be {BN_EPS} (resnets3d.py), got {bn.eps}")
                 pw = None if refresh else self._packed_weight(i, conv.weight).data_ptr()
                 p.conv[i] = L.R3dConv(pw, _dev_ptr(bn.weight), _dev_ptr(bn.bias), _dev_ptr(bn.running_mean), _dev_ptr(bn.running_var))
             if refresh:
-                self._refresh(trunk, p, device)
+                self._refresh(trunk, p, device, thin=video_grad)
             nbytes = int(lib.stlt_r3d_workspace_bytes(B, T, H, W))
             if nbytes == 0:
                 raise L.StltHipError(f"video_frames {tuple(video.shape)}: no trunk for this shape")
@@ -207,7 +223,9 @@ class TrunkRunner:
 class R3dTrunkFn(torch.autograd.Function):
     """The trunk with a tape: forward = stlt_r3d_train_forward (the features or the pooled features, bit for bit those of
     stlt_r3d_forward), backward = stlt_r3d_backward into the 53 conv weights' gradients (in place into a Trainer's flat buffer inside
-    its step, fresh tensors anywhere else: ops.grad_targets).  Each call owns its tape; video_frames gets no gradient."""
+    its step, fresh tensors anywhere else: ops.grad_targets).  Each call owns its tape.  When video_frames requires grad the backward is
+    stlt_r3d_backward_inputs: the same sweep, then the stem's thin data gradient into video_frames.grad (B, 3, T, H, W); with no conv
+    weight asking for a gradient it is the input-only sweep (dweight NULL: no weight-gradient launch)."""
 
     @staticmethod
     def forward(ctx, runner, p, video, pooled, *weights):
@@ -240,15 +258,90 @@ class R3dTrunkFn(torch.autograd.Function):
             raise L.StltHipError("R3dTrunkFn: the trunk's weights changed between this forward and its backward (an optimiser step or a load in "
                                  "between); run the backward before changing the weights")
         dout = dout.contiguous()
-        targets, grads = ops.grad_targets(ctx.weights, ctx.needs_input_grad[4:])
-        dws = [t if t is not None else torch.empty_like(w) for t, w in zip(targets, ctx.weights)]  # frozen convs: a scratch target
-        ws = ctx.runner.bws.get(int(lib.stlt_r3d_backward_workspace_bytes(B, T, H, W)), dout.device)
-        L.check(lib.stlt_r3d_backward(C.byref(ctx.params), L.R3dPointers(*[t.data_ptr() for t in ctx.dgrad]), ctx.tape.data_ptr(), ctx.tape.numel(),
-                                      B, T, H, W, None if ctx.pooled else dout.data_ptr(), dout.data_ptr() if ctx.pooled else None,
-                                      L.R3dPointers(*[t.data_ptr() for t in dws]), 1, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-                "stlt_r3d_backward")
+        want_video, want_weights = ctx.needs_input_grad[2], any(ctx.needs_input_grad[4:])
+        if not want_video and not want_weights:
+            ctx.tape = None
+            return (None,) * (4 + len(ctx.weights))
+        grads, dw_ptrs = (None,) * len(ctx.weights), None
+        if want_weights:
+            targets, grads = ops.grad_targets(ctx.weights, ctx.needs_input_grad[4:])
+            dws = [t if t is not None else torch.empty_like(w) for t, w in zip(targets, ctx.weights)]  # frozen convs: a scratch target
+            dw_ptrs = L.R3dPointers(*[t.data_ptr() for t in dws])
+        dgrad = L.R3dPointers(*[t.data_ptr() for t in ctx.dgrad])
+        dfeat, dpool = (None, dout.data_ptr()) if ctx.pooled else (dout.data_ptr(), None)
+        stream = torch.cuda.current_stream().cuda_stream
+        dvideo = None
+        if want_video:
+            if ctx.runner.thin_key != ctx.copies_key:
+                raise L.StltHipError("R3dTrunkFn: the stem's thin data-gradient copy does not belong to this forward's weights")
+            dvideo = torch.empty(B, 3, T, H, W, device=dout.device, dtype=torch.float32)
+            ws = ctx.runner.bws.get(int(lib.stlt_r3d_backward_inputs_workspace_bytes(B, T, H, W)), dout.device)
+            L.check(lib.stlt_r3d_backward_inputs(C.byref(ctx.params), dgrad, ctx.tape.data_ptr(), ctx.tape.numel(), B, T, H, W, dfeat, dpool, dw_ptrs, 1,
+                                                 dvideo.data_ptr(), ws.data_ptr(), ws.numel(), stream), "stlt_r3d_backward_inputs")
+        else:
+            ws = ctx.runner.bws.get(int(lib.stlt_r3d_backward_workspace_bytes(B, T, H, W)), dout.device)
+            L.check(lib.stlt_r3d_backward(C.byref(ctx.params), dgrad, ctx.tape.data_ptr(), ctx.tape.numel(), B, T, H, W, dfeat, dpool, dw_ptrs, 1,
+                                          ws.data_ptr(), ws.numel(), stream), "stlt_r3d_backward")
         ctx.tape = None
-        return (None, None, None, None, *grads)
+        return (None, None, dvideo, None, *grads)
+
+
+def stem_desc(B: int, T: int, H: int, W: int) -> "L.Conv3dDesc":
+    """The stem as the thin data gradient's descriptor (real input channels: 3)."""
+    return L.Conv3dDesc(B, T, H, W, 3, 64, 7, 7, 7, 1, 2, 2, 3, 3, 3)
+
+
+THIN_FLOATS = 1792 * 64  # stlt_conv3d_repack_dgrad_thin_floats of the stem: [jt 7][jh 4][jw 4][co / 4][column 16][4]
+
+
+@contextlib.contextmanager
+def inputs_only(module: nn.Module):
+    """Every parameter of ``module`` frozen for the duration, then as it was: the native Functions form a weight gradient only for a
+    parameter that requires grad, so a backward inside reaches the inputs alone (no weight-gradient product, no ``.grad`` touched)."""
+    was = [(q, q.requires_grad) for q in module.parameters()]
+    for q, _ in was:
+        q.requires_grad_(False)
+    try:
+        yield
+    finally:
+        for q, r in was:
+            q.requires_grad_(r)
+
+
+def saliency_seed(logits: torch.Tensor, target, who: str = "forward_saliency"):
+    """``target`` of a forward_saliency call (None: top-1; int64 (B,): that class; float (B, K): the seed itself) -> (seed (B, K), target as
+    returned), by stlt_saliency_seed, as Stlt.forward_saliency forms them."""
+    B, K = logits.shape
+    device = logits.device
+    if isinstance(target, torch.Tensor) and target.is_floating_point():
+        if tuple(target.shape) != (B, K) or target.device != device:
+            raise L.StltHipError(f"{who}: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
+        return target.detach().to(torch.float32).contiguous(), target
+    tgt = None
+    if target is not None:
+        if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
+            raise L.StltHipError(f"{who}: target is None, an int64 ({B},) tensor or a float ({B}, {K}) tensor on the batch's device")
+        tgt = target.contiguous()
+    seed = torch.empty(B, K, device=device, dtype=torch.float32)
+    logits = logits.detach().contiguous()
+    with torch.cuda.device(device):
+        L.check(L.load().stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), B, K, seed.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream), "stlt_saliency_seed")
+    return seed, (seed.argmax(dim=1) if target is None else target)
+
+
+def video_saliency(model: nn.Module, batch: Dict[str, torch.Tensor], target, name: str) -> Dict[str, torch.Tensor]:
+    """forward_saliency of a video-only model: its forward on a private leaf of ``video_frames`` with every parameter frozen
+    (``inputs_only``), the seed, and the input-only sweep."""
+    video = batch["video_frames"]
+    if not isinstance(video, torch.Tensor) or not video.is_cuda:
+        raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+    leaf = video.detach().requires_grad_(True)
+    with inputs_only(model), torch.enable_grad():
+        logits = model.forward(dict(batch, video_frames=leaf))[name]
+        seed, target = saliency_seed(logits, target)
+        (dvideo,) = torch.autograd.grad(logits, leaf, seed)
+    return {name: logits.detach(), "target": target, "video_frames_grad": dvideo}
 
 
 def _trunk_out(n: int, stem_stride: int = 1) -> int:
@@ -302,3 +395,13 @@ class Resnet3D(nn.Module):
     def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         _, pooled = self._runner.run(self.resnet, batch["video_frames"], features=False, pooled=True, name=self.trunk_name)
         return {"resnet3d": ops.LinearFn.apply(pooled, self.classifier.weight, self.classifier.bias)}
+
+    def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None) -> Dict[str, torch.Tensor]:
+        """The model's logits and the gradient of one raw logit per clip with respect to the pixels, in one pass: what the reference gives
+        for ``video_frames.requires_grad_()`` followed by ``logits[b, target[b]].backward()``.  The trunk's tape forward, stlt_saliency_seed,
+        then stlt_r3d_backward_inputs with dweight NULL — the input-only sweep: no weight-gradient launch, no parameter's ``.grad`` touched,
+        whether or not the parameters are trainable (``train_trunk`` is not needed).
+        -> {"resnet3d": (B, num_classes) logits, "target": the selected classes, "video_frames_grad": (B, 3, T, H, W) float32}.
+        ``target`` as in Stlt.forward_saliency: None (each clip's top-1 class), an int64 (B,) tensor, or a float (B, num_classes) seed.
+        Inference call; this model has no dropout, so there is none to refuse."""
+        return video_saliency(self, batch, target, "resnet3d")
