@@ -588,7 +588,10 @@ int stlt_caf_forward_attention(const stlt_caf_params* p, const stlt_inputs* in, 
  * n_split splits the contraction: 1 = whole tiles; > 1 = that many k-ranges, whose partial products go to `workspace`
  * (stlt_conv3d_workspace_bytes(d, n_split) bytes) and are summed in split order by a second launch — deterministic, bit-identical
  * from run to run; 0 = the library's plan for the shape (host arithmetic over the shape alone), split only when the workspace lent
- * holds what the plan needs. */
+ * holds what the plan needs.  An explicit n_split is a request: the contraction has ceil(K / 32) k-slabs, a request above that is
+ * clamped to it, and the ranges are ceil(slabs / n_split) slabs each, so the launch (and the workspace query, which counts the
+ * ranges actually launched) can come out below the request.  The data gradient clamps per parity class, and its query is the
+ * largest class's need. */
 typedef struct {
   int64_t B, T, H, W, c_in;   /* input (B, T, H, W, c_in) NDHWC */
   int64_t c_out;

@@ -334,6 +334,14 @@ int check_desc(const stlt_conv3d_desc* d, ConvGeom* g) {
 
 int64_t conv_split_bytes(const ConvGeom& g, int64_t splits) { return splits > 1 ? splits * (int64_t)g.M * g.N * (int64_t)sizeof(float) : 0; }
 
+// the k-ranges an explicit request of `splits` becomes over `slabs` k-slabs, as launch_conv and launch_dgrad divide them: at most one
+// per slab, every range cdiv(slabs, splits) slabs long (the last may be shorter), so the count can come out below the request
+inline int64_t conv_clamp_splits(int64_t slabs, int64_t splits) {
+  if (slabs <= 0 || splits <= 1) return 1;
+  if (splits > slabs) splits = slabs;
+  return cdiv(slabs, cdiv(slabs, splits));
+}
+
 int launch_conv(const ConvGeom& g, const float* x, const float* w, const float* bn_w, const float* bn_b, const float* bn_mean, const float* bn_var,
                 float eps, const float* res, int relu, float* y, int64_t splits, float* part, hipStream_t s) {
   const int bn = conv_bn_tile(g.N);
@@ -422,7 +430,7 @@ extern "C" {
 size_t stlt_conv3d_workspace_bytes(const stlt_conv3d_desc* d, int n_split) {
   ConvGeom g;
   if (check_desc(d, &g)) return 0;
-  const int64_t splits = n_split <= 0 ? conv_plan_splits(g.M, g.N, g.K) : n_split;
+  const int64_t splits = n_split <= 0 ? conv_plan_splits(g.M, g.N, g.K) : conv_clamp_splits(cdiv(g.K, CK), n_split);
   return (size_t)conv_split_bytes(g, splits);
 }
 
@@ -435,7 +443,7 @@ int stlt_conv3d_fwd(const stlt_conv3d_desc* d, const float* x, const float* w, c
   if (bn_w && (!bn_b || !bn_mean || !bn_var)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_fwd: BatchNorm needs all four of weight, bias, running mean, running var");
   if (((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_fwd: x and w must be 16-byte aligned");
   if (n_split < 0 || n_split > 1024) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_fwd: n_split must lie in [0, 1024]");
-  int64_t splits = n_split == 0 ? conv_plan_splits(g.M, g.N, g.K) : n_split;
+  int64_t splits = n_split == 0 ? conv_plan_splits(g.M, g.N, g.K) : conv_clamp_splits(cdiv(g.K, CK), n_split);
   if (n_split == 0 && (!workspace || workspace_bytes < (size_t)conv_split_bytes(g, splits))) splits = 1;  // automatic: split only into lent workspace
   if (splits > 1 && (!workspace || workspace_bytes < (size_t)conv_split_bytes(g, splits)))
     return stlt_set_error(STLT_EWORKSPACE, "stlt_conv3d_fwd: %lld splits need %lld workspace bytes, %zu lent", (long long)splits,
@@ -1339,7 +1347,7 @@ size_t stlt_conv3d_bwd_data_workspace_bytes(const stlt_conv3d_desc* d, int n_spl
   const int n = dgrad_plan(g, sub);
   int64_t mx = 0;
   for (int i = 0; i < n; ++i)
-    if (sub[i].g.K > 0 && n_split > 1) mx = std::max(mx, conv_split_bytes(sub[i].g, std::min<int64_t>(n_split, cdiv(sub[i].g.K, CK))));
+    if (sub[i].g.K > 0 && n_split > 1) mx = std::max(mx, conv_split_bytes(sub[i].g, conv_clamp_splits(cdiv(sub[i].g.K, CK), n_split)));
   return (size_t)mx;
 }
 

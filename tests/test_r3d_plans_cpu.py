@@ -4,11 +4,15 @@ split launch needs one slab of partial sums per split, so workspace bytes ÷ sla
 - each splitting op-level case of tests/test_r3d_gpu.py and tests/test_r3d_train_gpu.py reaches the count its comment names
   (PLANNED_SPLITS), so a change of the plans cannot make a case stop splitting unnoticed;
 - the whole-trunk sweep of tests/test_r3d_shapes_gpu.py reaches an unsplit and a >= 32-split forward, a >= 200-split weight gradient, a
-  split stride-2 data gradient, a stride-2 parity class without rows and odd input extents under stride 2 in t, h and w."""
+  split stride-2 data gradient, a stride-2 parity class without rows and odd input extents under stride 2 in t, h and w;
+- the general cases of tests/test_conv3d_general_gpu.py reach what their table says (negative sub-padding, unread planes, per-class split
+  clamping), and the forward, data-gradient and weight-gradient workspace queries equal what an enumeration of the convolution gives."""
 import ctypes
 
 import pytest
+import torch
 
+import test_conv3d_general_gpu as GEN
 import test_r3d_gpu as FWD
 import test_r3d_shapes_gpu as SWEEP
 import test_r3d_train_gpu as BWD
@@ -120,3 +124,109 @@ def test_sweep_reaches_the_plans(pkg):
     assert wg_max >= 200, wg_max
     assert dg_s2_split and rowless
     assert all(odd), odd
+
+
+# ---- the general op-level cases of tests/test_conv3d_general_gpu.py: what each reaches, and the three workspace queries, against an
+# enumeration of the convolution itself (which output positions read which input positions through which taps) ----
+def parity_classes(n, k, s, p):
+    """One dimension of a data gradient by brute force: every (input i, tap d, output o) with o·s - p + d = i, o unbounded (a dy index
+    outside [0, To) reads as zero), grouped by i mod s.  Per class: rows (inputs 0 <= i < n of that residue), taps (distinct d), and
+    first = the lowest dy index a row reads, relative to the row's own index a = i // s (the same for every row of a class)."""
+    out = []
+    for r in range(s):
+        rows = [i for i in range(n) if i % s == r]
+        rel = {}
+        for i in range(r, r + 4 * s, s):  # four rows suffice to see that the pattern does not depend on the row
+            reach = [(d, (i + p - d) // s) for d in range(k) if (i + p - d) % s == 0]
+            rel.setdefault("taps", sorted(d for d, _ in reach))
+            assert rel["taps"] == sorted(d for d, _ in reach)
+            first = min(o for _, o in reach) - i // s if reach else None
+            assert rel.setdefault("first", first) == first
+        out.append({"rows": len(rows), "taps": len(rel["taps"]), "first": rel["first"]})
+    return out
+
+
+def _clamp(n, slabs):
+    """an explicit request of n ranges over `slabs` slabs of 32, as the launchers divide them"""
+    if slabs == 0 or n <= 1:
+        return 1
+    per = -(-slabs // min(n, slabs))
+    return -(-slabs // per)
+
+
+def _general_desc(pkg, case):
+    B, Ci, T, H, W, Co, k, s, p, _ = GEN.CASES[case]
+    return pkg._lib.Conv3dDesc(B, T, H, W, Ci, Co, *k, *s, *p), (B, Ci, T, H, W, Co, k, s, p)
+
+
+@pytest.mark.parametrize("case", GEN.DGRAD)
+def test_general_dgrad_workspace_matches_the_enumerated_classes(pkg, case):
+    lib = pkg._lib.load()
+    d, (B, Ci, T, H, W, Co, k, s, p) = _general_desc(pkg, case)
+    per_dim = [parity_classes(n, kk, ss, pp) for n, kk, ss, pp in zip((T, H, W), k, s, p)]
+    classes = [(B * a["rows"] * b["rows"] * c["rows"], a["taps"] * b["taps"] * c["taps"] * Co) for a in per_dim[0] for b in per_dim[1] for c in per_dim[2]]
+    assert sum(M for M, _ in classes) == B * T * H * W and sum(K for _, K in classes) == k[0] * k[1] * k[2] * Co
+    for n in (1, 2, 3, 1024):
+        want = 0
+        for M, K in classes:
+            splits = _clamp(n, -(-K // 32))
+            want = max(want, splits * M * Ci * 4 if splits > 1 else 0)
+        assert dgrad_bytes(lib, d, n) == want, (case, n)
+    assert dgrad_bytes(lib, d, 1) == 0
+
+
+@pytest.mark.parametrize("case", GEN.ALL)
+def test_general_forward_and_wgrad_workspace(pkg, case):
+    lib = pkg._lib.load()
+    d, (B, Ci, T, H, W, Co, k, s, p) = _general_desc(pkg, case)
+    M, _ = _dims(B, T, H, W, Co, k, s, p)
+    K = k[0] * k[1] * k[2] * Ci
+    for n in (1, 2, 3, 1024):
+        splits = _clamp(n, -(-K // 32))
+        assert int(lib.stlt_conv3d_workspace_bytes(ctypes.byref(d), n)) == (splits * M * Co * 4 if splits > 1 else 0), (case, n)
+        if case in GEN.WGRAD:  # the weight gradient always goes through its partial slabs: one (c_out, K) slab per range of m-slabs
+            assert int(lib.stlt_conv3d_bwd_weight_workspace_bytes(ctypes.byref(d), n)) == _clamp(n, -(-M // 32)) * Co * K * 4, (case, n)
+    assert int(lib.stlt_conv3d_workspace_bytes(ctypes.byref(d), 1)) == 0
+
+
+def test_general_cases_reach_what_they_claim():
+    def dims(case):
+        B, Ci, T, H, W, Co, k, s, p, n_split = GEN.CASES[case]
+        return [parity_classes(n, kk, ss, pp) for n, kk, ss, pp in zip((T, H, W), k, s, p)], Co, n_split
+
+    # negative sub-padding: a class whose rows start reading dy one past their own index, in t, h and w
+    for case in ("k345_s2_p234_negpad", "k322_s2_p211_negpad"):
+        per_dim, _, _ = dims(case)
+        assert all(any(c["first"] == 1 for c in dim) for dim in per_dim), (case, per_dim)
+    per_dim, _, _ = dims("k322_s2_p211_negpad")
+    assert all(any(c["first"] == 1 and c["taps"] == 1 for c in dim) for dim in per_dim)
+    # planes no window reads, in t, h and w; the other data-gradient cases have none where the table does not say so
+    B, Ci, T, H, W, Co, k, s, p, _ = GEN.CASES["k222_s2_p000_unread"]
+    assert [GEN.unread_planes(n, kk, ss, pp) for n, kk, ss, pp in zip((T, H, W), k, s, p)] == [[T - 1], [H - 1], [W - 1]]
+    B, Ci, T, H, W, Co, k, s, p, _ = GEN.CASES["k222_s3_p011"]
+    assert all(GEN.unread_planes(n, kk, ss, pp) for n, kk, ss, pp in zip((T, H, W), k, s, p))  # stride above the kernel: gaps
+    # even kernels under stride 2: every class has taps, and one explicit request of 3 becomes different counts in different classes
+    per_dim, Co, n_split = dims("k234_s2_p011_split3")
+    taps = sorted({a["taps"] * b["taps"] * c["taps"] for a in per_dim[0] for b in per_dim[1] for c in per_dim[2]})
+    assert taps == [2, 4] and n_split == 3
+    assert sorted({_clamp(n_split, -(-t * Co // 32)) for t in taps}) == [2, 3]
+    assert GEN.CASES["k234_s2_p011"][:9] == GEN.CASES["k234_s2_p011_split3"][:9]
+    # stride 1: the data gradient's padding is k - 1 - p, so first = -(k - 1 - p): "full" (p = 0) and none (p = k - 1)
+    assert [c[0]["first"] for c in dims("k333_p000_valid")[0]] == [-2, -2, -2]
+    assert [c[0]["first"] for c in dims("k333_p222_grow")[0]] == [0, 0, 0]
+    # no exchange of two dimensions maps a case onto itself
+    for case, (B, Ci, T, H, W, Co, k, s, p, _) in GEN.CASES.items():
+        sig = list(zip((T, H, W), k, s, p))
+        assert len(set(sig)) == 3, (case, sig)
+    # which families run which cases
+    assert set(GEN.ALL) - set(GEN.WGRAD) == {"k212_cout5"}
+    assert set(GEN.WGRAD) - set(GEN.DGRAD) == {"k133_s122_p011", "k151_s213_p040", "k222_s3_p011"}
+
+
+@pytest.mark.parametrize("case", GEN.ALL)
+def test_general_integer_references_stay_exact(case):
+    """the integer variant's float64 references of |x|, |w|, |dy| bound every partial sum of the fp32 kernels: below 2^24, so exact"""
+    R = GEN.references(case, integer=True)
+    assert max(R[key].max().item() for key in ("y_mag", "dx_mag", "dw_mag")) < 2 ** 24
+    x, w, dy = GEN.inputs(case, integer=True)
+    assert all(t.abs().max().item() == 2 and torch.equal(t, t.round()) for t in (x, w, dy))
