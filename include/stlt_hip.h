@@ -757,6 +757,68 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* grads, c
                                float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, float* d_boxes, float* d_scores,
                                stlt_stream_t stream);
 
+/* ---- attention relevance: which object, in which frame, a prediction rests on (gradient-weighted attention rollout: Chefer, Gur, Wolf,
+ * "Generic Attention-model Explainability", 2021).  On the reference this takes need_weights=True on the nn.MultiheadAttention layers of
+ * models.py:46-55,118-128, retain_grad on every layer's weights, a backward from the logit and a Python loop over the layers; here every
+ * ingredient lies in memory during the input-only reverse sweep: the tape holds each layer's packed QKV, and the gradient wrt the attention
+ * core's output (dctx) is in scratch right before the layer's attention backward. ---- */
+
+/* Gradient-weighted attention probabilities of one layer, averaged over the heads:
+ *   abar[s,i,j] = (1/H) * sum_h max( P_h[s,i,j] * G_h[s,i,j], 0 ),   G_h[s,i,j] = dctx_h[s,i,:] · v_h[s,j,:]
+ * qkv (S*L, 3*H*dh) packed q | k | v, dctx (S*L, H*dh) the gradient wrt the attention core's output, kpm (S*L) bytes (1 = padded key), abar (S, L, L).
+ * P_h is exactly what stlt_attn_probs_fwd defines with per_head == 1: the same masks, a masked entry exactly 0, a fully masked row zeros, query
+ * rows not filtered by kpm.  G_h is the gradient wrt P_h taken as an independent variable (ctx_h = P_h·V_h, models.py:46-55 through
+ * F.multi_head_attention_forward), dropout off.  Every element of abar is written; masked entries are exactly 0.  The heads are summed in
+ * their order in registers (no atomics): the same bits on every run.
+ * 1 <= L <= 256, 1 <= dh <= 256 (the domain of stlt_attn_core_bwd).  dh == 64 with L <= 64 (every released checkpoint, every layout of the
+ * reference) runs on the MFMA kernel of csrc/attn_grad_probs.hip (stlt_attn_probs_fwd's dataflow with a second pair of operands, V and dctx),
+ * everything else on its vector-ALU kernel.
+ * Alignment: dh % 4 == 0 (16-byte reads, both kernels): qkv and dctx 16 bytes (refused otherwise); other dh: 4 bytes; abar 4 bytes; kpm bytes.
+ * Every bad argument is STLT_EINVAL with a message and launches nothing. */
+int stlt_attn_grad_probs(const float* qkv, const float* dctx, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh,
+                         float* abar, stlt_stream_t stream);
+
+/* Rollout of the layers' maps through the residual connections: abar (n_layers, S, L, L) -> R (S, L, L),
+ *   R_0 = I,   R_l = R_{l-1} + abar_l · R_{l-1}   for l = 1 .. n_layers    (layer 1 is abar[0], the layer next to the input)
+ * ONE launch for the whole chain at every length: the columns of R never mix, so a workgroup keeps a block of columns of an item's R in LDS
+ * (ping-pong) while the layers stream in from memory — every column for L <= 64 (several items per workgroup when L is small), blocks of 16
+ * columns for 64 < L <= 256; no second buffer is needed from the caller at any length.  fp32 FMA over k in ascending order: the same bits
+ * on every run.  n_layers == 0 writes the identity (abar may then be NULL).  0 <= n_layers <= 64, 1 <= L <= 256; abar, R 4 bytes.
+ * Every bad argument is STLT_EINVAL with a message and launches nothing. */
+int stlt_attn_rollout(const float* abar, int64_t n_layers, int64_t S, int64_t L, float* R, stlt_stream_t stream);
+
+/* Relevance of object slot n of frame t for clip b's prediction:
+ *   rel[b,t,n] = r_temporal[b, lengths[b]-1, t] * r_spatial[b,t,0,n]
+ * r_temporal (B, T, T) and r_spatial (B*T, N, N) are the two towers' rollouts.  Row 0 of a frame is its CLS token, the row the frames embedding
+ * reads (models.py:79); row lengths[b]-1 of a clip is the frame the head reads (models.py:189-192).  rel (B, T, N); a length outside
+ * 1 ... T makes the clip's entries NaN (the convention of stlt_loss_fwd_bwd).  Pointers 4 bytes, lengths (int64) 8; STLT_EINVAL otherwise. */
+int stlt_relevance_combine(const float* r_temporal, const float* r_spatial, const int64_t* lengths, int64_t B, int64_t T, int64_t N, float* rel,
+                           stlt_stream_t stream);
+
+typedef struct {
+  float *abar_spatial;     /* (n_spatial, B*T, N, N): every spatial layer's gradient-weighted map; NULL only when n_spatial == 0 */
+  float *abar_temporal;    /* (n_temporal, B, T, T); NULL only when n_temporal == 0 */
+  float *rollout_spatial;  /* (B, T, N, N) */
+  float *rollout_temporal; /* (B, T, T)    */
+  float *relevance;        /* (B, T, N)    */
+} stlt_relevance_maps;
+
+/* The relevance of the objects of a batch for the objective whose gradient wrt the logits is `dlogits` (stlt_saliency_seed: one raw logit per
+ * clip), on the tape of a stlt_train_forward with dropout 0: the arguments of stlt_train_backward_inputs without the gradient table and
+ * without d_boxes / d_scores, plus the sinks.  It runs the input-only sweep (no weight-gradient product, no parameter reduction, no side
+ * stream) with one stlt_attn_grad_probs launch on (the layer's packed QKV, dctx) immediately before each attention backward, stops once the
+ * first spatial layer's map is written (the layer-0 input product and the embedding backward are not needed), then launches the two rollouts
+ * and the combine.  All five maps are overwritten.  Entries of padded frames and padded object slots of `relevance` are exactly 0: a padded key's
+ * column of every abar is 0 and the temporal mask is causal, so the rollouts' entries that the combine reads there are sums of exact zeros.
+ * In the last layer of a tower only the rows that are read afterwards (the CLS rows / frame lengths-1) carry a gradient: the other rows of that
+ * layer's abar are exactly 0, as autograd has them.
+ * STLT_EINVAL before any launch: STLT_FLAG_SKIP_PADDING (the maps have the padded geometry), dropout_p != 0, STLT_FLAG_TRAIN_UPPER_ONLY /
+ * _LOWER_ONLY / _BACKBONE, N or T above 256, a NULL or misaligned (4 bytes) map.  tape / scratch: as stlt_train_backward.
+ * No allocation, no synchronisation, capturable.  Profiling: the maps under STLT_K_ATTN_PROBS, rollouts and combine under STLT_K_MISC. */
+int stlt_train_backward_relevance(const stlt_params* p, const stlt_inputs* in, const void* tape, size_t tape_bytes, void* scratch,
+                                  size_t scratch_bytes, const float* dlogits, float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx,
+                                  const stlt_relevance_maps* maps, stlt_stream_t stream);
+
 /* ---- optimiser step of the training loop (reference train.py:128-131 with utils/train_inference_utils.py:37-54) ----
  * The reverse sweep writes all parameter gradients into ONE flat fp32 buffer (what a data-parallel run all-reduces).
  * stlt_grad_norm: out[0] = ||g||_2 over the n floats, out[1] = min(1, max_norm / (out[0] + 1e-6)) — the factor
@@ -957,10 +1019,10 @@ int stlt_eval_average_precision(const float* scores, const float* truths, int64_
 #define STLT_K_GELU 9          /* stand-alone GELU forward (training tape) / backward */
 #define STLT_K_EMBED_BWD 10    /* embedding / frames-embedding backward */
 #define STLT_K_OPTIM 11        /* criterion, gradient norm, AdamW */
-#define STLT_K_MISC 12         /* row gathers / scatters, column sums, ragged index, the head's small products */
+#define STLT_K_MISC 12         /* row gathers / scatters, column sums, ragged index, the head's small products, relevance rollouts and combine */
 #define STLT_K_MHSA_FUSED 13    /* fused in-projection + causal attention core (stlt_mhsa_fused_fwd): temporal tower */
 #define STLT_K_MHSA_FUSED_SPATIAL 14  /* the same kernel's non-causal launches (spatial tower) */
-#define STLT_K_ATTN_PROBS 15    /* attention probabilities (stlt_attn_probs_fwd, stlt_attn_probs_cross_fwd; one launch per layer of stlt_forward_attention / stlt_caf_forward_attention) */
+#define STLT_K_ATTN_PROBS 15    /* attention probabilities (stlt_attn_probs_fwd, stlt_attn_probs_cross_fwd; one launch per layer of stlt_forward_attention / stlt_caf_forward_attention) and their gradient-weighted form (stlt_attn_grad_probs; one launch per layer of stlt_train_backward_relevance) */
 #define STLT_K_CONV_DGRAD_THIN 16  /* the thin-input data gradient (stlt_conv3d_bwd_data_thin; once per stlt_r3d_backward_inputs with dvideo) */
 #define STLT_K_COUNT 17
 /* The switch is process-wide; the records (and both calls below) belong to the device that is CURRENT when they are made: a

@@ -89,6 +89,11 @@ class CafAttentionMaps(C.Structure):
                                    "fusion_appearance")]
 
 
+class RelevanceMaps(C.Structure):
+    """stlt_relevance_maps: the sinks of stlt_train_backward_relevance"""
+    _fields_ = [(n, _vp) for n in ("abar_spatial", "abar_temporal", "rollout_spatial", "rollout_temporal", "relevance")]
+
+
 class Inputs(C.Structure):
     _fields_ = [("B", C.c_int64), ("T", C.c_int64), ("N", C.c_int64)] + [
         (n, _vp) for n in ("categories", "boxes", "scores", "kpm_boxes", "frame_types", "kpm_frames", "lengths")] + [
@@ -214,6 +219,11 @@ SIGNATURES = {
                                       C.c_size_t, _vp, C.c_float, C.c_uint64, C.c_int, _vp, _vp]),
     "stlt_train_backward_inputs": (C.c_int, [C.POINTER(Params), C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, _vp,
                                              C.c_size_t, _vp, C.c_float, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp]),
+    "stlt_attn_grad_probs": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_attn_rollout": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_relevance_combine": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_train_backward_relevance": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_float, C.c_uint64, C.c_int,
+                                                _vp, C.POINTER(RelevanceMaps), _vp]),
     "stlt_embed_bwd_inputs": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "stlt_saliency_seed": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "stlt_linear_bwd_scratch_bytes": (C.c_size_t, [C.c_int64]),

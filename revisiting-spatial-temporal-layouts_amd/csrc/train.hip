@@ -319,13 +319,22 @@ struct Tower {
   const AttnBwdRagged* rgp() const { return ragged ? &rg : nullptr; }
 };
 
+// Relevance sink of a tower's reverse sweep (stlt_train_backward_relevance), carried the way LayerOpts carries the probabilities sink through
+// the forward towers: layer l's gradient-weighted attention map (attn_grad_probs.hip) goes to abar + l * S*L*L, written from the layer's
+// packed QKV on the tape and dctx right before its attention backward.  stop_at_first: the sweep needs nothing below layer 0's map, so the
+// layer returns once it is written.  No sink (every other entry point): not one launch more or less.
+struct RelSink { float* abar; bool stop_at_first; };
+static int relevance_map(const Tower& tw, int64_t l, const float* qkv, const float* dctx, const RelSink& rel, hipStream_t s) {
+  return launch_attn_grad_probs(qkv, dctx, tw.kpm, tw.causal, tw.S, tw.L, tw.H, tw.d / tw.H, rel.abar + l * tw.S * tw.L * tw.L, s);
+}
+
 // backward of layer l of a tower.  dy: gradient wrt the layer output (M,d) in ts.A; on return ts.A holds the gradient wrt the layer
 // input.  The layer takes the queue's next set of operand buffers — bufB / bufD / bufE (M,d), bufQ (M,3d), bufH (M,4d), scratch with zero
 // row padding — waiting for the flush that still reads it, if any; ts.C (M,d) is chain-only scratch.
 // The four output gradients of the layer's Linears stay alive until the end of the layer, where their weight-gradient products are left with the
 // queue: df in bufD / da in bufE (dropout off: df in bufB, the residual-path gradient — StltHalfBwd::branch), du in bufH, dqkv in bufQ.
 static int layer_backward(const Tower& tw, int64_t l, const stlt_layer_params* g, const TowerScratch& ts, const Scratch& sc, StltDrop dr,
-                          hipStream_t s, DwQueue& q) {
+                          hipStream_t s, DwQueue& q, const RelSink* rel = nullptr) {
   const stlt_layer_params& lp = tw.layers[l];
   const stlt_layer_params gl = g ? *g : stlt_layer_params{};  // null members are skipped
   const LayerTape& t = tw.tape[l];
@@ -342,6 +351,10 @@ static int layer_backward(const Tower& tw, int64_t l, const stlt_layer_params* g
   // x1 = LN1(x + drop(a)), a = ctx·Woᵀ + bo: ds1 (in bufB when dropout is on: its ds2 is dead by then), da in bufE, bufC = dctx
   const StltHalfBwd att{dr.thr ? bufB : bufE, bufE, nullptr, bufC, sc.rs, ffn.wt, ffn.wt_floats};
   TRY(stlt_attn_half_bwd_train(attn_half(lp), attn_half(gl), bufC, t.x, t.a, 1e-5f, M, d, dr, site0 + 1, nullptr, att, s));
+  if (rel) {
+    TRY(relevance_map(tw, l, t.qkv, bufC, *rel, s));
+    if (rel->stop_at_first && l == 0) return 0;
+  }
   // ctx = attention(qkv) with dropout on the probabilities
   TRY(launch_attn_bwd(t.qkv, bufC, tw.kpm, tw.causal, tw.S, tw.L, tw.H, d / tw.H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), tw.rgp()));  // bufQ = dqkv; in_proj_b += colsum(dqkv)
   // qkv = x·Winᵀ + bin
@@ -408,7 +421,7 @@ static int zero_rows(float* buf, int64_t width, int64_t r0, int64_t r1, hipStrea
 // input rows.  Scratch roles as in layer_backward, on the tower's own set; the gradient-side operands of the weight-gradient products are
 // zeroed between n and its round-up to 32 first (those rows belong to other layers' data in the shared buffers).
 static int layer_backward_tail(const Tower& tw, int64_t l, const stlt_layer_params* g, const float* dy, const TowerScratch& ts, const Scratch& sc,
-                               StltDrop dr, hipStream_t s) {
+                               StltDrop dr, hipStream_t s, const RelSink* rel = nullptr) {
   const stlt_layer_params& lp = tw.layers[l];
   const stlt_layer_params gl = g ? *g : stlt_layer_params{};
   const LayerTape& t = tw.tape[l];
@@ -436,6 +449,10 @@ static int layer_backward_tail(const Tower& tw, int64_t l, const stlt_layer_para
   TRY(weight_grad_all(items, 3, sc, s));
   // the other rows' attention outputs were never read: their dctx is zero
   TRY(launch_scatter_rows(bufC, rows, n, d, bufH, M, s));                                           // bufH (as M x d) = dctx
+  if (rel) {
+    TRY(relevance_map(tw, l, t.qkv, bufH, *rel, s));
+    if (rel->stop_at_first && l == 0) return 0;
+  }
   TRY(launch_attn_bwd(t.qkv, bufH, tw.kpm, tw.causal, tw.S, tw.L, tw.H, d / tw.H, bufQ, s, dr, site0, stlt_grad(gl.in_proj_b), sc.rs->chunk(), tw.rgp()));  // bufQ = dqkv
   TRY(weight_grad(bufQ, 3 * d, t.x, d, tw.Mp, stlt_grad(gl.in_proj_w), sc, s));
   TRY(launch_scatter_rows(att.ds, rows, n, d, bufC, M, s));                                            // residual path: ds1 on the picked rows only
@@ -448,15 +465,15 @@ static int layer_backward_tail(const Tower& tw, int64_t l, const stlt_layer_para
 // read (the tail layer takes it as it is, a tower without one scatters it over zeros); nullptr: ts.A already holds the gradient wrt every output row.
 // g: the tower's gradient table, or nullptr.  The closing flush launches what a grouping queue still holds (nothing when it flushes per layer).
 static int tower_backward(const Tower& tw, const stlt_layer_params* g, const float* dy, const TowerScratch& ts, const Scratch& sc, StltDrop dr,
-                          hipStream_t s, DwQueue& q) {
+                          hipStream_t s, DwQueue& q, const RelSink* rel = nullptr) {
   int64_t l = tw.n_layers - 1;
   if (tw.tail) {
-    TRY(layer_backward_tail(tw, l, g ? &g[l] : nullptr, dy, ts, sc, dr, s));
+    TRY(layer_backward_tail(tw, l, g ? &g[l] : nullptr, dy, ts, sc, dr, s, rel));
     --l;
   } else if (dy) {
     TRY(launch_scatter_rows(dy, tw.rows, tw.n, tw.d, ts.A, tw.Mp, s));
   }
-  for (; l >= 0; --l) TRY(layer_backward(tw, l, g ? &g[l] : nullptr, ts, sc, dr, s, q));
+  for (; l >= 0; --l) TRY(layer_backward(tw, l, g ? &g[l] : nullptr, ts, sc, dr, s, q, rel));
   return dwq_flush(q, sc, s);
 }
 
@@ -542,6 +559,15 @@ static int plan_rows(Plan& pl, const stlt_params* p, const stlt_inputs* in, bool
   return 0;
 }
 
+// The end of a relevance sweep: both rollouts, the combine, and what every exit of the sweep does.
+static int relevance_finish(const stlt_params* p, const stlt_inputs* in, const stlt_relevance_maps* maps, StltReduceScope& red, hipStream_t s) {
+  const int64_t B = in->B, T = in->T, N = in->N;
+  TRY(launch_attn_rollout(maps->abar_spatial, p->n_spatial, B * T, N, maps->rollout_spatial, s));
+  TRY(launch_attn_rollout(maps->abar_temporal, p->n_temporal, B, T, maps->rollout_temporal, s));
+  TRY(launch_relevance_combine(maps->rollout_temporal, maps->rollout_spatial, in->lengths, B, T, N, maps->relevance, s));
+  return red.flush();
+}
+
 }  // namespace
 
 extern "C" {
@@ -615,10 +641,10 @@ int stlt_train_backward(const stlt_params* p, const stlt_params* g, const stlt_i
 
 // The same sweep, carried one step further: from the gradient wrt the pre-LayerNorm embedding sum to the gradient wrt the layout itself
 // (what autograd gives the reference for batch["boxes"] / batch["scores"] as leaves, models.py:29-39).  Both outputs NULL: stlt_train_backward.
-int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const stlt_inputs* in, const void* tape_mem,
-                               size_t tape_bytes, void* scratch_mem, size_t scratch_bytes, const float* dlogits,
-                               float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, float* d_boxes, float* d_scores,
-                               stlt_stream_t stream) {
+// (`maps`: stlt_train_backward_relevance's sinks — its caller has checked them — or nullptr, which is every other entry point)
+static int reverse_sweep(const stlt_params* p, const stlt_params* g, const stlt_inputs* in, const void* tape_mem, size_t tape_bytes, void* scratch_mem,
+                         size_t scratch_bytes, const float* dlogits, float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, float* d_boxes,
+                         float* d_scores, const stlt_relevance_maps* maps, stlt_stream_t stream) {
   TRY(check_train(p, in, flags));
   if (!g || !dlogits || !tape_mem || !scratch_mem) return stlt_set_error(STLT_EINVAL, "stlt_train_backward: null argument");
   if (d_scores && !d_boxes) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_inputs: d_scores comes with d_boxes");
@@ -684,9 +710,11 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
   if (g->fc1_b) TRY(launch_colsum_acc(sc.hB, d, B, d, stlt_grad(g->fc1_b), red.chunk(), s));
   TRY(launch_gemm(0, 1, sc.hB, d, p->fc1_w, d, nullptr, nullptr, 0, sc.hA, d, 0, B, d, d, 1, STLT_ACT_NONE, s));  // hA = dh0
   // ---- temporal transformer: hA is the gradient wrt the last frame's row of every clip (models.py:189-192)
-  TRY(tower_backward(pl.tp, g->temporal, sc.hA, sc.tp, sc, dr, s, q_tp));
+  const RelSink rel_tp{maps ? maps->abar_temporal : nullptr, p->n_spatial == 0};
+  TRY(tower_backward(pl.tp, g->temporal, sc.hA, sc.tp, sc, dr, s, q_tp, maps ? &rel_tp : nullptr));
   }  // upper half: sc.tp.A now holds the gradient wrt the temporal tower's input
   if (!do_lower) { TRY(red.flush()); return dw_side_join(&side, s); }
+  if (maps && p->n_spatial == 0) return relevance_finish(p, in, maps, red, s);  // no spatial map to sweep on for
   // ---- frames embeddings (models.py:98-111).  The gradient wrt the frames' CLS rows goes to tp.C, a chain-only buffer: the temporal
   // tower's last weight-gradient products may still be reading its operand sets on the side stream.
   float* d_cls = sc.tp.C;
@@ -696,7 +724,9 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
   TRY(launch_frames_bwd(d_cls, in->frame_types, B, T, N, d, dense_scatter ? sc.sp.A : nullptr, stlt_grad(g->pos_emb), stlt_grad(g->type_emb), red.chunk(), s,
                         ragged ? ix.f_row_of : nullptr, !no_param_grads));
   // ---- spatial transformer (its queue flushes per layer)
-  TRY(tower_backward(pl.sp, g->spatial, dense_scatter ? nullptr : d_cls, sc.sp, sc, dr, s, q_sp));
+  const RelSink rel_sp{maps ? maps->abar_spatial : nullptr, true};
+  TRY(tower_backward(pl.sp, g->spatial, dense_scatter ? nullptr : d_cls, sc.sp, sc, dr, s, q_sp, maps ? &rel_sp : nullptr));
+  if (maps) return relevance_finish(p, in, maps, red, s);  // the layer-0 input product and the embedding backward are not needed
   // ---- category / box / score embeddings (models.py:29-39); sp.C for the same reason as tp.C above
   TRY(launch_ln_bwd(sc.sp.A, d, t.s_embed, d, nullptr, 0, p->emb_ln_w, p->ln_eps, tok, d, sc.sp.C, d, stlt_grad(g->emb_ln_w), stlt_grad(g->emb_ln_b),
                     red.chunk(), s, dr, 0, nullptr, STLT_SITE_EMBED));
@@ -707,6 +737,39 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
     TRY(launch_embed_bwd_inputs(sc.sp.C, p->box_w, d_scores ? p->score_w : nullptr, tok, d, d_boxes, d_scores, B * T * N, s, ragged ? ix.t_orig : nullptr));
   TRY(red.flush());
   return dw_side_join(&side, s);
+}
+
+int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const stlt_inputs* in, const void* tape_mem,
+                               size_t tape_bytes, void* scratch_mem, size_t scratch_bytes, const float* dlogits,
+                               float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx, float* d_boxes, float* d_scores,
+                               stlt_stream_t stream) {
+  return reverse_sweep(p, g, in, tape_mem, tape_bytes, scratch_mem, scratch_bytes, dlogits, dropout_p, dropout_seed, flags, ctx, d_boxes, d_scores, nullptr,
+                       stream);
+}
+
+// Attention relevance of a prediction: the input-only sweep (an all-NULL gradient table: no weight-gradient product, no parameter reduction,
+// no side stream) with one stlt_attn_grad_probs launch in front of every attention backward, then the two rollouts and the combine.
+int stlt_train_backward_relevance(const stlt_params* p, const stlt_inputs* in, const void* tape_mem, size_t tape_bytes, void* scratch_mem,
+                                  size_t scratch_bytes, const float* dlogits, float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx,
+                                  const stlt_relevance_maps* maps, stlt_stream_t stream) {
+  TRY(check_train(p, in, flags));
+  if (!maps) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: null maps");
+  if (flags & STLT_FLAG_SKIP_PADDING)
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: STLT_FLAG_SKIP_PADDING is not supported (the maps have the padded geometry)");
+  if (flags & (STLT_FLAG_TRAIN_UPPER_ONLY | STLT_FLAG_TRAIN_LOWER_ONLY | STLT_FLAG_TRAIN_BACKBONE))
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: the relevance needs the whole sweep from the logits (no UPPER_ONLY / LOWER_ONLY / TRAIN_BACKBONE)");
+  if (dropout_p != 0.f) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: dropout_p must be 0 (the gradient wrt the probabilities is defined with dropout off)");
+  if (in->N > AB_MAX_ROWS || in->T > AB_MAX_ROWS)
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: sequences of at most %d tokens (N=%lld, T=%lld)", AB_MAX_ROWS, (long long)in->N, (long long)in->T);
+  if (!maps->rollout_spatial || !maps->rollout_temporal || !maps->relevance || (p->n_spatial > 0 && !maps->abar_spatial) || (p->n_temporal > 0 && !maps->abar_temporal))
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: null map (abar_spatial / abar_temporal may be NULL only for a tower without layers)");
+  for (const StltNamedPtr& q : {StltNamedPtr{"abar_spatial", maps->abar_spatial}, StltNamedPtr{"abar_temporal", maps->abar_temporal},
+                                StltNamedPtr{"rollout_spatial", maps->rollout_spatial}, StltNamedPtr{"rollout_temporal", maps->rollout_temporal},
+                                StltNamedPtr{"relevance", maps->relevance}})
+    if ((uintptr_t)q.p & 3) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: %s must be 4-byte aligned", q.name);
+  if ((uintptr_t)in->lengths & 7) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: lengths must be 8-byte aligned");
+  const stlt_params none{};  // names no parameter gradient at all
+  return reverse_sweep(p, &none, in, tape_mem, tape_bytes, scratch_mem, scratch_bytes, dlogits, 0.f, dropout_seed, flags, ctx, nullptr, nullptr, maps, stream);
 }
 
 }  // extern "C"

@@ -367,6 +367,29 @@ class StltBackbone(nn.Module):
                 step["drop"][0], step["drop"][1], step["flags"] | extra_flags, ctx_handle, None if d_boxes is None else d_boxes.data_ptr(),
                 None if d_scores is None else d_scores.data_ptr(), torch.cuda.current_stream().cuda_stream), "stlt_train_backward_inputs")
 
+    def _train_relevance(self, step, dout, out=None):
+        """stlt_train_backward_relevance on the tape of `step` from the seed `dout` -> the five maps (`out`: maps of an earlier call to
+        write into again, e.g. under graph capture).  No gradient table, no context: the input-only sweep has no side stream."""
+        self._check_tape(step)
+        lib = L.load()
+        (B, T, N), device, d = step["shape"], step["device"], self.config.hidden_size
+        p, _, _ = self.c_params(step["head"])
+        tape = self._train_buf("tape", int(lib.stlt_train_tape_bytes(B, T, N, d, p.n_spatial, p.n_temporal)), device)
+        scratch = self._train_buf("scratch", int(lib.stlt_train_scratch_bytes(B, T, N, d, p.n_categories)), device)
+        dl = dout.contiguous().float()
+        if out is None:
+            new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)  # noqa: E731
+            out = {"spatial_layers": new(p.n_spatial, B, T, N, N), "temporal_layers": new(p.n_temporal, B, T, T), "spatial_rollout": new(B, T, N, N),
+                   "temporal_rollout": new(B, T, T), "relevance": new(B, T, N)}
+        ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
+        maps = L.RelevanceMaps(ptr(out["spatial_layers"]), ptr(out["temporal_layers"]), ptr(out["spatial_rollout"]), ptr(out["temporal_rollout"]),
+                               ptr(out["relevance"]))
+        with torch.cuda.device(device):
+            L.check(lib.stlt_train_backward_relevance(
+                C.byref(p), C.byref(step["inp"]), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(), dl.data_ptr(), step["drop"][0],
+                step["drop"][1], step["flags"], None, C.byref(maps), torch.cuda.current_stream().cuda_stream), "stlt_train_backward_relevance")
+        return out
+
     def _flags(self) -> int:
         return ((L.FLAG_CLS_ONLY_LAST_SPATIAL if self.cls_only_last_spatial else 0)
                 | (L.FLAG_LAST_ROW_ONLY_TEMPORAL if self.last_row_only_temporal else 0)
@@ -539,6 +562,28 @@ class Stlt(nn.Module):
         outs = bb._whole_path("stlt_forward_attention", batch, self.prediction_head, ops.attention_workspace_bytes, 0, maps, before=(int(bool(per_head)),))
         return dict(zip(("stlt", "spatial_attention", "temporal_attention"), outs))
 
+    def _parse_target(self, what: str, target, B: int, device):
+        """The three forms of a saliency / relevance target -> (int64 classes or None, float seed or None); both None: top-1."""
+        K = self.prediction_head.fc2.weight.shape[0]
+        if isinstance(target, torch.Tensor) and target.is_floating_point():
+            if tuple(target.shape) != (B, K) or target.device != device:
+                raise L.StltHipError(f"{what}: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
+            return None, target.detach().to(torch.float32).contiguous()
+        if target is not None:
+            if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
+                raise L.StltHipError(f"{what}: target is None, an int64 ({B},) tensor or a float ({B}, {K}) tensor on the batch's device")
+            return target.contiguous(), None
+        return None, None
+
+    def _logit_seed(self, logits: torch.Tensor, tgt, seed) -> torch.Tensor:
+        """d(objective)/d(logits) of a saliency / relevance pass: the caller's float seed, or stlt_saliency_seed's one-hot rows"""
+        if seed is None:
+            seed = torch.empty_like(logits)
+            with torch.cuda.device(logits.device):
+                L.check(L.load().stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), logits.shape[0], logits.shape[1], seed.data_ptr(),
+                                                    torch.cuda.current_stream().cuda_stream), "stlt_saliency_seed")
+        return seed
+
     @torch.no_grad()
     def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None) -> Dict[str, torch.Tensor]:
         """The model's logits and the gradient of one raw logit per clip with respect to the layout, in one pass: which object's
@@ -559,19 +604,10 @@ class Stlt(nn.Module):
             raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
         if not batch["categories"].is_cuda:
             raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
-        lib = L.load()
         device = batch["categories"].device
         head = self.prediction_head
-        B, K = batch["categories"].shape[0], head.fc2.weight.shape[0]
-        tgt = seed = None
-        if isinstance(target, torch.Tensor) and target.is_floating_point():
-            if tuple(target.shape) != (B, K) or target.device != device:
-                raise L.StltHipError(f"forward_saliency: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
-            seed = target.detach().to(torch.float32).contiguous()
-        elif target is not None:
-            if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
-                raise L.StltHipError(f"forward_saliency: target is None, an int64 ({B},) tensor or a float ({B}, {K}) tensor on the batch's device")
-            tgt = target.contiguous()
+        B = batch["categories"].shape[0]
+        tgt, seed = self._parse_target("forward_saliency", target, B, device)
         # (dropout is off here, so the forward draws no seed; the tape is overwritten: a pending backward of an earlier forward will refuse)
         logits, step = bb._train_forward(batch, head, L.FLAG_SKIP_PADDING if bb.skip_padding else 0)
         _, T, N = step["shape"]
@@ -579,17 +615,50 @@ class Stlt(nn.Module):
         new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)  # noqa: E731
         d_boxes = new(B, T, N, 4)
         d_scores = new(B, T, N) if "scores" in batch else None
-        if seed is None:
-            seed = new(B, K)
-            with torch.cuda.device(device):
-                L.check(lib.stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), B, K, seed.data_ptr(),
-                                               torch.cuda.current_stream().cuda_stream), "stlt_saliency_seed")
+        seed = self._logit_seed(logits, tgt, seed)
         bb._train_backward(step, g, seed, None, d_boxes, d_scores)
         if target is None:
             target = seed.argmax(dim=1)  # the one-hot row's only 1: the class the kernel picked (lowest index on ties), still on the device
         out = {"stlt": logits, "target": target, "boxes_grad": d_boxes}
         if d_scores is not None:
             out["scores_grad"] = d_scores
+        return out
+
+    @torch.no_grad()
+    def forward_relevance(self, batch: Dict[str, torch.Tensor], target=None, return_layers: bool = False) -> Dict[str, torch.Tensor]:
+        """The model's logits and the relevance of every object of every frame for one logit per clip, in one pass: which object, in which
+        frame, the prediction rests on.  Gradient-weighted attention rollout (Chefer, Gur, Wolf 2021): each layer's attention probabilities
+        are weighted by the gradient of the target logit with respect to them, the positive part is averaged over the heads
+        (stlt_attn_grad_probs), and the layers are rolled up through the residual connections, R_l = R_{l-1} + abar_l·R_{l-1}
+        (stlt_attn_rollout); the relevance joins the two towers, relevance[b,t,n] = temporal_rollout[b, lengths[b]-1, t] *
+        spatial_rollout[b,t,0,n] (stlt_relevance_combine).  On the reference this takes need_weights=True, hooks and retain_grad on every
+        layer and a Python loop; here it is stlt_train_forward with dropout 0, stlt_saliency_seed and stlt_train_backward_relevance: the
+        input-only sweep with one extra launch per layer.
+        -> {"stlt": (B, num_classes) float32 logits, "target": the selected classes, "relevance": (B, T, N), "spatial_rollout": (B, T, N, N),
+            "temporal_rollout": (B, T, T)}; with `return_layers` also the per-layer maps "spatial_layers": (n_spatial, B, T, N, N) and
+            "temporal_layers": (n_temporal, B, T, T).
+        `target` as in forward_saliency: None — each clip's top-1 class; an int64 (B,) tensor; a float (B, num_classes) seed.  Entries of
+        padded object slots and of padded frames of "relevance" are exactly 0.  Padded schedule only (N, T <= 256).  Inference only: touches
+        no parameter's .grad.  Like forward_saliency it runs on the backbone's one activation tape, so an autograd backward still pending
+        from an earlier forward refuses to run afterwards."""
+        bb = self.backbone
+        if bb._dropout_live():
+            raise L.StltHipError("forward_relevance is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if bb.skip_padding:
+            raise L.StltHipError("forward_relevance runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
+        if not batch["categories"].is_cuda:
+            raise L.StltHipError("forward_relevance runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        device = batch["categories"].device
+        tgt, seed = self._parse_target("forward_relevance", target, batch["categories"].shape[0], device)
+        logits, step = bb._train_forward(batch, self.prediction_head, 0)
+        seed = self._logit_seed(logits, tgt, seed)
+        maps = bb._train_relevance(step, seed)
+        if target is None:
+            target = seed.argmax(dim=1)
+        out = {"stlt": logits, "target": target, "relevance": maps["relevance"], "spatial_rollout": maps["spatial_rollout"],
+               "temporal_rollout": maps["temporal_rollout"]}
+        if return_layers:
+            out["spatial_layers"], out["temporal_layers"] = maps["spatial_layers"], maps["temporal_layers"]
         return out
 
 

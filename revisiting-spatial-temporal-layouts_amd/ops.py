@@ -287,6 +287,50 @@ def attn_probs(qkv: torch.Tensor, kpm: torch.Tensor, causal: bool, num_heads: in
     return probs
 
 
+def attn_grad_probs(qkv: torch.Tensor, dctx: torch.Tensor, kpm: torch.Tensor, causal: bool, num_heads: int):
+    """Gradient-weighted attention probabilities of one layer (include/stlt_hip.h: stlt_attn_grad_probs): qkv (S,L,3d) packed [q;k;v],
+    dctx (S,L,d) the gradient wrt the attention core's output, kpm (S,L) bool/uint8 (True = key masked).
+    -> abar (S,L,L) = mean over the heads of max(P_h * G_h, 0), G_h[s,i,j] = dctx_h[s,i,:] · v_h[s,j,:].  Masked entries are exactly 0;
+    L <= 256, head dim <= 256."""
+    lib = L.load()
+    _chk(qkv, torch.float32, "qkv"); _chk(dctx, torch.float32, "dctx")
+    kpm = _mask_u8(kpm, "kpm")
+    S, Lq, d3 = qkv.shape
+    assert tuple(kpm.shape) == (S, Lq) and d3 % (3 * num_heads) == 0 and tuple(dctx.shape) == (S, Lq, d3 // 3)
+    abar = torch.empty(S, Lq, Lq, device=qkv.device, dtype=torch.float32)
+    L.check(lib.stlt_attn_grad_probs(_p(qkv), _p(dctx), _p(kpm), int(bool(causal)), S, Lq, num_heads, d3 // 3 // num_heads, _p(abar), _stream()),
+            "stlt_attn_grad_probs")
+    return abar
+
+
+def attn_rollout(abar: torch.Tensor):
+    """Rollout of per-layer maps through the residual connections (include/stlt_hip.h: stlt_attn_rollout): abar (n_layers, ..., L, L) ->
+    R (..., L, L) with R_0 = I, R_l = R_{l-1} + abar_l · R_{l-1}; no layers: the identity.  One launch; L <= 256."""
+    lib = L.load()
+    _chk(abar, torch.float32, "abar")
+    if abar.dim() < 3 or abar.shape[-1] != abar.shape[-2]:
+        raise L.StltHipError(f"abar: expected (n_layers, ..., L, L), got {tuple(abar.shape)}")
+    n_layers, Lq = abar.shape[0], abar.shape[-1]
+    S = 1
+    for n in abar.shape[1:-2]:
+        S *= n
+    R = torch.empty(abar.shape[1:], device=abar.device, dtype=torch.float32)
+    L.check(lib.stlt_attn_rollout(_p(abar) if n_layers else None, n_layers, S, Lq, _p(R), _stream()), "stlt_attn_rollout")
+    return R
+
+
+def relevance_combine(rollout_temporal: torch.Tensor, rollout_spatial: torch.Tensor, lengths: torch.Tensor):
+    """rel[b,t,n] = rollout_temporal[b, lengths[b]-1, t] * rollout_spatial[b,t,0,n] (include/stlt_hip.h: stlt_relevance_combine):
+    rollout_temporal (B,T,T), rollout_spatial (B,T,N,N), lengths (B,) int64 -> rel (B,T,N)."""
+    lib = L.load()
+    _chk(rollout_temporal, torch.float32, "rollout_temporal"); _chk(rollout_spatial, torch.float32, "rollout_spatial"); _chk(lengths, torch.int64, "lengths")
+    B, T, N = rollout_spatial.shape[:3]
+    assert tuple(rollout_spatial.shape) == (B, T, N, N) and tuple(rollout_temporal.shape) == (B, T, T) and tuple(lengths.shape) == (B,)
+    rel = torch.empty(B, T, N, device=rollout_spatial.device, dtype=torch.float32)
+    L.check(lib.stlt_relevance_combine(_p(rollout_temporal), _p(rollout_spatial), _p(lengths), B, T, N, _p(rel), _stream()), "stlt_relevance_combine")
+    return rel
+
+
 def _rows_view(t: torch.Tensor, name: str):
     """(S, L, d) float32 GPU tensor whose rows may be strided (a column slice of a wider packed buffer): -> its row stride in floats"""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
