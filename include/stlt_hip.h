@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define STLT_VERSION 110  /* 110: training-loop contexts (stlt_ctx) in the backward calls; block backward buffers split into keep / work */
+#define STLT_VERSION 111  /* 111: stlt_adamw_step takes lr, beta1, beta2, eps as double (binary-incompatible: was float); 110: training-loop contexts (stlt_ctx) in the backward calls; block backward buffers split into keep / work */
 
 #define STLT_EINVAL (-1)   /* bad shape / null pointer / unsupported size */
 #define STLT_EWORKSPACE (-2) /* workspace too small */
@@ -825,7 +825,9 @@ int stlt_train_backward_relevance(const stlt_params* p, const stlt_inputs* in, c
  * torch.nn.utils.clip_grad_norm_ scales the gradients by (max_norm <= 0: out[1] = 1).  scratch: >= 1024 floats.
  * stlt_adamw_step: torch.optim.AdamW.step (decoupled weight decay, bias correction, fp32) over a device table of
  * chunks; element i of a chunk is parameter param[i], its gradient flat_grad[flat_offset + i] (scaled by
- * norm_and_clip[1] when given) and its moments exp_avg / exp_avg_sq at the same flat offset.  step counts from 1. */
+ * norm_and_clip[1] when given) and its moments exp_avg / exp_avg_sq at the same flat offset.  step counts from 1.  lr, beta1, beta2 and
+ * eps are doubles, as torch holds them: 1 - beta2 taken from a beta2 already rounded to fp32 is off by 1.3e-5 of its value (0.999), and
+ * with it every increment of exp_avg_sq. */
 typedef struct {
   float* param;
   int64_t flat_offset;
@@ -921,7 +923,7 @@ int stlt_loss_fwd_bwd(const float* logits, const void* labels, int kind, int64_t
 int stlt_saliency_seed(const float* logits, const int64_t* target, int64_t B, int64_t K, float* dlogits, stlt_stream_t stream);
 int stlt_grad_norm(const float* flat_grad, int64_t n, float max_norm, float* scratch, float* out, stlt_stream_t stream);
 int stlt_adamw_step(const stlt_opt_chunk* chunks_dev, int64_t n_chunks, const float* flat_grad, float* exp_avg, float* exp_avg_sq,
-                    const float* norm_and_clip, float lr, float beta1, float beta2, float eps, int64_t step, stlt_stream_t stream);
+                    const float* norm_and_clip, double lr, double beta1, double beta2, double eps, int64_t step, stlt_stream_t stream);
 
 /* ---- block-level training calls for the fusion models (CAF / CACNF / LCF; reference models.py:328-431, 239-246) ----
  * One native forward and one native reverse call per residual block, so an optimisation step of a fusion model is a few

@@ -215,10 +215,19 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
     for (int t = 0; t < 6; ++t) f.w[t] = *reinterpret_cast<const f32x4*>(s + w_row + (6 * (p & 1) + t) * 16 * FK + off);
   };
   f32x4 acc[12];  // tile t = 16 output columns: q channels 16 t .. (t < 4), k (4 <= t < 8), v (t >= 8); lane (li_, lg_): token li_, channels 4 lg_ .. + 3
-  auto init_acc = [&](int it) {
-    const float* src = bias_lds + (it & 1) * FN + 4 * lg_;
+  // The accumulators start from zero and meet the bias once, behind the item's last k-step (add_bias, at the head of the attention phase).
+  // Started from the bias strip, each of the d products that v_mfma_f32_16x16x4_f32 adds one at a time rounded at the bias's magnitude: where
+  // the projected values are mostly bias (inputs of 0.03 under a bias of 0.1) q, k, v came out 10 * 2^-24 of their scale off, against 1.7 from
+  // the stand-alone product and 2.2 from torch.  Item it's strip stays in its half of bias_lds until the loaders' dma_bias(it + 2), which
+  // they issue in the last k-step of item it + 1, behind both barriers of item it's attention phase.
+  auto zero_acc = [&]() {
 #pragma unroll
-    for (int t = 0; t < 12; ++t) acc[t] = *reinterpret_cast<const f32x4*>(src + 16 * t);
+    for (int t = 0; t < 12; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  };
+  auto add_bias = [&](int it, int lg) {
+    const float* src = bias_lds + (it & 1) * FN + 4 * lg;
+#pragma unroll
+    for (int t = 0; t < 12; ++t) acc[t] += *reinterpret_cast<const f32x4*>(src + 16 * t);
   };
   auto mfma_phase = [&](int p, const Frags& f, int e_lo, int e_hi) {
     const int c = p >> 1, t0 = 6 * (p & 1);
@@ -230,7 +239,7 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
   };
 
   __builtin_amdgcn_s_barrier();  // the loaders' counted wait + this barrier publish step 0 and the first bias strip
-  init_acc(0);
+  zero_acc();
   int c_it = 0, c_kt = 0, stage = 0;
   unsigned pad_byte = 1u;
   read_phase(0, 0, F[0]);
@@ -265,6 +274,7 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
     // being hoisted out of the item loop into registers the k-loop cannot spare (it spilled 12 - 51 of them)
     int li = li_, lg = lg_;
     asm volatile("" : "+v"(li), "+v"(lg));
+    add_bias(c_it, lg);  // the item's strip was published before its first k-step; the fragment registers are dead here
     const int row0 = grp * a.rows_per_item;                                         // first token row of the item
     const int rows_here = (M - row0) < a.rows_per_item ? (M - row0) : a.rows_per_item;  // whole sequences: a multiple of L
     const int L = a.L;
@@ -396,11 +406,11 @@ __global__ __launch_bounds__(F_THREADS, 3) void mhsa16_kernel(const Mhsa16Args a
     }
     ++c_it;
     c_kt = 0;
-    // next item: accumulators from its bias strip (published by the last k-step's barrier), first fragments.  (Requesting them right behind
+    // next item: cleared accumulators, first fragments.  (Requesting them right behind
     // attention barrier 2, under the softmax and PV, measured slower: 6 131 against 6 060 us for 32 768 frames of 7, 866 - 877 against 860 us
     // for 1 024 clips of 32 frames, profiles/round6_mhsa_window_ab.txt.)
     if (step + 1 < total_steps) {
-      init_acc(c_it);
+      zero_acc();
       read_phase(stage, 0, F[0]);
     }
   }

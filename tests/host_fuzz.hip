@@ -162,7 +162,7 @@ void fuzz_rowwise_and_attention() {
   tally(stlt_dropout(F<float>(1), F<float>(2), n, coin(6) ? 1.0f : 0.1f, rnd(), (uint32_t)rnd(), s));
   tally(stlt_loss_fwd_bwd(F<float>(1), F<char>(2), (int)uni(-1, 2), B, dim(174, 1 << 20), 0.25f, F<float>(3), F<float>(4), F<float>(5), s));
   tally(stlt_grad_norm(F<float>(1), n, coin(2) ? 0.f : 5.f, F<float>(2), F<float>(3), s));
-  tally(stlt_adamw_step(F<stlt_opt_chunk>(1), dim(8192, 1ll << 31), F<float>(2), F<float>(3), F<float>(4), coin(2) ? nullptr : FA<float>(5), 5e-5f, 0.9f, 0.999f, 1e-8f,
+  tally(stlt_adamw_step(F<stlt_opt_chunk>(1), dim(8192, 1ll << 31), F<float>(2), F<float>(3), F<float>(4), coin(2) ? nullptr : FA<float>(5), 5e-5, 0.9, 0.999, 1e-8,
                         dim(1000, 1ll << 40), s));
   tally(stlt_eval_topk(F<float>(1), dim(174, 1 << 20), F<int64_t>(2), B, dim(174, 1 << 20), F<int64_t>(3), s));
   tally(stlt_eval_store_sigmoid(F<float>(1), dim(157, 1 << 20), F<float>(2), B, dim(157, 1 << 20), F<double>(3), F<double>(4), dim(1000, 1ll << 40), s));

@@ -96,7 +96,7 @@ def test_the_three_names_are_declared_bound_and_exported(pkg):
         assert hasattr(lib, name)
     assert "models.py:46-55,118-128" in header  # the reference lines the three calls extend
     assert re.search(r"#define STLT_K_ATTN_PROBS\s+15\b", header) and pkg._lib.K_NAMES[15] == "attn_probs"
-    assert lib.stlt_version() == 110
+    assert lib.stlt_version() == 111
     # workspace sizing is host arithmetic: the dense forward's buffers
     assert pkg.ops.attention_workspace_bytes(8, 32, 7, 768, 174) == pkg.ops.workspace_bytes(8, 32, 7, 768, 174) > 0
     assert pkg.ops.attention_workspace_bytes(0, 32, 7, 768, 174) == 0

@@ -48,7 +48,7 @@ def test_new_entries_agree_between_header_exports_and_bindings(pkg):
                                                            "float* d_boxes", "float* d_scores", "stlt_stream_t stream"]
     assert _prototype(header, "stlt_saliency_seed") == ["const float* logits", "const int64_t* target", "int64_t B", "int64_t K", "float* dlogits",
                                                         "stlt_stream_t stream"]
-    assert lib.stlt_version() == 110
+    assert lib.stlt_version() == 111
 
 
 def test_train_backward_signature_is_unchanged(pkg):
