@@ -624,7 +624,9 @@ typedef struct {
   stlt_r3d_conv conv[STLT_R3D_CONVS];
   float bn_eps;               /* 1e-5 */
 } stlt_r3d_params;
-/* workspace of stlt_r3d_forward for video (B, 3, T, H, W): pure host arithmetic, callable without a GPU; 0 for B <= 0 */
+/* workspace of stlt_r3d_forward for video (B, 3, T, H, W): pure host arithmetic, callable without a GPU; 0 for B <= 0 and for every
+ * shape the trunk refuses (T, H or W above 4096, B above 2^20, or one of the 53 convolutions beyond stlt_conv3d_fwd's limits), as
+ * stlt_r3d_tape_bytes and stlt_r3d_backward_workspace_bytes: the three come from one plan and are 0 for the same shapes */
 size_t stlt_r3d_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W);
 /* Resnet3D.forward_features (models.py:221-222) on video (B, 3, T, H, W) NCDHW fp32 -> features (B, 2048, To, Ho, Wo) NCDHW
  * ((B, 2048, 2, 4, 4) for 32 x 112 x 112 clips) and/or pooled (B, 2048), its global average (either may be NULL, not both).
@@ -645,7 +647,8 @@ int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, in
  *     (n_split 0: the library's plan); the workspace is always needed.  accumulate != 0 adds into dw.
  *   stlt_maxpool3d_ndhwc_train: stlt_maxpool3d_ndhwc that also writes each output's window argmax (0..26, first maximum in scan order);
  *   stlt_maxpool3d_ndhwc_bwd: dx (B, T, H, W, C) from dy and argmax, a deterministic gather, then 0 where mask <= 0 (NULL: none).
- * Every result is bit-identical from run to run. */
+ * Every result is bit-identical from run to run.  The two workspace queries return 0 for a descriptor their launch refuses for its
+ * shape: a stride above 2 or kt·kh·kw·c_out of 2^31 or more (data gradient), c_out·K above 2^40 floats (weight gradient). */
 size_t stlt_conv3d_bwd_data_workspace_bytes(const stlt_conv3d_desc* d, int n_split);
 size_t stlt_conv3d_bwd_weight_workspace_bytes(const stlt_conv3d_desc* d, int n_split);
 int stlt_conv3d_repack_dgrad(const float* w, const stlt_conv3d_desc* d, const float* scale, float* out, stlt_stream_t stream);

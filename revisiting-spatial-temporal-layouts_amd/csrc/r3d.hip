@@ -16,6 +16,7 @@
 // shape always runs the same summation order.
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 #include "common.h"
 
 namespace {
@@ -300,6 +301,27 @@ inline int64_t out_dim(int64_t in, int64_t k, int64_t s, int64_t p) { return (in
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int conv_bn_tile(int64_t N) { return N <= 64 ? 64 : 128; }
 
+// Π v > limit for non-negative factors, without forming a product past the limit: the shape checks bound each extent by 2^24 (or not
+// at all: a batch), so a product of four or five of them overflows int64 before any limit could be applied to it
+inline bool prod_over(std::initializer_list<int64_t> v, int64_t limit) {
+  int64_t p = 1;
+  for (int64_t x : v) {
+    if (x > 0 && p > limit / x) return true;
+    p *= x;
+  }
+  return false;
+}
+
+// The split arithmetic of every launcher and workspace query, forward (k-slabs), data gradient (k-slabs of a parity class) and weight
+// gradient (m-slabs): a request of `want` ranges over `slabs` slabs becomes at most one range per slab, every range cdiv(slabs, ranges)
+// slabs long (the last may be shorter), so the count can come out below the request.  No slabs, or want <= 1: one range.
+struct SplitRanges { int64_t splits, per; };
+inline SplitRanges split_ranges(int64_t slabs, int64_t want) {
+  if (slabs <= 0 || want <= 1) return {1, slabs > 0 ? slabs : 1};
+  const int64_t per = cdiv(slabs, std::min(want, slabs));
+  return {cdiv(slabs, per), per};
+}
+
 // number of contraction splits for an (M, N, K) conv launch (1: whole tiles, no workspace)
 int64_t conv_plan_splits(int64_t M, int64_t N, int64_t K) {
   const int64_t tiles = cdiv(M, BM) * cdiv(N, conv_bn_tile(N));
@@ -308,9 +330,7 @@ int64_t conv_plan_splits(int64_t M, int64_t N, int64_t K) {
   int64_t splits = cdiv(SPLIT_TARGET_WG, tiles);
   if (splits > slabs / SPLIT_MIN_SLABS) splits = slabs / SPLIT_MIN_SLABS;
   if (splits > SPLIT_MAX) splits = SPLIT_MAX;
-  if (splits < 2) return 1;
-  const int64_t per = cdiv(slabs, splits);
-  return cdiv(slabs, per);
+  return split_ranges(slabs, splits).splits;
 }
 
 int check_desc(const stlt_conv3d_desc* d, ConvGeom* g) {
@@ -323,9 +343,10 @@ int check_desc(const stlt_conv3d_desc* d, ConvGeom* g) {
   if (d->c_in % 4) return stlt_set_error(STLT_EINVAL, "conv3d: c_in must be a multiple of 4 (pad the channels: stlt_ncdhw_to_ndhwc, stlt_conv3d_repack), got %lld", (long long)d->c_in);
   const int64_t To = out_dim(d->T, d->kt, d->st, d->pt), Ho = out_dim(d->H, d->kh, d->sh, d->ph), Wo = out_dim(d->W, d->kw, d->sw, d->pw);
   if (To <= 0 || Ho <= 0 || Wo <= 0) return stlt_set_error(STLT_EINVAL, "conv3d: the kernel is larger than the padded input");
-  const int64_t M = d->B * To * Ho * Wo, K = d->kt * d->kh * d->kw * d->c_in;
-  if (M > 0x7fffff00LL || K > 0x7fffff00LL || d->B * d->T * d->H * d->W > 0x7fffff00LL || M * d->c_out > (1LL << 40))
+  if (prod_over({d->B, To, Ho, Wo}, 0x7fffff00LL) || prod_over({d->kt, d->kh, d->kw, d->c_in}, 0x7fffff00LL) ||
+      prod_over({d->B, d->T, d->H, d->W}, 0x7fffff00LL) || prod_over({d->B, To, Ho, Wo, d->c_out}, 1LL << 40))
     return stlt_set_error(STLT_EINVAL, "conv3d: shape too large");
+  const int64_t M = d->B * To * Ho * Wo, K = d->kt * d->kh * d->kw * d->c_in;
   if (cdiv(M, BM) > 0x7fffffffLL || cdiv(d->c_out, 64) > 65535) return stlt_set_error(STLT_EINVAL, "conv3d: too many output tiles");
   *g = ConvGeom{(int)d->B, (int)d->T, (int)d->H, (int)d->W, (int)d->c_in, (int)To, (int)Ho, (int)Wo, (int)d->c_out, (int)d->kt, (int)d->kh, (int)d->kw,
                 (int)d->st, (int)d->sh, (int)d->sw, (int)d->pt, (int)d->ph, (int)d->pw, (int)M, (int)K};
@@ -334,21 +355,13 @@ int check_desc(const stlt_conv3d_desc* d, ConvGeom* g) {
 
 int64_t conv_split_bytes(const ConvGeom& g, int64_t splits) { return splits > 1 ? splits * (int64_t)g.M * g.N * (int64_t)sizeof(float) : 0; }
 
-// the k-ranges an explicit request of `splits` becomes over `slabs` k-slabs, as launch_conv and launch_dgrad divide them: at most one
-// per slab, every range cdiv(slabs, splits) slabs long (the last may be shorter), so the count can come out below the request
-inline int64_t conv_clamp_splits(int64_t slabs, int64_t splits) {
-  if (slabs <= 0 || splits <= 1) return 1;
-  if (splits > slabs) splits = slabs;
-  return cdiv(slabs, cdiv(slabs, splits));
-}
+// the forward's split count for a caller's n_split (<= 0: the plan for the shape)
+int64_t conv_splits(const ConvGeom& g, int n_split) { return n_split <= 0 ? conv_plan_splits(g.M, g.N, g.K) : split_ranges(cdiv(g.K, CK), n_split).splits; }
 
 int launch_conv(const ConvGeom& g, const float* x, const float* w, const float* bn_w, const float* bn_b, const float* bn_mean, const float* bn_var,
-                float eps, const float* res, int relu, float* y, int64_t splits, float* part, hipStream_t s) {
+                float eps, const float* res, int relu, float* y, int64_t want_splits, float* part, hipStream_t s) {
   const int bn = conv_bn_tile(g.N);
-  const int64_t slabs = cdiv(g.K, CK);
-  if (splits > slabs) splits = slabs;
-  const int64_t per = cdiv(slabs, splits);
-  splits = cdiv(slabs, per);
+  const auto [splits, per] = split_ranges(cdiv(g.K, CK), want_splits);
   const dim3 grid((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.N, bn), (unsigned)splits), block(256);
   float* dst = splits > 1 ? part : y;
   const DgEpi none{};
@@ -365,63 +378,12 @@ int launch_conv(const ConvGeom& g, const float* x, const float* w, const float* 
   return 0;
 }
 
-// ---- the trunk's plan: the 53 convolutions in state-dict order (stem; per block conv1, conv2, conv3, [downsample]) ----
-constexpr int R3D_BLOCKS[4] = {3, 4, 6, 3};
-constexpr int R3D_PLANES[4] = {64, 128, 256, 512};
-
-struct TrunkDims {
-  int64_t act_elems = 0;    // largest block-level activation (per buffer)
-  int64_t stem_elems = 0;   // stem output
-  int64_t part_bytes = 0;   // largest split-K partial buffer
-  int64_t To = 0, Ho = 0, Wo = 0;
-  bool ok = false;
-};
-
-// walk the trunk's shapes (no launches): the workspace plan of stlt_r3d_workspace_bytes and stlt_r3d_forward
-TrunkDims trunk_dims(int64_t B, int64_t T, int64_t H, int64_t W) {
-  TrunkDims d;
-  auto conv = [&](int64_t& t, int64_t& h, int64_t& w, int64_t cin, int64_t cout, int k, int s, int p, int st_t) {
-    const int64_t to = out_dim(t, k, st_t, p), ho = out_dim(h, k, s, p), wo = out_dim(w, k, s, p);
-    const int64_t M = B * to * ho * wo, K = (int64_t)k * k * k * cin;
-    const int64_t sp = conv_plan_splits(M, cout, K);
-    if (sp > 1) d.part_bytes = std::max<int64_t>(d.part_bytes, sp * M * cout * (int64_t)sizeof(float));
-    t = to; h = ho; w = wo;
-    return M * cout;
-  };
-  int64_t t = T, h = H, w = W;
-  // stem: 7x7x7, stride (1, 2, 2), pad 3 — 3 (padded to 4) -> 64
-  {
-    const int64_t to = out_dim(t, 7, 1, 3), ho = out_dim(h, 7, 2, 3), wo = out_dim(w, 7, 2, 3);
-    if (to <= 0 || ho <= 0 || wo <= 0) return d;
-    const int64_t M = B * to * ho * wo, sp = conv_plan_splits(M, 64, 343 * 4);
-    if (sp > 1) d.part_bytes = std::max<int64_t>(d.part_bytes, sp * M * 64 * (int64_t)sizeof(float));
-    d.stem_elems = M * 64;
-    t = to; h = ho; w = wo;
-  }
-  t = out_dim(t, 3, 2, 1); h = out_dim(h, 3, 2, 1); w = out_dim(w, 3, 2, 1);  // max-pool
-  int64_t cin = 64;
-  d.act_elems = B * t * h * w * cin;
-  for (int L = 0; L < 4; ++L) {
-    const int64_t planes = R3D_PLANES[L];
-    for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk) {
-      const int s = (L > 0 && blk == 0) ? 2 : 1;
-      int64_t t1 = t, h1 = h, w1 = w;
-      d.act_elems = std::max(d.act_elems, conv(t1, h1, w1, cin, planes, 1, 1, 0, 1));
-      d.act_elems = std::max(d.act_elems, conv(t1, h1, w1, planes, planes, 3, s, 1, s));
-      d.act_elems = std::max(d.act_elems, conv(t1, h1, w1, planes, planes * 4, 1, 1, 0, 1));
-      if (blk == 0) {
-        int64_t t2 = t, h2 = h, w2 = w;
-        conv(t2, h2, w2, cin, planes * 4, 1, s, 0, s);
-      }
-      t = t1; h = h1; w = w1;
-      cin = planes * 4;
-    }
-  }
-  d.To = t; d.Ho = h; d.Wo = w;
-  d.ok = true;
-  return d;
+// the shape check of the three max-pool entry points
+int check_pool_shape(const char* who, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C) {
+  if (B < 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || T > (1 << 24) || H > (1 << 24) || W > (1 << 24) || C > (1 << 24) || prod_over({B, T, H, W, C}, 1LL << 40))
+    return stlt_set_error(STLT_EINVAL, "%s: bad shape", who);
+  return 0;
 }
-
 
 }  // namespace
 
@@ -430,8 +392,7 @@ extern "C" {
 size_t stlt_conv3d_workspace_bytes(const stlt_conv3d_desc* d, int n_split) {
   ConvGeom g;
   if (check_desc(d, &g)) return 0;
-  const int64_t splits = n_split <= 0 ? conv_plan_splits(g.M, g.N, g.K) : conv_clamp_splits(cdiv(g.K, CK), n_split);
-  return (size_t)conv_split_bytes(g, splits);
+  return (size_t)conv_split_bytes(g, conv_splits(g, n_split));
 }
 
 int stlt_conv3d_fwd(const stlt_conv3d_desc* d, const float* x, const float* w, const float* bn_w, const float* bn_b, const float* bn_mean,
@@ -443,7 +404,7 @@ int stlt_conv3d_fwd(const stlt_conv3d_desc* d, const float* x, const float* w, c
   if (bn_w && (!bn_b || !bn_mean || !bn_var)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_fwd: BatchNorm needs all four of weight, bias, running mean, running var");
   if (((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_fwd: x and w must be 16-byte aligned");
   if (n_split < 0 || n_split > 1024) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_fwd: n_split must lie in [0, 1024]");
-  int64_t splits = n_split == 0 ? conv_plan_splits(g.M, g.N, g.K) : conv_clamp_splits(cdiv(g.K, CK), n_split);
+  int64_t splits = conv_splits(g, n_split);
   if (n_split == 0 && (!workspace || workspace_bytes < (size_t)conv_split_bytes(g, splits))) splits = 1;  // automatic: split only into lent workspace
   if (splits > 1 && (!workspace || workspace_bytes < (size_t)conv_split_bytes(g, splits)))
     return stlt_set_error(STLT_EWORKSPACE, "stlt_conv3d_fwd: %lld splits need %lld workspace bytes, %zu lent", (long long)splits,
@@ -453,7 +414,8 @@ int stlt_conv3d_fwd(const stlt_conv3d_desc* d, const float* x, const float* w, c
 
 int stlt_conv3d_repack(const float* w, int64_t c_out, int64_t c_in, int64_t kt, int64_t kh, int64_t kw, int64_t c_pad, float* out, stlt_stream_t stream) {
   if (!w || !out) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_repack: null pointer");
-  if (c_out <= 0 || c_in <= 0 || kt <= 0 || kh <= 0 || kw <= 0 || c_pad < c_in || c_pad > (1 << 20) || kt * kh * kw > (1 << 20) || c_out > (1 << 24))
+  if (c_out <= 0 || c_in <= 0 || kt <= 0 || kh <= 0 || kw <= 0 || c_pad < c_in || c_pad > (1 << 20) || prod_over({kt, kh, kw}, 1 << 20) || c_out > (1 << 24) ||
+      prod_over({c_out, kt, kh, kw, c_pad}, 1LL << 40))
     return stlt_set_error(STLT_EINVAL, "stlt_conv3d_repack: bad shape");
   const int64_t n = c_out * kt * kh * kw * c_pad;
   hipLaunchKernelGGL(conv3d_repack_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, w, c_out, (int)c_in, (int)(kt * kh * kw),
@@ -463,7 +425,7 @@ int stlt_conv3d_repack(const float* w, int64_t c_out, int64_t c_in, int64_t kt, 
 
 int stlt_ncdhw_to_ndhwc(const float* x, int64_t B, int64_t C, int64_t T, int64_t H, int64_t W, int64_t c_pad, float* y, stlt_stream_t stream) {
   if (!x || !y) return stlt_set_error(STLT_EINVAL, "stlt_ncdhw_to_ndhwc: null pointer");
-  if (B < 0 || C <= 0 || T <= 0 || H <= 0 || W <= 0 || c_pad < C || c_pad > (1 << 20) || B * T * H * W * c_pad > (1LL << 40))
+  if (B < 0 || C <= 0 || T <= 0 || H <= 0 || W <= 0 || c_pad < C || c_pad > (1 << 20) || prod_over({B, T, H, W, c_pad}, 1LL << 40))
     return stlt_set_error(STLT_EINVAL, "stlt_ncdhw_to_ndhwc: bad shape");
   const int64_t n = B * T * H * W * c_pad;
   if (n == 0) return 0;
@@ -473,7 +435,7 @@ int stlt_ncdhw_to_ndhwc(const float* x, int64_t B, int64_t C, int64_t T, int64_t
 
 int stlt_ndhwc_to_ncdhw(const float* x, int64_t B, int64_t P, int64_t C, float* y, stlt_stream_t stream) {
   if (!x || !y) return stlt_set_error(STLT_EINVAL, "stlt_ndhwc_to_ncdhw: null pointer");
-  if (B < 0 || P <= 0 || C <= 0 || C > (1 << 24) || B * P * C > (1LL << 40)) return stlt_set_error(STLT_EINVAL, "stlt_ndhwc_to_ncdhw: bad shape");
+  if (B < 0 || P <= 0 || C <= 0 || C > (1 << 24) || prod_over({B, P, C}, 1LL << 40)) return stlt_set_error(STLT_EINVAL, "stlt_ndhwc_to_ncdhw: bad shape");
   const int64_t n = B * P * C;
   if (n == 0) return 0;
   hipLaunchKernelGGL(ndhwc_to_ncdhw_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, B, P, (int)C, y);
@@ -482,8 +444,7 @@ int stlt_ndhwc_to_ncdhw(const float* x, int64_t B, int64_t P, int64_t C, float* 
 
 int stlt_maxpool3d_ndhwc(const float* x, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, float* y, stlt_stream_t stream) {
   if (!x || !y) return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc: null pointer");
-  if (B < 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || T > (1 << 24) || H > (1 << 24) || W > (1 << 24) || C > (1 << 24) || B * T * H * W * C > (1LL << 40))
-    return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc: bad shape");
+  if (int e = check_pool_shape("stlt_maxpool3d_ndhwc", B, T, H, W, C)) return e;
   const int64_t To = out_dim(T, 3, 2, 1), Ho = out_dim(H, 3, 2, 1), Wo = out_dim(W, 3, 2, 1);
   const int64_t n = B * To * Ho * Wo * C;
   if (n == 0) return 0;
@@ -494,101 +455,10 @@ int stlt_maxpool3d_ndhwc(const float* x, int64_t B, int64_t T, int64_t H, int64_
 
 int stlt_avgpool_ndhwc(const float* x, int64_t B, int64_t P, int64_t C, float* y, stlt_stream_t stream) {
   if (!x || !y) return stlt_set_error(STLT_EINVAL, "stlt_avgpool_ndhwc: null pointer");
-  if (B < 0 || P <= 0 || C <= 0 || P > (1 << 24) || C > (1 << 24) || B * P * C > (1LL << 40)) return stlt_set_error(STLT_EINVAL, "stlt_avgpool_ndhwc: bad shape");
+  if (B < 0 || P <= 0 || C <= 0 || P > (1 << 24) || C > (1 << 24) || prod_over({B, P, C}, 1LL << 40)) return stlt_set_error(STLT_EINVAL, "stlt_avgpool_ndhwc: bad shape");
   if (B == 0) return 0;
   hipLaunchKernelGGL(avgpool_ndhwc_kernel, dim3((unsigned)cdiv(B * C, 256)), dim3(256), 0, (hipStream_t)stream, x, B, (int)P, (int)C, y);
   return stlt_check_launch("avgpool_ndhwc_kernel");
-}
-
-size_t stlt_r3d_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
-  if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || T > 4096 || H > 4096 || W > 4096 || B > (1 << 20)) return 0;
-  const TrunkDims d = trunk_dims(B, T, H, W);
-  if (!d.ok) return 0;
-  const int64_t f = sizeof(float);
-  return (size_t)(stlt_align256(B * T * H * W * 4 * f) + 3 * stlt_align256(d.act_elems * f) + stlt_align256(std::max(d.stem_elems, 2 * d.act_elems) * f) +
-                  stlt_align256(d.part_bytes));
-}
-
-int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
-                     float* features, float* pooled, stlt_stream_t stream) {
-  if (!p || !video || (!features && !pooled)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_forward: null pointer");
-  if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || T > 4096 || H > 4096 || W > 4096 || B > (1 << 20)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_forward: bad video shape");
-  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
-    const stlt_r3d_conv& c = p->conv[i];
-    if (!c.w || !c.bn_w || !c.bn_b || !c.bn_mean || !c.bn_var) return stlt_set_error(STLT_EINVAL, "stlt_r3d_forward: conv %d has a null weight or BatchNorm buffer", i);
-    if ((uintptr_t)c.w & 15) return stlt_set_error(STLT_EINVAL, "stlt_r3d_forward: packed weight %d is not 16-byte aligned", i);
-  }
-  const TrunkDims d = trunk_dims(B, T, H, W);
-  if (!d.ok || d.To <= 0 || d.Ho <= 0 || d.Wo <= 0) return stlt_set_error(STLT_EINVAL, "stlt_r3d_forward: video too small for the trunk");
-  const size_t need = stlt_r3d_workspace_bytes(B, T, H, W);
-  if (!workspace || workspace_bytes < need)
-    return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_forward: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  if ((uintptr_t)workspace & 255) return stlt_set_error(STLT_EINVAL, "stlt_r3d_forward: workspace must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t f = sizeof(float);
-  char* base = (char*)workspace;
-  float* xin = (float*)base; base += stlt_align256(B * T * H * W * 4 * f);
-  float* X0 = (float*)base; base += stlt_align256(d.act_elems * f);
-  float* X1 = (float*)base; base += stlt_align256(d.act_elems * f);
-  float* DS = (float*)base; base += stlt_align256(d.act_elems * f);
-  float* T1 = (float*)base;
-  float* T2 = T1 + d.act_elems;
-  base += stlt_align256(std::max(d.stem_elems, 2 * d.act_elems) * f);
-  float* part = (float*)base;
-  const float eps = p->bn_eps;
-
-  if (int e = stlt_ncdhw_to_ndhwc(video, B, 3, T, H, W, 4, xin, stream)) return e;
-  int ci = 0;
-  // conv helper: x (B, t, h, w, cin) -> y; t/h/w updated to the output's
-  auto conv = [&](const float* x, int64_t& t, int64_t& h, int64_t& w, int64_t cin, int64_t cout, int k, int sp, int st_t, int pad, const float* res, int relu,
-                  float* y) -> int {
-    const stlt_conv3d_desc desc{B, t, h, w, cin, cout, k, k, k, st_t, sp, sp, pad, pad, pad};
-    ConvGeom g;
-    if (int e = check_desc(&desc, &g)) return e;
-    const stlt_r3d_conv& c = p->conv[ci++];
-    const int64_t splits = conv_plan_splits(g.M, g.N, g.K);
-    if (int e = launch_conv(g, x, c.w, c.bn_w, c.bn_b, c.bn_mean, c.bn_var, eps, res, relu, y, splits, part, s)) return e;
-    t = g.To; h = g.Ho; w = g.Wo;
-    return 0;
-  };
-  int64_t t = T, h = H, w = W;
-  // stem (7x7x7, stride (1,2,2), pad 3) + bn1 + relu, then the max-pool
-  if (int e = conv(xin, t, h, w, 4, 64, 7, 2, 1, 3, nullptr, 1, T1)) return e;
-  if (int e = stlt_maxpool3d_ndhwc(T1, B, t, h, w, 64, X0, stream)) return e;
-  t = out_dim(t, 3, 2, 1); h = out_dim(h, 3, 2, 1); w = out_dim(w, 3, 2, 1);
-  int64_t cin = 64;
-  float *cur = X0, *nxt = X1;
-  for (int L = 0; L < 4; ++L) {
-    const int64_t planes = R3D_PLANES[L];
-    for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk) {
-      const int sp = (L > 0 && blk == 0) ? 2 : 1;
-      int64_t t1 = t, h1 = h, w1 = w;
-      if (int e = conv(cur, t1, h1, w1, cin, planes, 1, 1, 1, 0, nullptr, 1, T1)) return e;              // conv1 + bn1 + relu
-      if (int e = conv(T1, t1, h1, w1, planes, planes, 3, sp, sp, 1, nullptr, 1, T2)) return e;          // conv2 + bn2 + relu (stride)
-      // conv3 + bn3 (+ shortcut) + relu; the downsample (1x1x1, stride, + BN) comes after conv3 in state-dict order
-      const int c3 = ci;
-      const float* shortcut = cur;
-      if (blk == 0) {
-        ci = c3 + 1;
-        int64_t t2 = t, h2 = h, w2 = w;
-        if (int e = conv(cur, t2, h2, w2, cin, planes * 4, 1, sp, sp, 0, nullptr, 0, DS)) return e;
-        shortcut = DS;
-        ci = c3;
-      }
-      if (int e = conv(T2, t1, h1, w1, planes, planes * 4, 1, 1, 1, 0, shortcut, 1, nxt)) return e;
-      if (blk == 0) ci = c3 + 2;
-      t = t1; h = h1; w = w1;
-      cin = planes * 4;
-      std::swap(cur, nxt);
-    }
-  }
-  if (ci != STLT_R3D_CONVS) return stlt_set_error(STLT_EINVAL, "stlt_r3d_forward: internal plan error (%d convs)", ci);
-  const int64_t P = t * h * w;
-  if (features)
-    if (int e = stlt_ndhwc_to_ncdhw(cur, B, P, cin, features, stream)) return e;
-  if (pooled)
-    if (int e = stlt_avgpool_ndhwc(cur, B, P, cin, pooled, stream)) return e;
-  return 0;
 }
 
 }  // extern "C"
@@ -675,7 +545,8 @@ __global__ __launch_bounds__(256) void conv3d_repack_dgrad_kernel(const float* _
   }
 }
 
-// the trunk's fixed plan, conv i in state-dict order: (c_out, c_in, k, stride); the stem is 7x7x7 stride (1, 2, 2) pad 3
+// the trunk's fixed plan, conv i in state-dict order: (c_out, c_in, k, stride); the stem is 7x7x7 stride (1, 2, 2) pad 3.
+// The one statement of which block has a downsample and which stride: the batched repack reads it on the device, trunk_plan on the host.
 struct R3dConvMeta { int cout, cin, k, s; };
 __host__ __device__ inline R3dConvMeta r3d_conv_meta(int i) {
   if (i == 0) return {64, 3, 7, 2};
@@ -1107,7 +978,7 @@ int check_thin_desc(const stlt_conv3d_desc* d, const char* who, ThinGeom* g) {
   if (d->c_out % 4) return stlt_set_error(STLT_EINVAL, "%s: c_out must be a multiple of 4 (dy's rows are read as 16-byte quads), got %lld", who, (long long)d->c_out);
   const int64_t To = d->T, Ho = (d->H - 1) / 2 + 1, Wo = (d->W - 1) / 2 + 1;
   const int64_t tiles_i = cdiv(Ho, TH_TI), tiles_j = cdiv(Wo, TH_TJ);
-  if (d->B * d->T * tiles_i * tiles_j > 0x7fffff00LL || d->B * d->T * d->H * d->W * 4 > (1LL << 40) || d->B * To * Ho * Wo * d->c_out > (1LL << 40))
+  if (prod_over({d->B, d->T, tiles_i, tiles_j}, 0x7fffff00LL) || prod_over({d->B, d->T, d->H, d->W, 4}, 1LL << 40) || prod_over({d->B, To, Ho, Wo, d->c_out}, 1LL << 40))
     return stlt_set_error(STLT_EINVAL, "%s: shape too large", who);
   if (g) *g = ThinGeom{(int)d->B, (int)d->T, (int)d->H, (int)d->W, (int)To, (int)Ho, (int)Wo, (int)d->c_out, (int)d->c_in, (int)tiles_i, (int)tiles_j};
   return 0;
@@ -1166,6 +1037,9 @@ int dgrad_plan(const ConvGeom& f, SubConv* out) {
   return n;
 }
 
+// what the data gradient asks beyond check_desc: at most 2^3 parity classes (SubConv[8]), and a contraction, taps · c_out, that is an int
+bool dgrad_fits(const ConvGeom& g) { return g.st <= 2 && g.sh <= 2 && g.sw <= 2 && !prod_over({g.kt, g.kh, g.kw, g.N}, 0x7fffff00LL); }
+
 // a class without taps (K = 0) or without rows (M = 0: an input extent of 1 under stride 2) is never split
 int64_t dgrad_splits(const ConvGeom& s) { return s.K > 0 && s.M > 0 ? conv_plan_splits(s.M, s.N, s.K) : 1; }
 
@@ -1191,12 +1065,7 @@ int launch_dgrad(const ConvGeom& f, const float* dy, const float* wd, const floa
     if (c.g.M == 0 || (skip_empty && c.g.K == 0)) continue;
     c.e.sc = sc; c.e.mask = mask; c.e.add = add;
     const int bn = conv_bn_tile(c.g.N);
-    const int64_t slabs = cdiv(c.g.K, CK);
-    int64_t splits = n_split > 0 ? n_split : dgrad_splits(c.g);
-    if (slabs > 0 && splits > slabs) splits = slabs;
-    if (slabs == 0) splits = 1;
-    const int64_t per = slabs > 0 ? cdiv(slabs, splits) : 1;
-    if (slabs > 0) splits = cdiv(slabs, per);
+    const auto [splits, per] = split_ranges(cdiv(c.g.K, CK), n_split > 0 ? n_split : dgrad_splits(c.g));
     if (splits > 1 && (!part || part_bytes < conv_split_bytes(c.g, splits)))
       return stlt_set_error(STLT_EWORKSPACE, "stlt_conv3d_bwd_data: %lld splits need %lld workspace bytes, %lld lent", (long long)splits,
                             (long long)conv_split_bytes(c.g, splits), (long long)part_bytes);
@@ -1229,20 +1098,17 @@ int64_t wgrad_plan_splits(const ConvGeom& g) {
   int64_t splits = cdiv(WG_TARGET_WG, tiles);
   splits = std::min(splits, slabs / WG_MIN_SLABS);
   splits = std::min(splits, WG_SPLIT_MAX);
-  if (splits < 1) splits = 1;
-  const int64_t per = cdiv(slabs, splits);
-  return cdiv(slabs, per);
+  return split_ranges(slabs, splits).splits;
 }
+
+// the weight gradient's partial slabs hold c_out · K floats each: past 2^40 of them the byte count of WG_SPLIT_MAX slabs leaves int64
+bool wgrad_fits(const ConvGeom& g) { return !prod_over({g.N, g.K}, 1LL << 40); }
 
 int64_t wgrad_ws_bytes(const ConvGeom& g, int64_t splits) { return splits * (int64_t)g.N * g.K * (int64_t)sizeof(float); }
 
 int launch_wgrad(const ConvGeom& g, const float* x, const float* dy, int cin_w, const float* scale, const float* bn_w, const float* bn_var, float eps,
-                 int accumulate, float* dw, int64_t splits, float* part, hipStream_t s) {
-  const int64_t slabs = cdiv(g.M, CK);
-  if (splits > slabs) splits = slabs;
-  if (splits < 1) splits = 1;
-  const int64_t per = cdiv(slabs, splits);
-  splits = cdiv(slabs, per);
+                 int accumulate, float* dw, int64_t want_splits, float* part, hipStream_t s) {
+  const auto [splits, per] = split_ranges(cdiv(g.M, CK), want_splits);
   const int ta = wgrad_tile(g.N);
   const dim3 grid((unsigned)cdiv(g.N, ta), (unsigned)cdiv(g.K, WG_TK), (unsigned)splits), block(256);
   if (ta == 64)
@@ -1256,67 +1122,103 @@ int launch_wgrad(const ConvGeom& g, const float* x, const float* dy, int cin_w, 
   return stlt_check_launch("conv3d_wgrad_finish_kernel");
 }
 
-// ---- the whole trunk's geometry: every conv's ConvGeom (forward), the tape's layout and the backward's workspace ----
+// ---- the whole trunk, stated once.  trunk_plan is the only function that knows R3D-50's structure: it walks r3d_conv_meta's table
+// (the stem; per block conv1, conv2, conv3 and, in a layer's first block, the downsample) through check_desc and lays out the three
+// buffers.  The size queries return its byte counts; the forward and the reverse sweep add its offsets to the caller's bases.
+//   inference workspace  [xin][X0][X1][DS][T1 | T2][part]   X0 / X1: the block outputs, ping-pong (X0 first holds the max-pool's);
+//                        T1 / T2: conv1's / conv2's (T1 first holds the stem's); DS: the downsample's; part: split-forward partials
+//   tape                 [xin][stem][pool][argmax], then per block [conv1][conv2][output]
+//   backward workspace   [G3][G2][G1][GX][GS][part]          gradients at a block's output, conv2, conv1 and input; GS: at the stem's
+//                        output; part: the largest weight- or data-gradient partial
+constexpr int R3D_LAYERS = 4;                                       // each opens with the one block that has a downsample
+constexpr int R3D_NBLOCKS = (STLT_R3D_CONVS - 1 - R3D_LAYERS) / 3;  // 53 = the stem + 3 per block + a downsample per layer
+
+struct TrunkBlock {
+  int conv1;             // conv1's index; conv2, conv3 and (ds) the downsample follow it in state-dict order
+  bool ds;
+  int64_t x, a1, a2, y;  // tape slots: the block's input (the block before's output; the first block's: the max-pool's), conv1, conv2, output
+};
+
 struct TrunkPlan {
   ConvGeom g[STLT_R3D_CONVS];
-  int64_t xin = 0, stem = 0, pool = 0, argmax = 0;       // tape offsets (bytes)
-  int64_t a1[16], a2[16], y[16];                         // per block
-  int64_t tape_bytes = 0;
-  int64_t stem_elems = 0, pool_elems = 0, act_elems = 0; // act: largest block-level activation
-  int64_t bwd_part_bytes = 0;                            // largest dgrad / wgrad partial
-  int Tp = 0, Hp = 0, Wp = 0;                            // max-pool output
-  bool ok = false;
+  int64_t fwd_splits[STLT_R3D_CONVS];
+  TrunkBlock blk[R3D_NBLOCKS];
+  int64_t stem_elems, pool_elems, act_elems;  // act: the largest block-level activation
+  int64_t fwd_part_bytes, bwd_part_bytes;     // the largest split-forward partial; the largest dgrad / wgrad partial
+  struct { int64_t xin, stem, pool, argmax, bytes; } tape;  // byte offsets; the blocks' slots are in blk[]
+  struct { int64_t xin, x[2], ds, t1, t2, part, bytes; } ws;
+  struct { int64_t g3, g2, g1, gx, gs, part, bytes; } bws;
+};
+
+struct Carver {  // consecutive 256-byte aligned buffers
+  int64_t off = 0;
+  int64_t take(int64_t bytes) { const int64_t o = off; off += (int64_t)stlt_align256((size_t)bytes); return o; }
 };
 
 bool trunk_plan(int64_t B, int64_t T, int64_t H, int64_t W, TrunkPlan* P) {
   TrunkPlan& p = *P;
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || T > 4096 || H > 4096 || W > 4096 || B > (1 << 20)) return false;
   const int64_t f = sizeof(float);
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { const int64_t o = off; off += stlt_align256(bytes); return o; };
-  auto geom = [&](int i, int64_t t, int64_t h, int64_t w, int64_t cin, int64_t cout, int k, int st, int sp, int pad) -> bool {
-    const stlt_conv3d_desc d{B, t, h, w, cin, cout, k, k, k, st, sp, sp, pad, pad, pad};
-    return check_desc(&d, &p.g[i]) == 0;
+  // conv i over an input of (t, h, w): the table's cubic kernel with padding k / 2, channels stored in quads, stride s (the stem: 1 in t)
+  auto geom = [&](int i, int64_t t, int64_t h, int64_t w) -> bool {
+    const R3dConvMeta m = r3d_conv_meta(i);
+    const int64_t pad = m.k / 2;
+    const stlt_conv3d_desc d{B, t, h, w, (m.cin + 3) / 4 * 4, m.cout, m.k, m.k, m.k, i == 0 ? 1 : m.s, m.s, m.s, pad, pad, pad};
+    if (check_desc(&d, &p.g[i])) return false;
+    p.fwd_splits[i] = conv_plan_splits(p.g[i].M, p.g[i].N, p.g[i].K);
+    return true;
   };
-  if (!geom(0, T, H, W, 4, 64, 7, 1, 2, 3)) return false;
+  auto elems = [&](int i) { return (int64_t)p.g[i].M * p.g[i].N; };
+  if (!geom(0, T, H, W)) return false;
   const ConvGeom& s0 = p.g[0];
-  p.stem_elems = (int64_t)s0.M * 64;
-  const int64_t Tp = out_dim(s0.To, 3, 2, 1), Hp = out_dim(s0.Ho, 3, 2, 1), Wp = out_dim(s0.Wo, 3, 2, 1);
-  p.Tp = (int)Tp; p.Hp = (int)Hp; p.Wp = (int)Wp;
-  p.pool_elems = B * Tp * Hp * Wp * 64;
-  p.xin = take(B * T * H * W * 4 * f);
-  p.stem = take(p.stem_elems * f);
-  p.pool = take(p.pool_elems * f);
-  p.argmax = take(p.pool_elems);
+  const int64_t Tp = out_dim(s0.To, 3, 2, 1), Hp = out_dim(s0.Ho, 3, 2, 1), Wp = out_dim(s0.Wo, 3, 2, 1);  // the max-pool
+  p.stem_elems = elems(0);
+  p.pool_elems = B * Tp * Hp * Wp * s0.N;
+  Carver tape;
+  p.tape.xin = tape.take(B * T * H * W * 4 * f);
+  p.tape.stem = tape.take(p.stem_elems * f);
+  p.tape.pool = tape.take(p.pool_elems * f);
+  p.tape.argmax = tape.take(p.pool_elems);
   p.act_elems = p.pool_elems;
-  int64_t t = Tp, h = Hp, w = Wp, cin = 64;
-  int ci = 1, blk_i = 0;
-  for (int L = 0; L < 4; ++L) {
-    const int64_t planes = R3D_PLANES[L];
-    for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk, ++blk_i) {
-      const int s = (L > 0 && blk == 0) ? 2 : 1;
-      if (!geom(ci, t, h, w, cin, planes, 1, 1, 1, 0)) return false;
-      const ConvGeom& c1 = p.g[ci];
-      if (!geom(ci + 1, c1.To, c1.Ho, c1.Wo, planes, planes, 3, s, s, 1)) return false;
-      const ConvGeom& c2 = p.g[ci + 1];
-      if (!geom(ci + 2, c2.To, c2.Ho, c2.Wo, planes, planes * 4, 1, 1, 1, 0)) return false;
-      if (blk == 0 && !geom(ci + 3, t, h, w, cin, planes * 4, 1, s, s, 0)) return false;
-      const ConvGeom& c3 = p.g[ci + 2];
-      p.a1[blk_i] = take((int64_t)c1.M * c1.N * f);
-      p.a2[blk_i] = take((int64_t)c2.M * c2.N * f);
-      p.y[blk_i] = take((int64_t)c3.M * c3.N * f);
-      p.act_elems = std::max({p.act_elems, (int64_t)c1.M * c1.N, (int64_t)c2.M * c2.N, (int64_t)c3.M * c3.N});
-      t = c3.To; h = c3.Ho; w = c3.Wo;
-      cin = planes * 4;
-      ci += blk == 0 ? 4 : 3;
-    }
+  int64_t t = Tp, h = Hp, w = Wp, x = p.tape.pool;
+  int i = 1;
+  for (TrunkBlock& k : p.blk) {
+    k.conv1 = i;
+    k.ds = r3d_conv_meta(i + 3).cout == r3d_conv_meta(i + 2).cout;  // the entry behind conv3 projects onto this block's output: its downsample
+    if (!geom(i, t, h, w) || !geom(i + 1, p.g[i].To, p.g[i].Ho, p.g[i].Wo) || !geom(i + 2, p.g[i + 1].To, p.g[i + 1].Ho, p.g[i + 1].Wo)) return false;
+    if (k.ds && !geom(i + 3, t, h, w)) return false;
+    k.x = x;
+    k.a1 = tape.take(elems(i) * f);
+    k.a2 = tape.take(elems(i + 1) * f);
+    k.y = tape.take(elems(i + 2) * f);
+    p.act_elems = std::max({p.act_elems, elems(i), elems(i + 1), elems(i + 2)});
+    t = p.g[i + 2].To; h = p.g[i + 2].Ho; w = p.g[i + 2].Wo; x = k.y;
+    i += k.ds ? 4 : 3;
   }
-  p.tape_bytes = off;
-  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
-    p.bwd_part_bytes = std::max(p.bwd_part_bytes, wgrad_ws_bytes(p.g[i], wgrad_plan_splits(p.g[i])));
-    if (i > 0) p.bwd_part_bytes = std::max(p.bwd_part_bytes, dgrad_ws_bytes(p.g[i]));
+  p.tape.bytes = tape.off;
+  p.fwd_part_bytes = p.bwd_part_bytes = 0;
+  for (int c = 0; c < STLT_R3D_CONVS; ++c) {
+    p.fwd_part_bytes = std::max(p.fwd_part_bytes, conv_split_bytes(p.g[c], p.fwd_splits[c]));
+    p.bwd_part_bytes = std::max(p.bwd_part_bytes, wgrad_ws_bytes(p.g[c], wgrad_plan_splits(p.g[c])));
+    if (c > 0) p.bwd_part_bytes = std::max(p.bwd_part_bytes, dgrad_ws_bytes(p.g[c]));  // the stem's data gradient is the thin kernel: no scratch
   }
-  p.ok = true;
+  Carver ws;
+  p.ws.xin = ws.take(B * T * H * W * 4 * f);
+  p.ws.x[0] = ws.take(p.act_elems * f);
+  p.ws.x[1] = ws.take(p.act_elems * f);
+  p.ws.ds = ws.take(p.act_elems * f);
+  p.ws.t1 = ws.take(std::max(p.stem_elems, 2 * p.act_elems) * f);  // one region: the stem's output is dead once the blocks write T1 and T2
+  p.ws.t2 = p.ws.t1 + p.act_elems * f;
+  p.ws.part = ws.take(p.fwd_part_bytes);
+  p.ws.bytes = ws.off;
+  Carver bws;
+  p.bws.g3 = bws.take(p.act_elems * f);
+  p.bws.g2 = bws.take(p.act_elems * f);
+  p.bws.g1 = bws.take(p.act_elems * f);
+  p.bws.gx = bws.take(p.act_elems * f);
+  p.bws.gs = bws.take(p.stem_elems * f);
+  p.bws.part = bws.take(p.bwd_part_bytes);
+  p.bws.bytes = bws.off;
   return true;
 }
 
@@ -1330,24 +1232,19 @@ int check_r3d_params(const stlt_r3d_params* p, const char* who) {
   return 0;
 }
 
-int64_t r3d_bwd_ws_bytes(const TrunkPlan& p) {
-  const int64_t f = sizeof(float);
-  return 4 * stlt_align256(p.act_elems * f) + stlt_align256(p.stem_elems * f) + stlt_align256(p.bwd_part_bytes);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t stlt_conv3d_bwd_data_workspace_bytes(const stlt_conv3d_desc* d, int n_split) {
   ConvGeom g;
-  if (check_desc(d, &g)) return 0;
+  if (check_desc(d, &g) || !dgrad_fits(g)) return 0;
   if (n_split <= 0) return (size_t)dgrad_ws_bytes(g);
   SubConv sub[8];
   const int n = dgrad_plan(g, sub);
   int64_t mx = 0;
   for (int i = 0; i < n; ++i)
-    if (sub[i].g.K > 0 && n_split > 1) mx = std::max(mx, conv_split_bytes(sub[i].g, conv_clamp_splits(cdiv(sub[i].g.K, CK), n_split)));
+    mx = std::max(mx, conv_split_bytes(sub[i].g, split_ranges(cdiv(sub[i].g.K, CK), n_split).splits));
   return (size_t)mx;
 }
 
@@ -1370,6 +1267,7 @@ int stlt_conv3d_bwd_data(const stlt_conv3d_desc* d, const float* dy, const float
   if (g.N % 4) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: c_out must be a multiple of 4 (it is the contraction's channel count), got %d", g.N);
   if (g.st > 2 || g.sh > 2 || g.sw > 2 || g.st != g.sh || g.st != g.sw)
     return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: strides must be equal and at most 2");
+  if (!dgrad_fits(g)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: shape too large");
   if (((uintptr_t)dy & 15) || ((uintptr_t)w_dgrad & 15)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: dy and w_dgrad must be 16-byte aligned");
   if (n_split < 0 || n_split > 1024) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_data: n_split must lie in [0, 1024]");
   const size_t need = stlt_conv3d_bwd_data_workspace_bytes(d, n_split);
@@ -1380,12 +1278,9 @@ int stlt_conv3d_bwd_data(const stlt_conv3d_desc* d, const float* dy, const float
 
 size_t stlt_conv3d_bwd_weight_workspace_bytes(const stlt_conv3d_desc* d, int n_split) {
   ConvGeom g;
-  if (check_desc(d, &g)) return 0;
+  if (check_desc(d, &g) || !wgrad_fits(g)) return 0;
   if (n_split < 0 || n_split > 4096) return 0;
-  const int64_t slabs = cdiv(g.M, CK);
-  int64_t splits = n_split == 0 ? wgrad_plan_splits(g) : std::min<int64_t>(n_split, slabs);
-  splits = cdiv(slabs, cdiv(slabs, splits));
-  return (size_t)wgrad_ws_bytes(g, splits);
+  return (size_t)wgrad_ws_bytes(g, split_ranges(cdiv(g.M, CK), n_split == 0 ? wgrad_plan_splits(g) : n_split).splits);
 }
 
 int stlt_conv3d_bwd_weight(const stlt_conv3d_desc* d, const float* x, const float* dy, const float* scale, int64_t c_in_w, int accumulate, int n_split,
@@ -1394,6 +1289,7 @@ int stlt_conv3d_bwd_weight(const stlt_conv3d_desc* d, const float* x, const floa
   if (int e = check_desc(d, &g)) return e;
   if (!x || !dy || !dw) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: null pointer");
   if (g.N % 4) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: c_out must be a multiple of 4, got %d", g.N);
+  if (!wgrad_fits(g)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: shape too large");
   if (c_in_w <= 0 || c_in_w > g.C) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: c_in_w must lie in [1, c_in]");
   if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15)) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: x and dy must be 16-byte aligned");
   if (n_split < 0 || n_split > 4096) return stlt_set_error(STLT_EINVAL, "stlt_conv3d_bwd_weight: n_split must lie in [0, 4096]");
@@ -1406,8 +1302,7 @@ int stlt_conv3d_bwd_weight(const stlt_conv3d_desc* d, const float* x, const floa
 
 int stlt_maxpool3d_ndhwc_train(const float* x, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, float* y, uint8_t* argmax, stlt_stream_t stream) {
   if (!x || !y || !argmax) return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_train: null pointer");
-  if (B < 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || T > (1 << 24) || H > (1 << 24) || W > (1 << 24) || C > (1 << 24) || B * T * H * W * C > (1LL << 40))
-    return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_train: bad shape");
+  if (int e = check_pool_shape("stlt_maxpool3d_ndhwc_train", B, T, H, W, C)) return e;
   const int64_t To = out_dim(T, 3, 2, 1), Ho = out_dim(H, 3, 2, 1), Wo = out_dim(W, 3, 2, 1);
   const int64_t n = B * To * Ho * Wo * C;
   if (n == 0) return 0;
@@ -1419,8 +1314,7 @@ int stlt_maxpool3d_ndhwc_train(const float* x, int64_t B, int64_t T, int64_t H, 
 int stlt_maxpool3d_ndhwc_bwd(const float* dy, const uint8_t* argmax, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, const float* mask, float* dx,
                              stlt_stream_t stream) {
   if (!dy || !argmax || !dx) return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_bwd: null pointer");
-  if (B < 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || T > (1 << 24) || H > (1 << 24) || W > (1 << 24) || C > (1 << 24) || B * T * H * W * C > (1LL << 40))
-    return stlt_set_error(STLT_EINVAL, "stlt_maxpool3d_ndhwc_bwd: bad shape");
+  if (int e = check_pool_shape("stlt_maxpool3d_ndhwc_bwd", B, T, H, W, C)) return e;
   const int64_t To = out_dim(T, 3, 2, 1), Ho = out_dim(H, 3, 2, 1), Wo = out_dim(W, 3, 2, 1);
   const int64_t n = B * T * H * W * C;
   if (n == 0) return 0;
@@ -1429,16 +1323,24 @@ int stlt_maxpool3d_ndhwc_bwd(const float* dy, const uint8_t* argmax, int64_t B, 
   return stlt_check_launch("maxpool3d_bwd_kernel");
 }
 
+// the whole-trunk size queries: the plan's byte counts (0 for a shape the plan refuses)
+size_t stlt_r3d_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
+  TrunkPlan p;
+  return trunk_plan(B, T, H, W, &p) ? (size_t)p.ws.bytes : 0;
+}
+
 size_t stlt_r3d_tape_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
   TrunkPlan p;
-  if (!trunk_plan(B, T, H, W, &p)) return 0;
-  return (size_t)p.tape_bytes;
+  return trunk_plan(B, T, H, W, &p) ? (size_t)p.tape.bytes : 0;
 }
 
 size_t stlt_r3d_backward_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
   TrunkPlan p;
-  if (!trunk_plan(B, T, H, W, &p)) return 0;
-  return (size_t)r3d_bwd_ws_bytes(p);
+  return trunk_plan(B, T, H, W, &p) ? (size_t)p.bws.bytes : 0;
+}
+
+size_t stlt_r3d_backward_inputs_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
+  return stlt_r3d_backward_workspace_bytes(B, T, H, W);  // the thin data gradient needs no scratch of its own
 }
 
 int stlt_r3d_repack_all(const float* const* weights, const stlt_r3d_params* p, float* const* fwd, float* const* dgrad, stlt_stream_t stream) {
@@ -1462,63 +1364,76 @@ int stlt_r3d_repack_all(const float* const* weights, const stlt_r3d_params* p, f
   return stlt_check_launch("r3d_repack_all_kernel");
 }
 
-int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
-                           void* tape, size_t tape_bytes, float* features, float* pooled, stlt_stream_t stream) {
-  if (int e = check_r3d_params(p, "stlt_r3d_train_forward")) return e;
-  if (!video || !tape || (!features && !pooled)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_train_forward: null pointer");
+}  // extern "C"
+
+// The trunk's forward, written once.  stlt_r3d_forward (tape == NULL) keeps its activations in the workspace's ping-pong buffers and
+// runs the plain max-pool; stlt_r3d_train_forward writes every activation to its tape slot and runs the max-pool that records the
+// argmax.  Nothing else differs, so the two give the same outputs bit for bit.
+static int r3d_forward(const char* who, bool train, const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace,
+                       size_t workspace_bytes, void* tape, size_t tape_bytes, float* features, float* pooled, stlt_stream_t stream) {
+  if (int e = check_r3d_params(p, who)) return e;
+  if (!video || (train && !tape) || (!features && !pooled)) return stlt_set_error(STLT_EINVAL, "%s: null pointer", who);
   TrunkPlan P;
-  if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_train_forward: bad video shape or too small for the trunk");
-  const size_t need = stlt_r3d_workspace_bytes(B, T, H, W);
-  if (!workspace || workspace_bytes < need)
-    return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_train_forward: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  if (tape_bytes < (size_t)P.tape_bytes) return stlt_set_error(STLT_EWORKSPACE, "stlt_r3d_train_forward: tape of %zu bytes, %lld needed", tape_bytes, (long long)P.tape_bytes);
-  if (((uintptr_t)workspace & 255) || ((uintptr_t)tape & 255)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_train_forward: workspace and tape must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
+  if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "%s: bad video shape or too small for the trunk", who);
+  if (!workspace || workspace_bytes < (size_t)P.ws.bytes)
+    return stlt_set_error(STLT_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, (size_t)P.ws.bytes);
+  if (train && tape_bytes < (size_t)P.tape.bytes)
+    return stlt_set_error(STLT_EWORKSPACE, "%s: tape of %zu bytes, %lld needed", who, tape_bytes, (long long)P.tape.bytes);
+  if (((uintptr_t)workspace & 255) || ((uintptr_t)tape & 255))
+    return stlt_set_error(STLT_EINVAL, "%s: %s must be 256-byte aligned", who, train ? "workspace and tape" : "workspace");
+  char* ws = (char*)workspace;
   char* tp = (char*)tape;
-  const TrunkDims d = trunk_dims(B, T, H, W);
-  // the forward's workspace layout: [xin][X0][X1][DS][T1 | T2][part]; only DS and part are used here
-  char* base = (char*)workspace;
-  base += stlt_align256(B * T * H * W * 4 * (int64_t)sizeof(float)) + 2 * stlt_align256(d.act_elems * (int64_t)sizeof(float));
-  float* DS = (float*)base;
-  base += stlt_align256(d.act_elems * (int64_t)sizeof(float)) + stlt_align256(std::max(d.stem_elems, 2 * d.act_elems) * (int64_t)sizeof(float));
-  float* part = (float*)base;
-  const float eps = p->bn_eps;
+  auto at = [](char* base, int64_t off) { return (float*)(base + off); };
+  float* xin = train ? at(tp, P.tape.xin) : at(ws, P.ws.xin);
+  float* stem = train ? at(tp, P.tape.stem) : at(ws, P.ws.t1);
+  float* pool = train ? at(tp, P.tape.pool) : at(ws, P.ws.x[0]);
+  float* DS = at(ws, P.ws.ds);
+  float* part = at(ws, P.ws.part);
   auto conv = [&](int i, const float* x, const float* res, int relu, float* y) -> int {
-    const ConvGeom& g = P.g[i];
     const stlt_r3d_conv& c = p->conv[i];
-    return launch_conv(g, x, c.w, c.bn_w, c.bn_b, c.bn_mean, c.bn_var, eps, res, relu, y, conv_plan_splits(g.M, g.N, g.K), part, s);
+    return launch_conv(P.g[i], x, c.w, c.bn_w, c.bn_b, c.bn_mean, c.bn_var, p->bn_eps, res, relu, y, P.fwd_splits[i], part, (hipStream_t)stream);
   };
-  float* xin = (float*)(tp + P.xin);
   if (int e = stlt_ncdhw_to_ndhwc(video, B, 3, T, H, W, 4, xin, stream)) return e;
-  float* stem = (float*)(tp + P.stem);
-  if (int e = conv(0, xin, nullptr, 1, stem)) return e;
-  float* pool = (float*)(tp + P.pool);
-  if (int e = stlt_maxpool3d_ndhwc_train(stem, B, P.g[0].To, P.g[0].Ho, P.g[0].Wo, 64, pool, (uint8_t*)(tp + P.argmax), stream)) return e;
+  const ConvGeom& s0 = P.g[0];
+  if (int e = conv(0, xin, nullptr, 1, stem)) return e;  // stem + bn1 + relu
+  if (int e = train ? stlt_maxpool3d_ndhwc_train(stem, B, s0.To, s0.Ho, s0.Wo, s0.N, pool, (uint8_t*)(tp + P.tape.argmax), stream)
+                    : stlt_maxpool3d_ndhwc(stem, B, s0.To, s0.Ho, s0.Wo, s0.N, pool, stream))
+    return e;
   const float* cur = pool;
-  int ci = 1, bi = 0;
-  for (int L = 0; L < 4; ++L)
-    for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk, ++bi) {
-      float* a1 = (float*)(tp + P.a1[bi]);
-      float* a2 = (float*)(tp + P.a2[bi]);
-      float* y = (float*)(tp + P.y[bi]);
-      if (int e = conv(ci, cur, nullptr, 1, a1)) return e;
-      if (int e = conv(ci + 1, a1, nullptr, 1, a2)) return e;
-      const float* shortcut = cur;
-      if (blk == 0) {
-        if (int e = conv(ci + 3, cur, nullptr, 0, DS)) return e;
-        shortcut = DS;
-      }
-      if (int e = conv(ci + 2, a2, shortcut, 1, y)) return e;
-      cur = y;
-      ci += blk == 0 ? 4 : 3;
+  for (int b = 0; b < R3D_NBLOCKS; ++b) {
+    const TrunkBlock& k = P.blk[b];
+    float* a1 = train ? at(tp, k.a1) : at(ws, P.ws.t1);
+    float* a2 = train ? at(tp, k.a2) : at(ws, P.ws.t2);
+    float* y = train ? at(tp, k.y) : at(ws, P.ws.x[(b + 1) & 1]);
+    if (int e = conv(k.conv1, cur, nullptr, 1, a1)) return e;     // conv1 + bn1 + relu
+    if (int e = conv(k.conv1 + 1, a1, nullptr, 1, a2)) return e;  // conv2 + bn2 + relu (the block's stride)
+    const float* shortcut = cur;
+    if (k.ds) {  // 1x1x1 under the block's stride, + BN
+      if (int e = conv(k.conv1 + 3, cur, nullptr, 0, DS)) return e;
+      shortcut = DS;
     }
-  const ConvGeom& last = P.g[STLT_R3D_CONVS - 1];  // conv3 of the last block (no downsample there)
+    if (int e = conv(k.conv1 + 2, a2, shortcut, 1, y)) return e;  // conv3 + bn3 + shortcut, relu
+    cur = y;
+  }
+  const ConvGeom& last = P.g[P.blk[R3D_NBLOCKS - 1].conv1 + 2];
   const int64_t Pn = (int64_t)last.To * last.Ho * last.Wo;
   if (features)
     if (int e = stlt_ndhwc_to_ncdhw(cur, B, Pn, last.N, features, stream)) return e;
   if (pooled)
     if (int e = stlt_avgpool_ndhwc(cur, B, Pn, last.N, pooled, stream)) return e;
   return 0;
+}
+
+extern "C" {
+
+int stlt_r3d_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
+                     float* features, float* pooled, stlt_stream_t stream) {
+  return r3d_forward("stlt_r3d_forward", false, p, video, B, T, H, W, workspace, workspace_bytes, nullptr, 0, features, pooled, stream);
+}
+
+int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t B, int64_t T, int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
+                           void* tape, size_t tape_bytes, float* features, float* pooled, stlt_stream_t stream) {
+  return r3d_forward("stlt_r3d_train_forward", true, p, video, B, T, H, W, workspace, workspace_bytes, tape, tape_bytes, features, pooled, stream);
 }
 
 }  // extern "C"
@@ -1538,21 +1453,19 @@ static int r3d_backward_sweep(const char* who, const stlt_r3d_params* p, const f
     return stlt_set_error(STLT_EINVAL, "%s: the stem's thin dgrad copy (dgrad_w[0], stlt_conv3d_repack_dgrad_thin) is null or not 16-byte aligned", who);
   TrunkPlan P;
   if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "%s: bad video shape or too small for the trunk", who);
-  if (tape_bytes < (size_t)P.tape_bytes) return stlt_set_error(STLT_EWORKSPACE, "%s: tape of %zu bytes, %lld needed", who, tape_bytes, (long long)P.tape_bytes);
-  const int64_t need = r3d_bwd_ws_bytes(P);
-  if (!workspace || workspace_bytes < (size_t)need)
-    return stlt_set_error(STLT_EWORKSPACE, "%s: workspace of %zu bytes, %lld needed", who, workspace_bytes, (long long)need);
+  if (tape_bytes < (size_t)P.tape.bytes) return stlt_set_error(STLT_EWORKSPACE, "%s: tape of %zu bytes, %lld needed", who, tape_bytes, (long long)P.tape.bytes);
+  if (!workspace || workspace_bytes < (size_t)P.bws.bytes)
+    return stlt_set_error(STLT_EWORKSPACE, "%s: workspace of %zu bytes, %lld needed", who, workspace_bytes, (long long)P.bws.bytes);
   if (((uintptr_t)workspace & 255) || ((uintptr_t)tape & 255)) return stlt_set_error(STLT_EINVAL, "%s: workspace and tape must be 256-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
-  const char* tp = (const char*)tape;
-  const int64_t f = sizeof(float);
-  char* base = (char*)workspace;
-  float* G3 = (float*)base; base += stlt_align256(P.act_elems * f);   // masked pre-ReLU gradient at the block's output
-  float* G2 = (float*)base; base += stlt_align256(P.act_elems * f);
-  float* G1 = (float*)base; base += stlt_align256(P.act_elems * f);
-  float* GX = (float*)base; base += stlt_align256(P.act_elems * f);   // ... at its input (the previous block's G3)
-  float* GS = (float*)base; base += stlt_align256(P.stem_elems * f);  // at the stem's output
-  float* part = (float*)base;
+  auto taped = [&](int64_t off) { return (const float*)((const char*)tape + off); };
+  auto work = [&](int64_t off) { return (float*)((char*)workspace + off); };
+  float* G3 = work(P.bws.g3);  // masked pre-ReLU gradient at the block's output
+  float* G2 = work(P.bws.g2);
+  float* G1 = work(P.bws.g1);
+  float* GX = work(P.bws.gx);  // ... at its input (the block before's G3)
+  float* GS = work(P.bws.gs);  // at the stem's output
+  float* part = work(P.bws.part);
   const float eps = p->bn_eps;
   auto wgrad = [&](int i, const float* x, const float* g) -> int {
     if (!dweight) return 0;  // the input-only sweep: no weight-gradient product
@@ -1563,36 +1476,27 @@ static int r3d_backward_sweep(const char* who, const stlt_r3d_params* p, const f
   auto dgrad = [&](int i, const float* g, const float* mask, const float* add, float* dx) {
     return launch_dgrad(P.g[i], g, dgrad_w[i], nullptr, mask, add, dx, part, P.bwd_part_bytes, 0, s, add == dx);
   };
-  // blocks in order: their conv index and tape slots
-  int first_conv[16];
   {
-    int ci = 1, bi = 0;
-    for (int L = 0; L < 4; ++L)
-      for (int blk = 0; blk < R3D_BLOCKS[L]; ++blk, ++bi) { first_conv[bi] = ci; ci += blk == 0 ? 4 : 3; }
-  }
-  {
-    const ConvGeom& last = P.g[STLT_R3D_CONVS - 1];
+    const TrunkBlock& top = P.blk[R3D_NBLOCKS - 1];
+    const ConvGeom& last = P.g[top.conv1 + 2];
     const int64_t Pn = (int64_t)last.To * last.Ho * last.Wo;
     const int64_t n = B * Pn * last.N;
-    hipLaunchKernelGGL(r3d_grad_in_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, dpooled, dfeatures, (const float*)(tp + P.y[15]), B, (int)Pn,
-                       last.N, G3);
+    hipLaunchKernelGGL(r3d_grad_in_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, dpooled, dfeatures, taped(top.y), B, (int)Pn, last.N, G3);
     if (int e = stlt_check_launch("r3d_grad_in_kernel")) return e;
   }
-  for (int bi = 15; bi >= 0; --bi) {
-    const int ci = first_conv[bi];
-    const bool has_ds = bi == 0 || bi == 3 || bi == 7 || bi == 13;
-    const float* a1 = (const float*)(tp + P.a1[bi]);
-    const float* a2 = (const float*)(tp + P.a2[bi]);
-    const float* x = bi == 0 ? (const float*)(tp + P.pool) : (const float*)(tp + P.y[bi - 1]);
-    const float* xmask = bi == 0 ? nullptr : x;  // the max-pool output has no ReLU after it
+  for (int bi = R3D_NBLOCKS - 1; bi >= 0; --bi) {
+    const TrunkBlock& k = P.blk[bi];
+    const int ci = k.conv1;
+    const float *a1 = taped(k.a1), *a2 = taped(k.a2), *x = taped(k.x);
+    const float* xmask = bi > 0 ? x : nullptr;  // the first block reads the max-pool output, which has no ReLU after it
     if (int e = wgrad(ci + 2, a2, G3)) return e;
     if (int e = dgrad(ci + 2, G3, a2, nullptr, G2)) return e;
     if (int e = wgrad(ci + 1, a1, G2)) return e;
     if (int e = dgrad(ci + 1, G2, a1, nullptr, G1)) return e;
     if (int e = wgrad(ci, x, G1)) return e;
     // block input: conv1's data gradient + the shortcut's (identity: G3 itself), masked by the input's ReLU
-    if (int e = dgrad(ci, G1, xmask, has_ds ? nullptr : G3, GX)) return e;
-    if (has_ds) {
+    if (int e = dgrad(ci, G1, xmask, k.ds ? nullptr : G3, GX)) return e;
+    if (k.ds) {
       if (int e = wgrad(ci + 3, x, G3)) return e;
       if (int e = dgrad(ci + 3, G3, xmask, GX, GX)) return e;
     }
@@ -1600,12 +1504,11 @@ static int r3d_backward_sweep(const char* who, const stlt_r3d_params* p, const f
   }
   // G3 now holds the gradient at the max-pool output: max-pool backward with the stem's ReLU mask, then the stem's weight gradient
   const ConvGeom& s0 = P.g[0];
-  const float* stem = (const float*)(tp + P.stem);
-  if (int e = stlt_maxpool3d_ndhwc_bwd(G3, (const uint8_t*)(tp + P.argmax), B, s0.To, s0.Ho, s0.Wo, 64, stem, GS, stream)) return e;
-  if (int e = wgrad(0, (const float*)(tp + P.xin), GS)) return e;
+  if (int e = stlt_maxpool3d_ndhwc_bwd(G3, (const uint8_t*)taped(P.tape.argmax), B, s0.To, s0.Ho, s0.Wo, s0.N, taped(P.tape.stem), GS, stream)) return e;
+  if (int e = wgrad(0, taped(P.tape.xin), GS)) return e;
   if (!dvideo) return 0;
   // the stem's data gradient, straight into video_frames' layout (the BN scale is folded into the thin copy)
-  const ThinGeom tg{(int)B, (int)T, (int)H, (int)W, s0.To, s0.Ho, s0.Wo, 64, 3, (int)cdiv(s0.Ho, TH_TI), (int)cdiv(s0.Wo, TH_TJ)};
+  const ThinGeom tg{(int)B, (int)T, (int)H, (int)W, s0.To, s0.Ho, s0.Wo, s0.N, 3, (int)cdiv(s0.Ho, TH_TI), (int)cdiv(s0.Wo, TH_TJ)};
   return launch_dgrad_thin(tg, GS, dgrad_w[0], dvideo, 1, s);
 }
 
@@ -1620,10 +1523,6 @@ int stlt_r3d_backward(const stlt_r3d_params* p, const float* const* dgrad_w, con
   }
   return r3d_backward_sweep("stlt_r3d_backward", p, dgrad_w, tape, tape_bytes, B, T, H, W, dfeatures, dpooled, dweight, accumulate, nullptr, workspace,
                             workspace_bytes, stream);
-}
-
-size_t stlt_r3d_backward_inputs_workspace_bytes(int64_t B, int64_t T, int64_t H, int64_t W) {
-  return stlt_r3d_backward_workspace_bytes(B, T, H, W);  // the thin data gradient needs no scratch of its own
 }
 
 int stlt_r3d_backward_inputs(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H,

@@ -292,6 +292,119 @@ void fuzz_whole_path() {
   (void)stlt_set_train_side_stream((int)uni(-1, 1));
 }
 
+// ---- the video trunk (csrc/r3d.hip): op-level Conv3d, pools and layouts, then the whole-trunk calls ----
+struct Lent { void* p; size_t n; };
+// a workspace (or tape) for a call that needs `need` bytes: exact mostly; one byte short, absent, empty or misaligned sometimes
+Lent lend(int slot, size_t need) {
+  switch (rnd() % 10) {
+    case 0: return {FA<char>(slot), need ? need - 1 : 0};
+    case 1: return {nullptr, need};
+    case 2: return {FA<char>(slot), 0};
+    case 3: return {fake(slot, true), need};
+    default: return {FA<char>(slot), need};
+  }
+}
+
+stlt_conv3d_desc conv_desc() {
+  stlt_conv3d_desc d;
+  d.B = dim(8, 1ll << 25); d.T = dim(16, 1ll << 25); d.H = dim(56, 1ll << 25); d.W = dim(56, 1ll << 25);
+  d.c_in = coin(4) ? dim(64, 1ll << 25) : 4 * uni(1, 128);
+  d.c_out = coin(4) ? dim(64, 1ll << 25) : 4 * uni(1, 512);
+  int64_t* k = &d.kt;
+  for (int i = 0; i < 3; ++i) {
+    k[i] = coin(8) ? dim(3, 1ll << 25) : uni(1, 7);
+    k[3 + i] = coin(8) ? dim(2, 1ll << 25) : uni(1, 3);
+    k[6 + i] = coin(8) ? uni(-1, 9) : uni(0, k[i] > 1 ? k[i] - 1 : 0);
+  }
+  if (coin(2)) d.sh = d.sw = d.st;  // the data gradient takes equal strides only
+  return d;
+}
+
+void fuzz_conv3d() {
+  void* s = nullptr;
+  stlt_conv3d_desc d = conv_desc();
+  const stlt_conv3d_desc* dp = coin(40) ? nullptr : &d;
+  const int n_split = coin(3) ? 0 : (int)dim(8, 5000);
+  const bool bn = coin(2);
+  Lent w = lend(300, stlt_conv3d_workspace_bytes(dp, n_split));
+  tally(stlt_conv3d_fwd(dp, F<float>(301), F<float>(302), bn ? FA<float>(303) : nullptr, bn && !coin(10) ? FA<float>(304) : nullptr, bn ? FA<float>(305) : nullptr,
+                        bn ? FA<float>(306) : nullptr, 1e-5f, coin(2) ? nullptr : FA<float>(307), (int)uni(0, 1), n_split, w.p, w.n, F<float>(308), s));
+  w = lend(300, stlt_conv3d_bwd_data_workspace_bytes(dp, n_split));
+  tally(stlt_conv3d_bwd_data(dp, F<float>(309), F<float>(310), coin(2) ? nullptr : FA<float>(311), coin(2) ? nullptr : FA<float>(312), coin(2) ? nullptr : FA<float>(313),
+                             n_split, w.p, w.n, F<float>(314), s));
+  w = lend(300, stlt_conv3d_bwd_weight_workspace_bytes(dp, n_split));
+  tally(stlt_conv3d_bwd_weight(dp, F<float>(315), F<float>(316), coin(2) ? nullptr : FA<float>(317), coin(6) ? dim(4, 1ll << 25) : d.c_in - uni(0, 1), (int)uni(0, 1), n_split, w.p,
+                               w.n, F<float>(318), s));
+  tally(stlt_conv3d_repack(F<float>(319), d.c_out, d.c_in - uni(0, 3), d.kt, d.kh, d.kw, coin(8) ? dim(64, 1ll << 25) : d.c_in, F<float>(320), s));
+  tally(stlt_conv3d_repack_dgrad(F<float>(319), dp, coin(2) ? nullptr : FA<float>(321), F<float>(322), s));
+  g_calls += 3;
+  // the thin pair takes one geometry (7x7x7, stride (1, 2, 2), padding 3, at most 4 input channels): that one mostly, the general descriptor sometimes
+  stlt_conv3d_desc t = d;
+  if (!coin(4)) {
+    t.kt = t.kh = t.kw = 7; t.st = 1; t.sh = t.sw = 2; t.pt = t.ph = t.pw = 3;
+    t.c_in = coin(8) ? dim(4, 64) : uni(1, 4);
+    t.c_out = coin(8) ? dim(64, 1ll << 25) : 4 * uni(1, 64);
+  }
+  (void)stlt_conv3d_repack_dgrad_thin_floats(coin(40) ? nullptr : &t);
+  ++g_calls;
+  tally(stlt_conv3d_repack_dgrad_thin(F<float>(323), coin(40) ? nullptr : &t, coin(2) ? nullptr : FA<float>(324), F<float>(325), s));
+  tally(stlt_conv3d_bwd_data_thin(coin(40) ? nullptr : &t, F<float>(326), F<float>(327), F<float>(328), coin(8) ? (int)uni(-1, 3) : (int)uni(0, 1), s));
+  const int64_t B = dim(8, 1ll << 40), T = dim(16, 1ll << 25), H = dim(56, 1ll << 25), W = dim(56, 1ll << 25), C = dim(64, 1ll << 25), P = dim(3136, 1ll << 40);
+  tally(stlt_ncdhw_to_ndhwc(F<float>(329), B, coin(2) ? 3 : C, T, H, W, coin(2) ? 4 : dim(64, 1ll << 25), F<float>(330), s));
+  tally(stlt_ndhwc_to_ncdhw(F<float>(331), B, P, C, F<float>(332), s));
+  tally(stlt_maxpool3d_ndhwc(F<float>(333), B, T, H, W, C, F<float>(334), s));
+  tally(stlt_maxpool3d_ndhwc_train(F<float>(333), B, T, H, W, C, F<float>(334), F<uint8_t>(335), s));
+  tally(stlt_maxpool3d_ndhwc_bwd(F<float>(336), F<uint8_t>(335), B, T, H, W, C, coin(2) ? nullptr : FA<float>(337), F<float>(338), s));
+  tally(stlt_avgpool_ndhwc(F<float>(339), B, P, C, F<float>(340), s));
+}
+
+long g_trunk_ok[4];  // stlt_r3d_forward, stlt_r3d_train_forward, stlt_r3d_backward, stlt_r3d_backward_inputs
+void tally_trunk(int which, int rc) { tally(rc); g_trunk_ok[which] += rc == 0; }
+
+void fuzz_r3d() {
+  void* s = nullptr;
+  // the video: a small clip mostly (every size walks all 53 convolutions), the limits of the trunk and past them sometimes
+  const bool wild = coin(5);
+  const int64_t B = wild ? dim(4, 1ll << 21) : uni(1, 4), T = wild ? dim(16, 4100) : uni(1, 33), H = wild ? dim(112, 4100) : uni(1, 130),
+                W = wild ? dim(112, 4100) : uni(1, 130);
+  // pointers: valid for two calls in three, otherwise each of them null or misaligned now and then
+  const bool tidy = !coin(3);
+  stlt_r3d_params p;
+  const float* weights[STLT_R3D_CONVS];
+  float *fwd[STLT_R3D_CONVS], *dg[STLT_R3D_CONVS], *dw[STLT_R3D_CONVS];
+  for (int i = 0; i < STLT_R3D_CONVS; ++i) {
+    auto ptr = [&](int slot) { return tidy ? FA<float>(slot) : F<float>(slot); };
+    p.conv[i] = stlt_r3d_conv{ptr(400 + i), ptr(460), ptr(461), ptr(462), ptr(463)};
+    weights[i] = ptr(470 + i); fwd[i] = ptr(400 + i); dg[i] = ptr(530 + i); dw[i] = ptr(590 + i);
+  }
+  p.bn_eps = 1e-5f;
+  if (coin(6)) fwd[rnd() % STLT_R3D_CONVS] = nullptr;  // a copy that is not wanted ...
+  if (coin(30)) dg[0] = nullptr;                        // ... and the stem's data-gradient copy, which stlt_r3d_repack_all ignores
+  tally(stlt_r3d_repack_all(coin(40) ? nullptr : weights, coin(40) ? nullptr : &p, fwd, dg, s));
+  const size_t ws = stlt_r3d_workspace_bytes(B, T, H, W), tape = stlt_r3d_tape_bytes(B, T, H, W), bws = stlt_r3d_backward_workspace_bytes(B, T, H, W);
+  (void)stlt_r3d_backward_inputs_workspace_bytes(B, T, H, W);
+  g_calls += 4;
+  auto lend_or_exact = [&](int slot, size_t need) { return tidy ? Lent{FA<char>(slot), need} : lend(slot, need); };
+  auto out = [&](int slot) { return coin(3) ? nullptr : FA<float>(slot); };
+  float *features = out(650), *pooled = features && !coin(3) ? nullptr : FA<float>(651);
+  if (!tidy && coin(4)) features = pooled = nullptr;
+  const stlt_r3d_params* pp = !tidy && coin(10) ? nullptr : &p;
+  const float* video = tidy ? FA<float>(652) : F<float>(652);
+  Lent w = lend_or_exact(653, ws), t = lend_or_exact(654, tape);
+  tally_trunk(0, stlt_r3d_forward(pp, video, B, T, H, W, w.p, w.n, features, pooled, s));
+  tally_trunk(1, stlt_r3d_train_forward(pp, video, B, T, H, W, w.p, w.n, t.p, t.n, features, pooled, s));
+  // the gradient seed: exactly one of the two, both or neither sometimes
+  const float *dfeat = coin(2) ? FA<float>(655) : nullptr, *dpool = dfeat ? nullptr : FA<float>(656);
+  if (!tidy && coin(4)) { dfeat = coin(2) ? FA<float>(655) : nullptr; dpool = dfeat ? FA<float>(656) : nullptr; }
+  w = lend_or_exact(657, bws);
+  const int acc = (int)uni(0, 1);
+  tally_trunk(2, stlt_r3d_backward(pp, !tidy && coin(10) ? nullptr : dg, t.p, t.n, B, T, H, W, dfeat, dpool, !tidy && coin(6) ? nullptr : dw, acc, w.p, w.n, s));
+  float* dvideo = coin(2) ? FA<float>(658) : nullptr;
+  float* const* dwp = dvideo && coin(2) ? nullptr : dw;  // the input-only sweep
+  if (!tidy && coin(6)) { dvideo = nullptr; dwp = nullptr; }
+  tally_trunk(3, stlt_r3d_backward_inputs(pp, dg, t.p, t.n, B, T, H, W, dfeat, dpool, dwp, acc, dvideo, w.p, w.n, s));
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -311,8 +424,12 @@ int main(int argc, char** argv) {
     fuzz_products();
     fuzz_rowwise_and_attention();
     fuzz_whole_path();
+    fuzz_conv3d();
+    fuzz_r3d();
     if ((i & 1023) == 1023) (void)stlt_prof_take_gemm_flops();
   }
+  printf("host_fuzz: r3d calls that returned 0: forward %ld train_forward %ld backward %ld backward_inputs %ld\n", g_trunk_ok[0], g_trunk_ok[1], g_trunk_ok[2],
+         g_trunk_ok[3]);
   printf("host_fuzz: %ld iterations, %ld calls, %ld returned 0 (the rest refused their arguments); kernel launches configured: %ld , refused by the runtime: %ld ; last error: %s\n",
          iters, g_calls, g_ok, stlt_fake_hip_launches(), stlt_fake_hip_refused(), stlt_last_error());
   return 0;

@@ -83,3 +83,7 @@ def test_host_launchers_are_clean_under_asan_and_ubsan(seed):
     assert f"host_fuzz: {ITERS} iterations" in r.stdout, tail
     launches = int(r.stdout.split("kernel launches configured: ")[1].split()[0])
     assert launches > 20 * ITERS, tail  # the whole-path entry points really walked their launch sequences
+    # ... and so did each of the video trunk's: none of the four is refused every time
+    counts = r.stdout.split("r3d calls that returned 0: ")[1].split("\n")[0].split()
+    assert counts[0::2] == ["forward", "train_forward", "backward", "backward_inputs"], tail
+    assert all(int(n) >= 20 for n in counts[1::2]), tail

@@ -126,6 +126,61 @@ def test_sweep_reaches_the_plans(pkg):
     assert all(odd), odd
 
 
+# ---- the whole-trunk size queries against an enumeration of the 53 descriptors and the op-level queries ----
+QUERY_SHAPES = list(SWEEP.SHAPES) + [SWEEP.BIG, (2, 32, 112, 112), (1, 1, 1, 1), (2, 3, 17, 9), (5, 7, 33, 40)]
+OVERSIZED = [(2 ** 20, 32, 112, 112), (1, 4096, 4096, 4096)]  # within the trunk's own limits, refused by a conv's (rows and elements below 2^31)
+
+
+def _a(n):
+    return -(-n // 256) * 256
+
+
+def enumerated_sizes(pkg, lib, B, T, H, W):
+    """(inference workspace, tape, backward workspace) bytes from the descriptors: block-level activations, and per conv the op-level
+    workspace queries with n_split = 0 (the library's plan, which is what the trunk runs)."""
+    descs = trunk_descs(B, T, H, W)
+    out_elems, fwd_ws, wg_ws, dg_ws = [], [], [], []
+    for b, t, h, w, ci, co, k, s, p in descs:
+        d = _desc(pkg, b, t, h, w, ci, co, (k,) * 3, s, (p,) * 3)
+        M, _ = _dims(b, t, h, w, co, (k,) * 3, s, (p,) * 3)
+        out_elems.append(M * co)
+        fwd_ws.append(int(lib.stlt_conv3d_workspace_bytes(ctypes.byref(d), 0)))
+        wg_ws.append(int(lib.stlt_conv3d_bwd_weight_workspace_bytes(ctypes.byref(d), 0)))
+        dg_ws.append(int(lib.stlt_conv3d_bwd_data_workspace_bytes(ctypes.byref(d), 0)))
+    stem = out_elems[0]
+    _, t, h, w = descs[1][:4]  # the first block's conv1 reads the max-pool's output
+    pool = B * t * h * w * 64
+    blocks, i = [], 1
+    for n in BLOCKS:
+        for b in range(n):
+            blocks.append(out_elems[i:i + 3])  # conv1, conv2, conv3; the downsample's output is no larger than conv3's
+            i += 4 if b == 0 else 3
+    assert i == 53 and len(blocks) == 16
+    act = max([pool] + [e for blk in blocks for e in blk])
+    video = _a(16 * B * T * H * W)
+    infer = video + 3 * _a(4 * act) + _a(4 * max(stem, 2 * act)) + _a(max(fwd_ws))
+    tape = video + _a(4 * stem) + _a(4 * pool) + _a(pool) + sum(_a(4 * e) for blk in blocks for e in blk)
+    bwd = 4 * _a(4 * act) + _a(4 * stem) + _a(max(wg_ws + dg_ws[1:]))
+    return infer, tape, bwd
+
+
+def trunk_queries(lib, shape):
+    return int(lib.stlt_r3d_workspace_bytes(*shape)), int(lib.stlt_r3d_tape_bytes(*shape)), int(lib.stlt_r3d_backward_workspace_bytes(*shape))
+
+
+@pytest.mark.parametrize("shape", QUERY_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_trunk_size_queries_match_the_enumeration(pkg, shape):
+    lib = pkg._lib.load()
+    assert trunk_queries(lib, shape) == enumerated_sizes(pkg, lib, *shape)
+
+
+def test_trunk_size_queries_pinned_and_oversized(pkg):
+    lib = pkg._lib.load()
+    assert trunk_queries(lib, (1, 8, 64, 64)) == (16252928, 10575872, 34603008)
+    for shape in OVERSIZED:  # all three refuse what one of the trunk's convs refuses
+        assert trunk_queries(lib, shape) == (0, 0, 0), shape
+
+
 # ---- the general op-level cases of tests/test_conv3d_general_gpu.py: what each reaches, and the three workspace queries, against an
 # enumeration of the convolution itself (which output positions read which input positions through which taps) ----
 def parity_classes(n, k, s, p):
