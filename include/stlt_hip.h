@@ -815,12 +815,62 @@ typedef struct {
  * column of every abar is 0 and the temporal mask is causal, so the rollouts' entries that the combine reads there are sums of exact zeros.
  * In the last layer of a tower only the rows that are read afterwards (the CLS rows / frame lengths-1) carry a gradient: the other rows of that
  * layer's abar are exactly 0, as autograd has them.
+ * With STLT_FLAG_TRAIN_BACKBONE (the layout branch of a fusion model, on the tape of a stlt_train_forward with that flag) `dlogits` is the
+ * (B, T, d) gradient of the backbone's output, as in stlt_train_backward; the per-layer maps and the two rollouts are written, and
+ * maps->relevance must be NULL: stlt_relevance_combine_joint reads the rollouts out for the fusion models.
  * STLT_EINVAL before any launch: STLT_FLAG_SKIP_PADDING (the maps have the padded geometry), dropout_p != 0, STLT_FLAG_TRAIN_UPPER_ONLY /
- * _LOWER_ONLY / _BACKBONE, N or T above 256, a NULL or misaligned (4 bytes) map.  tape / scratch: as stlt_train_backward.
+ * _LOWER_ONLY, N or T above 256, a NULL or misaligned (4 bytes) map, a relevance map given with _BACKBONE.  tape / scratch: as stlt_train_backward.
  * No allocation, no synchronisation, capturable.  Profiling: the maps under STLT_K_ATTN_PROBS, rollouts and combine under STLT_K_MISC. */
 int stlt_train_backward_relevance(const stlt_params* p, const stlt_inputs* in, const void* tape, size_t tape_bytes, void* scratch,
                                   size_t scratch_bytes, const float* dlogits, float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx,
                                   const stlt_relevance_maps* maps, stlt_stream_t stream);
+
+/* ---- attention relevance of the fusion models (CAF / CACNF / LCF): how much of a class decision came through the video tokens and how much
+ * through the layout.  T layout frames and A = app_tokens + 1 appearance tokens (token 0 is the CLS token, models.py:247-262) form one stacked
+ * token set of J = T + A: joint index t is frame t, joint index T + a is appearance token a.  This is the bi-modal rule of Chefer, Gur, Wolf,
+ * "Generic Attention-model Explainability for Interpreting Bi-Modal and Encoder-Decoder Transformers" (ICCV 2021) without its row
+ * normalisation: the rule of stlt_attn_rollout continued over two token sets. ---- */
+
+/* stlt_attn_grad_probs for queries and keys that lie in different buffers and differ in number — the CrossAttentionLayer of the fusion models
+ * (models.py:362-382, called at 411-419):
+ *   abar[s,i,j] = (1/H) * sum_h max( P_h[s,i,j] * G_h[s,i,j], 0 ),   G_h[s,i,j] = dctx_h[s,i,:] · v_h[s,j,:]
+ * q rows ldq floats apart ((S*Lq) rows), k and v rows ldkv floats apart ((S*Lk) rows); only the first H*dh columns of each are read.  A cross
+ * block's buffers: q (S*Lq, d), the packed kv (S*Lk, 2d) as k = kv, v = kv + d, ldkv = 2d; a packed self block's: q = qkv, k = qkv + d,
+ * v = qkv + 2d, ldq = ldkv = 3d.  dctx (S*Lq, H*dh), abar (S, Lq, Lk).  P_h is exactly what stlt_attn_probs_cross_fwd defines with
+ * per_head == 1: the same masks (kpm: (S*Lk) bytes over the key tokens, never NULL; causal requires Lq == Lk), a masked entry exactly 0, a
+ * fully masked row zeros.  Every element of abar is written; the heads are summed in their order in registers: the same bits on every run.
+ * 1 <= Lq, Lk <= 256, 1 <= dh <= 256 (the domain of stlt_attn_bwd).  dh == 64 with Lk <= 64 (any Lq: every fusion block of the reference's
+ * shapes) runs on the MFMA kernel of csrc/attn_grad_probs_cross.hip and needs q, k, v and dctx 16-byte aligned and ldq, ldkv multiples of 4
+ * (refused otherwise); everything else on its vector-ALU kernel, pointers and strides 4 bytes.  abar 4 bytes; kpm bytes.  Routed by what was
+ * measured (profiles/fusion_relevance_bench.md): an MFMA shape with more than 32 keys and fewer than 128 work units, S * ceil(Lq / 16), also
+ * runs on the vector-ALU kernel — the same contract and refusals, results equal to fp32 rounding.
+ * Every bad argument is STLT_EINVAL with a message and launches nothing. */
+int stlt_attn_grad_probs_cross(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const float* dctx, const uint8_t* kpm,
+                               int causal, int64_t S, int64_t Lq, int64_t Lk, int64_t H, int64_t dh, float* abar, stlt_stream_t stream);
+
+/* Rollout over the stacked token set: R (S, J, J),
+ *   R_0 = blockdiag(r_layout (S,T,T), r_appearance (S,A,A))        (a NULL pointer: the identity block)
+ * and for fusion layer l = 1 .. n_fusion (CrossModalModule.forward, models.py:403-431) three steps R <- R + X·R:
+ *   1. X = [[0, l2a_l], [a2l_l, 0]]                  both cross blocks read the layer's input: one simultaneous step (411-419)
+ *   2. X = blockdiag(f_layout_l, f_appearance_l[0])  layout_attn and appearance_attn (421-427)
+ *   3. X = blockdiag(0, f_appearance_l[1])           appearance_ffn, a SelfAttentionLayer (models.py:401); layout_ffn has no attention
+ * The maps have the geometry of stlt_caf_attention_maps: layout_to_appearance (n, S, T, A), appearance_to_layout (n, S, A, T), fusion_layout
+ * (n, S, T, T), fusion_appearance (n, 2, S, A, A).  Only the non-zero quadrants are read.  ONE launch for the whole chain: the columns of R
+ * never mix, so a workgroup keeps 16 columns of one item's R in LDS (ping-pong, 64 KB at J = 512) while the maps stream in from memory.
+ * fp32 FMA over k in ascending order: the same bits on every run.  n_fusion == 0 (LCF) writes the block-diagonal (the maps may be NULL).
+ * 0 <= n_fusion <= 64, 1 <= T, A <= 256; every pointer 4 bytes.  Every bad argument is STLT_EINVAL with a message and launches nothing. */
+int stlt_attn_rollout_joint(const float* r_layout, const float* r_appearance, const float* layout_to_appearance, const float* appearance_to_layout,
+                            const float* fusion_layout, const float* fusion_appearance, int64_t n_fusion, int64_t S, int64_t T, int64_t A, float* R,
+                            stlt_stream_t stream);
+
+/* The read-out of a fusion model's head: row[b,:] = w_layout * R[b, lengths[b]-1, :] + w_appearance * R[b, T, :] — the frame the layout head
+ * reads (models.py:189-192) and the appearance CLS token (models.py:260-262); (1,0) for the "stlt" head, (0,1) for "resnet3d", (1,1) for "caf",
+ * "lcf" and "ensemble" (models.py:486-498, 520-549).
+ *   frame_rel[b,t] = row[b,t]     app_rel[b,a] = row[b,T+a]     rel[b,t,n] = frame_rel[b,t] * r_spatial[b,t,0,n]
+ * R (B, J, J), r_spatial (B*T, N, N) the spatial tower's rollout; rel (B, T, N), frame_rel (B, T), app_rel (B, A).  A length outside 1 ... T
+ * makes all three outputs of that clip NaN (the convention of stlt_relevance_combine).  Pointers 4 bytes, lengths (int64) 8; STLT_EINVAL otherwise. */
+int stlt_relevance_combine_joint(const float* R, const float* r_spatial, const int64_t* lengths, int64_t B, int64_t T, int64_t A, int64_t N,
+                                 float w_layout, float w_appearance, float* rel, float* frame_rel, float* app_rel, stlt_stream_t stream);
 
 /* ---- optimiser step of the training loop (reference train.py:128-131 with utils/train_inference_utils.py:37-54) ----
  * The reverse sweep writes all parameter gradients into ONE flat fp32 buffer (what a data-parallel run all-reduces).
@@ -983,6 +1033,15 @@ int stlt_attn_block_bwd_train(const stlt_attn_block_params* p, const stlt_attn_b
                               int64_t Lq, const float* c, int64_t Lk, const uint8_t* kpm, int causal, int64_t S, float drop_p, uint64_t seed,
                               uint32_t site0, const float* q, const float* kv, const float* ctx, const float* a, const float* dy, float* dx,
                               float* dc, stlt_ctx* tctx, void* keep, size_t keep_bytes, void* work, size_t work_bytes, stlt_stream_t stream);
+/* The input-only reverse call of an attention block for the fusion models' relevance (SelfAttentionLayer / CrossAttentionLayer, models.py:
+ * 345-382): stlt_attn_block_bwd_train with every member of `g` NULL, drop_p == 0 and no context — the same buffers, the same launches, dx and
+ * dc the same bits — plus ONE launch right before the attention backward, on what lies in memory there (the block's q | kv and the gradient
+ * wrt the attention core's output): stlt_attn_grad_probs for a packed self block (c == NULL), stlt_attn_grad_probs_cross otherwise, into
+ * abar (S, Lq, Lk).  Lq, Lk <= 256; abar 4 bytes, q and kv 16 bytes; refused (STLT_EINVAL) before any launch otherwise. */
+int stlt_attn_block_bwd_relevance(const stlt_attn_block_params* p, int64_t d, int64_t H, float eps, const float* x, int64_t Lq, const float* c,
+                                  int64_t Lk, const uint8_t* kpm, int causal, int64_t S, const float* q, const float* kv, const float* ctx,
+                                  const float* a, const float* dy, float* dx, float* dc, float* abar, void* keep, size_t keep_bytes, void* work,
+                                  size_t work_bytes, stlt_stream_t stream);
 int stlt_ffn_block_fwd_train(const stlt_ffn_block_params* p, int64_t d, float eps, int act, int inner_dropout, const float* x, int64_t M,
                              float drop_p, uint64_t seed, uint32_t site0, float* u, float* h, float* f, float* out, void* gemm_scratch,
                              size_t gemm_scratch_bytes, stlt_stream_t stream);

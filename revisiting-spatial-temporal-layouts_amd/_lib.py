@@ -224,6 +224,12 @@ SIGNATURES = {
     "stlt_relevance_combine": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "stlt_train_backward_relevance": (C.c_int, [C.POINTER(Params), C.POINTER(Inputs), _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_float, C.c_uint64, C.c_int,
                                                 _vp, C.POINTER(RelevanceMaps), _vp]),
+    "stlt_attn_grad_probs_cross": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp,
+                                             _vp]),
+    "stlt_attn_rollout_joint": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_relevance_combine_joint": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "stlt_attn_block_bwd_relevance": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int, C.c_int64, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "stlt_embed_bwd_inputs": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "stlt_saliency_seed": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "stlt_linear_bwd_scratch_bytes": (C.c_size_t, [C.c_int64]),

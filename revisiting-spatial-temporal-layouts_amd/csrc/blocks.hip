@@ -178,6 +178,48 @@ int stlt_attn_half_bwd_train(const stlt_attn_block_params& p, const stlt_attn_bl
   return stlt_input_grad(b.branch(dr), d, p.out_proj_w, d, d, nullptr, 0, b.dx, d, rows, b.wt, b.wt_floats, s);  // dctx = da·Wo
 }
 
+// the reverse call of an attention block behind stlt_attn_block_bwd_train (abar == NULL: its launches and nothing else) and
+// stlt_attn_block_bwd_relevance (abar: one more launch, the block's gradient-weighted map, right before the attention backward)
+static int attn_block_bwd(const char* fn, const stlt_attn_block_params* p, const stlt_attn_block_params* g, int64_t d, int64_t H, float eps, const float* x,
+                          int64_t Lq, const float* c, int64_t Lk, const uint8_t* kpm, int causal, int64_t S, float drop_p, uint64_t seed, uint32_t site0,
+                          const float* q, const float* kv, const float* ctx, const float* a, const float* dy, float* dx, float* dc, float* abar,
+                          stlt_ctx* tctx, void* keep, size_t keep_bytes, void* work, size_t work_bytes, stlt_stream_t stream) {
+  if (!p || !g || !x || !kpm || !q || !ctx || !a || !dy || !dx || !keep || !work || (c && !kv)) return stlt_set_error(STLT_EINVAL, "%s: null argument", fn);
+  if (!stlt_heads_ok(d, H)) return stlt_set_error(STLT_EINVAL, "%s: need d %% H == 0, a head dim of at most 256 and d %% 4 == 0", fn);
+  if (S < 0 || Lq <= 0 || Lk <= 0 || S > (int64_t)0x7fffffff / (Lq > Lk ? Lq : Lk)) return stlt_set_error(STLT_EINVAL, "%s: bad shape (S %lld, Lq %lld, Lk %lld)", fn, (long long)S, (long long)Lq, (long long)Lk);
+  if (S == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t Mq = S * Lq, Mk = S * Lk;
+  const BlockScratch sc = block_scratch((char*)keep, (char*)work, Mq > Mk ? Mq : Mk, d, BLOCK_ATTN);
+  if (keep_bytes < sc.keep_total) return stlt_set_error(STLT_EWORKSPACE, "%s: keep buffer %zu B < required %zu B", fn, keep_bytes, sc.keep_total);
+  if (work_bytes < sc.work_total) return stlt_set_error(STLT_EWORKSPACE, "%s: work buffer %zu B < required %zu B", fn, work_bytes, sc.work_total);
+  StltCtxScope scope(tctx, s);
+  if (scope.error()) return scope.error();
+  const StltDrop dr = stlt_drop_make(drop_p, seed);
+  StltGemmScratch lend(sc.lin, STLT_GEMM_SCRATCH_BYTES);
+  StltReduceScope red(sc.red_pool, sc.red_floats * 4, sc.red, sc.red_floats, s);
+  // out = LN(x + drop(a)), a = ctx·Woᵀ + bo: ds = residual-path gradient, da = gradient wrt a (= ds without dropout); dctx = da·Wo
+  const StltHalfBwd hb{sc.ds, sc.da, nullptr, sc.dctx, &red, sc.wt, sc.wt_floats};
+  TRY(stlt_attn_half_bwd_train(*p, *g, dy, x, a, eps, Mq, d, dr, site0 + 1, nullptr, hb, s));
+  DwList dws;
+  dws.add(hb.branch(dr), d, ctx, d, Mq, stlt_grad(g->out_proj_w));
+  // relevance: the block's gradient-weighted attention map from what lies in memory right here — the tape's Q and K/V, and dctx
+  if (abar && !c) TRY(launch_attn_grad_probs(q, sc.dctx, kpm, causal, S, Lq, H, d / H, abar, s));
+  if (abar && c) TRY(launch_attn_grad_probs_cross(q, d, kv, kv + d, 2 * d, sc.dctx, kpm, causal, S, Lq, Lk, H, d / H, abar, s));
+  if (!c) {
+    // packed self-attention: dqkv (Mq, 3d); in_proj_b += its column sums (accumulated by the attention backward)
+    TRY(launch_attn_bwd(q, sc.dctx, kpm, causal, S, Lq, H, d / H, sc.dq, s, dr, site0, stlt_grad(g->in_proj_b), red.chunk()));
+    TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, 3 * d, d, dx, sc.ds, stlt_grad(g->in_proj_w), nullptr, dws, sc, s));  // dx = dqkv·Win + ds
+  } else {
+    TRY(stlt_attn_bwd(q, d, kv, kv + d, 2 * d, sc.dctx, kpm, causal, S, Lq, Lk, H, d / H, drop_p, seed, site0, sc.dq, d, sc.dkv, sc.dkv + d, 2 * d, stream));
+    TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, d, d, dx, sc.ds, stlt_grad(g->in_proj_w), stlt_grad(g->in_proj_b), dws, sc, s));  // dx = dq·Wq + ds
+    TRY(linear_bwd(c, p->in_proj_w + d * d, sc.dkv, Mk, 2 * d, d, dc, nullptr, g->in_proj_w ? stlt_grad(g->in_proj_w) + d * d : nullptr,
+                   g->in_proj_b ? stlt_grad(g->in_proj_b) + d : nullptr, dws, sc, s));
+  }
+  TRY(red.flush());
+  return flush_dw(dws, sc, s);
+}
+
 extern "C" {
 
 int stlt_ctx_dw_defer(stlt_ctx* c, int mode) {
@@ -259,37 +301,22 @@ int stlt_attn_block_bwd_train(const stlt_attn_block_params* p, const stlt_attn_b
                               int64_t Lq, const float* c, int64_t Lk, const uint8_t* kpm, int causal, int64_t S, float drop_p, uint64_t seed,
                               uint32_t site0, const float* q, const float* kv, const float* ctx, const float* a, const float* dy, float* dx,
                               float* dc, stlt_ctx* tctx, void* keep, size_t keep_bytes, void* work, size_t work_bytes, stlt_stream_t stream) {
-  if (!p || !g || !x || !kpm || !q || !ctx || !a || !dy || !dx || !keep || !work || (c && !kv)) return stlt_set_error(STLT_EINVAL, "stlt_attn_block_bwd_train: null argument");
-  if (!stlt_heads_ok(d, H)) return stlt_set_error(STLT_EINVAL, "stlt_attn_block_bwd_train: need d %% H == 0, a head dim of at most 256 and d %% 4 == 0");
-  if (S < 0 || Lq <= 0 || Lk <= 0 || S > (int64_t)0x7fffffff / (Lq > Lk ? Lq : Lk)) return stlt_set_error(STLT_EINVAL, "stlt_attn_block_bwd_train: bad shape (S %lld, Lq %lld, Lk %lld)", (long long)S, (long long)Lq, (long long)Lk);
-  if (S == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t Mq = S * Lq, Mk = S * Lk;
-  const BlockScratch sc = block_scratch((char*)keep, (char*)work, Mq > Mk ? Mq : Mk, d, BLOCK_ATTN);
-  if (keep_bytes < sc.keep_total) return stlt_set_error(STLT_EWORKSPACE, "stlt_attn_block_bwd_train: keep buffer %zu B < required %zu B", keep_bytes, sc.keep_total);
-  if (work_bytes < sc.work_total) return stlt_set_error(STLT_EWORKSPACE, "stlt_attn_block_bwd_train: work buffer %zu B < required %zu B", work_bytes, sc.work_total);
-  StltCtxScope scope(tctx, s);
-  if (scope.error()) return scope.error();
-  const StltDrop dr = stlt_drop_make(drop_p, seed);
-  StltGemmScratch lend(sc.lin, STLT_GEMM_SCRATCH_BYTES);
-  StltReduceScope red(sc.red_pool, sc.red_floats * 4, sc.red, sc.red_floats, s);
-  // out = LN(x + drop(a)), a = ctx·Woᵀ + bo: ds = residual-path gradient, da = gradient wrt a (= ds without dropout); dctx = da·Wo
-  const StltHalfBwd hb{sc.ds, sc.da, nullptr, sc.dctx, &red, sc.wt, sc.wt_floats};
-  TRY(stlt_attn_half_bwd_train(*p, *g, dy, x, a, eps, Mq, d, dr, site0 + 1, nullptr, hb, s));
-  DwList dws;
-  dws.add(hb.branch(dr), d, ctx, d, Mq, stlt_grad(g->out_proj_w));
-  if (!c) {
-    // packed self-attention: dqkv (Mq, 3d); in_proj_b += its column sums (accumulated by the attention backward)
-    TRY(launch_attn_bwd(q, sc.dctx, kpm, causal, S, Lq, H, d / H, sc.dq, s, dr, site0, stlt_grad(g->in_proj_b), red.chunk()));
-    TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, 3 * d, d, dx, sc.ds, stlt_grad(g->in_proj_w), nullptr, dws, sc, s));  // dx = dqkv·Win + ds
-  } else {
-    TRY(stlt_attn_bwd(q, d, kv, kv + d, 2 * d, sc.dctx, kpm, causal, S, Lq, Lk, H, d / H, drop_p, seed, site0, sc.dq, d, sc.dkv, sc.dkv + d, 2 * d, stream));
-    TRY(linear_bwd(x, p->in_proj_w, sc.dq, Mq, d, d, dx, sc.ds, stlt_grad(g->in_proj_w), stlt_grad(g->in_proj_b), dws, sc, s));  // dx = dq·Wq + ds
-    TRY(linear_bwd(c, p->in_proj_w + d * d, sc.dkv, Mk, 2 * d, d, dc, nullptr, g->in_proj_w ? stlt_grad(g->in_proj_w) + d * d : nullptr,
-                   g->in_proj_b ? stlt_grad(g->in_proj_b) + d : nullptr, dws, sc, s));
-  }
-  TRY(red.flush());
-  return flush_dw(dws, sc, s);
+  return attn_block_bwd("stlt_attn_block_bwd_train", p, g, d, H, eps, x, Lq, c, Lk, kpm, causal, S, drop_p, seed, site0, q, kv, ctx, a, dy, dx, dc, nullptr, tctx, keep,
+                        keep_bytes, work, work_bytes, stream);
+}
+
+// The input-only reverse call of an attention block (every parameter frozen, dropout off, no context) that also writes the block's
+// gradient-weighted attention map: dx and dc are the bits stlt_attn_block_bwd_train gives with an all-NULL gradient table and drop_p == 0.
+int stlt_attn_block_bwd_relevance(const stlt_attn_block_params* p, int64_t d, int64_t H, float eps, const float* x, int64_t Lq, const float* c, int64_t Lk,
+                                  const uint8_t* kpm, int causal, int64_t S, const float* q, const float* kv, const float* ctx, const float* a, const float* dy,
+                                  float* dx, float* dc, float* abar, void* keep, size_t keep_bytes, void* work, size_t work_bytes, stlt_stream_t stream) {
+  static const stlt_attn_block_params no_grads = {};
+  if (!abar) return stlt_set_error(STLT_EINVAL, "stlt_attn_block_bwd_relevance: null argument (abar)");
+  if ((uintptr_t)abar & 3) return stlt_set_error(STLT_EINVAL, "stlt_attn_block_bwd_relevance: abar must be 4-byte aligned");
+  if (((uintptr_t)q | (uintptr_t)kv) & 15) return stlt_set_error(STLT_EINVAL, "stlt_attn_block_bwd_relevance: q and kv must be 16-byte aligned");  // the map launch's rule, checked before any launch
+  if (Lq > 256 || Lk > 256) return stlt_set_error(STLT_EINVAL, "stlt_attn_block_bwd_relevance: sequence lengths %lld / %lld unsupported (1 ... 256)", (long long)Lq, (long long)Lk);
+  return attn_block_bwd("stlt_attn_block_bwd_relevance", p, &no_grads, d, H, eps, x, Lq, c, Lk, kpm, causal, S, 0.f, 0, 0, q, kv, ctx, a, dy, dx, dc, abar, nullptr, keep,
+                        keep_bytes, work, work_bytes, stream);
 }
 
 int stlt_ffn_block_fwd_train(const stlt_ffn_block_params* p, int64_t d, float eps, int act, int inner_dropout, const float* x, int64_t M,

@@ -387,6 +387,15 @@ int launch_attn_grad_probs(const float* qkv, const float* dctx, const uint8_t* k
                            hipStream_t s);
 int launch_attn_rollout(const float* abar, int64_t n_layers, int64_t S, int64_t L, float* R, hipStream_t s);
 int launch_relevance_combine(const float* r_temporal, const float* r_spatial, const int64_t* lengths, int64_t B, int64_t T, int64_t N, float* rel, hipStream_t s);
+// attn_grad_probs_cross.hip: the same across two token sets (include/stlt_hip.h: stlt_attn_grad_probs_cross, stlt_attn_rollout_joint,
+// stlt_relevance_combine_joint) — the map of a block whose queries (ldq) and keys / values (ldkv) lie in different buffers, abar (S,Lq,Lk); the rollout
+// over the J = T + A stacked tokens of the fusion layers' four kinds of maps into R (S,J,J) in one launch; the read-out of the rows the heads read
+int launch_attn_grad_probs_cross(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const float* dctx, const uint8_t* kpm, int causal,
+                                 int64_t S, int64_t Lq, int64_t Lk, int64_t H, int64_t dh, float* abar, hipStream_t s);
+int launch_attn_rollout_joint(const float* r_layout, const float* r_appearance, const float* l2a, const float* a2l, const float* f_layout, const float* f_appearance,
+                              int64_t n_fusion, int64_t S, int64_t T, int64_t A, float* R, hipStream_t s);
+int launch_relevance_combine_joint(const float* R, const float* r_spatial, const int64_t* lengths, int64_t B, int64_t T, int64_t A, int64_t N, float w_layout,
+                                   float w_appearance, float* rel, float* frame_rel, float* app_rel, hipStream_t s);
 
 // ragged layout (ragged.hip): index of the real tokens / frames of a padded batch, see RaggedIndex
 struct RaggedIndex {

@@ -564,7 +564,8 @@ static int relevance_finish(const stlt_params* p, const stlt_inputs* in, const s
   const int64_t B = in->B, T = in->T, N = in->N;
   TRY(launch_attn_rollout(maps->abar_spatial, p->n_spatial, B * T, N, maps->rollout_spatial, s));
   TRY(launch_attn_rollout(maps->abar_temporal, p->n_temporal, B, T, maps->rollout_temporal, s));
-  TRY(launch_relevance_combine(maps->rollout_temporal, maps->rollout_spatial, in->lengths, B, T, N, maps->relevance, s));
+  if (maps->relevance)  // (NULL under STLT_FLAG_TRAIN_BACKBONE: the fusion models read the rollouts out with stlt_relevance_combine_joint)
+    TRY(launch_relevance_combine(maps->rollout_temporal, maps->rollout_spatial, in->lengths, B, T, N, maps->relevance, s));
   return red.flush();
 }
 
@@ -692,7 +693,8 @@ static int reverse_sweep(const stlt_params* p, const stlt_params* g, const stlt_
     if (hipError_t e = hipMemcpyAsync(sc.tp.A, dlogits, (size_t)BT * d * sizeof(float), hipMemcpyDeviceToDevice, s); e != hipSuccess)
       return stlt_set_error((int)e, "train_backward: copy: %s", hipGetErrorString(e));
     TRY(zero_rows(sc.tp.A, d, BT, pl.tp.Mp, s));
-    TRY(tower_backward(pl.tp, g->temporal, nullptr, sc.tp, sc, dr, s, q_tp));
+    const RelSink rel_tp{maps ? maps->abar_temporal : nullptr, p->n_spatial == 0};
+    TRY(tower_backward(pl.tp, g->temporal, nullptr, sc.tp, sc, dr, s, q_tp, maps ? &rel_tp : nullptr));
   } else if (do_upper) {
   // ---- prediction head (models.py:162-163): logits = z2·W2ᵀ+b2, z2 = LN(z1), z1 = gelu(u0), u0 = h0·W1ᵀ+b1
   if (g->fc2_w) TRY(launch_small_gemm(dlogits, 1, K, t.z2, d, 1, stlt_grad(g->fc2_w), d, K, d, B, 1, s));   // (K,d) += dlogitsᵀ·z2
@@ -748,7 +750,8 @@ int stlt_train_backward_inputs(const stlt_params* p, const stlt_params* g, const
 }
 
 // Attention relevance of a prediction: the input-only sweep (an all-NULL gradient table: no weight-gradient product, no parameter reduction,
-// no side stream) with one stlt_attn_grad_probs launch in front of every attention backward, then the two rollouts and the combine.
+// no side stream) with one stlt_attn_grad_probs launch in front of every attention backward, then the two rollouts and the combine (the fusion
+// models' layout branch, STLT_FLAG_TRAIN_BACKBONE: from the gradient of the backbone's output, and without the combine).
 int stlt_train_backward_relevance(const stlt_params* p, const stlt_inputs* in, const void* tape_mem, size_t tape_bytes, void* scratch_mem,
                                   size_t scratch_bytes, const float* dlogits, float dropout_p, uint64_t dropout_seed, int flags, stlt_ctx* ctx,
                                   const stlt_relevance_maps* maps, stlt_stream_t stream) {
@@ -756,12 +759,15 @@ int stlt_train_backward_relevance(const stlt_params* p, const stlt_inputs* in, c
   if (!maps) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: null maps");
   if (flags & STLT_FLAG_SKIP_PADDING)
     return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: STLT_FLAG_SKIP_PADDING is not supported (the maps have the padded geometry)");
-  if (flags & (STLT_FLAG_TRAIN_UPPER_ONLY | STLT_FLAG_TRAIN_LOWER_ONLY | STLT_FLAG_TRAIN_BACKBONE))
-    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: the relevance needs the whole sweep from the logits (no UPPER_ONLY / LOWER_ONLY / TRAIN_BACKBONE)");
+  if (flags & (STLT_FLAG_TRAIN_UPPER_ONLY | STLT_FLAG_TRAIN_LOWER_ONLY))
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: the relevance needs the whole sweep of both towers (no UPPER_ONLY / LOWER_ONLY)");
+  const bool backbone = (flags & STLT_FLAG_TRAIN_BACKBONE) != 0;  // the seed is the (B,T,d) gradient of the backbone's output, as in stlt_train_backward
+  if (backbone && maps->relevance)
+    return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: relevance must be NULL with STLT_FLAG_TRAIN_BACKBONE (stlt_relevance_combine_joint reads the rollouts out)");
   if (dropout_p != 0.f) return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: dropout_p must be 0 (the gradient wrt the probabilities is defined with dropout off)");
   if (in->N > AB_MAX_ROWS || in->T > AB_MAX_ROWS)
     return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: sequences of at most %d tokens (N=%lld, T=%lld)", AB_MAX_ROWS, (long long)in->N, (long long)in->T);
-  if (!maps->rollout_spatial || !maps->rollout_temporal || !maps->relevance || (p->n_spatial > 0 && !maps->abar_spatial) || (p->n_temporal > 0 && !maps->abar_temporal))
+  if (!maps->rollout_spatial || !maps->rollout_temporal || (!backbone && !maps->relevance) || (p->n_spatial > 0 && !maps->abar_spatial) || (p->n_temporal > 0 && !maps->abar_temporal))
     return stlt_set_error(STLT_EINVAL, "stlt_train_backward_relevance: null map (abar_spatial / abar_temporal may be NULL only for a tower without layers)");
   for (const StltNamedPtr& q : {StltNamedPtr{"abar_spatial", maps->abar_spatial}, StltNamedPtr{"abar_temporal", maps->abar_temporal},
                                 StltNamedPtr{"rollout_spatial", maps->rollout_spatial}, StltNamedPtr{"rollout_temporal", maps->rollout_temporal},

@@ -95,10 +95,19 @@ class TransformerResnetFeatures(nn.Module):
 def _appearance_tokens(ab, feats, H: int, p: float):
     """projector, CLS token, position table and the ReLU encoder layers of TransformerResnet.forward_features (models.py:257-271) on the
     trunk's feature map (B, 2048, ...), batch-major (B, S+1, d), on the op-level native Functions."""
+    return _appearance_layers(ab, _appearance_embed(ab, feats), H, p)
+
+
+def _appearance_embed(ab, feats):
+    """the encoder's input: projector, CLS token in front, position table (models.py:257-266) -> (B, S+1, d)"""
     B, Cc = feats.shape[0], feats.shape[1]
     d = ab.projector.weight.shape[0]
     x = ops.LinearFn.apply(feats.flatten(2).transpose(1, 2).contiguous(), ab.projector.weight.view(d, Cc), ab.projector.bias)
-    x = torch.cat((ab.cls_token.view(1, 1, d).expand(B, -1, -1), x), dim=1) + ab.pos_embed.view(1, -1, d)
+    return torch.cat((ab.cls_token.view(1, 1, d).expand(B, -1, -1), x), dim=1) + ab.pos_embed.view(1, -1, d)
+
+
+def _appearance_layers(ab, x, H: int, p: float):
+    """the ReLU encoder layers (models.py:239-246, 267-271) on (B, S+1, d)"""
     for l in ab.transformer.layers:  # nn.TransformerEncoderLayer defaults: ReLU, post-norm, eps 1e-5, dropout 0.1
         sa = l.self_attn
         x = ops.AttnBlockFn.apply(x, None, None, False, H, 1e-5, p, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias,
@@ -154,6 +163,33 @@ class TransformerResnet(nn.Module):
         if self.training:
             raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
         return video_saliency(self, batch, target, "resnet3d")
+
+    def forward_relevance(self, batch: Dict[str, torch.Tensor], target=None, return_layers: bool = False) -> Dict[str, torch.Tensor]:
+        """The logits and the relevance of every appearance token for one raw logit per clip (the machinery of
+        CrossAttentionFusion.forward_relevance on the appearance encoder alone): {"resnet3d": logits, "target", "appearance_rollout"
+        (B,A,A), "appearance_relevance" (B,A) = appearance_rollout[:, 0, :] (the classifier reads the CLS token)}, with ``return_layers``
+        also "appearance_layers" (n_app,B,A,A).  The trunk runs without a tape: relevance stops at the appearance tokens."""
+        if self.training:
+            raise L.StltHipError("forward_relevance is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        video = batch["video_frames"]
+        if not isinstance(video, torch.Tensor) or not video.is_cuda:
+            raise L.StltHipError("forward_relevance runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        with torch.no_grad():
+            x0 = _appearance_embed(self, self.resnet._runner.run(self.resnet.resnet, video, name="….resnet.resnet")[0])
+        B, A = x0.shape[0], x0.shape[1]
+        layers = torch.zeros(len(self.transformer.layers), B, A, A, device=x0.device, dtype=torch.float32)
+        leaf = x0.detach().requires_grad_(True)
+        with inputs_only(self), torch.enable_grad():
+            with ops.RelevanceRecorder(list(layers)):
+                x = _appearance_layers(self, leaf, self.config.num_attention_heads, 0.0)
+                logits = ops.LinearFn.apply(x[:, 0].contiguous(), self.classifier.weight, self.classifier.bias)
+            seed, target = saliency_seed(logits, target, "forward_relevance")
+            torch.autograd.grad(logits, leaf, seed)
+        rollout = ops.attn_rollout(layers)
+        out = {"resnet3d": logits.detach(), "target": target, "appearance_rollout": rollout, "appearance_relevance": rollout[:, 0, :].contiguous()}
+        if return_layers:
+            out["appearance_layers"] = layers
+        return out
 
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
@@ -231,7 +267,10 @@ class CrossAttentionFusionBackbone(nn.Module):
             with torch.no_grad():
                 Lh = self.layout_branch.forward_batch_major(batch)
             self.layout_branch.train(was_training)
-        Ah = self._appearance_train(feats)
+        return self._fuse_train(batch, Lh, self._appearance_train(feats), fusion_head, layout_head, appearance_head)
+
+    def _fuse_train(self, batch, Lh, Ah, fusion_head, layout_head=None, appearance_head=None):
+        """run_train from the two branches' states on: Lh (B,T,d) layout frames, Ah (B,A,d) appearance tokens -> the fusion layers and the heads"""
         B, d = Lh.shape[0], Lh.shape[2]
         # row lengths - 1 of every clip (models.py:455-459) as a gather: its backward is one scatter-add, where advanced indexing
         # (Lh[arange(B), last]) sorts the indices and runs six launches.  Only a NEGATIVE row wraps around, as indexing wraps it; a row beyond
@@ -309,6 +348,70 @@ class CrossAttentionFusionBackbone(nn.Module):
         out["target"] = target
         for k, g in zip(keys, grads):
             out[k + "_grad"] = g if g is not None else torch.zeros_like(leaves[k])  # a head that does not read the input (CACNF's "stlt" and the video)
+        return out
+
+    RELEVANCE_WEIGHTS = {"stlt": (1.0, 0.0), "resnet3d": (0.0, 1.0)}  # (layout read-out row, appearance CLS row); every fused head: (1, 1)
+
+    def run_relevance(self, owner: nn.Module, names, batch: Dict[str, torch.Tensor], target, head, return_layers: bool, fusion_head, layout_head=None,
+                      appearance_head=None):
+        """forward_relevance of the fusion models (include/stlt_hip.h: the attention relevance of the fusion models).  The layout branch runs
+        on its native tape (stlt_train_forward with STLT_FLAG_TRAIN_BACKBONE, frozen or not); the appearance encoder, the fusion blocks and
+        the heads on the op-level Functions over private leaves with every parameter of ``owner`` frozen and a recorder, so that each
+        attention block's backward (stlt_attn_block_bwd_relevance) leaves its gradient-weighted map; one autograd.grad from the seeded head
+        to the two leaves; the layout sweep (stlt_train_backward_relevance) from the layout leaf's gradient; then the appearance rollout,
+        the joint rollout and the read-out.  -> the dict forward_relevance returns."""
+        who = "forward_relevance"
+        if self.training and (self.config.hidden_dropout_prob > 0 or len(self.appearance_branch.transformer.layers) > 0):
+            raise L.StltHipError(f"{who} is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if not batch["categories"].is_cuda:
+            raise L.StltHipError(f"{who} runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        lb, ab = self.layout_branch, self.appearance_branch
+        if lb.skip_padding:
+            raise L.StltHipError(f"{who} runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set layout_branch.skip_padding = False")
+        head = names[-1] if head is None else head
+        if head not in names:
+            raise L.StltHipError(f"{who}: head must be one of {names}, got {head!r}")
+        if "appearance_features" not in batch and "video_frames" not in batch:
+            raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))")
+        H = self.config.num_attention_heads
+        was_training = lb.training
+        lb.train(False)
+        try:
+            with torch.no_grad():  # the trunk (when the batch carries video_frames) runs without a tape: relevance stops at the appearance tokens
+                Lh, step = lb._train_forward(batch, None, L.FLAG_TRAIN_BACKBONE, stale=f"{who}: the layout branch ran another forward before the sweep")
+                x0 = _appearance_embed(ab, self._features(batch))
+        finally:
+            lb.train(was_training)
+        device = Lh.device
+        B, T, A = Lh.shape[0], Lh.shape[1], x0.shape[1]
+        n_app, n_fu = len(ab.transformer.layers), len(self.mm_fusion)
+        zeros = lambda *shape: torch.zeros(*shape, device=device, dtype=torch.float32)  # noqa: E731  (a block the head never reaches keeps its zeros)
+        layers = {"appearance_layers": zeros(n_app, B, A, A), "layout_to_appearance_layers": zeros(n_fu, B, T, A),
+                  "appearance_to_layout_layers": zeros(n_fu, B, A, T), "fusion_layout_layers": zeros(n_fu, B, T, T),
+                  "fusion_appearance_layers": zeros(n_fu, 2, B, A, A)}
+        slots = list(layers["appearance_layers"])
+        for l in range(n_fu):  # the order of _fuse_train's attention blocks (CrossModalModule.forward, models.py:403-431)
+            slots += [layers["layout_to_appearance_layers"][l], layers["appearance_to_layout_layers"][l], layers["fusion_layout_layers"][l],
+                      layers["fusion_appearance_layers"][l, 0], layers["fusion_appearance_layers"][l, 1]]
+        lay_leaf, app_leaf = Lh.detach().requires_grad_(True), x0.detach().requires_grad_(True)
+        with inputs_only(owner), torch.enable_grad():
+            with ops.RelevanceRecorder(slots):
+                outs = self._fuse_train(batch, lay_leaf, _appearance_layers(ab, app_leaf, H, 0.0), fusion_head, layout_head, appearance_head)
+            logits = dict(zip(names, (outs[1], outs[2], outs[0], outs[3]) if layout_head is not None else outs))
+            seed, target = saliency_seed(logits[head], target, who)
+            d_lay, _ = torch.autograd.grad(logits[head], [lay_leaf, app_leaf], seed, allow_unused=True)
+        with torch.no_grad():
+            maps = lb._train_relevance(step, torch.zeros_like(Lh) if d_lay is None else d_lay)  # (CACNF's "resnet3d" never reads the layout)
+            app_rollout = ops.attn_rollout(layers["appearance_layers"])
+            R = ops.attn_rollout_joint(maps["temporal_rollout"], app_rollout, layers["layout_to_appearance_layers"], layers["appearance_to_layout_layers"],
+                                       layers["fusion_layout_layers"], layers["fusion_appearance_layers"])
+            rel, frame_rel, app_rel = ops.relevance_combine_joint(R, maps["spatial_rollout"], batch["lengths"].to(device).contiguous(),
+                                                                  *self.RELEVANCE_WEIGHTS.get(head, (1.0, 1.0)))
+        out = {k: v.detach() for k, v in logits.items()}
+        out.update(target=target, relevance=rel, frame_relevance=frame_rel, appearance_relevance=app_rel, fusion_rollout=R,
+                   spatial_rollout=maps["spatial_rollout"], temporal_rollout=maps["temporal_rollout"], appearance_rollout=app_rollout)
+        if return_layers:
+            out.update(spatial_layers=maps["spatial_layers"], temporal_layers=maps["temporal_layers"], **layers)
         return out
 
     def _native_args(self, batch, fusion_head, layout_head, appearance_head):
@@ -409,6 +512,25 @@ class CrossAttentionFusion(nn.Module):
         ``.grad`` touched.  Inference call: training mode with live dropout is refused."""
         return self.caf_backbone.run_saliency(self, self.logit_names, batch, target, head, self.classifier)
 
+    def forward_relevance(self, batch: Dict[str, torch.Tensor], target=None, head=None, return_layers: bool = False) -> Dict[str, torch.Tensor]:
+        """The model's logits and how much of one raw logit per clip of head ``head`` (one of ``logit_names``; default the last) came through
+        each layout frame, each object and each appearance token: gradient-weighted attention rollout (Chefer, Gur, Wolf 2021, the bi-modal
+        rule without its row normalisation) over the T layout frames and A = appearance tokens + 1 (token 0 the CLS token) as one stacked
+        token set of J = T + A, joint index t = frame t, T + a = appearance token a.  Every attention block contributes
+        abar = mean over the heads of max(P * dLogit/dP, 0); the layout branch and the appearance encoder roll up on their own
+        (R_l = R_{l-1} + abar_l R_{l-1}), the fusion layers continue from blockdiag(temporal_rollout, appearance_rollout) with three steps
+        each (both cross-attention directions at once; layout_attn and appearance_attn; appearance_ffn), and the read-out row is
+        R[b, lengths[b]-1] for the layout state plus R[b, T] for the appearance CLS state (head "stlt": the first only, "resnet3d": the second).
+        ``target`` as in forward_saliency.
+        -> the logits under ``logit_names``, "target", "relevance" (B,T,N) = frame_relevance x spatial_rollout[b,t,0,n], "frame_relevance"
+        (B,T), "appearance_relevance" (B,A), "fusion_rollout" (B,J,J), "spatial_rollout" (B,T,N,N), "temporal_rollout" (B,T,T),
+        "appearance_rollout" (B,A,A); with ``return_layers`` also "spatial_layers", "temporal_layers", "appearance_layers" (n_app,B,A,A),
+        "layout_to_appearance_layers" (n_fusion,B,T,A), "appearance_to_layout_layers" (n_fusion,B,A,T), "fusion_layout_layers"
+        (n_fusion,B,T,T), "fusion_appearance_layers" (n_fusion,2,B,A,A).  Entries of padded frames and padded object slots are exactly 0;
+        the map of a block the head does not read is exactly 0.  With ``video_frames`` the trunk runs without a tape: relevance stops at the
+        appearance tokens.  Inference call, padded schedule, N, T, A <= 256: no parameter's ``.grad`` is touched, two calls give the same bits."""
+        return self.caf_backbone.run_relevance(self, self.logit_names, batch, target, head, return_layers, self.classifier)
+
 
 class CrossAttentionCentralNetFusion(nn.Module):
     """CACNF (models.py:501-549): ``forward(batch) -> {"stlt", "resnet3d", "caf", "ensemble"}``."""
@@ -436,6 +558,12 @@ class CrossAttentionCentralNetFusion(nn.Module):
         """As CrossAttentionFusion.forward_saliency with this model's four heads; an input the chosen head does not read gets zeros."""
         return self.backbone.run_saliency(self, self.logit_names, batch, target, head, self.fusion_classifier, self.layout_classifier,
                                           self.appearance_classifier)
+
+    def forward_relevance(self, batch: Dict[str, torch.Tensor], target=None, head=None, return_layers: bool = False) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_relevance with this model's four heads: "stlt" reads the layout branch alone and "resnet3d" the
+        appearance encoder alone (every fusion map exactly 0), "caf" and "ensemble" both."""
+        return self.backbone.run_relevance(self, self.logit_names, batch, target, head, return_layers, self.fusion_classifier, self.layout_classifier,
+                                           self.appearance_classifier)
 
 
 class LateConcatenationFusion(nn.Module):
@@ -491,6 +619,11 @@ class LateConcatenationFusion(nn.Module):
     def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None, head=None) -> Dict[str, torch.Tensor]:
         """As CrossAttentionFusion.forward_saliency."""
         return self._runner.run_saliency(self, self.logit_names, batch, target, head, self.classifier)
+
+    def forward_relevance(self, batch: Dict[str, torch.Tensor], target=None, head=None, return_layers: bool = False) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_relevance; LCF has no cross-modal layers, so "fusion_rollout" is the block-diagonal of the two
+        branches' rollouts and the four fusion maps have a leading dimension of 0."""
+        return self._runner.run_relevance(self, self.logit_names, batch, target, head, return_layers, self.classifier)
 
 
 from .models import models_factory  # noqa: E402

@@ -369,7 +369,9 @@ class StltBackbone(nn.Module):
 
     def _train_relevance(self, step, dout, out=None):
         """stlt_train_backward_relevance on the tape of `step` from the seed `dout` -> the five maps (`out`: maps of an earlier call to
-        write into again, e.g. under graph capture).  No gradient table, no context: the input-only sweep has no side stream."""
+        write into again, e.g. under graph capture).  No gradient table, no context: the input-only sweep has no side stream.  On a tape
+        of FLAG_TRAIN_BACKBONE (the fusion models' layout branch) `dout` is the (B,T,d) gradient of the backbone's output and there is no
+        "relevance": the fusion model reads the rollouts out itself (ops.relevance_combine_joint)."""
         self._check_tape(step)
         lib = L.load()
         (B, T, N), device, d = step["shape"], step["device"], self.config.hidden_size
@@ -380,10 +382,12 @@ class StltBackbone(nn.Module):
         if out is None:
             new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)  # noqa: E731
             out = {"spatial_layers": new(p.n_spatial, B, T, N, N), "temporal_layers": new(p.n_temporal, B, T, T), "spatial_rollout": new(B, T, N, N),
-                   "temporal_rollout": new(B, T, T), "relevance": new(B, T, N)}
-        ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
+                   "temporal_rollout": new(B, T, T)}
+            if not step["flags"] & L.FLAG_TRAIN_BACKBONE:
+                out["relevance"] = new(B, T, N)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
         maps = L.RelevanceMaps(ptr(out["spatial_layers"]), ptr(out["temporal_layers"]), ptr(out["spatial_rollout"]), ptr(out["temporal_rollout"]),
-                               ptr(out["relevance"]))
+                               ptr(out.get("relevance")))
         with torch.cuda.device(device):
             L.check(lib.stlt_train_backward_relevance(
                 C.byref(p), C.byref(step["inp"]), tape.data_ptr(), tape.numel(), scratch.data_ptr(), scratch.numel(), dl.data_ptr(), step["drop"][0],

@@ -364,6 +364,71 @@ def attn_probs_cross(q: torch.Tensor, k: torch.Tensor, kpm: Optional[torch.Tenso
     return probs
 
 
+def attn_grad_probs_cross(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dctx: torch.Tensor, kpm: Optional[torch.Tensor], causal: bool,
+                          num_heads: int):
+    """Gradient-weighted attention probabilities of a block whose queries and keys lie in different buffers (include/stlt_hip.h:
+    stlt_attn_grad_probs_cross): q (S,Lq,d) projected queries, k and v (S,Lk,d) projected keys and values — views with a row stride are
+    taken as they lie, k and v with the same one, e.g. `kv[..., :d]` and `kv[..., d:]` of a packed (S,Lk,2d) buffer — dctx (S,Lq,d) the
+    gradient wrt the attention core's output, kpm (S,Lk) bool/uint8 over the keys (True = masked) or None.
+    -> abar (S,Lq,Lk) = mean over the heads of max(P_h * G_h, 0), G_h[s,i,j] = dctx_h[s,i,:] · v_h[s,j,:].  Masked entries are exactly 0;
+    causal needs Lq == Lk; Lq, Lk <= 256, head dim <= 256."""
+    lib = L.load()
+    ldq, ldk, ldv = _rows_view(q, "q"), _rows_view(k, "k"), _rows_view(v, "v")
+    _chk(dctx, torch.float32, "dctx")
+    S, Lq, d = q.shape
+    Lk = k.shape[1]
+    if ldk != ldv:
+        raise L.StltHipError(f"k and v must have the same row stride (got {ldk} and {ldv})")
+    assert tuple(k.shape) == (S, Lk, d) and tuple(v.shape) == (S, Lk, d) and tuple(dctx.shape) == (S, Lq, d) and d % num_heads == 0
+    if kpm is None:
+        kpm = torch.zeros(S, Lk, dtype=torch.uint8, device=q.device)
+    kpm = _mask_u8(kpm, "kpm")
+    assert tuple(kpm.shape) == (S, Lk)
+    abar = torch.empty(S, Lq, Lk, device=q.device, dtype=torch.float32)
+    L.check(lib.stlt_attn_grad_probs_cross(_p(q), ldq, _p(k), _p(v), ldk, _p(dctx), _p(kpm), int(bool(causal)), S, Lq, Lk, num_heads, d // num_heads,
+                                           _p(abar), _stream()), "stlt_attn_grad_probs_cross")
+    return abar
+
+
+def attn_rollout_joint(rollout_layout: Optional[torch.Tensor], rollout_appearance: Optional[torch.Tensor], layout_to_appearance: torch.Tensor,
+                       appearance_to_layout: torch.Tensor, fusion_layout: torch.Tensor, fusion_appearance: torch.Tensor):
+    """Rollout over the T layout frames and A appearance tokens of a fusion model as one stacked token set (include/stlt_hip.h:
+    stlt_attn_rollout_joint): rollout_layout (B,T,T) and rollout_appearance (B,A,A) the two branches' rollouts (None: the identity), and the
+    fusion layers' maps layout_to_appearance (n,B,T,A), appearance_to_layout (n,B,A,T), fusion_layout (n,B,T,T), fusion_appearance
+    (n,2,B,A,A) -> R (B,T+A,T+A).  No fusion layers (n == 0): the block-diagonal.  One launch; T, A <= 256."""
+    lib = L.load()
+    maps = (layout_to_appearance, appearance_to_layout, fusion_layout, fusion_appearance)
+    for t, name in zip(maps, ("layout_to_appearance", "appearance_to_layout", "fusion_layout", "fusion_appearance")):
+        _chk(t, torch.float32, name)
+    n, B, T, A = layout_to_appearance.shape
+    want = ((n, B, T, A), (n, B, A, T), (n, B, T, T), (n, 2, B, A, A))
+    if any(tuple(t.shape) != w for t, w in zip(maps, want)):
+        raise L.StltHipError(f"the fusion maps must be {want}, got {[tuple(t.shape) for t in maps]}")
+    for t, name, w in ((rollout_layout, "rollout_layout", (B, T, T)), (rollout_appearance, "rollout_appearance", (B, A, A))):
+        if t is not None and tuple(_chk(t, torch.float32, name).shape) != w:
+            raise L.StltHipError(f"{name}: expected {w}, got {tuple(t.shape)}")
+    R = torch.empty(B, T + A, T + A, device=layout_to_appearance.device, dtype=torch.float32)
+    L.check(lib.stlt_attn_rollout_joint(_p(rollout_layout), _p(rollout_appearance), *[_p(t) if n else None for t in maps], n, B, T, A, _p(R), _stream()),
+            "stlt_attn_rollout_joint")
+    return R
+
+
+def relevance_combine_joint(fusion_rollout: torch.Tensor, rollout_spatial: torch.Tensor, lengths: torch.Tensor, w_layout: float, w_appearance: float):
+    """The read-out of a fusion model's head (include/stlt_hip.h: stlt_relevance_combine_joint): fusion_rollout (B,J,J) with J = T + A,
+    rollout_spatial (B,T,N,N), lengths (B,) int64; row = w_layout * R[b, lengths[b]-1] + w_appearance * R[b, T].
+    -> (relevance (B,T,N), frame_relevance (B,T), appearance_relevance (B,A))."""
+    lib = L.load()
+    _chk(fusion_rollout, torch.float32, "fusion_rollout"); _chk(rollout_spatial, torch.float32, "rollout_spatial"); _chk(lengths, torch.int64, "lengths")
+    B, T, N = rollout_spatial.shape[:3]
+    J = fusion_rollout.shape[-1]
+    A = J - T
+    assert tuple(rollout_spatial.shape) == (B, T, N, N) and tuple(fusion_rollout.shape) == (B, J, J) and A >= 1 and tuple(lengths.shape) == (B,)
+    rel, frame_rel, app_rel = (torch.empty(s, device=fusion_rollout.device, dtype=torch.float32) for s in ((B, T, N), (B, T), (B, A)))
+    L.check(lib.stlt_relevance_combine_joint(_p(fusion_rollout), _p(rollout_spatial), _p(lengths), B, T, A, N, float(w_layout), float(w_appearance), _p(rel),
+                                             _p(frame_rel), _p(app_rel), _stream()), "stlt_relevance_combine_joint")
+    return rel, frame_rel, app_rel
+
+
 def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
     """Probe attention of the per-prefix forward (include/stlt_hip.h: stlt_attn_prefix_probe_fwd).  qkv_frames, qkv_probes: (S,T,3d) packed
     [q;k;v] rows of the frame and of the probe stream, kpm (S,T) bool/uint8 (True = frame masked as a key).  Probe (s,t) attends to the frame
@@ -874,10 +939,47 @@ def _no_mask(S: int, Lk: int, device) -> torch.Tensor:
     return t
 
 
+class RelevanceRecorder:
+    """Where the attention blocks of ONE differentiable forward leave their gradient-weighted attention maps (include/stlt_hip.h:
+    stlt_attn_block_bwd_relevance): `slots` are the (S,Lq,Lk) float32 tensors — slices of zero-filled buffers — of the AttnBlockFn calls
+    made while the recorder is active, in call order.  Each forward call takes the next slot onto its own autograd ctx, so the backward —
+    which the autograd engine runs on another thread — finds it there; a block the backward never visits keeps its zeros.
+
+        with ops.RelevanceRecorder(slots) as rec: ...forward...      # every AttnBlockFn.apply in here records
+        torch.autograd.grad(...)                                      # the maps are written here
+    """
+    _active = None  # read by AttnBlockFn.forward only, on the thread that runs the forward
+
+    def __init__(self, slots):
+        self.slots = list(slots)
+        self.taken = 0
+
+    def __enter__(self):
+        if RelevanceRecorder._active is not None:
+            raise L.StltHipError("a RelevanceRecorder is already active")
+        RelevanceRecorder._active = self
+        return self
+
+    def __exit__(self, *exc):
+        RelevanceRecorder._active = None
+        return False
+
+    def take(self, S: int, Lq: int, Lk: int) -> torch.Tensor:
+        if self.taken >= len(self.slots):
+            raise L.StltHipError(f"RelevanceRecorder: more attention blocks ran than the {len(self.slots)} slots given")
+        t = self.slots[self.taken]
+        self.taken += 1
+        if tuple(t.shape) != (S, Lq, Lk):
+            raise L.StltHipError(f"RelevanceRecorder: slot {self.taken - 1} is {tuple(t.shape)}, the block's map is {(S, Lq, Lk)}")
+        return _chk(t, torch.float32, "abar")
+
+
 class AttnBlockFn(torch.autograd.Function):
     """One residual attention block as ONE native call each way (include/stlt_hip.h: stlt_attn_block_fwd_train / _bwd_train):
     LN_eps(x + drop(MHA(x, c, c) Woᵀ + bo)) — SelfAttentionLayer / CrossAttentionLayer of the fusion models (models.py:345-382)
-    and the attention half of nn.TransformerEncoderLayer.  x (S,Lq,d); c (S,Lk,d) or None (self-attention); kpm (S,Lk) or None."""
+    and the attention half of nn.TransformerEncoderLayer.  x (S,Lq,d); c (S,Lk,d) or None (self-attention); kpm (S,Lk) or None.
+    Inside a RelevanceRecorder the backward is stlt_attn_block_bwd_relevance, which also writes the block's gradient-weighted attention
+    map into the recorder's slot (every parameter frozen, dropout off); without one: the same launches as ever."""
 
     @staticmethod
     def forward(ctx, x, c, kpm, causal, heads, eps, drop_p, in_w, in_b, out_w, out_b, ln_w, ln_b):
@@ -899,6 +1001,8 @@ class AttnBlockFn(torch.autograd.Function):
         ctx.save_for_backward(x, c, kpm8, q, kv, att, a)
         ctx.ws = (in_w, in_b, out_w, out_b, ln_w, ln_b)
         ctx.meta = (bool(causal), heads, float(eps), p, seed, site)
+        rec = RelevanceRecorder._active
+        ctx.abar = None if rec is None else rec.take(S, Lq, Lk)
         return out
 
     @staticmethod
@@ -910,6 +1014,17 @@ class AttnBlockFn(torch.autograd.Function):
         Lk = Lq if c is None else c.shape[1]
         dy = dy.contiguous()
         ws = ctx.ws
+        if ctx.abar is not None:
+            if p != 0.0 or any(ctx.needs_input_grad[7:13]):
+                raise L.StltHipError("RelevanceRecorder: the map is defined with dropout off and every parameter frozen (model.train(False), inputs_only)")
+            dx = torch.empty_like(x)
+            dc = torch.empty_like(c) if (c is not None and ctx.needs_input_grad[1]) else None
+            params = L.AttnBlockParams(*[_p(t) for t in ws])
+            kb, wb = _block_buffers(0, S * max(Lq, Lk), d, x.device, None, False, ())
+            L.check(lib.stlt_attn_block_bwd_relevance(C.byref(params), d, heads, eps, _p(x), Lq, _p(c), Lk, _p(kpm8), int(causal), S, _p(q), _p(kv), _p(att),
+                                                      _p(a), _p(dy), _p(dx), _p(dc), _p(ctx.abar), kb.data_ptr(), kb.numel(), wb.data_ptr(), wb.numel(),
+                                                      _stream()), "stlt_attn_block_bwd_relevance")
+            return (dx, dc) + (None,) * 11
         targets, grads = grad_targets(ws, ctx.needs_input_grad[7:13])
         dx = torch.empty_like(x)
         dc = torch.empty_like(c) if (c is not None and ctx.needs_input_grad[1]) else None
