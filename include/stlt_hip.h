@@ -1070,6 +1070,50 @@ int stlt_eval_store_sigmoid(const float* logits, int64_t ld, const float* labels
 int stlt_eval_average_precision(const float* scores, const float* truths, int64_t n, int64_t C, double* ap, double* positives,
                                 uint8_t* scratch, stlt_stream_t stream);
 
+/* ---- the perturbation test of an attribution map (csrc/perturb.hip; Chefer, Gur, Wolf 2021) ----
+ * Rank the real object tokens of every clip by a map, delete the first k of them for a rising k, score the logits of every reduced batch.
+ * All three calls are stream-ordered, allocate nothing, read nothing back and are capturable in a hipGraph; a bad extent or a NULL required
+ * pointer is STLT_EINVAL with a message and launches nothing.  Alignment: none beyond the element types' (floats / int32 4, int64 8): every
+ * access is one element wide.  Only the logical extents are touched.
+ *
+ * stlt_perturb_rank: the removal order of each clip.  scores (B,T,N) for unit STLT_PERTURB_OBJECT, (B,T) for STLT_PERTURB_FRAME; kpm_boxes
+ * (B,T,N) src_key_padding_mask_boxes; lengths (B,).  Candidates of clip b — object: slots (t,n) with t < lengths[b]-1 (never the extract frame
+ * the dataset appends, datasets.py:97-113), n >= 1 (never the CLS slot, datasets.py:70-72) and mask 0; frame: frames t < lengths[b]-1 that hold
+ * at least one such slot.  Order: by score, descending (1) or ascending (0), compared as floats with -0 == +0; ties go to the lower flat
+ * index (t*N+n, or t) in both orders; NaN is removed last in both orders.  rank (same shape as scores, int32) = position in the removal order
+ * (0 = first) for candidates, -1 elsewhere; n_candidates (B,) int32.  One workgroup per clip sorts packed 64-bit keys in LDS, so
+ * T*N <= stlt_perturb_max_items() (16384) for both units; beyond it STLT_EINVAL.
+ *
+ * stlt_perturb_apply: the batch `in` (stlt_inputs: B, T, N and the seven tensors; scores may be NULL; the row counts are not read) with the
+ * first k candidates deleted, for every step s in [s0, s1], 0 <= s0 <= s1 <= steps, steps >= 1: k = floor(s * n_candidates[b] / steps)
+ * (64-bit product).  The (s1-s0+1)*B output clips are step-major: clip (s-s0)*B + b is clip b at step s.  Deleted are the candidates with
+ * 0 <= rank < k — for unit frame every slot n >= 1 with mask 0 of the frames with rank < k.  A deleted slot is what the reference's dataset
+ * and collater make of a slot without a detection (datasets.py:88-93, 274-278): category 0, box (0,0,0,0), score 0 (when the batch has
+ * scores), mask 1.  Everything else is copied bit for bit: the kept slots, lengths, kpm_frames and the frame types — except that a frame
+ * t < lengths[b]-1 that had a real slot and has none left gets empty_frame_type (frame2type["empty"], datasets.py:64-69).  Slots are not
+ * compacted.  rank and n_candidates must be what stlt_perturb_rank wrote for this very batch and unit (rank's shape tells the unit's); they are
+ * trusted, not checked: other values delete other slots, inside the extents all the same.  removed (steps+1, B) int32: rows s0 .. s1 receive k; the other rows are not touched.  Step 0 reproduces the input, step
+ * `steps` deletes every candidate.  The outputs must not overlap the inputs.
+ *
+ * stlt_perturb_curve: logits (S,B,K), row s*B+b at logits + (s*B+b)*ld, ld >= K.  The target class of clip b is target[b] (int64), or with
+ * target == NULL the arg-max of its step-0 row (first maximum on ties: stlt_eval_topk's rule), which is written to target_out (B,) — required
+ * then, optional (a copy of target) otherwise.  prob (S,B): activation STLT_PERTURB_SOFTMAX — exp(x_t - max) / sum_j exp(x_j - max);
+ * STLT_PERTURB_SIGMOID — 1 / (1 + exp(-x_t)); evaluated in float64 and rounded to fp32 once (one value per row is kept).  hit (S,B) uint8: softmax — 1 when no class beats the target (a larger logit, or an equal logit
+ * at a lower index: the prediction EvaluatorSomething.process counts, evaluation.py:21-34); sigmoid — 1 when x_t > 0.  A target outside
+ * [0, K) gives prob 0 and hit 0.  One wave per row. */
+#define STLT_PERTURB_OBJECT 0
+#define STLT_PERTURB_FRAME 1
+#define STLT_PERTURB_SOFTMAX 0
+#define STLT_PERTURB_SIGMOID 1
+int64_t stlt_perturb_max_items(void);
+int stlt_perturb_rank(const float* scores, const uint8_t* kpm_boxes, const int64_t* lengths, int64_t B, int64_t T, int64_t N, int unit, int descending,
+                      int32_t* rank, int32_t* n_candidates, stlt_stream_t stream);
+int stlt_perturb_apply(const stlt_inputs* in, const int32_t* rank, const int32_t* n_candidates, int unit, int64_t steps, int64_t s0, int64_t s1,
+                       int64_t empty_frame_type, int64_t* categories, float* boxes, float* scores, uint8_t* kpm_boxes, int64_t* frame_types,
+                       uint8_t* kpm_frames, int64_t* lengths, int32_t* removed, stlt_stream_t stream);
+int stlt_perturb_curve(const float* logits, int64_t ld, const int64_t* target, int activation, int64_t S, int64_t B, int64_t K, float* prob, uint8_t* hit,
+                       int64_t* target_out, stlt_stream_t stream);
+
 /* ---- per-kernel timing (bench.py roofline leg): hipEvents around every launch of the whole-path calls ---- */
 #define STLT_K_EMBED 0
 #define STLT_K_GEMM 1

@@ -18,6 +18,8 @@ FLAG_TRAIN_UPPER_ONLY = 8
 FLAG_TRAIN_LOWER_ONLY = 16
 FLAG_TRAIN_BACKBONE = 32
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
+PERTURB_UNITS = {"object": 0, "frame": 1}          # STLT_PERTURB_OBJECT / _FRAME
+PERTURB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # STLT_PERTURB_SOFTMAX / _SIGMOID
 
 _f = C.POINTER(C.c_float)
 _i64 = C.POINTER(C.c_int64)
@@ -271,6 +273,10 @@ SIGNATURES = {
     "stlt_debug_buffer_bytes": (C.c_size_t, []),
     "stlt_set_gemm_split_bf16": (C.c_int, [C.c_int]),
     "stlt_eval_average_precision": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp]),
+    "stlt_perturb_max_items": (C.c_int64, []),
+    "stlt_perturb_rank": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "stlt_perturb_apply": (C.c_int, [C.POINTER(Inputs), _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "stlt_perturb_curve": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp]),
     "stlt_grad_norm": (C.c_int, [_vp, C.c_int64, C.c_float, _vp, _vp, _vp]),
     "stlt_adamw_step": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
     "stlt_prof_enable": (C.c_int, [C.c_int]),

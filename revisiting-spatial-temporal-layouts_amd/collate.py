@@ -101,3 +101,110 @@ def prefix_batch(batch: Dict[str, torch.Tensor], t: int) -> Dict[str, object]:
     out.pop("num_real_tokens", None)  # counted for the whole clips
     out.pop("num_real_frames", None)
     return out
+
+
+
+def _perturb_args(order: str, unit: str) -> bool:
+    if order not in ("descending", "ascending"):
+        raise L.StltHipError(f"order: expected 'descending' or 'ascending', got {order!r}")
+    if unit not in ("object", "frame"):
+        raise L.StltHipError(f"unit: expected 'object' or 'frame', got {unit!r}")
+    return order == "descending"
+
+
+def perturb_rank(scores: torch.Tensor, kpm_boxes: torch.Tensor, lengths: torch.Tensor, unit: str = "object", order: str = "descending"):
+    """The removal order of the perturbation test (include/stlt_hip.h: stlt_perturb_rank) -> (rank int32 of scores' shape, n_candidates (B,)
+    int32).  Candidates of clip b: the object slots (t, n) with t < lengths[b]-1, n >= 1 and mask False (unit "object": scores (B,T,N)), or
+    the frames t < lengths[b]-1 holding one (unit "frame": scores (B,T)).  rank = position in the removal order — by score, descending or
+    ascending, -0 == +0, ties to the lower flat index, NaN last in both orders — and -1 for everything that is no candidate.  Device tensors
+    go through the kernel; CPU tensors take the torch form below, same integers."""
+    descending = _perturb_args(order, unit)
+    B, T, N = kpm_boxes.shape
+    want = (B, T, N) if unit == "object" else (B, T)
+    if tuple(scores.shape) != want:
+        raise L.StltHipError(f"scores: unit {unit!r} takes {want}, got {tuple(scores.shape)}")
+    max_slots = L.load().stlt_perturb_max_items()  # a clip's T*N slots are sorted inside one workgroup's LDS; the torch form keeps the same domain
+    if T * N > max_slots:
+        raise L.StltHipError(f"T*N = {T * N} slots exceed the {max_slots} a clip is ranked with (STLT_EINVAL)")
+    if scores.is_cuda:
+        return ops.perturb_rank(scores.to(torch.float32).contiguous(), kpm_boxes, lengths, unit, descending)
+    t_idx = torch.arange(T)[None, :, None]
+    cand = (t_idx < (lengths.to(torch.int64) - 1)[:, None, None]) & (torch.arange(N)[None, None, :] >= 1) & ~kpm_boxes.bool()
+    cand = (cand if unit == "object" else cand.any(dim=2)).reshape(B, -1)
+    v = scores.to(torch.float32).double().reshape(B, -1)
+    nan = torch.isnan(v)
+    v = torch.where(nan | (v == 0), torch.zeros_like(v), -v if descending else v)  # canonical: -0 == +0; NaN sorted below
+    order_ = torch.sort(v, dim=1, stable=True).indices
+    for flag in (nan, ~cand):  # stable partitions: NaN behind the numbers, non-candidates behind the candidates
+        order_ = order_.gather(1, torch.sort(flag.gather(1, order_).to(torch.int8), dim=1, stable=True).indices)
+    n_cand = cand.sum(dim=1)
+    pos = torch.arange(v.shape[1])[None, :].expand(B, -1)
+    rank = torch.empty(B, v.shape[1], dtype=torch.int64).scatter_(1, order_, torch.where(pos < n_cand[:, None], pos, torch.full_like(pos, -1)))
+    return rank.to(torch.int32).reshape(want), n_cand.to(torch.int32)
+
+
+def perturb_batch(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: int = 10, order: str = "descending", unit: str = "object", step_range=None,
+                  dataset_name: str = "something") -> Dict[str, object]:
+    """The batches of the perturbation test (Chefer, Gur, Wolf 2021): `batch` with the first k candidates of the removal order deleted, for
+    every step s of `step_range` = (s0, s1) (default: all of 0 .. steps), k = floor(s * n_candidates[b] / steps).  The result holds
+    (s1-s0+1)*B clips, step-major: clip (s-s0)*B + b is clip b at step s.  A deleted slot is what the reference's dataset and collater make
+    of a slot without a detection (datasets.py:88-93, 274-278): category 0, box (0,0,0,0), score 0, mask True; a frame that had an object
+    and has none left gets the dataset's frame type "empty" (datasets.py:64-69).  Everything else is copied; slots are not compacted.
+    Step 0 is the batch itself, step `steps` has no candidate left.  Also returned: "removed" (s1-s0+1, B) int32 — k per step and clip — and
+    "n_candidates" (B,) int32.  Other per-clip entries (labels, video_id, any tensor or list whose leading extent is B) are tiled to the new
+    clip count; num_real_tokens / num_real_frames, when present, are multiplied by the number of steps written (upper bounds, which the
+    inference calls accept).  Device tensors go through stlt_perturb_rank / stlt_perturb_apply; CPU tensors take the torch form, same bits."""
+    _perturb_args(order, unit)
+    steps = int(steps)
+    if steps < 1:
+        raise L.StltHipError(f"steps must be >= 1, got {steps}")
+    s0, s1 = (0, steps) if step_range is None else (int(step_range[0]), int(step_range[1]))
+    if not 0 <= s0 <= s1 <= steps:
+        raise L.StltHipError(f"step_range: expected 0 <= s0 <= s1 <= steps = {steps}, got ({s0}, {s1})")
+    empty_type = DATASETS[dataset_name]["empty"]  # frame2type["empty"] (src/modelling/configs.py:40-78)
+    cats = batch["categories"]
+    B, T, N = cats.shape
+    n = s1 - s0 + 1
+    rank, n_cand = perturb_rank(scores, batch["src_key_padding_mask_boxes"], batch["lengths"], unit, order)
+    if cats.is_cuda:
+        core = {k: batch[k] for k, _, _ in ops.PERTURB_KEYS if k in batch}
+        for k in ("categories", "frame_types", "lengths"):
+            core[k] = core[k].to(torch.int64).contiguous()
+        core["boxes"] = core["boxes"].to(torch.float32).contiguous()
+        if "scores" in core:
+            core["scores"] = core["scores"].to(torch.float32).contiguous()
+        new = ops.perturb_apply(core, rank, n_cand, steps, s0, s1, empty_type)
+        removed = new.pop("removed")[s0:s1 + 1]
+    else:
+        k = (torch.arange(s0, s1 + 1, dtype=torch.int64)[:, None] * n_cand.to(torch.int64)[None, :]) // steps  # (n, B)
+        kpm = batch["src_key_padding_mask_boxes"]
+        slot_rank = rank if unit == "object" else torch.where((torch.arange(N)[None, None, :] >= 1) & ~kpm.bool(), rank[:, :, None], torch.full((), -1, dtype=torch.int32))
+        slot_rank = slot_rank.to(torch.int64)
+        gone = (slot_rank[None] >= 0) & (slot_rank[None] < k[:, :, None, None])      # (n, B, T, N)
+        had = (slot_rank >= 0).any(dim=2)                                            # (B, T)
+        left = ((slot_rank[None] >= 0) & ~gone).any(dim=3)                           # (n, B, T)
+        tile = lambda t: t.unsqueeze(0).expand(n, *t.shape)  # noqa: E731
+        new = {"categories": torch.where(gone, torch.zeros((), dtype=cats.dtype), tile(cats)),
+               "boxes": torch.where(gone[..., None], torch.zeros((), dtype=batch["boxes"].dtype), tile(batch["boxes"])),
+               "src_key_padding_mask_boxes": torch.where(gone, torch.ones((), dtype=kpm.dtype), tile(kpm)),
+               "frame_types": torch.where(had[None] & ~left, torch.full((), empty_type, dtype=batch["frame_types"].dtype), tile(batch["frame_types"])),
+               "src_key_padding_mask_frames": tile(batch["src_key_padding_mask_frames"]), "lengths": tile(batch["lengths"])}
+        if "scores" in batch:
+            new["scores"] = torch.where(gone, torch.zeros((), dtype=batch["scores"].dtype), tile(batch["scores"]))
+        new = {key: v.reshape(n * B, *v.shape[2:]).contiguous() for key, v in new.items()}
+        removed = k.to(torch.int32)
+    out = {}
+    for key, v in batch.items():
+        if key in new:
+            continue
+        if key in ("num_real_tokens", "num_real_frames"):
+            out[key] = int(v) * n
+        elif isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B:
+            out[key] = v.repeat((n,) + (1,) * (v.dim() - 1))
+        elif isinstance(v, (list, tuple)) and len(v) == B:
+            out[key] = type(v)(list(v) * n)
+        else:
+            out[key] = v
+    out.update(new)
+    out["removed"], out["n_candidates"] = removed, n_cand
+    return out

@@ -7,11 +7,13 @@ counters stay on the device: the reference's per-batch `.cpu()` synchronisation 
 """
 from __future__ import annotations
 
+import itertools
 from typing import Callable, Dict, Iterable, Optional
 
 import torch
 
 from . import dist as D
+from ._lib import StltHipError
 
 
 def topk_counts(logits: torch.Tensor, labels: torch.Tensor, ks=(1, 5)) -> torch.Tensor:
@@ -110,3 +112,140 @@ def run_prefix_inference(model, batches: Iterable[Dict[str, torch.Tensor]], devi
         D.all_reduce_sum_(counts, world)
     counts = counts.cpu()
     return {"top1": counts[:, 0].clone(), "top5": counts[:, 1].clone(), "num_clips": counts[:, 2].clone()}
+
+
+def perturb_curve(logits: torch.Tensor, target: Optional[torch.Tensor] = None, activation: str = "softmax"):
+    """The curves of the perturbation test from logits (S,B,K): -> (prob (S,B) float32 — the target class's softmax probability, or its
+    sigmoid; hit (S,B) bool — no class beats the target (a larger logit, or an equal logit at a lower index), or for sigmoid its logit is
+    positive; target (B,) int64 — as given, or the arg-max of each clip's step-0 row, first maximum on ties).  A target outside [0, K)
+    gives prob 0 and hit False.  Device logits go through the library (include/stlt_hip.h: stlt_perturb_curve); CPU logits take the
+    torch form (the not-gpu tests, stand-in models)."""
+    if logits.is_cuda:
+        from . import ops
+        x = logits if logits.dtype == torch.float32 else logits.float()
+        if x.stride(-1) != 1 or x.stride(0) != x.shape[1] * x.stride(1):
+            x = x.contiguous()
+        return ops.perturb_curve(x, None if target is None else target.to(device=logits.device, dtype=torch.int64).contiguous(), activation)
+    if activation not in ("softmax", "sigmoid"):
+        raise StltHipError(f"activation: expected 'softmax' or 'sigmoid', got {activation!r}")
+    x = logits.float()
+    S, B, K = x.shape
+    if target is None:
+        top = x[0].max(dim=1, keepdim=True).values
+        target = (x[0] == top).to(torch.int64).argmax(dim=1)  # the first maximum
+    target = target.to(torch.int64)
+    valid = (target >= 0) & (target < K)
+    idx = target.clamp(0, K - 1)[None, :, None].expand(S, B, 1)
+    xt = x.gather(2, idx)  # (S,B,1)
+    if activation == "sigmoid":
+        prob, hit = torch.sigmoid(xt[..., 0]), xt[..., 0] > 0
+    else:
+        prob = torch.softmax(x, dim=2).gather(2, idx)[..., 0]
+        cls = torch.arange(K)[None, None, :]
+        hit = ~((x > xt) | ((x == xt) & (cls < idx))).any(dim=2)
+    return torch.where(valid[None], prob, torch.zeros(())), hit & valid[None], target
+
+
+_PERTURB_METHODS = ("relevance", "saliency", "attention", "random")
+
+
+def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """One (B,T,N) score per object slot from `method`: "relevance" — forward_relevance's map; "saliency" — |boxes_grad| summed over the four
+    coordinates, plus |scores_grad| when the batch has scores; "attention" — the last layers' raw attention joined like the relevance,
+    temporal_attention[-1][b, lengths[b]-1, t] * spatial_attention[-1][b,t,0,n]; "random" — uniform numbers from `generator`; or a callable
+    (model, batch) -> scores."""
+    if callable(method):
+        return method(model, batch)
+    if method == "relevance":
+        return model.forward_relevance(batch)["relevance"]
+    if method == "saliency":
+        out = model.forward_saliency(batch)
+        s = out["boxes_grad"].abs().sum(-1)
+        return s + out["scores_grad"].abs() if "scores_grad" in out else s
+    if method == "attention":
+        out = model.forward_attention(batch)
+        B = batch["categories"].shape[0]
+        rows = torch.arange(B, device=batch["lengths"].device)
+        return out["temporal_attention"][-1][rows, batch["lengths"] - 1][:, :, None] * out["spatial_attention"][-1][:, :, 0, :]
+    if method == "random":
+        cats = batch["categories"]
+        return torch.rand(tuple(cats.shape), generator=generator, device=cats.device, dtype=torch.float32)
+    raise StltHipError(f"method: expected one of {_PERTURB_METHODS} or a callable (model, batch) -> scores, got {method!r}")
+
+
+@torch.no_grad()
+def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], method="relevance", steps: int = 10,
+                          orders=("descending", "ascending"), unit: str = "object", target: str = "top1", rank: int = 0, world: int = 1,
+                          forward: Optional[Callable] = None, activation: str = "softmax", dataset_name: str = "something", seed: int = 0,
+                          device=None) -> Dict[str, object]:
+    """The perturbation test of Chefer, Gur and Wolf (2021) over an iterable of collated batches, every batch sharded over the ranks as in
+    `run_inference`.  Per clip: rank the real object tokens (unit "frame": the frames, scored by the sum of their objects n >= 1) by the
+    map `method` gives (attribution_scores), delete the first k of them for k rising over `steps` steps — the highest-scored first for
+    order "descending", the lowest first for "ascending" —, run the model on every reduced batch, and follow the target class: "top1" —
+    the model's own prediction on the untouched clip —, or "label" — batch["labels"].
+    `forward` defaults to `model.forward_perturbed`; with a callable (batch) -> (n, K) logits the reduced batches come from
+    `collate.perturb_batch` and the curves from `perturb_curve`, which serves any model (the fusion models on precomputed features, a
+    stand-in on the CPU).  The sums stay on the device while the batches run — fp64 probability and int64 hit per step, the clip count —
+    and are all-reduced once at the end.  `device`: where the batches are moved to and the sums are kept (default: the device of the
+    model's parameters; a model without parameters: wherever the first batch lies).  `seed` seeds the "random" method's device generator.
+    -> {"fractions": [s / steps], order: {"prob": mean target probability per step, "accuracy": share of clips whose target is still the
+    prediction per step, "auc_prob", "auc_accuracy": the trapezoid areas over the fractions, "num_clips"}}.  A faithful map makes the
+    descending curves fall fast (small areas) and keeps the ascending ones flat (large areas)."""
+    from . import collate
+    if target not in ("top1", "label"):
+        raise StltHipError(f"target: expected 'top1' or 'label', got {target!r}")
+    if not callable(method) and method not in _PERTURB_METHODS:
+        raise StltHipError(f"method: expected one of {_PERTURB_METHODS} or a callable (model, batch) -> scores, got {method!r}")
+    orders = tuple(orders)
+    for o in orders:
+        collate._perturb_args(o, unit)
+    steps = int(steps)
+    if steps < 1:
+        raise StltHipError(f"steps must be >= 1, got {steps}")
+    if hasattr(model, "train"):
+        model.train(False)
+    S = steps + 1
+    if device is None and isinstance(model, torch.nn.Module):
+        device = next((q.device for q in model.parameters()), None)
+    batches = iter(batches)
+    first = next(batches, None)
+    if device is None:
+        device = first["categories"].device if first is not None else "cpu"
+    device = torch.device(device)
+    gen = torch.Generator(device=device).manual_seed(seed + rank) if method == "random" else None
+    prob_sum = torch.zeros(len(orders), S, dtype=torch.float64, device=device)
+    hit_sum = torch.zeros(len(orders), S, dtype=torch.int64, device=device)
+    n_clips = torch.zeros(1, dtype=torch.int64, device=device)
+    for batch in itertools.chain(() if first is None else (first,), batches):
+        mine = D.shard_batch(batch, rank, world)
+        mine = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in mine.items()}
+        B = D.batch_size(mine)
+        if B == 0:
+            continue
+        scores = attribution_scores(model, mine, method, gen).to(torch.float32)
+        if unit == "frame":
+            scores = scores[:, :, 1:].sum(dim=2)
+        tgt = mine["labels"].to(torch.int64) if target == "label" else None
+        for i, order in enumerate(orders):
+            if forward is None:
+                out = model.forward_perturbed(mine, scores.contiguous(), steps=steps, order=order, unit=unit, target=tgt, dataset_name=dataset_name, activation=activation)
+                prob, hit = out["prob"], out["hit"]
+            else:
+                pb = collate.perturb_batch(mine, scores, steps=steps, order=order, unit=unit, dataset_name=dataset_name)
+                logits = forward(pb)
+                prob, hit, _ = perturb_curve(logits.reshape(S, B, -1), tgt, activation)
+            prob_sum[i] += prob.sum(dim=1, dtype=torch.float64)
+            hit_sum[i] += hit.sum(dim=1)
+        n_clips += B
+    packed = torch.cat([prob_sum.reshape(-1), hit_sum.reshape(-1).double(), n_clips.double()])  # counts are exact in fp64 below 2^53
+    D.all_reduce_sum_(packed, world)
+    packed = packed.cpu()
+    n = int(packed[-1].item())
+    fractions = [s / steps for s in range(S)]
+    result: Dict[str, object] = {"fractions": fractions}
+    trapezoid = lambda c: float((c.sum() - 0.5 * (c[0] + c[-1])) / steps)  # noqa: E731
+    for i, order in enumerate(orders):
+        p = packed[i * S:(i + 1) * S] / max(n, 1)
+        a = packed[(len(orders) + i) * S:(len(orders) + i + 1) * S] / max(n, 1)
+        result[order] = {"prob": p.tolist(), "accuracy": a.tolist(), "auc_prob": trapezoid(p), "auc_accuracy": trapezoid(a), "num_clips": n}
+    return result

@@ -665,6 +665,62 @@ class Stlt(nn.Module):
             out["spatial_layers"], out["temporal_layers"] = maps["spatial_layers"], maps["temporal_layers"]
         return out
 
+    @torch.no_grad()
+    def forward_perturbed(self, batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: int = 10, order: str = "descending", unit: str = "object",
+                          target=None, steps_per_pass: Optional[int] = None, dataset_name: str = "something", activation: str = "softmax") -> Dict[str, torch.Tensor]:
+        """The perturbation test of an attribution map on this model (Chefer, Gur, Wolf 2021): the clips' object tokens (unit "object",
+        scores (B,T,N)) or frames (unit "frame", scores (B,T)) are ranked by `scores` (include/stlt_hip.h: stlt_perturb_rank), the first
+        k = floor(s * n_candidates / steps) of the removal order are deleted for s = 0 .. steps (stlt_perturb_apply — a deleted slot is a
+        slot without a detection as the reference's dataset and collater make it, datasets.py:64-69, 88-93, 274-278), the ordinary
+        `forward` runs on every reduced batch, and one launch reads the curves off the logits (stlt_perturb_curve).  order "descending"
+        deletes the highest-scored first (a faithful map makes the target's probability fall fast), "ascending" the lowest-scored first
+        (it should stay flat).  -> {"stlt": (S,B,K) float32 logits with S = steps+1, "prob": (S,B) the target class's softmax probability,
+        "hit": (S,B) bool — the target is still the prediction, "auc": (B,) the trapezoid of prob over the steps divided by `steps`,
+        "target": (B,) int64, "removed": (S,B) int32 — k per step and clip, "n_candidates": (B,) int32}.
+        `target`: None — each clip's top-1 class on the unperturbed batch (step 0) — or an int64 (B,) tensor.  steps_per_pass: how many
+        steps one forward holds (default: all S, one forward on S*B clips; 1: S forwards on B clips).  Works with `backbone.skip_padding` on
+        and off; num_real_tokens / num_real_frames of the batch are carried as upper bounds (no read-back).  `dataset_name` names the frame
+        type "empty"; activation "sigmoid" (Action Genome's multi-label head) makes prob the target's sigmoid and hit "its logit is positive".
+        Inference only: refuses live dropout and CPU tensors, as forward_saliency does."""
+        from .. import collate
+        bb = self.backbone
+        if bb._dropout_live():
+            raise L.StltHipError("forward_perturbed is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
+        if not batch["categories"].is_cuda or not (isinstance(scores, torch.Tensor) and scores.is_cuda):
+            raise L.StltHipError("forward_perturbed runs on the GPU: the batch or the scores hold CPU tensors (move the model and the batch to a cuda device)")
+        descending = collate._perturb_args(order, unit)
+        steps = int(steps)
+        if steps < 1:
+            raise L.StltHipError(f"forward_perturbed: steps must be >= 1, got {steps}")
+        S = steps + 1
+        per = S if steps_per_pass is None else int(steps_per_pass)
+        if per < 1:
+            raise L.StltHipError(f"forward_perturbed: steps_per_pass must be >= 1, got {steps_per_pass}")
+        device = batch["categories"].device
+        B = batch["categories"].shape[0]
+        if target is not None and (not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device):
+            raise L.StltHipError(f"forward_perturbed: target is None or an int64 ({B},) tensor on the batch's device")
+        head = self.prediction_head
+        K = head.fc2.weight.shape[0]
+        core = {k: batch[k].contiguous() for k, _, _ in ops.PERTURB_KEYS if k in batch}
+        counts = {k: batch[k] for k in ("num_real_tokens", "num_real_frames") if k in batch}
+        if any(isinstance(v, torch.Tensor) and v.is_cuda for v in counts.values()):
+            raise L.StltHipError("num_real_tokens / num_real_frames must be host integers (a device tensor would have to be read back, which is what they are there to avoid)")
+        counts = {k: int(v) for k, v in counts.items()}
+        rank, n_cand = ops.perturb_rank(scores, core["src_key_padding_mask_boxes"], core["lengths"], unit, descending)
+        logits = torch.empty(S, B, K, device=device, dtype=torch.float32)
+        removed = torch.empty(S, B, device=device, dtype=torch.int32)
+        empty_type = collate.DATASETS[dataset_name]["empty"]
+        for s0 in range(0, S, per):
+            s1 = min(s0 + per, S) - 1
+            part = ops.perturb_apply(core, rank, n_cand, steps, s0, s1, empty_type, removed=removed)
+            part.pop("removed")
+            part.update({k: v * (s1 - s0 + 1) for k, v in counts.items()})
+            bb._whole_path("stlt_forward", part, head, ops.workspace_bytes, bb._flags(), lambda *a, s0=s0, s1=s1: (logits[s0:s1 + 1].view(-1, K),), before=(None,))
+        prob, hit, tgt = ops.perturb_curve(logits, target, activation)
+        auc = (prob.sum(0) - 0.5 * (prob[0] + prob[-1])) / steps
+        return {"stlt": logits, "prob": prob, "hit": hit, "auc": auc, "target": tgt, "removed": removed, "n_candidates": n_cand}
+
 
 class _StltTrainFn(torch.autograd.Function):
     """Autograd shell of the native training step: forward = stlt_train_forward (records the tape), backward =

@@ -429,6 +429,112 @@ def relevance_combine_joint(fusion_rollout: torch.Tensor, rollout_spatial: torch
     return rel, frame_rel, app_rel
 
 
+def _perturb_unit(unit) -> int:
+    if unit not in L.PERTURB_UNITS:
+        raise L.StltHipError(f"unit: expected 'object' or 'frame', got {unit!r}")
+    return L.PERTURB_UNITS[unit]
+
+
+def perturb_rank(scores: torch.Tensor, kpm_boxes: torch.Tensor, lengths: torch.Tensor, unit: str = "object", descending: bool = True):
+    """The removal order of the perturbation test (include/stlt_hip.h: stlt_perturb_rank): scores (B,T,N) float32 for unit "object", (B,T)
+    for "frame"; kpm_boxes (B,T,N) bool/uint8; lengths (B,) int64.  -> (rank int32, scores' shape: position in the removal order of every
+    candidate, -1 elsewhere; n_candidates (B,) int32).  T*N <= 16384."""
+    lib = L.load()
+    u = _perturb_unit(unit)
+    _chk(scores, torch.float32, "scores"); _chk(lengths, torch.int64, "lengths")
+    kpm = _mask_u8(kpm_boxes, "src_key_padding_mask_boxes")
+    if kpm.dim() != 3:
+        raise L.StltHipError(f"src_key_padding_mask_boxes: expected (B,T,N), got {tuple(kpm.shape)}")
+    B, T, N = kpm.shape
+    want = (B, T, N) if u == 0 else (B, T)
+    if tuple(scores.shape) != want:
+        raise L.StltHipError(f"scores: unit {unit!r} takes {want}, got {tuple(scores.shape)}")
+    if tuple(lengths.shape) != (B,):
+        raise L.StltHipError(f"lengths: expected ({B},), got {tuple(lengths.shape)}")
+    rank = torch.empty(want, device=scores.device, dtype=torch.int32)
+    n_cand = torch.empty(B, device=scores.device, dtype=torch.int32)
+    L.check(lib.stlt_perturb_rank(_p(scores), _p(kpm), _p(lengths), B, T, N, u, int(bool(descending)), _p(rank), _p(n_cand), _stream()), "stlt_perturb_rank")
+    return rank, n_cand
+
+
+# the tensors of a collated batch the perturbation calls read and write: (key, dtype at the C-ABI, dimensions); collate.py and models.py use this table
+PERTURB_KEYS = (("categories", torch.int64, 3), ("boxes", torch.float32, 4), ("scores", torch.float32, 3), ("src_key_padding_mask_boxes", torch.uint8, 3),
+                 ("frame_types", torch.int64, 2), ("src_key_padding_mask_frames", torch.uint8, 2), ("lengths", torch.int64, 1))
+
+
+def perturb_apply(batch, rank: torch.Tensor, n_candidates: torch.Tensor, steps: int, s0: int, s1: int, empty_frame_type: int, removed: Optional[torch.Tensor] = None):
+    """Steps s0 .. s1 of the perturbation test's batches (include/stlt_hip.h: stlt_perturb_apply): `batch` holds the collated tensors
+    (categories, boxes, [scores], both masks, frame_types, lengths), rank / n_candidates come from perturb_rank (rank (B,T,N): unit object,
+    (B,T): unit frame).  -> dict of the same tensors for (s1-s0+1)*B clips, step-major, plus "removed" (steps+1, B) int32 whose rows
+    s0 .. s1 are written (`removed`: write into this buffer; a fresh one holds -1 in the other rows)."""
+    lib = L.load()
+    cats = _chk(batch["categories"], torch.int64, "categories")
+    if cats.dim() != 3:
+        raise L.StltHipError(f"categories must be (B,T,N), got {tuple(cats.shape)}")
+    B, T, N = cats.shape
+    steps, s0, s1 = int(steps), int(s0), int(s1)
+    if steps < 1 or not 0 <= s0 <= s1 <= steps:
+        raise L.StltHipError(f"steps >= 1 and 0 <= s0 <= s1 <= steps, got steps={steps}, s0={s0}, s1={s1}")
+    _chk(rank, torch.int32, "rank"); _chk(n_candidates, torch.int32, "n_candidates")
+    if tuple(rank.shape) not in ((B, T, N), (B, T)) or tuple(n_candidates.shape) != (B,):
+        raise L.StltHipError(f"rank is ({B},{T},{N}) (unit object) or ({B},{T}) (unit frame) and n_candidates ({B},), got {tuple(rank.shape)}, {tuple(n_candidates.shape)}")
+    unit = 0 if rank.dim() == 3 else 1
+    shapes = {3: (B, T, N), 4: (B, T, N, 4), 2: (B, T), 1: (B,)}
+    n = s1 - s0 + 1
+    inp, out, keep = L.Inputs(), {}, []
+    inp.B, inp.T, inp.N = B, T, N
+    for key, dtype, nd in PERTURB_KEYS:
+        if key == "scores" and key not in batch:
+            continue
+        t = batch[key]
+        if tuple(t.shape) != shapes[nd]:
+            raise L.StltHipError(f"{key}: expected shape {shapes[nd]}, got {tuple(t.shape)}")
+        was_bool = t.dtype == torch.bool
+        t = _mask_u8(t, key) if dtype == torch.uint8 else _chk(t, dtype, key)
+        keep.append(t)
+        o = torch.empty((n * B,) + shapes[nd][1:], device=cats.device, dtype=dtype)
+        out[key] = o.view(torch.bool) if was_bool else o
+        setattr(inp, {"src_key_padding_mask_boxes": "kpm_boxes", "src_key_padding_mask_frames": "kpm_frames"}.get(key, key), t.data_ptr())
+        keep.append(o)
+    if removed is None:
+        removed = torch.full((steps + 1, B), -1, device=cats.device, dtype=torch.int32)
+    else:
+        _chk(removed, torch.int32, "removed")
+        if tuple(removed.shape) != (steps + 1, B):
+            raise L.StltHipError(f"removed: expected ({steps + 1}, {B}), got {tuple(removed.shape)}")
+    L.check(lib.stlt_perturb_apply(C.byref(inp), _p(rank), _p(n_candidates), unit, steps, s0, s1, int(empty_frame_type), _p(out["categories"]), _p(out["boxes"]),
+                                   _p(out.get("scores")), _p(out["src_key_padding_mask_boxes"]), _p(out["frame_types"]), _p(out["src_key_padding_mask_frames"]),
+                                   _p(out["lengths"]), _p(removed), _stream()), "stlt_perturb_apply")
+    out["removed"] = removed
+    return out
+
+
+def perturb_curve(logits: torch.Tensor, target: Optional[torch.Tensor] = None, activation: str = "softmax"):
+    """The curves of the perturbation test (include/stlt_hip.h: stlt_perturb_curve): logits (S,B,K) float32, rows contiguous (the row pitch
+    may exceed K); target (B,) int64 or None (the arg-max of each clip's step-0 row).  -> (prob (S,B) float32: the target's softmax
+    probability or sigmoid; hit (S,B) bool: the target is the prediction (sigmoid: its logit is positive); target (B,) int64)."""
+    lib = L.load()
+    if activation not in L.PERTURB_ACTIVATIONS:
+        raise L.StltHipError(f"activation: expected 'softmax' or 'sigmoid', got {activation!r}")
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise L.StltHipError(f"logits: expected a GPU tensor (the STLT hot path has no CPU fallback), got {getattr(logits, 'device', type(logits))}")
+    if logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[0] < 1:
+        raise L.StltHipError(f"logits: expected float32 (S,B,K) with S >= 1, got {logits.dtype} {tuple(logits.shape)}")
+    S, B, K = logits.shape
+    if K < 1 or logits.stride(2) != 1 or logits.stride(1) < K or logits.stride(0) != B * logits.stride(1):
+        raise L.StltHipError(f"logits: rows must be contiguous and one pitch apart, got strides {logits.stride()}")
+    if target is not None:
+        _chk(target, torch.int64, "target")
+        if tuple(target.shape) != (B,):
+            raise L.StltHipError(f"target: expected ({B},), got {tuple(target.shape)}")
+    prob = torch.empty(S, B, device=logits.device, dtype=torch.float32)
+    hit = torch.empty(S, B, device=logits.device, dtype=torch.uint8)
+    tgt = torch.empty(B, device=logits.device, dtype=torch.int64)
+    L.check(lib.stlt_perturb_curve(_p(logits), logits.stride(1), _p(target), L.PERTURB_ACTIVATIONS[activation], S, B, K, _p(prob), _p(hit), _p(tgt), _stream()),
+            "stlt_perturb_curve")
+    return prob, hit.view(torch.bool), tgt
+
+
 def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
     """Probe attention of the per-prefix forward (include/stlt_hip.h: stlt_attn_prefix_probe_fwd).  qkv_frames, qkv_probes: (S,T,3d) packed
     [q;k;v] rows of the frame and of the probe stream, kpm (S,T) bool/uint8 (True = frame masked as a key).  Probe (s,t) attends to the frame
