@@ -1114,6 +1114,39 @@ int stlt_perturb_apply(const stlt_inputs* in, const int32_t* rank, const int32_t
 int stlt_perturb_curve(const float* logits, int64_t ld, const int64_t* target, int activation, int64_t S, int64_t B, int64_t K, float* prob, uint8_t* hit,
                        int64_t* target_out, stlt_stream_t stream);
 
+/* ---- the perturbation test on the appearance side: video cells and feature columns (csrc/perturb.hip) ----
+ * The reference's appearance encoder takes no key-padding mask (src/modelling/models.py:269, self.transformer(src=features)), so an appearance
+ * token is deleted at the input.  The unit is the CELL: x (B,Cch,T,H,W) float32 contiguous is cut into blocks of (ct,ch,cw) along (T,H,W),
+ * ragged last blocks included: the grid is Gt = ceil(T/ct), Gh = ceil(H/ch), Gw = ceil(W/cw), C = Gt*Gh*Gw, cell c = (gt*Gh + gh)*Gw + gw
+ * covers frames [ct gt, min(ct gt+ct, T)), rows [ch gh, min(ch gh+ch, H)), columns [cw gw, min(cw gw+cw, W)) of every channel.  For
+ * video_frames (B,3,T,H,W) and the R3D-50 trunk the cell is (16,32,32): the trunk's total stride (stem (1,2,2), max-pool 2, three stride-2
+ * stages, each rounding the extent up), so that cell c is the stride block — not the receptive field — of appearance token 1 + c
+ * (features.flatten(2), models.py:260; token 0 is the CLS token, models.py:262-264, and never a candidate).  For precomputed
+ * appearance_features (B,Cf,Gt,Gh,Gw) the cell is (1,1,1): the feature column itself.  The three calls share the contract of the three above:
+ * stream-ordered, no allocation, no read-back, capturable; STLT_EINVAL with a message and no launch on a bad extent or a NULL required
+ * pointer; alignment of the element type only (16-byte accesses are chosen by the pointers' alignment, see below).  A clip holds fewer than
+ * 2^31 elements and at most stlt_perturb_max_items() cells.
+ *
+ * stlt_perturb_rank_cells: scores (B,C) -> rank (B,C) int32, the position of every cell in the removal order (0 = removed first), and
+ * n_candidates (B,) int32 = C: every cell is a candidate.  The order is stlt_perturb_rank's, by the same LDS sort: floats compared with
+ * -0 == +0, ties to the lower flat index in both orders, NaN removed last in both orders.  C <= stlt_perturb_max_items(), else STLT_EINVAL.
+ *
+ * stlt_perturb_apply_cells: for every step s in [s0, s1], 0 <= s0 <= s1 <= steps, steps >= 1, s1-s0+1 <= 256: x with the cells of
+ * 0 <= rank < k set to `fill`, k = floor(s * n_candidates[b] / steps) (64-bit product); every other element is copied bit for bit.  fill 0.0
+ * is mid-grey after the reference's Normalize(0.5, 0.5) (src/modelling/datasets.py:151).  out ((s1-s0+1)*B, Cch,T,H,W) is step-major like
+ * stlt_perturb_apply's: clip (s-s0)*B + b is clip b at step s.  removed ((s1-s0+1), B) int32, optional (NULL): k per step and clip.  rank
+ * (B,C) with C the grid's cell count and n_candidates are trusted, not checked: other values blank other cells, inside the extents all the
+ * same.  Every source element is read once and written s1-s0+1 times.  Lane accesses are 16 bytes wide when W % 4 == 0, cw % 4 == 0 and x and
+ * out are 16-byte aligned, one float wide otherwise: the same bits either way.  out must not overlap x.
+ *
+ * stlt_cell_pool_abs: out (B,C)[b,c] = the sum of |g| over cell c and all channels of g (B,Cch,T,H,W): video_frames_grad or
+ * appearance_features_grad as a per-cell saliency map, as the layout side sums |boxes_grad| over the four coordinates.  The summation
+ * order is fixed (no atomics): two launches give the same bits; the error is that of a tree sum of non-negative fp32 terms. */
+int stlt_perturb_rank_cells(const float* scores, int64_t B, int64_t C, int descending, int32_t* rank, int32_t* n_candidates, stlt_stream_t stream);
+int stlt_perturb_apply_cells(const float* x, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, const int32_t* rank,
+                             const int32_t* n_candidates, int64_t steps, int64_t s0, int64_t s1, float fill, float* out, int32_t* removed, stlt_stream_t stream);
+int stlt_cell_pool_abs(const float* g, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, float* out, stlt_stream_t stream);
+
 /* ---- per-kernel timing (bench.py roofline leg): hipEvents around every launch of the whole-path calls ---- */
 #define STLT_K_EMBED 0
 #define STLT_K_GEMM 1

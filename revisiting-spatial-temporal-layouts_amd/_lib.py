@@ -277,6 +277,9 @@ SIGNATURES = {
     "stlt_perturb_rank": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp]),
     "stlt_perturb_apply": (C.c_int, [C.POINTER(Inputs), _vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "stlt_perturb_curve": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp]),
+    "stlt_perturb_rank_cells": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "stlt_perturb_apply_cells": (C.c_int, [_vp] + [C.c_int64] * 8 + [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_float, _vp, _vp, _vp]),
+    "stlt_cell_pool_abs": (C.c_int, [_vp] + [C.c_int64] * 8 + [_vp, _vp]),
     "stlt_grad_norm": (C.c_int, [_vp, C.c_int64, C.c_float, _vp, _vp, _vp]),
     "stlt_adamw_step": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
     "stlt_prof_enable": (C.c_int, [C.c_int]),

@@ -131,7 +131,14 @@ def perturb_rank(scores: torch.Tensor, kpm_boxes: torch.Tensor, lengths: torch.T
     t_idx = torch.arange(T)[None, :, None]
     cand = (t_idx < (lengths.to(torch.int64) - 1)[:, None, None]) & (torch.arange(N)[None, None, :] >= 1) & ~kpm_boxes.bool()
     cand = (cand if unit == "object" else cand.any(dim=2)).reshape(B, -1)
-    v = scores.to(torch.float32).double().reshape(B, -1)
+    rank, n_cand = _rank_torch(scores.reshape(B, -1), cand, descending)
+    return rank.reshape(want), n_cand
+
+
+def _rank_torch(scores: torch.Tensor, cand: torch.Tensor, descending: bool):
+    """The torch form of the rank kernels on CPU tensors: scores, cand (B,M) -> (rank (B,M) int32, n_candidates (B,) int32)"""
+    B = scores.shape[0]
+    v = scores.to(torch.float32).double()
     nan = torch.isnan(v)
     v = torch.where(nan | (v == 0), torch.zeros_like(v), -v if descending else v)  # canonical: -0 == +0; NaN sorted below
     order_ = torch.sort(v, dim=1, stable=True).indices
@@ -140,7 +147,7 @@ def perturb_rank(scores: torch.Tensor, kpm_boxes: torch.Tensor, lengths: torch.T
     n_cand = cand.sum(dim=1)
     pos = torch.arange(v.shape[1])[None, :].expand(B, -1)
     rank = torch.empty(B, v.shape[1], dtype=torch.int64).scatter_(1, order_, torch.where(pos < n_cand[:, None], pos, torch.full_like(pos, -1)))
-    return rank.to(torch.int32).reshape(want), n_cand.to(torch.int32)
+    return rank.to(torch.int32), n_cand.to(torch.int32)
 
 
 def perturb_batch(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: int = 10, order: str = "descending", unit: str = "object", step_range=None,
@@ -206,5 +213,114 @@ def perturb_batch(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: i
         else:
             out[key] = v
     out.update(new)
+    out["removed"], out["n_candidates"] = removed, n_cand
+    return out
+
+
+VIDEO_CELL = (16, 32, 32)  # the R3D-50 trunk's total stride in (T, H, W): stem (1,2,2), max-pool 2, three stride-2 stages
+
+
+def appearance_cells(batch: Dict[str, torch.Tensor]):
+    """What the appearance side of the perturbation test deletes in `batch` -> (key, cell extents (ct,ch,cw), grid (Gt,Gh,Gw)).
+    `video_frames` (B,3,T,H,W): the stride block of one appearance token, VIDEO_CELL, on the grid the trunk's own plan gives for this video
+    (modelling.resnet3d: the extents of its feature map) — a video for which the blocks and the plan disagree is refused.  Without
+    `video_frames`, `appearance_features` (B,Cf,Gt,Gh,Gw): the feature column, (1,1,1)."""
+    from .modelling.resnet3d import _trunk_out
+    if "video_frames" in batch:
+        v = batch["video_frames"]
+        if v.dim() != 5:
+            raise L.StltHipError(f"video_frames must be (B, 3, T, H, W), got {tuple(v.shape)}")
+        _, _, T, H, W = v.shape
+        ct, ch, cw = VIDEO_CELL
+        grid = (-(-T // ct), -(-H // ch), -(-W // cw))
+        plan = (_trunk_out(T), _trunk_out(H, 2), _trunk_out(W, 2))
+        if grid != plan:
+            raise L.StltHipError(f"video_frames {tuple(v.shape)}: the cells {VIDEO_CELL} give the grid {grid}, the trunk's plan {plan} tokens")
+        return "video_frames", VIDEO_CELL, grid
+    if "appearance_features" in batch:
+        f = batch["appearance_features"]
+        if f.dim() != 5:
+            raise L.StltHipError(f"appearance_features must be (B, Cf, Gt, Gh, Gw), got {tuple(f.shape)}")
+        return "appearance_features", (1, 1, 1), tuple(f.shape[2:])
+    raise L.StltHipError("the batch needs `video_frames` or `appearance_features`")
+
+
+def cell_scores(scores: torch.Tensor, B: int, n_cells: int) -> torch.Tensor:
+    """`scores` of an appearance call as (B,C) float32: (B,C) cell scores as they are, (B,C+1) token scores without the CLS column"""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.shape[0] != B or scores.shape[1] not in (n_cells, n_cells + 1):
+        raise L.StltHipError(f"scores: the appearance side takes ({B},{n_cells}) cell scores or ({B},{n_cells + 1}) token scores (CLS first), "
+                             f"got {tuple(scores.shape) if isinstance(scores, torch.Tensor) else type(scores)}")
+    if scores.shape[1] == n_cells + 1:
+        scores = scores[:, 1:]
+    return scores.to(torch.float32).contiguous()
+
+
+def perturb_rank_cells(scores: torch.Tensor, order: str = "descending"):
+    """The removal order of video cells or feature columns (include/stlt_hip.h: stlt_perturb_rank_cells): scores (B,C), every cell a
+    candidate -> (rank (B,C) int32, n_candidates (B,) int32 = C), by perturb_rank's order rule.  Device tensors go through the kernel; CPU
+    tensors take the torch form, same integers."""
+    descending = _perturb_args(order, "object")
+    if scores.dim() != 2 or scores.shape[1] < 1:
+        raise L.StltHipError(f"scores: expected (B,C) with C >= 1, got {tuple(scores.shape)}")
+    max_items = L.load().stlt_perturb_max_items()
+    if scores.shape[1] > max_items:
+        raise L.StltHipError(f"C = {scores.shape[1]} cells exceed the {max_items} a clip is ranked with (STLT_EINVAL)")
+    if scores.is_cuda:
+        return ops.perturb_rank_cells(scores.to(torch.float32).contiguous(), descending)
+    return _rank_torch(scores, torch.ones(scores.shape, dtype=torch.bool), descending)
+
+
+def cell_index(shape, cell) -> torch.Tensor:
+    """(T,H,W) int64: the flat cell index of every position of a (T,H,W) volume cut into cells of (ct,ch,cw)"""
+    (T, H, W), (ct, ch, cw) = shape, cell
+    Gh, Gw = -(-H // ch), -(-W // cw)
+    return ((torch.arange(T) // ct)[:, None, None] * Gh + (torch.arange(H) // ch)[None, :, None]) * Gw + (torch.arange(W) // cw)[None, None, :]
+
+
+def perturb_cells(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: int = 10, order: str = "descending", step_range=None,
+                  fill: float = 0.0) -> Dict[str, object]:
+    """The appearance counterpart of perturb_batch: `batch` with the first k cells of the removal order deleted from `video_frames` — or
+    from `appearance_features` when the batch has no `video_frames` — for every step s of `step_range` = (s0, s1) (default: all of
+    0 .. steps), k = floor(s * C / steps).  A cell (appearance_cells) is the stride block of one appearance token: frames
+    [16 gt, 16 gt+16), rows [32 gh, 32 gh+32), columns [32 gw, 32 gw+32), clipped to the video, all channels; it is the block the trunk's
+    strides map onto token 1 + (gt*Gh + gh)*Gw + gw, not the token's receptive field.  Deleting it sets its pixels to `fill` (0.0:
+    mid-grey after the reference's Normalize(0.5, 0.5), datasets.py:151); the reference's appearance encoder takes no key-padding mask
+    (models.py:269), so a token cannot be masked instead.  On `appearance_features` the cell is the feature column: a weaker test — the
+    feature of a grey block is not `fill` — and the one there is when no trunk is loaded.  `scores`: (B,C) cell scores or (B,C+1) token
+    scores, CLS first (dropped).  The result holds (s1-s0+1)*B clips, step-major; every other per-clip entry, the layout tensors among
+    them, is tiled as perturb_batch tiles it.  Also returned: "removed" (s1-s0+1, B) int32 and "n_candidates" (B,) int32.  Device tensors
+    go through stlt_perturb_rank_cells / stlt_perturb_apply_cells; CPU tensors take the torch form, same bits."""
+    _perturb_args(order, "object")
+    steps = int(steps)
+    if steps < 1:
+        raise L.StltHipError(f"steps must be >= 1, got {steps}")
+    s0, s1 = (0, steps) if step_range is None else (int(step_range[0]), int(step_range[1]))
+    if not 0 <= s0 <= s1 <= steps:
+        raise L.StltHipError(f"step_range: expected 0 <= s0 <= s1 <= steps = {steps}, got ({s0}, {s1})")
+    key, cell, grid = appearance_cells(batch)
+    x = batch[key]
+    B = x.shape[0]
+    n = s1 - s0 + 1
+    rank, n_cand = perturb_rank_cells(cell_scores(scores, B, grid[0] * grid[1] * grid[2]), order)
+    if x.is_cuda:
+        new, removed = ops.perturb_apply_cells(x.to(torch.float32).contiguous(), cell, rank, n_cand, steps, s0, s1, fill)
+    else:
+        k = (torch.arange(s0, s1 + 1, dtype=torch.int64)[:, None] * n_cand.to(torch.int64)[None, :]) // steps  # (n, B)
+        gone = (rank.to(torch.int64)[None] >= 0) & (rank.to(torch.int64)[None] < k[:, :, None])  # (n, B, C)
+        mask = gone[:, :, cell_index(tuple(x.shape[2:]), cell)]  # (n, B, T, H, W)
+        new = torch.where(mask[:, :, None], torch.full((), float(fill), dtype=x.dtype), x[None]).reshape(n * B, *x.shape[1:]).contiguous()
+        removed = k.to(torch.int32)
+    out = {}
+    for name, v in batch.items():
+        if name == key:
+            out[name] = new
+        elif name in ("num_real_tokens", "num_real_frames"):
+            out[name] = int(v) * n
+        elif isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B:
+            out[name] = v.repeat((n,) + (1,) * (v.dim() - 1))
+        elif isinstance(v, (list, tuple)) and len(v) == B:
+            out[name] = type(v)(list(v) * n)
+        else:
+            out[name] = v
     out["removed"], out["n_candidates"] = removed, n_cand
     return out

@@ -11,6 +11,9 @@
 //                         moved as the integer it is stored as (bit for bit), frames that lost their last object change type.
 //   perturb_curve_kernel  one wave per logits row: the stabilised softmax probability (or the sigmoid) of the clip's target class and
 //                         whether any class beats it — eval_topk_kernel's rule (larger logit, or equal logit at a lower index).
+//   perturb_apply_cells_kernel / cell_pool_abs_kernel  the appearance side (further down): video cells and feature columns set to a fill
+//                         value per step, and |gradient| summed per cell.  Cells are ranked by perturb_rank_kernel<true>: the same sort.
+#include <cstring>
 #include "common.h"
 
 namespace {
@@ -30,22 +33,30 @@ __device__ __forceinline__ uint32_t removal_key(float v, int descending) {
   return descending ? ~u : u;
 }
 
+// CELLS: every item is a candidate (the video cells of stlt_perturb_rank_cells: no mask and no lengths are read); the sort is the same code
+template <bool CELLS>
 __global__ __launch_bounds__(PT_THREADS) void perturb_rank_kernel(const float* __restrict__ scores, const uint8_t* __restrict__ kpm, const int64_t* __restrict__ lengths,
                                                                   int T, int N, int unit_frame, int descending, int n_items, int n_pow2,
                                                                   int* __restrict__ rank, int* __restrict__ n_candidates) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];  // n_pow2 keys
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x;
-  const int64_t len = lengths[b];
-  const int64_t t_end = len - 1 < (int64_t)T ? len - 1 : (int64_t)T;  // frames [0, t_end) may hold candidates: never the extract frame, never past T
-  const uint8_t* m = kpm + b * (int64_t)T * N;
+  int64_t t_end = 0;
+  const uint8_t* m = nullptr;
+  if constexpr (!CELLS) {
+    const int64_t len = lengths[b];
+    t_end = len - 1 < (int64_t)T ? len - 1 : (int64_t)T;  // frames [0, t_end) may hold candidates: never the extract frame, never past T
+    m = kpm + b * (int64_t)T * N;
+  }
   const float* sc = scores + b * (int64_t)n_items;
   int* rk = rank + b * (int64_t)n_items;
   for (int i = tid; i < n_pow2; i += PT_THREADS) {
     unsigned long long k = PT_NONE;
     if (i < n_items) {
       bool cand;
-      if (unit_frame) {
+      if constexpr (CELLS) {
+        cand = true;
+      } else if (unit_frame) {
         cand = false;
         if (i < t_end)
           for (int n = 1; n < N; ++n) cand |= m[(int64_t)i * N + n] == 0;
@@ -192,6 +203,112 @@ __global__ __launch_bounds__(PT_THREADS) void perturb_curve_kernel(const float* 
   if (lane == 0) { prob[row] = (float)(exp((double)xy - (double)mx) / sum); hit[row] = beaten_by == 0 ? 1 : 0; }
 }
 
+// ---- the appearance side: video cells (the stride block of one appearance token) and feature columns ----
+// The reference's appearance encoder takes no key-padding mask (src/modelling/models.py:269, self.transformer(src=features)), so a token is
+// deleted at the input: cell (gt,gh,gw) of video_frames (B,3,T,H,W) — the block the trunk's strides map onto appearance token
+// 1 + (gt*Gh + gh)*Gw + gw (features.flatten(2), models.py:260) — is set to `fill`, 0.0 being mid-grey after Normalize(0.5, 0.5)
+// (src/modelling/datasets.py:151).  Precomputed appearance_features are the same tensor shape with cells of 1 x 1 x 1.
+
+constexpr int PC_ITEMS = 8;  // lane accesses of one thread of perturb_apply_cells_kernel (a block covers PT_THREADS * PC_ITEMS of them, more when the grid is large)
+constexpr int PC_NEVER = 0x7fffffff;
+
+struct CellGeom {  // one clip: (Cch, T, H, W) cut into cells of (ct, ch, cw); the grid is (Gt, Gh, Gw), ragged last cells on every axis
+  int Cch, T, H, W, ct, ch, cw, Gh, Gw;
+};
+
+// One workgroup per (clip, chunk of the clip's lane accesses).  LDS holds, per cell, the first step at which the cell is deleted,
+// ceil((rank+1) * steps / n_candidates) — step s deletes rank < floor(s * n / steps), which is s * n >= (rank+1) * steps — so every source
+// element is read once and written s1-s0+1 times, value or fill, on one compare per step.  VEC: 16-byte lane accesses (W % 4 == 0 and
+// cw % 4 == 0: the four floats lie in one cell and in one row); otherwise one float per access.
+template <bool VEC>
+__global__ __launch_bounds__(PT_THREADS) void perturb_apply_cells_kernel(const uint32_t* __restrict__ x, CellGeom g, int C, const int* __restrict__ rank,
+                                                                         const int* __restrict__ n_candidates, int64_t B, int64_t steps, int64_t s0, int n_steps,
+                                                                         uint32_t fill, uint32_t chunk, uint32_t chunks, uint32_t* __restrict__ out,
+                                                                         int* __restrict__ removed) {
+  extern __shared__ __attribute__((aligned(16))) int first_step[];  // C entries
+  const int64_t b = blockIdx.x / chunks;
+  const uint32_t part = blockIdx.x - (uint32_t)b * chunks;
+  const int tid = threadIdx.x;
+  const int64_t n = n_candidates[b];
+  for (int c = tid; c < C; c += PT_THREADS) {
+    const int r = rank[b * C + c];
+    int f = PC_NEVER;
+    if (r >= 0 && n > 0) {
+      const int64_t q = ((int64_t)(r + 1) * steps + n - 1) / n;  // (r+1) <= 2^14 and steps < 2^31: the product fits
+      f = q < PC_NEVER ? (int)q : PC_NEVER;
+    }
+    first_step[c] = f;
+  }
+  if (part == 0 && removed && tid < n_steps) removed[(int64_t)tid * B + b] = (int)((s0 + tid) * n / steps);
+  __syncthreads();
+  constexpr uint32_t LANE = VEC ? 4 : 1;
+  const uint32_t wq = (uint32_t)g.W / LANE;                                         // lane accesses of one row
+  const uint32_t items = (uint32_t)g.Cch * (uint32_t)g.T * (uint32_t)g.H * wq;      // ... of one clip (the launcher keeps the element count below 2^31)
+  const int64_t clip_elems = (int64_t)items * LANE;
+  const uint32_t lo = part * chunk, hi = lo + chunk < items ? lo + chunk : items;   // chunk * chunks < 2^32 (launcher)
+  const uint32_t* src = x + b * clip_elems;
+  for (uint32_t i = lo + tid; i < hi; i += PT_THREADS) {
+    const uint32_t row = i / wq, w = (i - row * wq) * LANE;
+    const uint32_t th = row % ((uint32_t)g.T * g.H);  // the channel does not matter: a cell spans them all
+    const uint32_t t = th / g.H, h = th - t * g.H;
+    const int f = first_step[((t / g.ct) * g.Gh + h / g.ch) * g.Gw + w / g.cw];
+    const int64_t off = (int64_t)i * LANE;
+    if constexpr (VEC) {
+      const uint4 v = *reinterpret_cast<const uint4*>(src + off);
+      const uint4 blank = make_uint4(fill, fill, fill, fill);
+      for (int ds = 0; ds < n_steps; ++ds)
+        *reinterpret_cast<uint4*>(out + ((int64_t)ds * B + b) * clip_elems + off) = (s0 + ds >= f) ? blank : v;
+    } else {
+      const uint32_t v = src[off];
+      for (int ds = 0; ds < n_steps; ++ds) out[((int64_t)ds * B + b) * clip_elems + off] = (s0 + ds >= f) ? fill : v;
+    }
+  }
+}
+
+// One workgroup per (clip, cell): sum of |g| over the cell and all channels in a fixed order — element e of the cell (channel-major, then
+// frame, row, column) goes to accumulator (e / PT_THREADS) % 4 of thread e % PT_THREADS; the four are added pairwise, then the wave by
+// xor-shuffles, then the four waves in order.  No atomics: the same bits on every launch.
+__global__ __launch_bounds__(PT_THREADS) void cell_pool_abs_kernel(const float* __restrict__ gr, CellGeom g, int Gt, float* __restrict__ out) {
+  __shared__ float wave_sum[PT_THREADS / 64];
+  const int C = Gt * g.Gh * g.Gw;
+  const int64_t b = blockIdx.x / C;
+  const int c = (int)(blockIdx.x - b * C);
+  const int gt = c / (g.Gh * g.Gw), gh = (c / g.Gw) % g.Gh, gw = c % g.Gw;
+  const int t0 = gt * g.ct, h0 = gh * g.ch, w0 = gw * g.cw;
+  const uint32_t nt = (uint32_t)(g.T - t0 < g.ct ? g.T - t0 : g.ct), nh = (uint32_t)(g.H - h0 < g.ch ? g.H - h0 : g.ch), nw = (uint32_t)(g.W - w0 < g.cw ? g.W - w0 : g.cw);
+  const uint32_t per_ch = nt * nh * nw, total = (uint32_t)g.Cch * per_ch;  // <= the clip's element count < 2^31
+  const float* base = gr + b * ((int64_t)g.Cch * g.T * g.H * g.W);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  uint32_t k = 0;
+  for (uint32_t e = threadIdx.x; e < total; e += PT_THREADS, k = (k + 1) & 3) {
+    const uint32_t ch = e / per_ch, r = e - ch * per_ch;
+    const uint32_t dt = r / (nh * nw), r2 = r - dt * (nh * nw);
+    const uint32_t dh = r2 / nw, dw = r2 - dh * nw;
+    const float v = fabsf(base[(((int64_t)ch * g.T + (t0 + dt)) * g.H + (h0 + dh)) * g.W + (w0 + dw)]);
+    acc[0] += k == 0 ? v : 0.f; acc[1] += k == 1 ? v : 0.f; acc[2] += k == 2 ? v : 0.f; acc[3] += k == 3 ? v : 0.f;  // adding +0 changes no bit of a non-negative sum
+  }
+  float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+}
+
+// the shared argument check of the two cell launchers: -> the grid, or an error message
+const char* cell_geometry(int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, CellGeom* g, int64_t* Gt, int64_t* C) {
+  const int64_t lim = 0x7fffffff;
+  if (B < 0 || B > lim || Cch <= 0 || T <= 0 || H <= 0 || W <= 0 || Cch > lim || T > lim || H > lim || W > lim) return "bad shape";
+  if (ct <= 0 || ch <= 0 || cw <= 0 || ct > lim || ch > lim || cw > lim) return "cell extents must be positive";
+  if (Cch > lim / T || Cch * T > lim / H || Cch * T * H > lim / W) return "a clip holds 2^31 elements or more";
+  const int64_t gt = (T + ct - 1) / ct, gh = (H + ch - 1) / ch, gw = (W + cw - 1) / cw;
+  if (gt > PT_MAX_ITEMS || gh > PT_MAX_ITEMS || gw > PT_MAX_ITEMS || gt * gh > PT_MAX_ITEMS || gt * gh * gw > PT_MAX_ITEMS) return "more cells than a clip is ranked with in LDS";
+  *g = CellGeom{(int)Cch, (int)T, (int)H, (int)W, (int)ct, (int)ch, (int)cw, (int)gh, (int)gw};
+  *Gt = gt;
+  *C = gt * gh * gw;
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -215,14 +332,14 @@ int stlt_perturb_rank(const float* scores, const uint8_t* kpm_boxes, const int64
   static StltPerDeviceOnce once;  // > 64 KB of dynamic LDS needs the attribute, per device
   bool& opted = once.flag();
   if (!opted) {
-    if (hipError_t e = hipFuncSetAttribute((const void*)perturb_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PT_MAX_ITEMS * 8); e != hipSuccess)
+    if (hipError_t e = hipFuncSetAttribute((const void*)perturb_rank_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PT_MAX_ITEMS * 8); e != hipSuccess)
       return stlt_set_error((int)e, "stlt_perturb_rank: hipFuncSetAttribute: %s", hipGetErrorString(e));
     opted = true;
   }
   hipStream_t s = (hipStream_t)stream;
   StltProfScope ps(STLT_K_MISC, s);
   stlt_prof_note("perturb_rank B=%lld T=%lld N=%lld unit=%d keys=%d", (long long)B, (long long)T, (long long)N, unit, n_pow2);
-  hipLaunchKernelGGL(perturb_rank_kernel, dim3((unsigned)B), dim3(PT_THREADS), lds, s, scores, kpm_boxes, lengths, (int)T, (int)N, unit == STLT_PERTURB_FRAME ? 1 : 0,
+  hipLaunchKernelGGL(perturb_rank_kernel<false>, dim3((unsigned)B), dim3(PT_THREADS), lds, s, scores, kpm_boxes, lengths, (int)T, (int)N, unit == STLT_PERTURB_FRAME ? 1 : 0,
                      descending, n_items, n_pow2, rank, n_candidates);
   return stlt_check_launch("perturb_rank_kernel");
 }
@@ -270,6 +387,88 @@ int stlt_perturb_curve(const float* logits, int64_t ld, const int64_t* target, i
   stlt_prof_note("perturb_curve S=%lld B=%lld K=%lld act=%d", (long long)S, (long long)B, (long long)K, activation);
   hipLaunchKernelGGL(perturb_curve_kernel, dim3((unsigned)((S * B + 3) / 4)), dim3(PT_THREADS), 0, s, logits, ld, target, S, B, (int)K, activation, prob, hit, target_out);
   return stlt_check_launch("perturb_curve_kernel");
+}
+
+int stlt_perturb_rank_cells(const float* scores, int64_t B, int64_t C, int descending, int32_t* rank, int32_t* n_candidates, stlt_stream_t stream) {
+  if (B < 0 || C <= 0 || B > 0x7fffffff) return stlt_set_error(STLT_EINVAL, "stlt_perturb_rank_cells: bad shape (B=%lld, C=%lld)", (long long)B, (long long)C);
+  if (C > PT_MAX_ITEMS)
+    return stlt_set_error(STLT_EINVAL, "stlt_perturb_rank_cells: C = %lld cells exceed the %d a clip is sorted with in LDS", (long long)C, PT_MAX_ITEMS);
+  if (descending != 0 && descending != 1) return stlt_set_error(STLT_EINVAL, "stlt_perturb_rank_cells: descending is 0 or 1, got %d", descending);
+  if (B == 0) return 0;
+  if (!scores || !rank || !n_candidates) return stlt_set_error(STLT_EINVAL, "stlt_perturb_rank_cells: null pointer");
+  int n_pow2 = 2;
+  while (n_pow2 < (int)C) n_pow2 <<= 1;
+  static StltPerDeviceOnce once;  // > 64 KB of dynamic LDS needs the attribute, per device
+  bool& opted = once.flag();
+  if (!opted) {
+    if (hipError_t e = hipFuncSetAttribute((const void*)perturb_rank_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PT_MAX_ITEMS * 8); e != hipSuccess)
+      return stlt_set_error((int)e, "stlt_perturb_rank_cells: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    opted = true;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  StltProfScope ps(STLT_K_MISC, s);
+  stlt_prof_note("perturb_rank_cells B=%lld C=%lld keys=%d", (long long)B, (long long)C, n_pow2);
+  // the cells are one "frame" of C items each: T = 1, N = C, no mask, no lengths
+  hipLaunchKernelGGL(perturb_rank_kernel<true>, dim3((unsigned)B), dim3(PT_THREADS), (size_t)n_pow2 * 8, s, scores, (const uint8_t*)nullptr, (const int64_t*)nullptr, 1, (int)C,
+                     0, descending, (int)C, n_pow2, rank, n_candidates);
+  return stlt_check_launch("perturb_rank_kernel<cells>");
+}
+
+int stlt_perturb_apply_cells(const float* x, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, const int32_t* rank,
+                             const int32_t* n_candidates, int64_t steps, int64_t s0, int64_t s1, float fill, float* out, int32_t* removed, stlt_stream_t stream) {
+  CellGeom g;
+  int64_t Gt, C;
+  if (const char* why = cell_geometry(B, Cch, T, H, W, ct, ch, cw, &g, &Gt, &C))
+    return stlt_set_error(STLT_EINVAL, "stlt_perturb_apply_cells: %s (B=%lld, x=(%lld,%lld,%lld,%lld), cells=(%lld,%lld,%lld))", why, (long long)B, (long long)Cch, (long long)T,
+                          (long long)H, (long long)W, (long long)ct, (long long)ch, (long long)cw);
+  if (steps < 1 || steps > 0x7fffffff || s0 < 0 || s1 < s0 || s1 > steps)
+    return stlt_set_error(STLT_EINVAL, "stlt_perturb_apply_cells: steps >= 1 and 0 <= s0 <= s1 <= steps (got steps=%lld, s0=%lld, s1=%lld)", (long long)steps, (long long)s0,
+                          (long long)s1);
+  const int64_t n_steps = s1 - s0 + 1;
+  if (n_steps > PT_THREADS)
+    return stlt_set_error(STLT_EINVAL, "stlt_perturb_apply_cells: %lld steps in one call (at most %d; split the range)", (long long)n_steps, PT_THREADS);
+  if (B == 0) return 0;
+  if (!x || !rank || !n_candidates || !out) return stlt_set_error(STLT_EINVAL, "stlt_perturb_apply_cells: null pointer");
+  const bool vec = W % 4 == 0 && cw % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const int64_t items = Cch * T * H * (vec ? W / 4 : W);
+  // a block re-reads the clip's C ranks, so it covers at least 4 C lane accesses; chunks * chunk >= items, below 2^32
+  int64_t chunk = (int64_t)PT_THREADS * PC_ITEMS;
+  if (chunk < 4 * C) chunk = (4 * C + PT_THREADS - 1) / PT_THREADS * PT_THREADS;
+  const int64_t chunks = (items + chunk - 1) / chunk;
+  if (chunks * B > 0x7fffffff) return stlt_set_error(STLT_EINVAL, "stlt_perturb_apply_cells: %lld workgroups in one call (at most 2^31 - 1)", (long long)(chunks * B));
+  uint32_t fill_bits;
+  memcpy(&fill_bits, &fill, 4);
+  hipStream_t s = (hipStream_t)stream;
+  StltProfScope ps(STLT_K_MISC, s);
+  stlt_prof_note("perturb_apply_cells B=%lld x=(%lld,%lld,%lld,%lld) cells=%lld steps=%lld [%lld,%lld] vec=%d", (long long)B, (long long)Cch, (long long)T, (long long)H,
+                 (long long)W, (long long)C, (long long)steps, (long long)s0, (long long)s1, (int)vec);
+  const dim3 grid((unsigned)(chunks * B)), block(PT_THREADS);
+  const size_t lds = (size_t)C * 4;
+  const uint32_t* xi = reinterpret_cast<const uint32_t*>(x);
+  uint32_t* oi = reinterpret_cast<uint32_t*>(out);
+  if (vec)
+    hipLaunchKernelGGL(perturb_apply_cells_kernel<true>, grid, block, lds, s, xi, g, (int)C, rank, n_candidates, B, steps, s0, (int)n_steps, fill_bits, (uint32_t)chunk,
+                       (uint32_t)chunks, oi, removed);
+  else
+    hipLaunchKernelGGL(perturb_apply_cells_kernel<false>, grid, block, lds, s, xi, g, (int)C, rank, n_candidates, B, steps, s0, (int)n_steps, fill_bits, (uint32_t)chunk,
+                       (uint32_t)chunks, oi, removed);
+  return stlt_check_launch("perturb_apply_cells_kernel");
+}
+
+int stlt_cell_pool_abs(const float* g, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, float* out, stlt_stream_t stream) {
+  CellGeom geom;
+  int64_t Gt, C;
+  if (const char* why = cell_geometry(B, Cch, T, H, W, ct, ch, cw, &geom, &Gt, &C))
+    return stlt_set_error(STLT_EINVAL, "stlt_cell_pool_abs: %s (B=%lld, g=(%lld,%lld,%lld,%lld), cells=(%lld,%lld,%lld))", why, (long long)B, (long long)Cch, (long long)T,
+                          (long long)H, (long long)W, (long long)ct, (long long)ch, (long long)cw);
+  if (B == 0) return 0;
+  if (B * C > 0x7fffffff) return stlt_set_error(STLT_EINVAL, "stlt_cell_pool_abs: %lld workgroups in one call (at most 2^31 - 1)", (long long)(B * C));
+  if (!g || !out) return stlt_set_error(STLT_EINVAL, "stlt_cell_pool_abs: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  StltProfScope ps(STLT_K_MISC, s);
+  stlt_prof_note("cell_pool_abs B=%lld g=(%lld,%lld,%lld,%lld) cells=%lld", (long long)B, (long long)Cch, (long long)T, (long long)H, (long long)W, (long long)C);
+  hipLaunchKernelGGL(cell_pool_abs_kernel, dim3((unsigned)(B * C)), dim3(PT_THREADS), 0, s, g, geom, (int)Gt, out);
+  return stlt_check_launch("cell_pool_abs_kernel");
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@ counters stay on the device: the reference's per-batch `.cpu()` synchronisation 
 """
 from __future__ import annotations
 
+import inspect
 import itertools
 from typing import Callable, Dict, Iterable, Optional
 
@@ -149,17 +150,68 @@ def perturb_curve(logits: torch.Tensor, target: Optional[torch.Tensor] = None, a
 _PERTURB_METHODS = ("relevance", "saliency", "attention", "random")
 
 
-def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+@torch.no_grad()
+def _appearance_cls_attention(model, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """What the CLS token of the appearance side attends to, (B,C): the fusion models' last fusion layer's appearance self-attention
+    (forward_attention: fusion_appearance_attention[-1, 0]; LCF has no fusion layer: appearance_attention[-1]); TransformerResnet — which
+    has no forward_attention — its last encoder layer's probabilities (ops.attn_probs on that layer's packed projections)."""
+    from . import _lib as L
+    from . import ops
+    if hasattr(model, "forward_attention"):
+        out = model.forward_attention(batch)
+        fa = out["fusion_appearance_attention"]
+        return (fa[-1, 0] if fa.shape[0] else out["appearance_attention"][-1])[:, 0, 1:]
+    from .modelling import fusion as F
+    H = model.config.num_attention_heads
+    x = F._appearance_embed(model, model.resnet._runner.run(model.resnet.resnet, batch["video_frames"], name="….resnet.resnet")[0])
+    layers = list(model.transformer.layers)
+    for l in layers[:-1]:
+        sa = l.self_attn
+        x = ops.AttnBlockFn.apply(x, None, None, False, H, 1e-5, 0.0, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, l.norm1.weight, l.norm1.bias)
+        x = ops.FfnBlockFn.apply(x, 1e-5, L.ACT_RELU, True, 0.0, l.linear1.weight, l.linear1.bias, l.linear2.weight, l.linear2.bias, l.norm2.weight, l.norm2.bias)
+    sa = layers[-1].self_attn
+    qkv = ops.LinearFn.apply(x.contiguous(), sa.in_proj_weight, sa.in_proj_bias)
+    kpm = torch.zeros(x.shape[0], x.shape[1], dtype=torch.uint8, device=x.device)
+    return ops.attn_probs(qkv.contiguous(), kpm, False, H)[:, 0, 1:]
+
+
+def appearance_attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator: Optional[torch.Generator] = None, head: Optional[str] = None) -> torch.Tensor:
+    """One (B,C) score per video cell (or feature column) from `method`, the appearance counterpart of attribution_scores: "relevance" —
+    forward_relevance's appearance_relevance[:, 1:]; "saliency" — |video_frames_grad| (or |appearance_features_grad|) summed over each
+    cell and all channels (stlt_cell_pool_abs); "attention" — the CLS row of the last appearance self-attention
+    (_appearance_cls_attention); "random" — uniform numbers from `generator`; or a callable (model, batch) -> scores.  `head` goes to the
+    fusion models' forward_relevance / forward_saliency.  Resnet3D has neither attention nor relevance and refuses the two."""
+    from . import collate, ops
+    if callable(method):
+        return method(model, batch)
+    kw = {} if head is None else {"head": head}
+    if method in ("relevance", "attention") and not hasattr(model, "forward_relevance"):
+        raise StltHipError(f"method {method!r}: {type(model).__name__} has no attention and no relevance; it takes 'saliency', 'random' or a callable")
+    if method == "relevance":
+        return model.forward_relevance(batch, **kw)["appearance_relevance"][:, 1:]
+    if method == "attention":
+        return _appearance_cls_attention(model, batch)
+    key, cell, grid = collate.appearance_cells({k: v for k, v in batch.items() if k != "video_frames"} if "appearance_features" in batch and hasattr(model, "forward_attention")
+                                               else batch)
+    if method == "saliency":
+        return ops.cell_pool_abs(model.forward_saliency(batch, **kw)[key + "_grad"].contiguous(), cell)
+    if method == "random":
+        return torch.rand((batch[key].shape[0], grid[0] * grid[1] * grid[2]), generator=generator, device=batch[key].device, dtype=torch.float32)
+    raise StltHipError(f"method: expected one of {_PERTURB_METHODS} or a callable (model, batch) -> scores, got {method!r}")
+
+
+def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator: Optional[torch.Generator] = None, head: Optional[str] = None) -> torch.Tensor:
     """One (B,T,N) score per object slot from `method`: "relevance" — forward_relevance's map; "saliency" — |boxes_grad| summed over the four
     coordinates, plus |scores_grad| when the batch has scores; "attention" — the last layers' raw attention joined like the relevance,
     temporal_attention[-1][b, lengths[b]-1, t] * spatial_attention[-1][b,t,0,n]; "random" — uniform numbers from `generator`; or a callable
-    (model, batch) -> scores."""
+    (model, batch) -> scores.  `head` (the fusion models): the logits the relevance and the saliency are taken from."""
     if callable(method):
         return method(model, batch)
+    kw = {} if head is None else {"head": head}
     if method == "relevance":
-        return model.forward_relevance(batch)["relevance"]
+        return model.forward_relevance(batch, **kw)["relevance"]
     if method == "saliency":
-        out = model.forward_saliency(batch)
+        out = model.forward_saliency(batch, **kw)
         s = out["boxes_grad"].abs().sum(-1)
         return s + out["scores_grad"].abs() if "scores_grad" in out else s
     if method == "attention":
@@ -177,7 +229,7 @@ def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator:
 def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], method="relevance", steps: int = 10,
                           orders=("descending", "ascending"), unit: str = "object", target: str = "top1", rank: int = 0, world: int = 1,
                           forward: Optional[Callable] = None, activation: str = "softmax", dataset_name: str = "something", seed: int = 0,
-                          device=None) -> Dict[str, object]:
+                          device=None, modality: str = "layout", head: Optional[str] = None, fill: float = 0.0) -> Dict[str, object]:
     """The perturbation test of Chefer, Gur and Wolf (2021) over an iterable of collated batches, every batch sharded over the ranks as in
     `run_inference`.  Per clip: rank the real object tokens (unit "frame": the frames, scored by the sum of their objects n >= 1) by the
     map `method` gives (attribution_scores), delete the first k of them for k rising over `steps` steps — the highest-scored first for
@@ -190,8 +242,16 @@ def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], met
     model's parameters; a model without parameters: wherever the first batch lies).  `seed` seeds the "random" method's device generator.
     -> {"fractions": [s / steps], order: {"prob": mean target probability per step, "accuracy": share of clips whose target is still the
     prediction per step, "auc_prob", "auc_accuracy": the trapezoid areas over the fractions, "num_clips"}}.  A faithful map makes the
-    descending curves fall fast (small areas) and keeps the ascending ones flat (large areas)."""
+    descending curves fall fast (small areas) and keeps the ascending ones flat (large areas).
+    `modality` "layout" (the default) is the above.  "appearance" deletes video cells — or feature columns of `appearance_features` — instead
+    (collate.perturb_cells; scores from appearance_attribution_scores, pixels set to `fill`) and serves Resnet3D, TransformerResnet and the
+    fusion models through their forward_perturbed; "both" (the fusion models) ranks each modality on its own by the same method and
+    removes the same fraction of each per step; a callable method then returns {"layout": ..., "appearance": ...}.  `head`: the logits
+    the maps and the curves are read from (the fusion models; default the last of `logit_names`).  With `forward=` the reduced batches of
+    "appearance" come from collate.perturb_cells, those of "both" from perturb_batch followed by perturb_cells on the same step."""
     from . import collate
+    if modality not in ("layout", "appearance", "both"):
+        raise StltHipError(f"modality: expected 'layout', 'appearance' or 'both', got {modality!r}")
     if target not in ("top1", "label"):
         raise StltHipError(f"target: expected 'top1' or 'label', got {target!r}")
     if not callable(method) and method not in _PERTURB_METHODS:
@@ -204,13 +264,19 @@ def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], met
         raise StltHipError(f"steps must be >= 1, got {steps}")
     if hasattr(model, "train"):
         model.train(False)
+    if forward is None:
+        params = inspect.signature(model.forward_perturbed).parameters
+        if modality != "layout" and "modality" not in params:
+            raise StltHipError(f"modality {modality!r}: {type(model).__name__}.forward_perturbed deletes layout tokens only")
+        if modality != "appearance" and "unit" not in params:
+            raise StltHipError(f"modality {modality!r}: {type(model).__name__} has the appearance side only")
     S = steps + 1
     if device is None and isinstance(model, torch.nn.Module):
         device = next((q.device for q in model.parameters()), None)
     batches = iter(batches)
     first = next(batches, None)
     if device is None:
-        device = first["categories"].device if first is not None else "cpu"
+        device = next((v.device for v in first.values() if isinstance(v, torch.Tensor)), "cpu") if first is not None else "cpu"
     device = torch.device(device)
     gen = torch.Generator(device=device).manual_seed(seed + rank) if method == "random" else None
     prob_sum = torch.zeros(len(orders), S, dtype=torch.float64, device=device)
@@ -222,16 +288,38 @@ def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], met
         B = D.batch_size(mine)
         if B == 0:
             continue
-        scores = attribution_scores(model, mine, method, gen).to(torch.float32)
-        if unit == "frame":
-            scores = scores[:, :, 1:].sum(dim=2)
+        if callable(method) and modality == "both":
+            both = method(model, mine)
+            lay, app = both["layout"].to(torch.float32), both["appearance"].to(torch.float32)
+        else:
+            lay = attribution_scores(model, mine, method, gen, head).to(torch.float32) if modality != "appearance" else None
+            app = appearance_attribution_scores(model, mine, method, gen, head).to(torch.float32) if modality != "layout" else None
+        if unit == "frame" and lay is not None:
+            lay = lay[:, :, 1:].sum(dim=2)
+        scores = {"layout": lay.contiguous(), "appearance": app.contiguous()} if modality == "both" else (lay if modality == "layout" else app).contiguous()
         tgt = mine["labels"].to(torch.int64) if target == "label" else None
         for i, order in enumerate(orders):
             if forward is None:
-                out = model.forward_perturbed(mine, scores.contiguous(), steps=steps, order=order, unit=unit, target=tgt, dataset_name=dataset_name, activation=activation)
+                kw = dict(steps=steps, order=order, target=tgt, activation=activation)
+                if "unit" in params:
+                    kw.update(unit=unit, dataset_name=dataset_name)
+                if "modality" in params:
+                    kw.update(modality=modality, fill=fill)
+                if "head" in params:
+                    kw.update(head=head)
+                out = model.forward_perturbed(mine, scores, **kw)
                 prob, hit = out["prob"], out["hit"]
             else:
-                pb = collate.perturb_batch(mine, scores, steps=steps, order=order, unit=unit, dataset_name=dataset_name)
+                pb = mine
+                if modality != "appearance":
+                    pb = collate.perturb_batch(pb, lay, steps=steps, order=order, unit=unit, dataset_name=dataset_name)
+                if modality != "layout":
+                    if modality == "both":  # step s of the layout meets step s of the appearance: the cells of each step's own clips
+                        cells = collate.perturb_cells(mine, app, steps=steps, order=order, fill=fill)
+                        key = collate.appearance_cells(mine)[0]
+                        pb = dict(pb, **{key: cells[key]})
+                    else:
+                        pb = collate.perturb_cells(pb, app, steps=steps, order=order, fill=fill)
                 logits = forward(pb)
                 prob, hit, _ = perturb_curve(logits.reshape(S, B, -1), tgt, activation)
             prob_sum[i] += prob.sum(dim=1, dtype=torch.float64)

@@ -191,6 +191,15 @@ class TransformerResnet(nn.Module):
             out["appearance_layers"] = layers
         return out
 
+    def forward_perturbed(self, batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: int = 10, order: str = "descending", modality: str = "appearance",
+                          target=None, steps_per_pass=None, fill: float = 0.0, activation: str = "softmax") -> Dict[str, torch.Tensor]:
+        """As Resnet3D.forward_perturbed: the deletion test of a per-cell map (``appearance_relevance[:, 1:]``, pooled |video_frames_grad|,
+        an attention row) on ``video_frames``; ``scores`` (B,A) lose their CLS column.  Training mode keeps the encoder's dropout live and
+        is refused."""
+        from .perturbed import forward_perturbed
+        return forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
+                                 activation=activation, dropout_live=self.training, modalities=("appearance",))
+
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
 
@@ -414,6 +423,12 @@ class CrossAttentionFusionBackbone(nn.Module):
             out.update(spatial_layers=maps["spatial_layers"], temporal_layers=maps["temporal_layers"], **layers)
         return out
 
+    def run_perturbed(self, owner: nn.Module, batch, scores, **kw):
+        """forward_perturbed of the fusion models (modelling/perturbed.py) with this backbone's answers: is dropout live, is there a trunk"""
+        from .perturbed import forward_perturbed
+        live = self.training and (self.config.hidden_dropout_prob > 0 or len(self.appearance_branch.transformer.layers) > 0)
+        return forward_perturbed(owner, batch, scores, dropout_live=live, has_trunk=getattr(self.appearance_branch, "resnet", None) is not None, **kw)
+
     def _native_args(self, batch, fusion_head, layout_head, appearance_head):
         """Marshal a batch and the parameters for the whole-path native calls (stlt_caf_forward_flags, stlt_caf_forward_attention):
         -> (stlt_caf_params, stlt_inputs, keep-alive, feature map, (B, T, N, feature channels, appearance tokens, classes))"""
@@ -531,6 +546,27 @@ class CrossAttentionFusion(nn.Module):
         appearance tokens.  Inference call, padded schedule, N, T, A <= 256: no parameter's ``.grad`` is touched, two calls give the same bits."""
         return self.caf_backbone.run_relevance(self, self.logit_names, batch, target, head, return_layers, self.classifier)
 
+    def forward_perturbed(self, batch: Dict[str, torch.Tensor], scores, steps: int = 10, order: str = "descending", modality: str = "appearance",
+                          unit: str = "object", target=None, head=None, steps_per_pass=None, fill: float = 0.0, dataset_name: str = "something",
+                          activation: str = "softmax") -> Dict[str, torch.Tensor]:
+        """The perturbation test of an attribution map on this model (Chefer, Gur, Wolf 2021), on either modality or on both.
+        modality "appearance": ``scores`` is (B,C) — one per cell of ``video_frames``, or per feature column of ``appearance_features``
+        when the batch carries those (collate.perturb_cells says what a cell is and why the feature form is the weaker test) — or (B,A)
+        token scores such as ``appearance_relevance``, whose CLS column is dropped; the cells are ranked (stlt_perturb_rank_cells), the
+        first k = floor(s * C / steps) are set to ``fill`` for s = 0 .. steps (stlt_perturb_apply_cells), the layout is untouched.
+        modality "layout": ``scores`` (B,T,N) for unit "object", (B,T) for "frame", exactly Stlt.forward_perturbed's deletion
+        (stlt_perturb_rank / stlt_perturb_apply), the video untouched.  modality "both": ``scores`` = {"layout": ..., "appearance": ...};
+        each modality is ranked on its own and step s removes the same fraction s / steps of each.  The ordinary ``forward`` runs on
+        every reduced batch (``steps_per_pass`` steps per pass; default all S = steps+1 in one pass, which equals
+        ``model(collate.perturb_cells(...))`` bit for bit), and one launch reads the curves off the logits of ``head`` (one of
+        ``logit_names``; default the last).  -> the (S,B,K) logits under every logit name, "prob" (S,B), "hit" (S,B) bool, "auc" (B,),
+        "target" (B,), "removed" (S,B) int32 and "n_candidates" (B,) — for "both": "removed_layout", "removed_appearance",
+        "n_candidates_layout", "n_candidates_appearance".  ``target``, ``dataset_name`` and ``activation`` as in Stlt.forward_perturbed.
+        ``layout_branch.skip_padding`` is honoured as ``forward`` honours it.  Inference only: refuses live dropout, CPU tensors, and
+        ``video_frames`` without ``appearance_trunk=True``."""
+        return self.caf_backbone.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
+                                          steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
+
 
 class CrossAttentionCentralNetFusion(nn.Module):
     """CACNF (models.py:501-549): ``forward(batch) -> {"stlt", "resnet3d", "caf", "ensemble"}``."""
@@ -564,6 +600,13 @@ class CrossAttentionCentralNetFusion(nn.Module):
         appearance encoder alone (every fusion map exactly 0), "caf" and "ensemble" both."""
         return self.backbone.run_relevance(self, self.logit_names, batch, target, head, return_layers, self.fusion_classifier, self.layout_classifier,
                                            self.appearance_classifier)
+
+    def forward_perturbed(self, batch: Dict[str, torch.Tensor], scores, steps: int = 10, order: str = "descending", modality: str = "appearance",
+                          unit: str = "object", target=None, head=None, steps_per_pass=None, fill: float = 0.0, dataset_name: str = "something",
+                          activation: str = "softmax") -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_perturbed with this model's four heads (``head`` default "ensemble")."""
+        return self.backbone.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
+                                          steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
 
 
 class LateConcatenationFusion(nn.Module):
@@ -624,6 +667,13 @@ class LateConcatenationFusion(nn.Module):
         """As CrossAttentionFusion.forward_relevance; LCF has no cross-modal layers, so "fusion_rollout" is the block-diagonal of the two
         branches' rollouts and the four fusion maps have a leading dimension of 0."""
         return self._runner.run_relevance(self, self.logit_names, batch, target, head, return_layers, self.classifier)
+
+    def forward_perturbed(self, batch: Dict[str, torch.Tensor], scores, steps: int = 10, order: str = "descending", modality: str = "appearance",
+                          unit: str = "object", target=None, head=None, steps_per_pass=None, fill: float = 0.0, dataset_name: str = "something",
+                          activation: str = "softmax") -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_perturbed."""
+        return self._runner.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
+                                          steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
 
 
 from .models import models_factory  # noqa: E402

@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -405,3 +405,14 @@ class Resnet3D(nn.Module):
         ``target`` as in Stlt.forward_saliency: None (each clip's top-1 class), an int64 (B,) tensor, or a float (B, num_classes) seed.
         Inference call; this model has no dropout, so there is none to refuse."""
         return video_saliency(self, batch, target, "resnet3d")
+
+    def forward_perturbed(self, batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: int = 10, order: str = "descending", modality: str = "appearance",
+                          target=None, steps_per_pass: Optional[int] = None, fill: float = 0.0, activation: str = "softmax") -> Dict[str, torch.Tensor]:
+        """The perturbation test of a per-cell map on this model, as CrossAttentionFusion.forward_perturbed with the appearance side alone
+        (``modality`` is "appearance"; this model reads no layout): the cells of ``video_frames`` — collate.perturb_cells says what a cell
+        is — are ranked by ``scores`` (B,C) (or (B,C+1), first column dropped), the first k = floor(s * C / steps) are set to ``fill`` for
+        s = 0 .. steps, and ``forward`` runs on every reduced video.  -> {"resnet3d": (S,B,K), "prob", "hit", "auc", "target", "removed",
+        "n_candidates"}."""
+        from .perturbed import forward_perturbed
+        return forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
+                                 activation=activation, modalities=("appearance",))

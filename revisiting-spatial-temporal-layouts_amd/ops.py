@@ -535,6 +535,78 @@ def perturb_curve(logits: torch.Tensor, target: Optional[torch.Tensor] = None, a
     return prob, hit.view(torch.bool), tgt
 
 
+def _cell_extents(x: torch.Tensor, cell, name: str):
+    """(B, Cch, T, H, W), (ct, ch, cw) and the grid (Gt, Gh, Gw) of a cell call on x (B,Cch,T,H,W) float32 contiguous"""
+    _chk(x, torch.float32, name)
+    if x.dim() != 5:
+        raise L.StltHipError(f"{name}: expected (B,Cch,T,H,W), got {tuple(x.shape)}")
+    try:
+        ct, ch, cw = (int(v) for v in cell)
+    except (TypeError, ValueError):
+        raise L.StltHipError(f"cell: expected three positive extents (ct, ch, cw), got {cell!r}") from None
+    if min(ct, ch, cw) < 1:
+        raise L.StltHipError(f"cell: expected three positive extents (ct, ch, cw), got {cell!r}")
+    B, Cch, T, H, W = x.shape
+    return (B, Cch, T, H, W), (ct, ch, cw), (-(-T // ct), -(-H // ch), -(-W // cw))
+
+
+def perturb_rank_cells(scores: torch.Tensor, descending: bool = True):
+    """The removal order of video cells or feature columns (include/stlt_hip.h: stlt_perturb_rank_cells): scores (B,C) float32, every cell a
+    candidate -> (rank (B,C) int32, n_candidates (B,) int32 = C).  C <= 16384."""
+    lib = L.load()
+    _chk(scores, torch.float32, "scores")
+    if scores.dim() != 2 or scores.shape[1] < 1:
+        raise L.StltHipError(f"scores: expected (B,C) with C >= 1, got {tuple(scores.shape)}")
+    B, Cn = scores.shape
+    rank = torch.empty(B, Cn, device=scores.device, dtype=torch.int32)
+    n_cand = torch.empty(B, device=scores.device, dtype=torch.int32)
+    L.check(lib.stlt_perturb_rank_cells(_p(scores), B, Cn, int(bool(descending)), _p(rank), _p(n_cand), _stream()), "stlt_perturb_rank_cells")
+    return rank, n_cand
+
+
+def perturb_apply_cells(x: torch.Tensor, cell, rank: torch.Tensor, n_candidates: torch.Tensor, steps: int, s0: int, s1: int, fill: float = 0.0,
+                        removed: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """Steps s0 .. s1 of x (B,Cch,T,H,W) with the first k cells of the removal order set to `fill` (include/stlt_hip.h:
+    stlt_perturb_apply_cells); cell = (ct, ch, cw), rank (B,C) / n_candidates (B,) from perturb_rank_cells with C the grid's cell count.
+    -> (out ((s1-s0+1)*B, Cch,T,H,W), step-major; removed (s1-s0+1, B) int32).  `out` / `removed`: write into these tensors (out may be any
+    float32 tensor of that many contiguous elements, whatever its alignment)."""
+    lib = L.load()
+    (B, Cch, T, H, W), (ct, ch, cw), grid = _cell_extents(x, cell, "x")
+    steps, s0, s1 = int(steps), int(s0), int(s1)
+    if steps < 1 or not 0 <= s0 <= s1 <= steps:
+        raise L.StltHipError(f"steps >= 1 and 0 <= s0 <= s1 <= steps, got steps={steps}, s0={s0}, s1={s1}")
+    n = s1 - s0 + 1
+    Cn = grid[0] * grid[1] * grid[2]
+    _chk(rank, torch.int32, "rank"); _chk(n_candidates, torch.int32, "n_candidates")
+    if tuple(rank.shape) != (B, Cn) or tuple(n_candidates.shape) != (B,):
+        raise L.StltHipError(f"rank is ({B},{Cn}) — the grid {grid} of cells {(ct, ch, cw)} — and n_candidates ({B},), got {tuple(rank.shape)}, {tuple(n_candidates.shape)}")
+    if out is None:
+        out = torch.empty((n * B, Cch, T, H, W), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, torch.float32, "out")
+        if out.numel() != n * x.numel():
+            raise L.StltHipError(f"out: expected {n * x.numel()} elements, got {out.numel()}")
+    if removed is None:
+        removed = torch.empty(n, B, device=x.device, dtype=torch.int32)
+    else:
+        _chk(removed, torch.int32, "removed")
+        if tuple(removed.shape) != (n, B):
+            raise L.StltHipError(f"removed: expected ({n}, {B}), got {tuple(removed.shape)}")
+    L.check(lib.stlt_perturb_apply_cells(_p(x), B, Cch, T, H, W, ct, ch, cw, _p(rank), _p(n_candidates), steps, s0, s1, float(fill), _p(out), _p(removed), _stream()),
+            "stlt_perturb_apply_cells")
+    return out, removed
+
+
+def cell_pool_abs(g: torch.Tensor, cell) -> torch.Tensor:
+    """The sum of |g| over every cell and all channels (include/stlt_hip.h: stlt_cell_pool_abs): g (B,Cch,T,H,W) float32, cell = (ct, ch, cw)
+    -> (B,C) float32, C the grid's cell count; a fixed summation order."""
+    lib = L.load()
+    (B, Cch, T, H, W), (ct, ch, cw), grid = _cell_extents(g, cell, "g")
+    out = torch.empty(B, grid[0] * grid[1] * grid[2], device=g.device, dtype=torch.float32)
+    L.check(lib.stlt_cell_pool_abs(_p(g), B, Cch, T, H, W, ct, ch, cw, _p(out), _stream()), "stlt_cell_pool_abs")
+    return out
+
+
 def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
     """Probe attention of the per-prefix forward (include/stlt_hip.h: stlt_attn_prefix_probe_fwd).  qkv_frames, qkv_probes: (S,T,3d) packed
     [q;k;v] rows of the frame and of the probe stream, kpm (S,T) bool/uint8 (True = frame masked as a key).  Probe (s,t) attends to the frame
