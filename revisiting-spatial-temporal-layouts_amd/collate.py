@@ -112,6 +112,36 @@ def _perturb_args(order: str, unit: str) -> bool:
     return order == "descending"
 
 
+def _step_range(steps, step_range=None, who: str = ""):
+    """`steps` >= 1 and the steps `step_range` = (s0, s1) asks for (default: all of 0 .. steps) -> (steps, s0, s1); `who` names the call
+    in front of the message.  Every perturbation call takes its `steps` check from here."""
+    steps = int(steps)
+    if steps < 1:
+        raise L.StltHipError(f"{who + ': ' if who else ''}steps must be >= 1, got {steps}")
+    s0, s1 = (0, steps) if step_range is None else (int(step_range[0]), int(step_range[1]))
+    if not 0 <= s0 <= s1 <= steps:
+        raise L.StltHipError(f"step_range: expected 0 <= s0 <= s1 <= steps = {steps}, got ({s0}, {s1})")
+    return steps, s0, s1
+
+
+def _tile_rest(batch, replaced, B: int, n: int) -> Dict[str, object]:
+    """Every entry of `batch` whose key is not in `replaced`, for n * B clips: per-clip entries (a tensor or a list whose leading extent is
+    B) tiled n times, num_real_tokens / num_real_frames multiplied by n, anything else as it is."""
+    out = {}
+    for key, v in batch.items():
+        if key in replaced:
+            continue
+        if key in ("num_real_tokens", "num_real_frames"):
+            out[key] = int(v) * n
+        elif isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B:
+            out[key] = v.repeat((n,) + (1,) * (v.dim() - 1))
+        elif isinstance(v, (list, tuple)) and len(v) == B:
+            out[key] = type(v)(list(v) * n)
+        else:
+            out[key] = v
+    return out
+
+
 def perturb_rank(scores: torch.Tensor, kpm_boxes: torch.Tensor, lengths: torch.Tensor, unit: str = "object", order: str = "descending"):
     """The removal order of the perturbation test (include/stlt_hip.h: stlt_perturb_rank) -> (rank int32 of scores' shape, n_candidates (B,)
     int32).  Candidates of clip b: the object slots (t, n) with t < lengths[b]-1, n >= 1 and mask False (unit "object": scores (B,T,N)), or
@@ -162,12 +192,7 @@ def perturb_batch(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: i
     clip count; num_real_tokens / num_real_frames, when present, are multiplied by the number of steps written (upper bounds, which the
     inference calls accept).  Device tensors go through stlt_perturb_rank / stlt_perturb_apply; CPU tensors take the torch form, same bits."""
     _perturb_args(order, unit)
-    steps = int(steps)
-    if steps < 1:
-        raise L.StltHipError(f"steps must be >= 1, got {steps}")
-    s0, s1 = (0, steps) if step_range is None else (int(step_range[0]), int(step_range[1]))
-    if not 0 <= s0 <= s1 <= steps:
-        raise L.StltHipError(f"step_range: expected 0 <= s0 <= s1 <= steps = {steps}, got ({s0}, {s1})")
+    steps, s0, s1 = _step_range(steps, step_range)
     empty_type = DATASETS[dataset_name]["empty"]  # frame2type["empty"] (src/modelling/configs.py:40-78)
     cats = batch["categories"]
     B, T, N = cats.shape
@@ -200,18 +225,7 @@ def perturb_batch(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: i
             new["scores"] = torch.where(gone, torch.zeros((), dtype=batch["scores"].dtype), tile(batch["scores"]))
         new = {key: v.reshape(n * B, *v.shape[2:]).contiguous() for key, v in new.items()}
         removed = k.to(torch.int32)
-    out = {}
-    for key, v in batch.items():
-        if key in new:
-            continue
-        if key in ("num_real_tokens", "num_real_frames"):
-            out[key] = int(v) * n
-        elif isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B:
-            out[key] = v.repeat((n,) + (1,) * (v.dim() - 1))
-        elif isinstance(v, (list, tuple)) and len(v) == B:
-            out[key] = type(v)(list(v) * n)
-        else:
-            out[key] = v
+    out = _tile_rest(batch, new, B, n)
     out.update(new)
     out["removed"], out["n_candidates"] = removed, n_cand
     return out
@@ -291,12 +305,7 @@ def perturb_cells(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: i
     them, is tiled as perturb_batch tiles it.  Also returned: "removed" (s1-s0+1, B) int32 and "n_candidates" (B,) int32.  Device tensors
     go through stlt_perturb_rank_cells / stlt_perturb_apply_cells; CPU tensors take the torch form, same bits."""
     _perturb_args(order, "object")
-    steps = int(steps)
-    if steps < 1:
-        raise L.StltHipError(f"steps must be >= 1, got {steps}")
-    s0, s1 = (0, steps) if step_range is None else (int(step_range[0]), int(step_range[1]))
-    if not 0 <= s0 <= s1 <= steps:
-        raise L.StltHipError(f"step_range: expected 0 <= s0 <= s1 <= steps = {steps}, got ({s0}, {s1})")
+    steps, s0, s1 = _step_range(steps, step_range)
     key, cell, grid = appearance_cells(batch)
     x = batch[key]
     B = x.shape[0]
@@ -310,17 +319,7 @@ def perturb_cells(batch: Dict[str, torch.Tensor], scores: torch.Tensor, steps: i
         mask = gone[:, :, cell_index(tuple(x.shape[2:]), cell)]  # (n, B, T, H, W)
         new = torch.where(mask[:, :, None], torch.full((), float(fill), dtype=x.dtype), x[None]).reshape(n * B, *x.shape[1:]).contiguous()
         removed = k.to(torch.int32)
-    out = {}
-    for name, v in batch.items():
-        if name == key:
-            out[name] = new
-        elif name in ("num_real_tokens", "num_real_frames"):
-            out[name] = int(v) * n
-        elif isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B:
-            out[name] = v.repeat((n,) + (1,) * (v.dim() - 1))
-        elif isinstance(v, (list, tuple)) and len(v) == B:
-            out[name] = type(v)(list(v) * n)
-        else:
-            out[name] = v
+    rest = _tile_rest(batch, (key,), B, n)
+    out = {name: new if name == key else rest[name] for name in batch}  # the batch's own key order
     out["removed"], out["n_candidates"] = removed, n_cand
     return out

@@ -7,7 +7,6 @@ counters stay on the device: the reference's per-batch `.cpu()` synchronisation 
 """
 from __future__ import annotations
 
-import inspect
 import itertools
 from typing import Callable, Dict, Iterable, Optional
 
@@ -155,7 +154,6 @@ def _appearance_cls_attention(model, batch: Dict[str, torch.Tensor]) -> torch.Te
     """What the CLS token of the appearance side attends to, (B,C): the fusion models' last fusion layer's appearance self-attention
     (forward_attention: fusion_appearance_attention[-1, 0]; LCF has no fusion layer: appearance_attention[-1]); TransformerResnet — which
     has no forward_attention — its last encoder layer's probabilities (ops.attn_probs on that layer's packed projections)."""
-    from . import _lib as L
     from . import ops
     if hasattr(model, "forward_attention"):
         out = model.forward_attention(batch)
@@ -165,10 +163,7 @@ def _appearance_cls_attention(model, batch: Dict[str, torch.Tensor]) -> torch.Te
     H = model.config.num_attention_heads
     x = F._appearance_embed(model, model.resnet._runner.run(model.resnet.resnet, batch["video_frames"], name="….resnet.resnet")[0])
     layers = list(model.transformer.layers)
-    for l in layers[:-1]:
-        sa = l.self_attn
-        x = ops.AttnBlockFn.apply(x, None, None, False, H, 1e-5, 0.0, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias, l.norm1.weight, l.norm1.bias)
-        x = ops.FfnBlockFn.apply(x, 1e-5, L.ACT_RELU, True, 0.0, l.linear1.weight, l.linear1.bias, l.linear2.weight, l.linear2.bias, l.norm2.weight, l.norm2.bias)
+    x = F._appearance_layers(model, x, H, 0.0, len(layers) - 1)
     sa = layers[-1].self_attn
     qkv = ops.LinearFn.apply(x.contiguous(), sa.in_proj_weight, sa.in_proj_bias)
     kpm = torch.zeros(x.shape[0], x.shape[1], dtype=torch.uint8, device=x.device)
@@ -237,8 +232,11 @@ def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], met
     the model's own prediction on the untouched clip —, or "label" — batch["labels"].
     `forward` defaults to `model.forward_perturbed`; with a callable (batch) -> (n, K) logits the reduced batches come from
     `collate.perturb_batch` and the curves from `perturb_curve`, which serves any model (the fusion models on precomputed features, a
-    stand-in on the CPU).  The sums stay on the device while the batches run — fp64 probability and int64 hit per step, the clip count —
-    and are all-reduced once at the end.  `device`: where the batches are moved to and the sums are kept (default: the device of the
+    stand-in on the CPU).  Which modalities `model.forward_perturbed` deletes from, and so which keywords it is called with, is the
+    model's `perturb_modalities`: ("layout",) — `unit` and `dataset_name` —, ("appearance",) — `modality` and `fill` —, or all three —
+    both sets and `head`; a model object without the attribute is taken for a layout-only one, as Stlt is (it is called with `unit` and
+    `dataset_name` and refused any other modality).  The sums stay on the device while the batches run — fp64 probability and int64 hit
+    per step, the clip count — and are all-reduced once at the end.  `device`: where the batches are moved to and the sums are kept (default: the device of the
     model's parameters; a model without parameters: wherever the first batch lies).  `seed` seeds the "random" method's device generator.
     -> {"fractions": [s / steps], order: {"prob": mean target probability per step, "accuracy": share of clips whose target is still the
     prediction per step, "auc_prob", "auc_accuracy": the trapezoid areas over the fractions, "num_clips"}}.  A faithful map makes the
@@ -259,16 +257,14 @@ def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], met
     orders = tuple(orders)
     for o in orders:
         collate._perturb_args(o, unit)
-    steps = int(steps)
-    if steps < 1:
-        raise StltHipError(f"steps must be >= 1, got {steps}")
+    steps, _, _ = collate._step_range(steps)
     if hasattr(model, "train"):
         model.train(False)
     if forward is None:
-        params = inspect.signature(model.forward_perturbed).parameters
-        if modality != "layout" and "modality" not in params:
+        sides = getattr(model, "perturb_modalities", ("layout",))
+        if modality != "layout" and "appearance" not in sides:
             raise StltHipError(f"modality {modality!r}: {type(model).__name__}.forward_perturbed deletes layout tokens only")
-        if modality != "appearance" and "unit" not in params:
+        if modality != "appearance" and "layout" not in sides:
             raise StltHipError(f"modality {modality!r}: {type(model).__name__} has the appearance side only")
     S = steps + 1
     if device is None and isinstance(model, torch.nn.Module):
@@ -301,11 +297,11 @@ def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], met
         for i, order in enumerate(orders):
             if forward is None:
                 kw = dict(steps=steps, order=order, target=tgt, activation=activation)
-                if "unit" in params:
+                if "layout" in sides:
                     kw.update(unit=unit, dataset_name=dataset_name)
-                if "modality" in params:
+                if "appearance" in sides:
                     kw.update(modality=modality, fill=fill)
-                if "head" in params:
+                if "both" in sides:
                     kw.update(head=head)
                 out = model.forward_perturbed(mine, scores, **kw)
                 prob, hit = out["prob"], out["hit"]

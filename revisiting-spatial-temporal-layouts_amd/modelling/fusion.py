@@ -30,10 +30,11 @@ from torch import nn
 
 from .. import _lib as L
 from .. import ops
+from . import explain
 from .configs import MultimodalModelConfig
 from .models import (ClassificationHead, StltBackbone, _dev_ptr, _EncoderLayerParams, _EncoderStack, _layout_requires_grad, _prep_inputs, _SelfAttnParams,
                      _Workspace)
-from .resnet3d import Resnet3D, inputs_only, saliency_seed, video_saliency
+from .resnet3d import Resnet3D, inputs_only, video_saliency
 
 
 class _AttnBlock(nn.Module):
@@ -106,9 +107,9 @@ def _appearance_embed(ab, feats):
     return torch.cat((ab.cls_token.view(1, 1, d).expand(B, -1, -1), x), dim=1) + ab.pos_embed.view(1, -1, d)
 
 
-def _appearance_layers(ab, x, H: int, p: float):
-    """the ReLU encoder layers (models.py:239-246, 267-271) on (B, S+1, d)"""
-    for l in ab.transformer.layers:  # nn.TransformerEncoderLayer defaults: ReLU, post-norm, eps 1e-5, dropout 0.1
+def _appearance_layers(ab, x, H: int, p: float, n_layers=None):
+    """the ReLU encoder layers (models.py:239-246, 267-271) on (B, S+1, d); ``n_layers``: the first so many only (default: all)"""
+    for l in list(ab.transformer.layers)[:n_layers]:  # nn.TransformerEncoderLayer defaults: ReLU, post-norm, eps 1e-5, dropout 0.1
         sa = l.self_attn
         x = ops.AttnBlockFn.apply(x, None, None, False, H, 1e-5, p, sa.in_proj_weight, sa.in_proj_bias, sa.out_proj.weight, sa.out_proj.bias,
                                   l.norm1.weight, l.norm1.bias)
@@ -146,6 +147,8 @@ class TransformerResnet(nn.Module):
         self.classifier = nn.Linear(d, config.num_classes)
         self.logit_names = ("resnet3d",)
 
+    perturb_modalities = ("appearance",)  # what forward_perturbed deletes from (infer.run_perturbation_test reads this)
+
     def forward_features(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         """(S+1, B, d), sequence-first like the reference's (models.py:271)"""
         feats = self.resnet._runner.run(self.resnet.resnet, batch["video_frames"], name="….resnet.resnet")[0]
@@ -160,20 +163,15 @@ class TransformerResnet(nn.Module):
         """As Resnet3D.forward_saliency: {"resnet3d": logits, "target", "video_frames_grad": (B, 3, T, H, W)} from the input-only sweep of
         the op-level Functions and the trunk (no weight-gradient product, no parameter's ``.grad`` touched).  Inference call: training mode
         keeps the appearance encoder's dropout live and is refused."""
-        if self.training:
-            raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        return video_saliency(self, batch, target, "resnet3d")
+        return video_saliency(self, batch, target, "resnet3d", dropout_live=self.training)
 
     def forward_relevance(self, batch: Dict[str, torch.Tensor], target=None, return_layers: bool = False) -> Dict[str, torch.Tensor]:
         """The logits and the relevance of every appearance token for one raw logit per clip (the machinery of
         CrossAttentionFusion.forward_relevance on the appearance encoder alone): {"resnet3d": logits, "target", "appearance_rollout"
         (B,A,A), "appearance_relevance" (B,A) = appearance_rollout[:, 0, :] (the classifier reads the CLS token)}, with ``return_layers``
         also "appearance_layers" (n_app,B,A,A).  The trunk runs without a tape: relevance stops at the appearance tokens."""
-        if self.training:
-            raise L.StltHipError("forward_relevance is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
         video = batch["video_frames"]
-        if not isinstance(video, torch.Tensor) or not video.is_cuda:
-            raise L.StltHipError("forward_relevance runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        explain.require_inference("forward_relevance", dropout_live=self.training, tensors=(video,))
         with torch.no_grad():
             x0 = _appearance_embed(self, self.resnet._runner.run(self.resnet.resnet, video, name="….resnet.resnet")[0])
         B, A = x0.shape[0], x0.shape[1]
@@ -183,7 +181,7 @@ class TransformerResnet(nn.Module):
             with ops.RelevanceRecorder(list(layers)):
                 x = _appearance_layers(self, leaf, self.config.num_attention_heads, 0.0)
                 logits = ops.LinearFn.apply(x[:, 0].contiguous(), self.classifier.weight, self.classifier.bias)
-            seed, target = saliency_seed(logits, target, "forward_relevance")
+            seed, target = explain.saliency_seed(logits, target, "forward_relevance")
             torch.autograd.grad(logits, leaf, seed)
         rollout = ops.attn_rollout(layers)
         out = {"resnet3d": logits.detach(), "target": target, "appearance_rollout": rollout, "appearance_relevance": rollout[:, 0, :].contiguous()}
@@ -196,9 +194,8 @@ class TransformerResnet(nn.Module):
         """As Resnet3D.forward_perturbed: the deletion test of a per-cell map (``appearance_relevance[:, 1:]``, pooled |video_frames_grad|,
         an attention row) on ``video_frames``; ``scores`` (B,A) lose their CLS column.  Training mode keeps the encoder's dropout live and
         is refused."""
-        from .perturbed import forward_perturbed
-        return forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
-                                 activation=activation, dropout_live=self.training, modalities=("appearance",))
+        return explain.forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
+                                         activation=activation, dropout_live=self.training, modalities=self.perturb_modalities)
 
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
@@ -332,17 +329,26 @@ class CrossAttentionFusionBackbone(nn.Module):
                                                ptrs[1], ptrs[2], ptrs[3], torch.cuda.current_stream().cuda_stream), "stlt_caf_forward")
         return outs
 
+    def _dropout_live(self, appearance_encoder: bool = True) -> bool:
+        """Would a forward in this mode draw a dropout mask?  Two rules stand side by side and are left as they are here.  run_saliency,
+        run_relevance and run_perturbed (``appearance_encoder=True``) count the appearance encoder's fixed 0.1 dropout (models.py:239-246)
+        next to ``hidden_dropout_prob``: any training-mode model with an appearance layer is refused.  run_attention
+        (``appearance_encoder=False``) asks about ``hidden_dropout_prob`` alone, as ``run`` does when it picks the native call: in
+        training mode with ``hidden_dropout_prob == 0`` it runs the inference kernels, which draw no mask.  Whether run_attention should
+        refuse that case too is open; changing it changes what a model refuses."""
+        return self.training and (self.config.hidden_dropout_prob > 0 or (appearance_encoder and len(self.appearance_branch.transformer.layers) > 0))
+
+    @staticmethod
+    def _named_logits(names, outs) -> Dict[str, torch.Tensor]:
+        """run()'s tuple under the model's ``logit_names``: (caf,) as it is, (caf, stlt, res, ens) as ("stlt", "resnet3d", "caf", "ensemble")"""
+        return dict(zip(names, (outs[1], outs[2], outs[0], outs[3]) if len(outs) == 4 else outs))
+
     def run_saliency(self, owner: nn.Module, names, batch: Dict[str, torch.Tensor], target, head, fusion_head, layout_head=None, appearance_head=None):
         """forward_saliency of the fusion models: run_train on private leaves of the batch's inputs — boxes, scores (when present) and
         video_frames or appearance_features — with every parameter of ``owner`` frozen (``inputs_only``), then one backward from the seeded
         head ``head`` of ``names`` to those leaves.  -> the dict forward_saliency returns."""
-        if self.training and (self.config.hidden_dropout_prob > 0 or len(self.appearance_branch.transformer.layers) > 0):
-            raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if not batch["categories"].is_cuda:
-            raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
-        head = names[-1] if head is None else head
-        if head not in names:
-            raise L.StltHipError(f"forward_saliency: head must be one of {names}, got {head!r}")
+        explain.require_inference("forward_saliency", dropout_live=self._dropout_live(), tensors=(batch["categories"],))
+        head = explain.pick_head("forward_saliency", names, head)
         app = "appearance_features" if "appearance_features" in batch else "video_frames"
         if app not in batch:
             raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))")
@@ -350,8 +356,8 @@ class CrossAttentionFusionBackbone(nn.Module):
         leaves = {k: batch[k].detach().requires_grad_(True) for k in keys}
         with inputs_only(owner), torch.enable_grad():
             outs = self.run_train(dict(batch, **leaves), fusion_head, layout_head, appearance_head)
-            logits = dict(zip(names, (outs[1], outs[2], outs[0], outs[3]) if layout_head is not None else outs))
-            seed, target = saliency_seed(logits[head], target)
+            logits = self._named_logits(names, outs)
+            seed, target = explain.saliency_seed(logits[head], target)
             grads = torch.autograd.grad(logits[head], [leaves[k] for k in keys], seed, allow_unused=True)
         out = {k: v.detach() for k, v in logits.items()}
         out["target"] = target
@@ -370,16 +376,10 @@ class CrossAttentionFusionBackbone(nn.Module):
         to the two leaves; the layout sweep (stlt_train_backward_relevance) from the layout leaf's gradient; then the appearance rollout,
         the joint rollout and the read-out.  -> the dict forward_relevance returns."""
         who = "forward_relevance"
-        if self.training and (self.config.hidden_dropout_prob > 0 or len(self.appearance_branch.transformer.layers) > 0):
-            raise L.StltHipError(f"{who} is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if not batch["categories"].is_cuda:
-            raise L.StltHipError(f"{who} runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
         lb, ab = self.layout_branch, self.appearance_branch
-        if lb.skip_padding:
-            raise L.StltHipError(f"{who} runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set layout_branch.skip_padding = False")
-        head = names[-1] if head is None else head
-        if head not in names:
-            raise L.StltHipError(f"{who}: head must be one of {names}, got {head!r}")
+        explain.require_inference(who, dropout_live=self._dropout_live(), tensors=(batch["categories"],))
+        explain.require_inference(who, skip_padding=lb.skip_padding, skip_padding_attr="layout_branch")  # this call refuses CPU tensors first
+        head = explain.pick_head(who, names, head)
         if "appearance_features" not in batch and "video_frames" not in batch:
             raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))")
         H = self.config.num_attention_heads
@@ -406,8 +406,8 @@ class CrossAttentionFusionBackbone(nn.Module):
         with inputs_only(owner), torch.enable_grad():
             with ops.RelevanceRecorder(slots):
                 outs = self._fuse_train(batch, lay_leaf, _appearance_layers(ab, app_leaf, H, 0.0), fusion_head, layout_head, appearance_head)
-            logits = dict(zip(names, (outs[1], outs[2], outs[0], outs[3]) if layout_head is not None else outs))
-            seed, target = saliency_seed(logits[head], target, who)
+            logits = self._named_logits(names, outs)
+            seed, target = explain.saliency_seed(logits[head], target, who)
             d_lay, _ = torch.autograd.grad(logits[head], [lay_leaf, app_leaf], seed, allow_unused=True)
         with torch.no_grad():
             maps = lb._train_relevance(step, torch.zeros_like(Lh) if d_lay is None else d_lay)  # (CACNF's "resnet3d" never reads the layout)
@@ -424,10 +424,8 @@ class CrossAttentionFusionBackbone(nn.Module):
         return out
 
     def run_perturbed(self, owner: nn.Module, batch, scores, **kw):
-        """forward_perturbed of the fusion models (modelling/perturbed.py) with this backbone's answers: is dropout live, is there a trunk"""
-        from .perturbed import forward_perturbed
-        live = self.training and (self.config.hidden_dropout_prob > 0 or len(self.appearance_branch.transformer.layers) > 0)
-        return forward_perturbed(owner, batch, scores, dropout_live=live, has_trunk=getattr(self.appearance_branch, "resnet", None) is not None, **kw)
+        """forward_perturbed of the fusion models (modelling/explain.py) with this backbone's answers: is dropout live, is there a trunk"""
+        return explain.forward_perturbed(owner, batch, scores, dropout_live=self._dropout_live(), has_trunk=getattr(self.appearance_branch, "resnet", None) is not None, **kw)
 
     def _native_args(self, batch, fusion_head, layout_head, appearance_head):
         """Marshal a batch and the parameters for the whole-path native calls (stlt_caf_forward_flags, stlt_caf_forward_attention):
@@ -460,12 +458,8 @@ class CrossAttentionFusionBackbone(nn.Module):
     def run_attention(self, batch: Dict[str, torch.Tensor], per_head: bool, fusion_head, layout_head=None, appearance_head=None):
         """The native forward with every attention map (include/stlt_hip.h: stlt_caf_forward_attention), beside run().
         -> (logits as run() returns them, {map name: tensor} in the order of MAP_NAMES).  Inference only, dense padded schedule."""
-        if self.training and self.config.hidden_dropout_prob > 0:
-            raise L.StltHipError("forward_attention is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if self.layout_branch.skip_padding:
-            raise L.StltHipError("forward_attention runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set layout_branch.skip_padding = False")
-        if not batch["categories"].is_cuda:
-            raise L.StltHipError("forward_attention runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        explain.require_inference("forward_attention", dropout_live=self._dropout_live(appearance_encoder=False), skip_padding=self.layout_branch.skip_padding,
+                                  skip_padding_attr="layout_branch", tensors=(batch["categories"],))
         lib = L.load()
         p, inp, keep, feats, (B, T, N, Cc, S, K) = self._native_args(batch, fusion_head, layout_head, appearance_head)
         device = feats.device
@@ -490,6 +484,8 @@ class CrossAttentionFusionBackbone(nn.Module):
 
 class CrossAttentionFusion(nn.Module):
     """CAF (models.py:486-498): ``forward(batch) -> {"caf": (B, num_classes)}``."""
+
+    perturb_modalities = explain.MODALITIES  # what forward_perturbed deletes from (infer.run_perturbation_test reads this)
 
     def __init__(self, config: MultimodalModelConfig):
         super().__init__()
@@ -571,6 +567,8 @@ class CrossAttentionFusion(nn.Module):
 class CrossAttentionCentralNetFusion(nn.Module):
     """CACNF (models.py:501-549): ``forward(batch) -> {"stlt", "resnet3d", "caf", "ensemble"}``."""
 
+    perturb_modalities = explain.MODALITIES  # what forward_perturbed deletes from (infer.run_perturbation_test reads this)
+
     def __init__(self, config: MultimodalModelConfig):
         super().__init__()
         self.config = config
@@ -581,14 +579,13 @@ class CrossAttentionCentralNetFusion(nn.Module):
         self.logit_names = ("stlt", "resnet3d", "caf", "ensemble")
 
     def forward(self, batch: Dict[str, torch.Tensor]):
-        caf, stlt, res, ens = self.backbone.run(batch, self.fusion_classifier, self.layout_classifier, self.appearance_classifier)
-        return {"stlt": stlt, "resnet3d": res, "caf": caf, "ensemble": ens}
+        return self.backbone._named_logits(self.logit_names, self.backbone.run(batch, self.fusion_classifier, self.layout_classifier, self.appearance_classifier))
 
     @torch.no_grad()
     def forward_attention(self, batch: Dict[str, torch.Tensor], per_head: bool = False) -> Dict[str, torch.Tensor]:
         """As CrossAttentionFusion.forward_attention, with this model's four logits (include/stlt_hip.h: stlt_caf_forward_attention)."""
-        (caf, stlt, res, ens), maps = self.backbone.run_attention(batch, per_head, self.fusion_classifier, self.layout_classifier, self.appearance_classifier)
-        return {"stlt": stlt, "resnet3d": res, "caf": caf, "ensemble": ens, **maps}
+        outs, maps = self.backbone.run_attention(batch, per_head, self.fusion_classifier, self.layout_classifier, self.appearance_classifier)
+        return {**self.backbone._named_logits(self.logit_names, outs), **maps}
 
     def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None, head=None) -> Dict[str, torch.Tensor]:
         """As CrossAttentionFusion.forward_saliency with this model's four heads; an input the chosen head does not read gets zeros."""
@@ -616,6 +613,8 @@ class LateConcatenationFusion(nn.Module):
     op-level training composition.  State-dict keys are the reference's (``layout_branch.*``, ``appearance_branch.*``,
     ``classifier.*``) minus ``…resnet.*``: the helper that owns the launch logic shares these modules without being
     registered as a child."""
+
+    perturb_modalities = explain.MODALITIES  # what forward_perturbed deletes from (infer.run_perturbation_test reads this)
 
     def __init__(self, config: MultimodalModelConfig):
         super().__init__()

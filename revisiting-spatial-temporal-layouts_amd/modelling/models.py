@@ -18,6 +18,7 @@ from torch import nn
 
 from .. import _lib as L
 from .. import ops
+from . import explain
 from .configs import StltModelConfig, model_configs_factory  # noqa: F401  (re-exported like the reference)
 
 _ENC_EPS = 1e-5  # nn.TransformerEncoderLayer default; config.layer_norm_eps is not forwarded (models.py:46-52,118-124)
@@ -492,6 +493,8 @@ class Stlt(nn.Module):
         self.prediction_head = ClassificationHead(config)
         self.logit_names = ("stlt",)
 
+    perturb_modalities = ("layout",)  # what forward_perturbed deletes from (infer.run_perturbation_test reads this)
+
     def _own_context(self):
         """The module's own training context (include/stlt_hip.h: stlt_ctx), made at the first autograd backward that runs outside a
         Trainer step: it owns the side stream of that sweep's weight-gradient products.  Not a parameter, not in the state dict."""
@@ -531,10 +534,7 @@ class Stlt(nn.Module):
         what `forward` returns for `collate.prefix_batch(batch, t)` — frames 0 .. t-1 of the clip followed by its own extract frame — so
         `stlt[b, lengths[b]-1]` is the ordinary forward's logits; invalid entries are 0.  Inference only, padded schedule."""
         bb = self.backbone
-        if bb._dropout_live():
-            raise L.StltHipError("forward_prefixes is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if bb.skip_padding:
-            raise L.StltHipError("forward_prefixes runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
+        explain.require_inference("forward_prefixes", dropout_live=bb._dropout_live(), skip_padding=bb.skip_padding)
         logits, = bb._whole_path("stlt_forward_prefixes", batch, self.prediction_head, ops.prefix_workspace_bytes, bb._flags(),
                                  lambda B, T, N, K, new: (new(B, T, K),))
         valid = torch.arange(logits.shape[1], device=logits.device)[None, :] < batch["lengths"].to(logits.device)[:, None]
@@ -554,39 +554,14 @@ class Stlt(nn.Module):
         `src_key_padding_mask_frames`.  Inference only, dense padded schedule: every layer runs on every row as the unfused pair, so the
         logits equal `forward`'s to fp32 rounding, not bit for bit."""
         bb = self.backbone
-        if bb._dropout_live():
-            raise L.StltHipError("forward_attention is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if bb.skip_padding:
-            raise L.StltHipError("forward_attention runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
-        if not batch["categories"].is_cuda:
-            raise L.StltHipError("forward_attention runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        explain.require_inference("forward_attention", dropout_live=bb._dropout_live(), skip_padding=bb.skip_padding, tensors=(batch["categories"],))
         H, n_sp, n_tp = self.config.num_attention_heads, self.config.num_spatial_layers, self.config.num_temporal_layers
         def maps(B, T, N, K, new):
             return (new(B, K), new((n_sp, B, T, H, N, N) if per_head else (n_sp, B, T, N, N)), new((n_tp, B, H, T, T) if per_head else (n_tp, B, T, T)))
         outs = bb._whole_path("stlt_forward_attention", batch, self.prediction_head, ops.attention_workspace_bytes, 0, maps, before=(int(bool(per_head)),))
         return dict(zip(("stlt", "spatial_attention", "temporal_attention"), outs))
 
-    def _parse_target(self, what: str, target, B: int, device):
-        """The three forms of a saliency / relevance target -> (int64 classes or None, float seed or None); both None: top-1."""
-        K = self.prediction_head.fc2.weight.shape[0]
-        if isinstance(target, torch.Tensor) and target.is_floating_point():
-            if tuple(target.shape) != (B, K) or target.device != device:
-                raise L.StltHipError(f"{what}: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
-            return None, target.detach().to(torch.float32).contiguous()
-        if target is not None:
-            if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
-                raise L.StltHipError(f"{what}: target is None, an int64 ({B},) tensor or a float ({B}, {K}) tensor on the batch's device")
-            return target.contiguous(), None
-        return None, None
-
-    def _logit_seed(self, logits: torch.Tensor, tgt, seed) -> torch.Tensor:
-        """d(objective)/d(logits) of a saliency / relevance pass: the caller's float seed, or stlt_saliency_seed's one-hot rows"""
-        if seed is None:
-            seed = torch.empty_like(logits)
-            with torch.cuda.device(logits.device):
-                L.check(L.load().stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), logits.shape[0], logits.shape[1], seed.data_ptr(),
-                                                    torch.cuda.current_stream().cuda_stream), "stlt_saliency_seed")
-        return seed
+    _logit_seed = staticmethod(explain.logit_seed)  # the seed of a saliency / relevance pass under its earlier name (tests/test_relevance_gpu.py calls it)
 
     @torch.no_grad()
     def forward_saliency(self, batch: Dict[str, torch.Tensor], target=None) -> Dict[str, torch.Tensor]:
@@ -604,14 +579,11 @@ class Stlt(nn.Module):
         skip_padding: when the batch carries num_real_tokens / num_real_frames).  Inference only: touches no parameter's .grad.  It runs
         on the backbone's one activation tape, so an autograd backward still pending from an earlier forward refuses to run afterwards."""
         bb = self.backbone
-        if bb._dropout_live():
-            raise L.StltHipError("forward_saliency is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if not batch["categories"].is_cuda:
-            raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+        explain.require_inference("forward_saliency", dropout_live=bb._dropout_live(), tensors=(batch["categories"],))
         device = batch["categories"].device
         head = self.prediction_head
         B = batch["categories"].shape[0]
-        tgt, seed = self._parse_target("forward_saliency", target, B, device)
+        tgt, seed = explain.parse_target("forward_saliency", target, B, head.fc2.weight.shape[0], device)  # a bad target is refused before the tape is overwritten
         # (dropout is off here, so the forward draws no seed; the tape is overwritten: a pending backward of an earlier forward will refuse)
         logits, step = bb._train_forward(batch, head, L.FLAG_SKIP_PADDING if bb.skip_padding else 0)
         _, T, N = step["shape"]
@@ -619,7 +591,7 @@ class Stlt(nn.Module):
         new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)  # noqa: E731
         d_boxes = new(B, T, N, 4)
         d_scores = new(B, T, N) if "scores" in batch else None
-        seed = self._logit_seed(logits, tgt, seed)
+        seed = explain.logit_seed(logits, tgt, seed)
         bb._train_backward(step, g, seed, None, d_boxes, d_scores)
         if target is None:
             target = seed.argmax(dim=1)  # the one-hot row's only 1: the class the kernel picked (lowest index on ties), still on the device
@@ -646,16 +618,11 @@ class Stlt(nn.Module):
         no parameter's .grad.  Like forward_saliency it runs on the backbone's one activation tape, so an autograd backward still pending
         from an earlier forward refuses to run afterwards."""
         bb = self.backbone
-        if bb._dropout_live():
-            raise L.StltHipError("forward_relevance is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if bb.skip_padding:
-            raise L.StltHipError("forward_relevance runs the padded schedule: skip_padding is not supported (STLT_EINVAL); set backbone.skip_padding = False")
-        if not batch["categories"].is_cuda:
-            raise L.StltHipError("forward_relevance runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
-        device = batch["categories"].device
-        tgt, seed = self._parse_target("forward_relevance", target, batch["categories"].shape[0], device)
+        explain.require_inference("forward_relevance", dropout_live=bb._dropout_live(), skip_padding=bb.skip_padding, tensors=(batch["categories"],))
+        cats = batch["categories"]
+        tgt, seed = explain.parse_target("forward_relevance", target, cats.shape[0], self.prediction_head.fc2.weight.shape[0], cats.device)
         logits, step = bb._train_forward(batch, self.prediction_head, 0)
-        seed = self._logit_seed(logits, tgt, seed)
+        seed = explain.logit_seed(logits, tgt, seed)
         maps = bb._train_relevance(step, seed)
         if target is None:
             target = seed.argmax(dim=1)
@@ -682,44 +649,23 @@ class Stlt(nn.Module):
         and off; num_real_tokens / num_real_frames of the batch are carried as upper bounds (no read-back).  `dataset_name` names the frame
         type "empty"; activation "sigmoid" (Action Genome's multi-label head) makes prob the target's sigmoid and hit "its logit is positive".
         Inference only: refuses live dropout and CPU tensors, as forward_saliency does."""
-        from .. import collate
-        bb = self.backbone
-        if bb._dropout_live():
-            raise L.StltHipError("forward_perturbed is an inference call: the model is in training mode with dropout > 0 (call model.train(False))")
-        if not batch["categories"].is_cuda or not (isinstance(scores, torch.Tensor) and scores.is_cuda):
-            raise L.StltHipError("forward_perturbed runs on the GPU: the batch or the scores hold CPU tensors (move the model and the batch to a cuda device)")
-        descending = collate._perturb_args(order, unit)
-        steps = int(steps)
-        if steps < 1:
-            raise L.StltHipError(f"forward_perturbed: steps must be >= 1, got {steps}")
-        S = steps + 1
-        per = S if steps_per_pass is None else int(steps_per_pass)
-        if per < 1:
-            raise L.StltHipError(f"forward_perturbed: steps_per_pass must be >= 1, got {steps_per_pass}")
-        device = batch["categories"].device
-        B = batch["categories"].shape[0]
-        if target is not None and (not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device):
-            raise L.StltHipError(f"forward_perturbed: target is None or an int64 ({B},) tensor on the batch's device")
-        head = self.prediction_head
+        bb, head = self.backbone, self.prediction_head
+        # this call refuses CPU tensors ahead of its argument checks (the shared routine: behind them), and scores that are not float32 and
+        # contiguous, as ops.perturb_rank does (the shared routine converts what the fusion models are handed): both stay as they were
+        explain.require_inference("forward_perturbed", dropout_live=bb._dropout_live(), tensors=(batch["categories"], scores), holder="the batch or the scores hold")
+        scores = ops._chk(scores, torch.float32, "scores")
         K = head.fc2.weight.shape[0]
-        core = {k: batch[k].contiguous() for k, _, _ in ops.PERTURB_KEYS if k in batch}
-        counts = {k: batch[k] for k in ("num_real_tokens", "num_real_frames") if k in batch}
-        if any(isinstance(v, torch.Tensor) and v.is_cuda for v in counts.values()):
-            raise L.StltHipError("num_real_tokens / num_real_frames must be host integers (a device tensor would have to be read back, which is what they are there to avoid)")
-        counts = {k: int(v) for k, v in counts.items()}
-        rank, n_cand = ops.perturb_rank(scores, core["src_key_padding_mask_boxes"], core["lengths"], unit, descending)
-        logits = torch.empty(S, B, K, device=device, dtype=torch.float32)
-        removed = torch.empty(S, B, device=device, dtype=torch.int32)
-        empty_type = collate.DATASETS[dataset_name]["empty"]
-        for s0 in range(0, S, per):
-            s1 = min(s0 + per, S) - 1
-            part = ops.perturb_apply(core, rank, n_cand, steps, s0, s1, empty_type, removed=removed)
-            part.pop("removed")
-            part.update({k: v * (s1 - s0 + 1) for k, v in counts.items()})
-            bb._whole_path("stlt_forward", part, head, ops.workspace_bytes, bb._flags(), lambda *a, s0=s0, s1=s1: (logits[s0:s1 + 1].view(-1, K),), before=(None,))
-        prob, hit, tgt = ops.perturb_curve(logits, target, activation)
-        auc = (prob.sum(0) - 0.5 * (prob[0] + prob[-1])) / steps
-        return {"stlt": logits, "prob": prob, "hit": hit, "auc": auc, "target": tgt, "removed": removed, "n_candidates": n_cand}
+
+        def run_pass(part, s0, s1, logits):
+            """stlt_forward writes the pass's logits straight into rows s0 .. s1 of the (S,B,K) result: no copy launch"""
+            if logits is None:
+                logits = {"stlt": torch.empty(int(steps) + 1, batch["categories"].shape[0], K, device=batch["categories"].device, dtype=torch.float32)}
+            bb._whole_path("stlt_forward", part, head, ops.workspace_bytes, bb._flags(), lambda *a: (logits["stlt"][s0:s1 + 1].view(-1, K),), before=(None,))
+            return logits
+
+        return explain.forward_perturbed(self, batch, scores, steps=steps, order=order, modality="layout", unit=unit, target=target,
+                                         steps_per_pass=steps_per_pass, dataset_name=dataset_name, activation=activation, modalities=self.perturb_modalities,
+                                         run_pass=run_pass)
 
 
 class _StltTrainFn(torch.autograd.Function):

@@ -31,6 +31,7 @@ from torch import nn
 
 from .. import _lib as L
 from .. import ops
+from . import explain
 from .models import _dev_ptr, _Workspace
 
 BLOCKS = (3, 4, 6, 3)
@@ -308,38 +309,15 @@ def inputs_only(module: nn.Module):
             q.requires_grad_(r)
 
 
-def saliency_seed(logits: torch.Tensor, target, who: str = "forward_saliency"):
-    """``target`` of a forward_saliency call (None: top-1; int64 (B,): that class; float (B, K): the seed itself) -> (seed (B, K), target as
-    returned), by stlt_saliency_seed, as Stlt.forward_saliency forms them."""
-    B, K = logits.shape
-    device = logits.device
-    if isinstance(target, torch.Tensor) and target.is_floating_point():
-        if tuple(target.shape) != (B, K) or target.device != device:
-            raise L.StltHipError(f"{who}: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
-        return target.detach().to(torch.float32).contiguous(), target
-    tgt = None
-    if target is not None:
-        if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or tuple(target.shape) != (B,) or target.device != device:
-            raise L.StltHipError(f"{who}: target is None, an int64 ({B},) tensor or a float ({B}, {K}) tensor on the batch's device")
-        tgt = target.contiguous()
-    seed = torch.empty(B, K, device=device, dtype=torch.float32)
-    logits = logits.detach().contiguous()
-    with torch.cuda.device(device):
-        L.check(L.load().stlt_saliency_seed(logits.data_ptr(), None if tgt is None else tgt.data_ptr(), B, K, seed.data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream), "stlt_saliency_seed")
-    return seed, (seed.argmax(dim=1) if target is None else target)
-
-
-def video_saliency(model: nn.Module, batch: Dict[str, torch.Tensor], target, name: str) -> Dict[str, torch.Tensor]:
+def video_saliency(model: nn.Module, batch: Dict[str, torch.Tensor], target, name: str, dropout_live: bool = False) -> Dict[str, torch.Tensor]:
     """forward_saliency of a video-only model: its forward on a private leaf of ``video_frames`` with every parameter frozen
-    (``inputs_only``), the seed, and the input-only sweep."""
+    (``inputs_only``), the seed, and the input-only sweep.  ``dropout_live``: the model's own answer."""
     video = batch["video_frames"]
-    if not isinstance(video, torch.Tensor) or not video.is_cuda:
-        raise L.StltHipError("forward_saliency runs on the GPU: the batch holds CPU tensors (move the model and the batch to a cuda device)")
+    explain.require_inference("forward_saliency", dropout_live=dropout_live, tensors=(video,))
     leaf = video.detach().requires_grad_(True)
     with inputs_only(model), torch.enable_grad():
         logits = model.forward(dict(batch, video_frames=leaf))[name]
-        seed, target = saliency_seed(logits, target)
+        seed, target = explain.saliency_seed(logits, target)
         (dvideo,) = torch.autograd.grad(logits, leaf, seed)
     return {name: logits.detach(), "target": target, "video_frames_grad": dvideo}
 
@@ -371,6 +349,8 @@ class Resnet3D(nn.Module):
         self.trunk_name = "resnet"
         self.train_trunk = bool(getattr(config, "train_trunk", False))
         object.__setattr__(self, "_runner", TrunkRunner(self.train_trunk))
+
+    perturb_modalities = ("appearance",)  # what forward_perturbed deletes from (infer.run_perturbation_test reads this)
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -413,6 +393,5 @@ class Resnet3D(nn.Module):
         is — are ranked by ``scores`` (B,C) (or (B,C+1), first column dropped), the first k = floor(s * C / steps) are set to ``fill`` for
         s = 0 .. steps, and ``forward`` runs on every reduced video.  -> {"resnet3d": (S,B,K), "prob", "hit", "auc", "target", "removed",
         "n_candidates"}."""
-        from .perturbed import forward_perturbed
-        return forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
-                                 activation=activation, modalities=("appearance",))
+        return explain.forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
+                                         activation=activation, modalities=self.perturb_modalities)  # no dropout in this model: never live
