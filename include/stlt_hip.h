@@ -479,7 +479,7 @@ int stlt_attn_probs_fwd(const float* qkv, const uint8_t* kpm, int causal, int64_
  * requires Lq == Lk.  Masked entries are written as exactly 0, a query row whose keys are all masked as zeros, every element of probs is
  * written; query rows are not filtered by any mask.  The head average is summed head by head in registers in a fixed order (no atomics):
  * the same bits on every run.
- * 1 <= Lq, Lk <= 1024, 1 <= dh <= 256.  dh == 64 with Lk <= 64 (any Lq) runs on the MFMA kernel of csrc/attn_probs_cross.hip and needs q
+ * 1 <= Lq, Lk <= 1024, 1 <= dh <= 256.  dh == 64 with Lk <= 64 (any Lq) runs on the MFMA kernel of csrc/attn_probs.hip and needs q
  * and k 16-byte aligned and ldq, ldk multiples of 4 (refused otherwise); everything else on its vector-ALU kernel, pointers and strides
  * 4 bytes.  probs 4 bytes; kpm bytes.  Every bad argument is STLT_EINVAL and launches nothing. */
 int stlt_attn_probs_cross_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const uint8_t* kpm, int causal, int64_t S, int64_t Lq,
@@ -840,7 +840,7 @@ int stlt_train_backward_relevance(const stlt_params* p, const stlt_inputs* in, c
  * per_head == 1: the same masks (kpm: (S*Lk) bytes over the key tokens, never NULL; causal requires Lq == Lk), a masked entry exactly 0, a
  * fully masked row zeros.  Every element of abar is written; the heads are summed in their order in registers: the same bits on every run.
  * 1 <= Lq, Lk <= 256, 1 <= dh <= 256 (the domain of stlt_attn_bwd).  dh == 64 with Lk <= 64 (any Lq: every fusion block of the reference's
- * shapes) runs on the MFMA kernel of csrc/attn_grad_probs_cross.hip and needs q, k, v and dctx 16-byte aligned and ldq, ldkv multiples of 4
+ * shapes) runs on the MFMA kernel of csrc/attn_grad_probs.hip and needs q, k, v and dctx 16-byte aligned and ldq, ldkv multiples of 4
  * (refused otherwise); everything else on its vector-ALU kernel, pointers and strides 4 bytes.  abar 4 bytes; kpm bytes.  Routed by what was
  * measured (profiles/fusion_relevance_bench.md): an MFMA shape with more than 32 keys and fewer than 128 work units, S * ceil(Lq / 16), also
  * runs on the vector-ALU kernel — the same contract and refusals, results equal to fp32 rounding.

@@ -1,4 +1,4 @@
-// Small device helpers of the vector-ALU attention kernels (attn_any.hip, attn_probs.hip's generic path): one wave per query row,
+// Small device helpers of the vector-ALU attention kernels (attn_any.hip, the generic paths of attn_probs.hip and attn_grad_probs.hip): one wave per query row,
 // the query broadcast from LDS.  The wave-wide sum beside wave_max is common.h's wave_sum.
 #pragma once
 #include "common.h"

@@ -376,18 +376,18 @@ int launch_prefix_zero_invalid(float* logits, const int64_t* lengths, int64_t B,
 // probs (S,L,L) averaged over the heads, or (S,H,L,L) with per_head; MFMA kernel for dh == 64 and L <= 64, vector ALU otherwise
 int launch_attn_probs(const float* qkv, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh, int per_head, float* probs,
                       hipStream_t s);
-// attn_probs_cross.hip: the same for queries and keys in different buffers (include/stlt_hip.h: stlt_attn_probs_cross_fwd) — launch_attn_general's
+// attn_probs.hip: the same for queries and keys in different buffers (include/stlt_hip.h: stlt_attn_probs_cross_fwd) — launch_attn_general's
 // probabilities: q rows ldq floats apart, k rows ldk floats apart, kpm (S*Lk) over the keys; probs (S,Lq,Lk), or (S,H,Lq,Lk) with per_head
 int launch_attn_probs_cross(const float* q, int64_t ldq, const float* k, int64_t ldk, const uint8_t* kpm, int causal, int64_t S, int64_t Lq,
                             int64_t Lk, int64_t H, int64_t dh, int per_head, float* probs, hipStream_t s);
-// attn_grad_probs.hip: attention relevance (include/stlt_hip.h: stlt_attn_grad_probs, stlt_attn_rollout, stlt_relevance_combine) — the head-averaged
+// attn_grad_probs.hip, attn_rollout.hip: attention relevance (include/stlt_hip.h: stlt_attn_grad_probs, stlt_attn_rollout, stlt_relevance_combine) — the head-averaged
 // positive part of probabilities x their gradient from a layer's packed QKV and dctx (L, dh <= 256), the rollout R_l = R_{l-1} + abar_l·R_{l-1}
 // of (n_layers,S,L,L) maps into R (S,L,L) in one launch, and rel[b,t,n] = R_temporal[b,lengths[b]-1,t] * R_spatial[b,t,0,n]
 int launch_attn_grad_probs(const float* qkv, const float* dctx, const uint8_t* kpm, int causal, int64_t S, int64_t L, int64_t H, int64_t dh, float* abar,
                            hipStream_t s);
 int launch_attn_rollout(const float* abar, int64_t n_layers, int64_t S, int64_t L, float* R, hipStream_t s);
 int launch_relevance_combine(const float* r_temporal, const float* r_spatial, const int64_t* lengths, int64_t B, int64_t T, int64_t N, float* rel, hipStream_t s);
-// attn_grad_probs_cross.hip: the same across two token sets (include/stlt_hip.h: stlt_attn_grad_probs_cross, stlt_attn_rollout_joint,
+// attn_grad_probs.hip, attn_rollout.hip: the same across two token sets (include/stlt_hip.h: stlt_attn_grad_probs_cross, stlt_attn_rollout_joint,
 // stlt_relevance_combine_joint) — the map of a block whose queries (ldq) and keys / values (ldkv) lie in different buffers, abar (S,Lq,Lk); the rollout
 // over the J = T + A stacked tokens of the fusion layers' four kinds of maps into R (S,J,J) in one launch; the read-out of the rows the heads read
 int launch_attn_grad_probs_cross(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const float* dctx, const uint8_t* kpm, int causal,

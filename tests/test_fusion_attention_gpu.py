@@ -83,19 +83,32 @@ def test_attn_probs_cross_vs_fp64(pkg, H, dh, Lq, Lk, causal):
     assert (out[False] - out[True].mean(dim=1)).abs().max().item() <= 1e-6
 
 
-@pytest.mark.parametrize("causal", [False, True])
-@pytest.mark.parametrize("L", [7, 33, 65])
-def test_attn_probs_cross_on_one_packed_buffer_is_attn_probs(pkg, L, causal):
-    """q and k as views of one packed QKV buffer, Lq == Lk: within 1e-6 of ops.attn_probs (the packed DIAG / FULL / generic kernels)."""
-    S, H, dh = 5, 4, 64
+# (L, dh): 17 = two key blocks, the 17th row alone in its block; 65 = generic, the second key of a lane; dh 20 = generic, scalar reads
+PACKED_VIEWS = [(7, 64), (16, 64), (17, 64), (33, 64), (64, 64), (65, 64), (33, 20)]
+
+
+@pytest.mark.parametrize("L,dh,causal", [(L, dh, c) for c in (False, True) for L, dh in PACKED_VIEWS],
+                         ids=[f"{L}{'' if dh == 64 else f'dh{dh}'}-{c}" for c in (False, True) for L, dh in PACKED_VIEWS])
+def test_attn_probs_cross_on_one_packed_buffer_is_attn_probs(pkg, L, dh, causal):
+    """q and k as views of one packed QKV buffer, Lq == Lk, against ops.attn_probs.  Above 16 tokens both entries run the same kernel on
+    the same views (the sided MFMA kernel up to 64 tokens at head dim 64, the vector kernel elsewhere): equal bit for bit, S = 3 with
+    some keys masked and the last sequence's keys all masked.  Up to 16 tokens the packed entry runs the diag form (several sequences to
+    a 16-row block, S = 5 leaves the last block partial) against one sided block: within 1e-6."""
+    same_kernel = L > 16
+    S, H = (3 if same_kernel else 5), 4
     d = H * dh
     qkv = _rand(S, L, 3 * d, seed=L, scale=1.5).to(DEV)
     kpm = (torch.rand(S, L, generator=torch.Generator().manual_seed(L)) < 0.3)
     kpm[:, 0] = False
+    if same_kernel:
+        kpm[S - 1, :] = True
     for per_head in (False, True):
         a = pkg.ops.attn_probs_cross(qkv[..., :d], qkv[..., d:2 * d], kpm.to(DEV), causal, H, per_head=per_head)
         b = pkg.ops.attn_probs(qkv, kpm.to(DEV), causal, H, per_head=per_head)
-        assert (a - b).abs().max().item() <= 1e-6
+        if same_kernel:
+            assert torch.equal(a, b) and (a[S - 1] == 0).all() and a[0].abs().max().item() > 0
+        else:
+            assert (a - b).abs().max().item() <= 1e-6
 
 
 @pytest.mark.parametrize("Lq,Lk", [(7, 40), (40, 7)])

@@ -114,12 +114,20 @@ def test_attn_grad_probs_cross_vs_fp64_inside_guard_bands(pkg, arena, Lq, Lk, ca
     _report(f"attn_grad_probs_cross Lq={Lq} Lk={Lk} H={H} dh={dh} causal={causal} worst err / max|ref|", f"{worst:.2e}")
 
 
-@pytest.mark.parametrize("causal", [False, True])
-@pytest.mark.parametrize("H,dh", [(2, 64), (3, 16), (2, 20)])
-@pytest.mark.parametrize("L", [7, 16, 33, 65])
-def test_cross_kernel_on_a_packed_buffer_agrees_with_attn_grad_probs(pkg, L, H, dh, causal):
-    """q = qkv, k = qkv + d, v = qkv + 2d, ld = 3d: stlt_attn_grad_probs' result within OP_CAP (and the fp64 formula's)"""
-    S, d = 4, H * dh
+# (S, L, H, dh, causal, same kernel).  S = 4: the two launchers run different kernels (diag against one sided block; the packed vector kernel
+# against the cross one — at L = 33 and head dim 64 too, where 12 units over three key blocks send the cross launcher to its vector kernel).
+# Head dim 64, 17 ... 64 tokens and enough units: both run the sided MFMA kernel on the same views — 3 x 17 (two key blocks, the 17th row alone
+# in its block), 43 x 33 (129 units, one above GX_MIN_UNITS at three key blocks), 32 x 64 (128 units at four key blocks).
+PACKED_VIEWS = ([(4, L, H, dh, c, False) for c in (False, True) for H, dh in ((2, 64), (3, 16), (2, 20)) for L in (7, 16, 33, 65)]
+                + [(S, L, 2, 64, c, True) for c in (False, True) for S, L in ((3, 17), (43, 33), (32, 64))])
+
+
+@pytest.mark.parametrize("S,L,H,dh,causal,same_kernel", PACKED_VIEWS,
+                         ids=[f"{f'{S}x' if same else ''}{L}-{H}-{dh}-{c}" for S, L, H, dh, c, same in PACKED_VIEWS])
+def test_cross_kernel_on_a_packed_buffer_agrees_with_attn_grad_probs(pkg, S, L, H, dh, causal, same_kernel):
+    """q = qkv, k = qkv + d, v = qkv + 2d, ld = 3d: stlt_attn_grad_probs' result within OP_CAP (and the fp64 formula's) — bit for bit where
+    both launchers run the same kernel"""
+    d = H * dh
     qkv, dctx = GA.rand(S, L, 3 * d, seed=L + dh).to(DEV), GA.rand(S, L, d, seed=L + dh + 1).to(DEV)
     kpm = torch.rand(S, L, generator=torch.Generator().manual_seed(L)) < 0.3
     kpm[:, 0] = False
@@ -129,6 +137,8 @@ def test_cross_kernel_on_a_packed_buffer_agrees_with_attn_grad_probs(pkg, L, H, 
     e = (_rel(got, want.cpu().double()), _rel(got, ref))
     _report(f"cross vs packed kernel L={L} H={H} dh={dh} causal={causal}: vs packed, vs fp64", f"{e[0]:.2e}, {e[1]:.2e}")
     assert max(e) <= OP_CAP
+    if same_kernel:
+        assert torch.equal(got, want)
 
 
 def test_attn_grad_probs_cross_refusals_leave_the_output_untouched(pkg, arena):

@@ -3,7 +3,7 @@
 per case.
 
   --build   (no GPU needed) build the A/B variant of the library whose cross-probabilities launcher sends every shape to the vector-ALU
-            kernel (csrc/attn_probs_cross.hip with -DSTLT_PROBS_CROSS_NO_MFMA) into build/variants/; run it before the measurement.
+            kernel (csrc/attn_probs.hip with -DSTLT_PROBS_CROSS_NO_MFMA) into build/variants/; run it before the measurement.
 
 1. The cross-probabilities launch (stlt_attn_probs_cross_fwd, ops.attn_probs_cross) against the cross-attention core (stlt_attn_cross_fwd,
    ops.attn_cross) on the same buffers — queries (S,Lq,d), packed keys / values (S,Lk,2d), 12 heads of 64 channels, about 30 % of the
@@ -65,7 +65,7 @@ def main():
     a = ap.parse_args()
     if a.build:
         builder = importlib.import_module(PKG + ".build")
-        print(builder.variant("probs_cross_generic", {"attn_probs_cross.hip": ["-DSTLT_PROBS_CROSS_NO_MFMA=1"]}))
+        print(builder.variant("probs_cross_generic", {"attn_probs.hip": ["-DSTLT_PROBS_CROSS_NO_MFMA=1"]}))
         return
     import torch
     if not torch.cuda.is_available():

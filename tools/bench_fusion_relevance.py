@@ -3,7 +3,7 @@
 line per case.
 
   --build   (no GPU needed) build the two A/B variants of the library into build/variants/: the cross grad-probs launcher sending every
-            shape to the vector-ALU kernel (csrc/attn_grad_probs_cross.hip with -DSTLT_GRAD_PROBS_CROSS_NO_MFMA), and sending every MFMA
+            shape to the vector-ALU kernel (csrc/attn_grad_probs.hip with -DSTLT_GRAD_PROBS_CROSS_NO_MFMA), and sending every MFMA
             shape to the MFMA kernel however few its work units (-DSTLT_GRAD_PROBS_CROSS_ALL_MFMA); run it before the measurement.
 
 1. part "kernel": the cross grad-probs launch (stlt_attn_grad_probs_cross) against the cross-attention backward (stlt_attn_bwd) on the same
@@ -92,7 +92,7 @@ def main():
     if a.build:
         builder = importlib.import_module(PKG + ".build")
         for tag, flag in VARIANTS.values():
-            print(builder.variant(tag, {"attn_grad_probs_cross.hip": [flag]}))
+            print(builder.variant(tag, {"attn_grad_probs.hip": [flag]}))
         return
     import torch
     if not torch.cuda.is_available():
