@@ -97,7 +97,9 @@ int stlt_embed_fwd(const int64_t* categories, const float* boxes, const float* s
  * M, N arbitrary.  K % 32 == 0 (every hidden size the released checkpoints use): f32-input MFMA (v_mfma_f32_32x32x2_f32), fp32
  * accumulate.  Any other K (hidden sizes like 100 or 200, which configs.py:92-111 allows): the same product and epilogues on
  * csrc/gemm_any.hip (zero-filled tiles staged through LDS by ordinary loads) — a compatibility path with the same tolerances, not a
- * tuned one.
+ * tuned one.  On every route (whole tiles, small tiles, stream-K, the split-k pair for a few rows, the compatibility path, the
+ * opt-in split-bf16 build) the sum over k starts from zero and the bias is added once to the finished sum, ahead of the activation:
+ * an output that is mostly bias keeps fp32 error at its own scale (tests/test_product_scale_gpu.py, profiles/product_scale.md).
  * Alignment: none beyond 4 bytes.  x or w off a 16-byte boundary, or ldx % 4 != 0, is routed to that compatibility path (four-byte
  * loads); y off a 16-byte boundary or ldy % 4 != 0 takes guarded scalar stores; bias is read one float at a time.  Gap columns
  * K .. ldx-1 of x are not read, N .. ldy-1 of y not written. */

@@ -378,7 +378,7 @@ static int ws_carve(const stlt_params* p, const stlt_inputs* in, int64_t min_slo
 }
 
 // The residual adds of a post-norm layer ride in the out-proj / FFN2 epilogues and the LayerNorm passes read one tensor
-// instead of two (bit-identical logits: the accumulators start from the bias, the residual is added last).  Round 2 measured
+// instead of two (bit-identical logits: the bias joins the finished sum, the residual is added last).  Round 2 measured
 // it a wash (the residual tile was read inside the exposed epilogue: LayerNorm 3.06 -> 2.00 ms, GEMMs +1.0 ms); with the
 // first half of a tile's residual pieces requested during the tile's last k-step (gemm.hip: RES_PF) the GEMMs
 // pay 0.4 ms and the forward gains 0.5 ms at cfg2 / 1024 clips (profiles/round3_fwd_residual_ab.txt).  STLT_FUSE_RESIDUAL=0

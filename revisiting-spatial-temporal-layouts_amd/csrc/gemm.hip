@@ -24,8 +24,9 @@
 //     output row and its 16 accumulator registers are 4 groups of 4 CONSECUTIVE output columns, so the epilogue is
 //     16-byte stores (16 per wave and tile instead of 64 scalar ones: the store tail is issue-bound, it cost 4 % at
 //     K = 768); products and summation order are unchanged, results are bit-identical to the untransposed form;
-//   * the bias is the accumulators' initial value, fetched one tile ahead (read from its LDS strip straight into
-//     the accumulator registers when a tile's epilogue re-initialises them).
+//   * the accumulators start from zero; the bias, fetched one tile ahead into an LDS strip, is added once after the tile's last
+//     k-step, ahead of the activation / add-source (as the stream-K fix-up adds it: started from the bias, all K / 2 additions of
+//     an element would round at the bias's magnitude, which an output that is mostly bias shows: profiles/product_scale.md).
 //
 // Wave specialisation (every launch, stream-K and grouped ones included): waves 8..11, one per SIMD, do nothing
 // but issue the LDS-DMA, and the eight MFMA waves issue none.  The CU's
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void gemm_nt_kernel(const float* _
   if constexpr (ACT == STLT_ACT_GELU_BWD) epi = epi_in;
   static_assert(!GROUP || SK, "grouped launches are stream-K launches");
   static_assert(ACT != STLT_ACT_GELU_BWD || (ADD && !GROUP), "the fused GELU backward reads u through the add-source");
-  constexpr int NBIAS = 2;  // bias strips, by tile parity
+  constexpr int NBIAS = 3;  // bias strips, by tile index mod 3: see dma_bias
   __shared__ __attribute__((aligned(16))) float smem[NSTAGE * STAGE_FLOATS + NBIAS * BN];  // operand stages + bias strips
 
   const int tid = threadIdx.x;
@@ -370,18 +371,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void gemm_nt_kernel(const float* _
     return f;
   };
 
-  // The bias is the accumulators' initial value (one column per lane: n is fixed per lane and N-tile), so the
-  // epilogue adds nothing.  The next tile's two bias values are fetched during the current tile's last k-step
-  // It travels like the operands: wave 0 DMAs the tile's 128 bias values into a small LDS strip (double
-  // buffered by tile parity) at the start of the previous tile's last k-step; that step's counted wait + barrier
-  // publish it, and every wave then reads its two columns with ordinary ds_reads.  (A VGPR-destination load here
-  // would make hipcc drain the DMA in flight with a vmcnt(0) at its first use.)
+  // The bias is added to the finished sums in the tile's epilogue (the accumulators start from zero).  It travels like the
+  // operands: the first loader wave DMAs the tile's 128 bias values into a small LDS strip at the start of the previous tile's
+  // last k-step; that step's counted wait + barrier publish it, and every wave reads its columns with ordinary ds_reads in the
+  // tile's epilogue.  (A VGPR-destination load here would make hipcc drain the DMA in flight with a vmcnt(0) at its first use.)
+  // Three strips, by tile index mod 3: the strip of tile t is read between the barrier of t's last k-step and the next one, and
+  // rewritten for tile t + 3 during the last k-step of t + 2, at least two barriers later (every tile has at least one k-step).
   float* bias_lds = smem + NSTAGE * STAGE_FLOATS;
   auto dma_bias = [&](int it) {
     if (bias && wave == GEMM_WAVES) {
       int m0, n0, split;
       tile_origin(it, m0, n0, split);
-      float* dst = bias_lds + (it & 1) * BN;
+      float* dst = bias_lds + (it % NBIAS) * BN;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         int n = n0 + i * 64 + lane;
@@ -433,25 +434,28 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void gemm_nt_kernel(const float* _
   // accumulator (a, b), register r of lane (lr, lh) holds output element
   //   row  = wm*64 + a*32 + lr                  (TA: wm*64 + 2*lr + a, the row-interleaved tiles of the ds_read_b64 fragments)
   //   col  = wn*64 + b*32 + i(r),  i(r) = (r&3) + 8*(r>>2) + 4*lh   (TB: wn*64 + 2*i(r) + b)
-  // Initial value = the tile's bias (forward layout only): registers 4q..4q+3 are columns 8q+4lh .. +3 of the strip.
-  auto init_acc = [&](int it, bool zero) {
-    if (bias && !TB && !zero) {
-      const float* src = bias_lds + (it & 1) * BN + wn * 64 + 4 * lh;
+  auto init_acc = [&]() {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(src + b * 32 + 8 * q);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { acc[0][b][4 * q + j] = v[j]; acc[1][b][4 * q + j] = v[j]; }
-        }
-    } else {
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
+        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  };
+  // the tile's bias joins the finished sums (forward layout only): registers 4q..4q+3 are columns 8q+4lh .. +3 of the strip
+  auto add_bias = [&](int it) {
+    if constexpr (!TA && !TB) {
+      if (bias) {
+        const float* src = bias_lds + (it % NBIAS) * BN + wn * 64 + 4 * lh;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(src + b * 32 + 8 * q);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { acc[0][b][4 * q + j] += v[j]; acc[1][b][4 * q + j] += v[j]; }
+          }
+      }
     }
   };
 
@@ -467,7 +471,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void gemm_nt_kernel(const float* _
 
   // ---- MFMA waves: nothing of theirs is in flight, the loaders' counted wait + this barrier publish step 0 ----
   __builtin_amdgcn_s_barrier();
-  init_acc(0, SK && !seg_complete(0));
+  init_acc();
   Frags fa = read_frags(0, 0), fb;  // ping-pong fragment registers: 4 chunk reads per step, so fa is "current" at every step start
 
   int c_it = 0, c_kt = kt_begin(0);  // MFMA stream position
@@ -531,6 +535,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void gemm_nt_kernel(const float* _
       }
       float* Yt = Y + (int64_t)split * slab_stride;
       const bool partial = SK && !seg_complete(c_it);
+      if (!partial) add_bias(c_it);  // (a partial segment's bias is the fix-up's)
       // 16-byte stores need 16-byte aligned rows (wave-uniform test); otherwise, and on ragged tiles, guarded scalars
       const bool vec_ok = (m0 + BM <= M) && (n0 + BN <= N) && (ldy & 3) == 0 && ((uintptr_t)Yt & 15) == 0 &&
                           (!ADD || ((ldr & 3) == 0 && ((uintptr_t)R & 15) == 0));
@@ -685,7 +690,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 3) void gemm_nt_kernel(const float* _
           }
         }
       }
-      if (c_it + 1 < my_tiles) init_acc(c_it + 1, SK && !seg_complete(c_it + 1));
+      if (c_it + 1 < my_tiles) init_acc();
       ++c_it;
       c_kt = kt_begin(c_it);
       if constexpr (GROUP) {
@@ -1329,7 +1334,7 @@ int launch_linear(const float* x, int64_t ldx, const float* w, const float* bias
 }
 
 // y = (x·Wᵀ + b) + r: the residual add of a post-norm layer in the product's epilogue (same rounding sequence as
-// storing the product and adding r in the LayerNorm pass: the accumulators start from b, r is added last)
+// storing the product and adding r in the LayerNorm pass: b joins the finished sum, r is added last)
 int launch_linear_add(const float* x, int64_t ldx, const float* w, const float* bias, const float* r, int64_t ldr, float* y,
                       int64_t ldy, int64_t M, int64_t N, int64_t K, hipStream_t s) {
   bool taken = false;

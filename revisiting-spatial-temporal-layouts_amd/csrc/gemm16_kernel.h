@@ -6,8 +6,9 @@
 // Structure (mhsa.hip's product phase): v_mfma_f32_16x16x4_f32; 8 MFMA waves arranged RB x CG (CG = 8 / RB): wave w owns the 16-row block
 // w % RB and the NTW = NT / CG column tiles of column group w / RB, transposed accumulators (lane = row, registers = 4 consecutive
 // columns -> 16-byte stores); 4 DMA-only loader waves two to five k-steps ahead (LDS-DMA with the source-side bank swizzle, as many
-// stages as fit ~150 KB, counted vmcnt, one barrier per k-step); bias as the accumulators' initial value from LDS strips DMA'd in front
-// of each tile's first k-step; persistent workgroups over XCD-contiguous tile ranges (column tile fastest, so that the workgroups of an
+// stages as fit ~150 KB, counted vmcnt, one barrier per k-step); accumulators from zero, the bias added to the finished sums from LDS
+// strips DMA'd in front of each tile's first k-step (started from the bias, every addition of an element would round at the bias's
+// magnitude: profiles/product_scale.md); persistent workgroups over XCD-contiguous tile ranges (column tile fastest, so that the workgroups of an
 // XCD share X row panels).  K % 32 == 0, N % 4 == 0.
 #pragma once
 #include "common.h"
@@ -125,11 +126,13 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
         }
       }
     };
-    // Bias strip of tile `it` (its accumulators' initial value), issued IN FRONT of the tile's first k-step: the counter is in order, so
+    // Bias strip of tile `it` (added to its sums in the tile's epilogue), issued IN FRONT of the tile's first k-step: the counter is in order, so
     // the wait that publishes that k-step publishes the strip as well.  (Until the end of round 4 the strip was issued one k-step before
     // it was read, behind up to LA - 1 newer steps the counted wait lets stay in flight: a race that was almost always won — the 3 KB of
-    // bias are L2-resident — and lost once in a 33 000-row launch of a test run.)  Four strips: the loaders are LA <= 5 steps ahead and a
-    // tile has nk >= 2 k-steps, so a strip is rewritten at the earliest 4 nk - LA >= 3 barriers after the MFMA waves read it.
+    // bias are L2-resident — and lost once in a 33 000-row launch of a test run.)  Four strips: the MFMA waves read the strip of tile t behind
+    // the barrier of t's last k-step, step (t + 1) nk - 1; the loaders, LA <= 5 steps ahead, rewrite it for tile t + 4 once they have passed
+    // the barrier of step (t + 4) nk - LA - 1, which with nk >= 2 k-steps per tile is never an earlier barrier than that of step (t + 1) nk —
+    // and that one the MFMA waves reach only after the epilogue.
     auto dma_bias = [&](int it) {  // BN bias values, 64 per instruction, dealt over the loaders
       if (a.bias && Ld * 64 < BN) {
         int tm, tn;
@@ -231,14 +234,15 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
       if (t0 + t < NTW) f.w[t] = *reinterpret_cast<const f32x4*>(s + w_row + (t0 + t) * 16 * QK + off);
   };
   f32x4 acc[NTW];
-  auto init_acc = [&](int it) {
+  auto init_acc = [&]() {
+#pragma unroll
+    for (int t = 0; t < NTW; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  };
+  auto add_bias = [&](int it) {  // the tile's bias joins the finished sums, ahead of the activation / add-source
     if (a.bias) {
       const float* src = bias_lds + (it & (Q_BIAS_STRIPS - 1)) * BN + cg * NTW * 16 + 4 * lg;
 #pragma unroll
-      for (int t = 0; t < NTW; ++t) acc[t] = *reinterpret_cast<const f32x4*>(src + 16 * t);
-    } else {
-#pragma unroll
-      for (int t = 0; t < NTW; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < NTW; ++t) acc[t] += *reinterpret_cast<const f32x4*>(src + 16 * t);
     }
   };
   auto mfma_phase = [&](int p, const Frags& f, int e_lo, int e_hi) {  // e outermost: an accumulator recurs every (tiles in the phase) MFMAs
@@ -257,6 +261,7 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
     // ---- epilogue of tile c_it: lane (li, lg) holds columns 16 (cg NTW + t) + 4 lg .. + 3 of row 16 rb + li
     int tm, tn;
     item_of(c_it, tm, tn);
+    add_bias(c_it);
     {
       int eli = li, elg = lg;  // opaque copies: the address arithmetic is recomputed per tile instead of living in registers across the k-loop
       asm volatile("" : "+v"(eli), "+v"(elg));
@@ -345,11 +350,11 @@ __global__ __launch_bounds__(Q_THREADS, 3) void gemm16_kernel(const Gemm16Args a
     }
     ++c_it;
     c_kt = 0;
-    if (step + 1 < total_steps) init_acc(c_it);  // next tile: accumulators from its bias strip (published by an earlier barrier)
+    if (step + 1 < total_steps) init_acc();
   };
 
   __builtin_amdgcn_s_barrier();  // the loaders' counted wait + this barrier publish step 0 (DEEP: and step 1) and the first bias strip
-  init_acc(0);
+  init_acc();
   if constexpr (DEEP) {
     struct Set { f32x4 x[2]; f32x4 w[2][NTW]; };  // a whole k-step of fragments: both k-chunks
     // read item q of a k-step's 2 (1 + NTW) fragments: chunk c = q / (1 + NTW), then x (i = 0) or column tile i - 1

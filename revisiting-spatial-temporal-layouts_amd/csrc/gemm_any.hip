@@ -108,15 +108,17 @@ __global__ __launch_bounds__(256) void gemm_any_kernel(const float* __restrict__
     }
 }
 
-// y[m][n] = act(bias[n] + part[0][m][n] + part[1][m][n] + ...) (+ r[m][n]): the partial tiles of a split product, summed in split order
+// y[m][n] = act((part[0][m][n] + part[1][m][n] + ...) + bias[n]) (+ r[m][n]): the partial tiles of a split product, summed in split order from
+// zero, the bias added to the finished sum (summed onto the bias, the partials would round at its magnitude: profiles/product_scale.md)
 __global__ __launch_bounds__(256) void skinny_finish_kernel(const float* __restrict__ part, int64_t split_stride, int splits, const float* __restrict__ bias,
                                                             const float* r, int64_t ldr, float* y, int64_t ldy, int M, int N, int act) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (int64_t)M * N) return;
   const int m = (int)(idx / N), n = (int)(idx - (int64_t)m * N);
-  float v = bias ? bias[n] : 0.f;
+  float v = 0.f;
   const float* p = part + idx;
   for (int z = 0; z < splits; ++z) v += p[(int64_t)z * split_stride];
+  if (bias) v += bias[n];
   if (act == STLT_ACT_GELU) v = gelu_epilogue(v);
   else if (act == STLT_ACT_RELU) v = fmaxf(v, 0.f);
   if (r) v += r[(int64_t)m * ldr + n];

@@ -15,8 +15,8 @@
 // (419 TFLOP/s-equivalent).  Measured 215-235 = 1.62-1.79x the f32 kernel: the chip is power-bound under bf16 MFMAs (it runs
 // this kernel at ~1.5 GHz) and after that the producer waves set the k-step; DESIGN.md section 3 has the numbers.
 //
-// Structure: 256 x 128 x 32 tiles, 8 MFMA waves (4 x 2 of 64 x 64 = 4 x 4 blocks of 16 x 16, transposed accumulators, bias as
-// their initial value) and 4 PRODUCER waves, persistent workgroups walking gemm.hip's XCD-contiguous band-major tile order,
+// Structure: 256 x 128 x 32 tiles, 8 MFMA waves (4 x 2 of 64 x 64 = 4 x 4 blocks of 16 x 16, transposed accumulators from zero, the bias
+// added to the finished sums) and 4 PRODUCER waves, persistent workgroups walking gemm.hip's XCD-contiguous band-major tile order,
 // one barrier per k-step.  The producers load the f32 operands with buffer loads into registers (two k-steps ahead, ~92 KB in
 // flight per workgroup), cut every element ONCE per workgroup and write three bf16 plane images to LDS; the MFMA waves read
 // ready bf16 fragments and issue nothing but ds_read_b128 and MFMAs.  Long launches cut the weight once for all workgroups in
@@ -152,12 +152,13 @@ __device__ __forceinline__ void split4(f32x4 v, u32x2& p0, u32x2& p1, u32x2& p2)
 
 // WPRE: W arrives already cut — three bf16 planes [3][N][K] written by w_planes_kernel (the weight is shared by every row
 // tile: cutting it once per launch takes a third of the cut off the producers) — in `W`, ldw unused
+constexpr int X_BIAS_STRIPS = 3;  // by tile index mod 3: see the producers' bias strip
 template <int ACT, bool ADD, bool WPRE>
 __global__ __launch_bounds__(X_THREADS, 3) void gemm_nt_bf16x3p_kernel(const float* __restrict__ X, int64_t ldx, const float* __restrict__ W,
                                                                       int64_t ldw, const float* __restrict__ bias, const float* __restrict__ R,
                                                                       int64_t ldr, float* __restrict__ Y, int64_t ldy, int M, int N, int K,
                                                                       int tiles_m, int tiles_n, unsigned long long* __restrict__ dbg) {
-  __shared__ __attribute__((aligned(16))) unsigned char pmem[2 * P_BUF + 2 * BN * 4];
+  __shared__ __attribute__((aligned(16))) unsigned char pmem[2 * P_BUF + X_BIAS_STRIPS * BN * 4];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -214,9 +215,12 @@ __global__ __launch_bounds__(X_THREADS, 3) void gemm_nt_bf16x3p_kernel(const flo
       return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rB, vB + ((j - 8) >> 1) * 16 * ldw4 + (j & 1) * 16, kt * (BK * 4), 0));
     };
     // bias strip: wave p carries columns [32p, 32p+32) of the NEXT tile's strip in one register, loaded every step and stored
-    // (into the strip buffer the MFMA waves are not reading) one step later — no branch and no wait of its own in this wave's
+    // (into a strip buffer the MFMA waves are not reading) one step later — no branch and no wait of its own in this wave's
     // load stream, so the counted waits the compiler derives for the operand registers stay exact.  The store of a tile's first
-    // step still carries the previous strip; the later steps overwrite it (K >= 2 k-steps, the launcher's condition)
+    // step still carries the previous strip; the later steps overwrite it (K >= 2 k-steps, the launcher's condition).  The MFMA
+    // waves add tile t's strip to the finished sums behind the barrier of t's last k-step; three strips by t mod 3: during tile
+    // t + 1 the producers write the strip of t + 2, and the strip of t is rewritten (for t + 3) from the first step of t + 2 on,
+    // at least two barriers after it was read
     auto bias_col = [&](int it) {  // this lane's column of tile it's strip (clamped to the matrix); two scalar divisions: once per tile
       it = it < my_tiles ? it : my_tiles - 1;
       int m0, n0;
@@ -225,7 +229,7 @@ __global__ __launch_bounds__(X_THREADS, 3) void gemm_nt_bf16x3p_kernel(const flo
       return n < N ? n : N - 1;
     };
     auto bias_load = [&](int n) { return bias ? bias[n] : 0.f; };
-    auto bias_store = [&](int it, float v) { bias_lds[(it & 1) * BN + 32 * p + (lane & 31)] = v; };
+    auto bias_store = [&](int it, float v) { bias_lds[(it % X_BIAS_STRIPS) * BN + 32 * p + (lane & 31)] = v; };
     int l_it = 0, l_kt = 0;
     auto load_step = [&](f32x4 (&S)[NPC]) {
       if (l_kt == 0 && l_it < my_tiles) set_tile(l_it);
@@ -318,13 +322,22 @@ __global__ __launch_bounds__(X_THREADS, 3) void gemm_nt_bf16x3p_kernel(const flo
   const int sw16 = (kq ^ ((0 - (lr16 >> 2)) & 3)) * 16;
   const int a_off = (wm * 64 + lr16) * 64 + sw16, b_off = P_B_BASE + (wn * 64 + lr16) * 64 + sw16;
   f32x4 acc[4][4];  // [bn][bm]
-  auto init_acc = [&](int it) {
+  auto init_acc = [&]() {
 #pragma unroll
-    for (int bn = 0; bn < 4; ++bn) {
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (bias) v = *reinterpret_cast<const f32x4*>(bias_lds + (it & 1) * BN + wn * 64 + bn * 16 + 4 * kq);
+    for (int bn = 0; bn < 4; ++bn)
 #pragma unroll
-      for (int bm = 0; bm < 4; ++bm) acc[bn][bm] = v;
+      for (int bm = 0; bm < 4; ++bm) acc[bn][bm] = f32x4{0.f, 0.f, 0.f, 0.f};
+  };
+  // the bias joins the finished sums (started from it, every one of the K / 32 * 6 additions of an element would round at the bias's
+  // magnitude: profiles/product_scale.md)
+  auto add_bias = [&](int it) {
+    if (bias) {
+#pragma unroll
+      for (int bn = 0; bn < 4; ++bn) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(bias_lds + (it % X_BIAS_STRIPS) * BN + wn * 64 + bn * 16 + 4 * kq);
+#pragma unroll
+        for (int bm = 0; bm < 4; ++bm) acc[bn][bm] += v;
+      }
     }
   };
   auto read_planes = [&](int buf, int off, int ps) {
@@ -347,7 +360,7 @@ __global__ __launch_bounds__(X_THREADS, 3) void gemm_nt_bf16x3p_kernel(const flo
   };
 
   __builtin_amdgcn_s_barrier();
-  init_acc(0);
+  init_acc();
   int c_it = 0, c_kt = 0;
   for (int step = 0; step < total_steps; ++step) {
     const int buf = step & 1;
@@ -364,8 +377,9 @@ __global__ __launch_bounds__(X_THREADS, 3) void gemm_nt_bf16x3p_kernel(const flo
     if (++c_kt < nk) continue;
     int m0, n0;
     walk.origin(c_it, m0, n0);
+    add_bias(c_it);
     store_block16<ACT, ADD>(acc, m0, n0, wm, wn, lr16, kq, R, ldr, Y, ldy, M, N);
-    if (c_it + 1 < my_tiles) init_acc(c_it + 1);
+    if (c_it + 1 < my_tiles) init_acc();
     ++c_it;
     c_kt = 0;
   }
@@ -451,6 +465,8 @@ int launch_linear_bf16x3(const float* x, int64_t ldx, const float* w, int64_t ld
   const int64_t cus = stlt_device_cus();
   StltProfScope ps(STLT_K_GEMM, s);
   stlt_prof_add_flops(2.0 * (double)M * (double)N * (double)K);
+  stlt_prof_note("gemm(split-bf16) M=%lld N=%lld K=%lld act=%d%s tile=256x128 tiles=%lld", (long long)M, (long long)N, (long long)K, act, r ? "+R" : "",
+                 (long long)(tiles_m * tiles_n));
   const dim3 grid((unsigned)cus), block(X_THREADS);
   // the weight cut once per launch into the lent stream-K scratch (free between launches, stream-ordered) when the launch is
   // long enough to pay for the extra 5-10 us kernel: at least four rounds of tiles (STLT_X3_WPRE=0 keeps the producers' own cut).

@@ -8,7 +8,8 @@ GELU points; a scalar is a row of one element), and one batch holds rows of very
 reference| and e = max |result - reference| / S: e_k for the kernel, e_t for torch's own fp32 implementation of the same op on the CPU on
 the same fp32 inputs.  E_t is the largest e_t among the rows of the case that share their scale parameters (their `group`).  A kernel row
 passes when e_k <= 4 * max(E_t, u) (an analytic term per element is taken off first where a documented approximation of that kernel calls for one);
-a row whose reference is identically zero must be exactly zero.  4: an equally sound fp32 evaluation in another order lands within about
+a row whose reference is identically zero must be exactly zero.  (An output may carry a second yardstick that is independent of the
+code under test; a group's bar is then 4 * max(E_t, E_c, u): tests/product_cases.py.)  4: an equally sound fp32 evaluation in another order lands within about
 2x of torch's error (two-pass LayerNorm emulated over d, mean/spread, spread and eps: worst 2.1x; the sound softmax gradient: 1.2x).
 
 The cases keep three conditions, which the CPU test asserts: every reference is finite, no element is left out of a comparison (the rows
@@ -37,18 +38,20 @@ MARGIN = 4.0
 YARD_CAP = 256.0
 FLT_MAX = 3.4028234663852886e38
 
-Out = collections.namedtuple("Out", "ref yard group")  # ref, yard: (rows, n) float64; group: one name per row
+Out = collections.namedtuple("Out", "ref yard group yard2", defaults=(None,))  # ref, yard: (rows, n) float64; group: one name per row; yard2: an optional second yardstick (tests/product_cases.py)
 
 
 def rows(t, n_rows):
     return t.detach().cpu().double().reshape(n_rows, -1)
 
 
-def out(ref, yard, group):
-    """One compared output: reference and yardstick as (rows, n) with one group name per row (a single name: the same for every row)."""
+def out(ref, yard, group, yard2=None):
+    """One compared output: reference and yardstick as (rows, n) with one group name per row (a single name: the same for every row).
+    yard2: a second fp32 evaluation that is independent of the code under test (tests/product_cases.py: an in-order chain); a group's
+    yardstick is then the larger of the two errors."""
     group = [group] * ref.shape[0] if isinstance(group, str) else list(group)
     assert ref.dim() == 2 and len(group) == ref.shape[0]
-    return Out(ref.double(), rows(yard, ref.shape[0]), group)
+    return Out(ref.double(), rows(yard, ref.shape[0]), group, None if yard2 is None else rows(yard2, ref.shape[0]))
 
 
 def scalar(ref, yard, group):
@@ -65,13 +68,24 @@ def row_errors(got, ref):
     return torch.where(zero, torch.where(err == 0, 0.0, math.inf).double(), err / scale.clamp_min(1e-300)), zero
 
 
-def yardstick(o):
-    """{group: E_t} — the largest torch-fp32 row error of each group (zero rows have no scale and set no bar)."""
-    e_t, zero = row_errors(o.yard, o.ref)
+def _group_worst(yard, o):
+    e_t, zero = row_errors(yard, o.ref)
     worst = {}
     for e, z, g in zip(e_t.tolist(), zero.tolist(), o.group):
         worst[g] = max(worst.get(g, 0.0), 0.0 if z else e)
     return worst
+
+
+def yardsticks(o):
+    """({group: E_t}, {group: E_c} or None): the largest row error of each group for torch's fp32 op and for the second yardstick, where
+    the output has one (zero rows have no scale and set no bar)."""
+    return _group_worst(o.yard, o), (None if o.yard2 is None else _group_worst(o.yard2, o))
+
+
+def yardstick(o):
+    """{group: E_t} — the largest torch-fp32 row error of each group; with a second yardstick max(E_t, E_c)."""
+    e_t, e_c = yardsticks(o)
+    return e_t if e_c is None else {g: max(e, e_c[g]) for g, e in e_t.items()}
 
 
 def judge(tag, got, o, term=None):
@@ -85,6 +99,7 @@ def judge(tag, got, o, term=None):
         err = torch.nan_to_num((rows(got, o.ref.shape[0]) - o.ref).abs(), nan=math.inf)
         e_k = torch.where(o.ref.abs().amax(1) == 0, e_raw, (err - term).clamp_min(0.0).amax(1) / o.ref.abs().amax(1).clamp_min(1e-300))
     e_t = yardstick(o)
+    e_1, e_2 = yardsticks(o)
     worst, fails = {}, []
     for i, (e, raw, g) in enumerate(zip(e_k.tolist(), e_raw.tolist(), o.group)):
         bar = MARGIN * max(e_t[g], U)
@@ -94,7 +109,8 @@ def judge(tag, got, o, term=None):
     lines = []
     for g, (e, raw) in worst.items():
         note = f" | after the analytic term {e / U:.2f}, ratio {e / max(e_t[g], U):.2f}" if term is not None else ""
-        lines.append(f"[scale] {tag} | {g} | e_k/u {raw / U:.2f} | E_t/u {e_t[g] / U:.2f} | ratio {raw / max(e_t[g], U):.2f}{note}")
+        yards = f"E_t/u {e_t[g] / U:.2f}" if e_2 is None else f"E_t/u {e_1[g] / U:.2f} | E_c/u {e_2[g] / U:.2f}"
+        lines.append(f"[scale] {tag} | {g} | e_k/u {raw / U:.2f} | {yards} | ratio {raw / max(e_t[g], U):.2f}{note}")
     print("\n".join(lines))
     return lines, fails
 
@@ -104,7 +120,7 @@ def conditions(o):
     bad = []
     if not bool(torch.isfinite(o.ref).all()):
         bad.append("a reference value is not finite")
-    if o.yard.shape != o.ref.shape:
+    if o.yard.shape != o.ref.shape or (o.yard2 is not None and o.yard2.shape != o.ref.shape):
         bad.append("the yardstick does not cover the reference")
     for g, e in yardstick(o).items():
         if not e <= YARD_CAP * U:

@@ -599,7 +599,7 @@ def test_linear_small_tiles_vs_fp64(pkg, M, N, K, tile_rows, tile_cols):
 @pytest.mark.parametrize("tile_rows,tile_cols", SMALL_TILES)
 @pytest.mark.parametrize("K", [64, 96, 128, 256])
 def test_linear_small_tiles_bias_strip_under_load(pkg, tile_rows, tile_cols, K):
-    """Many short tiles per workgroup (33 000 rows, 2 - 8 k-steps a tile): every tile's accumulators start from its own bias strip.  The
+    """Many short tiles per workgroup (33 000 rows, 2 - 8 k-steps a tile): every tile's sums take its own bias strip.  The
     strip is DMA'd in front of the tile's first k-step, so the counted wait that publishes that step publishes it too; round 4's first
     form issued it one k-step before it was read, behind loads the wait lets stay in flight, and lost that race once in a test run.
     A stale strip is another column tile's bias: the bias here is large and different per column, so it cannot hide in the tolerance."""

@@ -6,7 +6,8 @@ is compared at the large rows' scale.  Here every case comes from tests/scale_ca
 different magnitudes in one batch, each row judged on its own scale, the bar 4 * max(E_t, u) measured from torch's fp32 implementation on
 the same inputs; tests/test_off_unit_scale_cpu.py holds the cases to the conditions that make that bar mean something.  Kernels are
 reached through pkg.ops.* and the C ABI, as in tests/test_partition_regimes_gpu.py.  Every case prints e_k / u, E_t / u and their ratio
-per scale group (profiles/off_unit_scale.md keeps the table of one run).
+per scale group (profiles/off_unit_scale.md keeps the table of one run).  The products themselves — every GEMM route and the Conv3d forward — are
+held to the same rule, block by block, in tests/test_product_scale_gpu.py (profiles/product_scale.md).
 
 No kernel needed an analytic term (scale_cases.judge can take one off element by element for a documented approximation of a kernel, such
 as the stated 1.1e-7 of the epilogue's erf fit): every case holds the plain bar.

@@ -4,7 +4,7 @@ Every backward / reduction kernel outside the GEMMs cuts its rows into a capped 
 walk its part, and adds the partial rows in a fixed order.  The cut changes shape at fixed counts (one row per wave -> several with the
 next row prefetched -> a capped grid with ragged or empty trailing parts).  The cases below are the smallest counts on both sides of
 each such count, at unit scale (tests/test_off_unit_scale_gpu.py takes the same kernels off it, row by row against torch's own
-fp32 error), against plain fp64 references on the CPU, with the bars of the neighbouring op-level tests:
+fp32 error; the GEMMs and the Conv3d forward, on every route they can take: tests/test_product_scale_gpu.py, profiles/product_scale.md), against plain fp64 references on the CPU, with the bars of the neighbouring op-level tests:
 2e-5 of each result's max-abs scale (5e-5 for the column sums of the attention gradient, loss 2e-6 * max(1, |ref|), loss gradient
 1e-7, norm 1e-5 relative, reduce_slabs the element-wise bound of test_reduce_slabs).
 
