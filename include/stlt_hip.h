@@ -1148,6 +1148,68 @@ int stlt_perturb_rank_cells(const float* scores, int64_t B, int64_t C, int desce
 int stlt_perturb_apply_cells(const float* x, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, const int32_t* rank,
                              const int32_t* n_candidates, int64_t steps, int64_t s0, int64_t s1, float fill, float* out, int32_t* removed, stlt_stream_t stream);
 int stlt_cell_pool_abs(const float* g, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, float* out, stlt_stream_t stream);
+/* stlt_cell_pool_sum: the signed twin of stlt_cell_pool_abs — out (B,C)[b,c] = the sum of g itself over cell c and all channels: a signed
+ * attribution map (stlt_ig_reduce's attr) per cell.  The same kernel, extents, refusals and summation order; the error is that of a tree
+ * sum of fp32 terms of both signs (bounded by the sum of their magnitudes, not by the result). */
+int stlt_cell_pool_sum(const float* g, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, float* out, stlt_stream_t stream);
+
+/* ---- integrated gradients (csrc/integrated_gradients.hip) ----
+ * Sundararajan, Taly, Yan 2017: attr = (x - x0) * integral over alpha in [0,1] of dF/dx at x0 + alpha (x - x0), F the seeded logit, x0 a
+ * baseline; the attributions sum to F(x) - F(x0) (completeness).  The integral is the trapezoid rule on S = steps + 1 points, steps >= 1:
+ * alpha_s = s / steps, w_s = 1 / steps for 0 < s < steps and 1 / (2 steps) for s = 0 and s = steps (the weights sum to 1; both endpoints
+ * are on the path, so F(x) and F(x0) come out of the same passes).  The gradients are the existing input-only sweeps'; these entry points
+ * build the path, accumulate the quadrature and reduce the completeness gap.  They share one contract: stream-ordered, no allocation, no
+ * synchronisation, no read-back, capturable; STLT_EINVAL with a message and no launch on a NULL required pointer, steps < 1 (or >= 2^23),
+ * s0 < 0, s0 > s1, s1 > steps, more than STLT_IG_MAX_STEPS steps in one call, or a tensor of 2^31 elements or more; pointers need the
+ * alignment of their element type only.
+ *
+ * The fp32 arithmetic, exactly (fadd / fsub / fmul / fdiv: the IEEE operation rounded to nearest even, never contracted into an FMA — a
+ * numpy float32 restatement reproduces every bit):
+ *   alpha_s = fdiv((float)s, (float)steps)            w_s = fdiv(1, (float)steps), or fdiv(1, (float)(2 steps)) at s = 0 and s = steps
+ *   point_s = fadd(x0, fmul(alpha_s, fsub(x, x0)))    for 0 < s < steps; step 0 is x0's bits and step `steps` is x's bits, not computed
+ *   acc     = fadd(acc, fmul(w_s, g_s))               for s = s0, s0+1, ..., s1 in this order, starting from +0 (STLT_IG_BEGIN) or from acc
+ *   attr    = fmul(fsub(x, x0), acc)
+ * A NULL baseline stands for x0 = +0 (stlt_ig_path) or x0 = fill (the dense calls) in the same formulas.
+ *
+ * stlt_ig_path: steps s0 .. s1 of the layout batch `in` (stlt_inputs: B, T, N and the seven tensors; scores may be NULL; the row counts are
+ * not read), step-major like stlt_perturb_apply: clip (s-s0)*B + b is clip b at step s.  boxes (B,T,N,4) and scores (B,T,N) go to point_s
+ * with the baselines boxes0 / scores0 (same shapes, or NULL: zeros); categories, both masks, frame_types and lengths are copied bit for bit.
+ * One launch: every input element is read once, every step is written from registers.  Reads B*T*N slots of `in` and of the baselines,
+ * writes (s1-s0+1)*B*T*N slots of each output.  The outputs must not overlap the inputs.
+ *
+ * stlt_ig_path_dense: the same for one dense float32 tensor x of n elements per clip (video_frames (B,3,T,H,W), appearance_features, ...):
+ * out ((s1-s0+1)*B, n) step-major.  x0 (B,n), or NULL: every baseline element is `fill`.  Accesses are 16 bytes wide on the aligned body,
+ * with a scalar head and tail, when x, x0 and out have the same address modulo 16 and either one step is written or B*n % 4 == 0; one float
+ * wide otherwise: the same bits either way.  The grid is sized for the chip's 256 CUs, whatever the host.  Reads B*n, writes (s1-s0+1)*B*n.
+ *
+ * stlt_ig_reduce: g ((s1-s0+1)*B, n) — the gradients at the path points of steps s0 .. s1, step-major — is added into acc (B,n) in place,
+ * one element per lane, ascending s, no atomics.  flags: STLT_IG_BEGIN — acc starts from +0 and is not read (the first call of a sum);
+ * STLT_IG_FINISH — after the last step, attr (B,n) = (x - x0) * acc is written (x required; x0 (B,n), or NULL: `fill`).  The steps of a sum
+ * may be split over several calls in ascending order: (BEGIN, s0..k) then (k+1..s1, FINISH) gives the bits of (BEGIN | FINISH, s0..s1).
+ * grouped (B, n/group), optional with FINISH, 1 <= group <= 64 dividing n: the sum of each run of `group` consecutive attributions, added
+ * left to right, then extra (B, n/group) when given.  For the layout: scores first (attr_scores), then boxes with group 4, extra =
+ * attr_scores: grouped is object_attribution (B,T,N) = (((a_x1 + a_y1) + a_x2) + a_y2) + a_score.  acc, attr and grouped overlap neither g nor each other.
+ *
+ * stlt_ig_delta: delta (B,)[b] = the sum of up to three attribution tensors of clip b (a_i (B,n_i); n_i = 0: absent, a_i not read) minus
+ * sum_k seed[b,k] * (logits_x[b,k] - logits_x0[b,k]) ((B,K) each): the completeness gap, 0 for an exact integral.  Two stages over a fixed
+ * partition: stage 1 writes one fp32 partial per STLT_IG_DELTA_CHUNK consecutive elements of one tensor of one clip (lane t of 256 adds
+ * elements t, t+256, ... in order, then the wave, then the four waves) into scratch — stlt_ig_delta_scratch_bytes(B, n0, n1, n2) bytes,
+ * 4-byte aligned; stage 2, one workgroup per clip, adds the clip's partials and the K logit terms in fp64 and rounds once.  The chunk is a
+ * compile-time constant, so the bits do not depend on the grid: max_blocks (0: the default, sized for 256 CUs) caps stage 1's grid and
+ * changes nothing else.  One clip of 3*16*112*112 elements is 147 chunks.  Error against the exact sum of the fp32 attributions: below
+ * 2^-23 * (number of addends) * sum|a|. */
+#define STLT_IG_MAX_STEPS 256
+#define STLT_IG_DELTA_CHUNK 4096
+#define STLT_IG_BEGIN 1
+#define STLT_IG_FINISH 2
+int stlt_ig_path(const stlt_inputs* in, const float* boxes0, const float* scores0, int64_t steps, int64_t s0, int64_t s1, int64_t* categories, float* boxes,
+                 float* scores, uint8_t* kpm_boxes, int64_t* frame_types, uint8_t* kpm_frames, int64_t* lengths, stlt_stream_t stream);
+int stlt_ig_path_dense(const float* x, const float* x0, float fill, int64_t B, int64_t n, int64_t steps, int64_t s0, int64_t s1, float* out, stlt_stream_t stream);
+int stlt_ig_reduce(const float* g, int64_t B, int64_t n, int64_t steps, int64_t s0, int64_t s1, int flags, float* acc, const float* x, const float* x0, float fill,
+                   float* attr, int64_t group, const float* extra, float* grouped, stlt_stream_t stream);
+size_t stlt_ig_delta_scratch_bytes(int64_t B, int64_t n0, int64_t n1, int64_t n2);
+int stlt_ig_delta(const float* a0, int64_t n0, const float* a1, int64_t n1, const float* a2, int64_t n2, const float* seed, const float* logits_x,
+                  const float* logits_x0, int64_t B, int64_t K, int64_t max_blocks, void* scratch, size_t scratch_bytes, float* delta, stlt_stream_t stream);
 
 /* ---- per-kernel timing (bench.py roofline leg): hipEvents around every launch of the whole-path calls ---- */
 #define STLT_K_EMBED 0

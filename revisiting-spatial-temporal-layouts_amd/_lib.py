@@ -20,6 +20,9 @@ FLAG_TRAIN_BACKBONE = 32
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 PERTURB_UNITS = {"object": 0, "frame": 1}          # STLT_PERTURB_OBJECT / _FRAME
 PERTURB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # STLT_PERTURB_SOFTMAX / _SIGMOID
+IG_BEGIN, IG_FINISH = 1, 2  # STLT_IG_BEGIN / _FINISH
+IG_MAX_STEPS = 256          # STLT_IG_MAX_STEPS: the steps of one stlt_ig_path / _path_dense / _reduce call
+IG_DELTA_CHUNK = 4096       # STLT_IG_DELTA_CHUNK
 
 _f = C.POINTER(C.c_float)
 _i64 = C.POINTER(C.c_int64)
@@ -280,6 +283,12 @@ SIGNATURES = {
     "stlt_perturb_rank_cells": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp]),
     "stlt_perturb_apply_cells": (C.c_int, [_vp] + [C.c_int64] * 8 + [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_float, _vp, _vp, _vp]),
     "stlt_cell_pool_abs": (C.c_int, [_vp] + [C.c_int64] * 8 + [_vp, _vp]),
+    "stlt_cell_pool_sum": (C.c_int, [_vp] + [C.c_int64] * 8 + [_vp, _vp]),
+    "stlt_ig_path": (C.c_int, [C.POINTER(Inputs), _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "stlt_ig_path_dense": (C.c_int, [_vp, _vp, C.c_float, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "stlt_ig_reduce": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp, C.c_float, _vp, C.c_int64, _vp, _vp, _vp]),
+    "stlt_ig_delta_scratch_bytes": (C.c_size_t, [C.c_int64] * 4),
+    "stlt_ig_delta": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_size_t, _vp, _vp]),
     "stlt_grad_norm": (C.c_int, [_vp, C.c_int64, C.c_float, _vp, _vp, _vp]),
     "stlt_adamw_step": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
     "stlt_prof_enable": (C.c_int, [C.c_int]),

@@ -11,8 +11,8 @@
 //                         moved as the integer it is stored as (bit for bit), frames that lost their last object change type.
 //   perturb_curve_kernel  one wave per logits row: the stabilised softmax probability (or the sigmoid) of the clip's target class and
 //                         whether any class beats it — eval_topk_kernel's rule (larger logit, or equal logit at a lower index).
-//   perturb_apply_cells_kernel / cell_pool_abs_kernel  the appearance side (further down): video cells and feature columns set to a fill
-//                         value per step, and |gradient| summed per cell.  Cells are ranked by perturb_rank_kernel<true>: the same sort.
+//   perturb_apply_cells_kernel / cell_pool_kernel  the appearance side (further down): video cells and feature columns set to a fill
+//                         value per step, and |gradient| (or the signed attribution) summed per cell.  Cells are ranked by perturb_rank_kernel<true>: the same sort.
 #include <cstring>
 #include "common.h"
 
@@ -267,8 +267,10 @@ __global__ __launch_bounds__(PT_THREADS) void perturb_apply_cells_kernel(const u
 
 // One workgroup per (clip, cell): sum of |g| over the cell and all channels in a fixed order — element e of the cell (channel-major, then
 // frame, row, column) goes to accumulator (e / PT_THREADS) % 4 of thread e % PT_THREADS; the four are added pairwise, then the wave by
-// xor-shuffles, then the four waves in order.  No atomics: the same bits on every launch.
-__global__ __launch_bounds__(PT_THREADS) void cell_pool_abs_kernel(const float* __restrict__ gr, CellGeom g, int Gt, float* __restrict__ out) {
+// xor-shuffles, then the four waves in order.  No atomics: the same bits on every launch.  ABS = false is the signed twin (stlt_cell_pool_sum:
+// a signed attribution map pooled per cell) — the same order, the value itself in place of its magnitude.
+template <bool ABS>
+__global__ __launch_bounds__(PT_THREADS) void cell_pool_kernel(const float* __restrict__ gr, CellGeom g, int Gt, float* __restrict__ out) {
   __shared__ float wave_sum[PT_THREADS / 64];
   const int C = Gt * g.Gh * g.Gw;
   const int64_t b = blockIdx.x / C;
@@ -284,8 +286,9 @@ __global__ __launch_bounds__(PT_THREADS) void cell_pool_abs_kernel(const float* 
     const uint32_t ch = e / per_ch, r = e - ch * per_ch;
     const uint32_t dt = r / (nh * nw), r2 = r - dt * (nh * nw);
     const uint32_t dh = r2 / nw, dw = r2 - dh * nw;
-    const float v = fabsf(base[(((int64_t)ch * g.T + (t0 + dt)) * g.H + (h0 + dh)) * g.W + (w0 + dw)]);
-    acc[0] += k == 0 ? v : 0.f; acc[1] += k == 1 ? v : 0.f; acc[2] += k == 2 ? v : 0.f; acc[3] += k == 3 ? v : 0.f;  // adding +0 changes no bit of a non-negative sum
+    const float raw = base[(((int64_t)ch * g.T + (t0 + dt)) * g.H + (h0 + dh)) * g.W + (w0 + dw)];
+    const float v = ABS ? fabsf(raw) : raw;
+    acc[0] += k == 0 ? v : 0.f; acc[1] += k == 1 ? v : 0.f; acc[2] += k == 2 ? v : 0.f; acc[3] += k == 3 ? v : 0.f;  // adding +0 changes no bit of a non-negative sum (of a signed one: at most -0 into +0)
   }
   float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
 #pragma unroll
@@ -307,6 +310,24 @@ const char* cell_geometry(int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t 
   *Gt = gt;
   *C = gt * gh * gw;
   return nullptr;
+}
+
+// the launcher of stlt_cell_pool_abs and stlt_cell_pool_sum
+template <bool ABS>
+int cell_pool(const char* who, const float* g, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, float* out, stlt_stream_t stream) {
+  CellGeom geom;
+  int64_t Gt, C;
+  if (const char* why = cell_geometry(B, Cch, T, H, W, ct, ch, cw, &geom, &Gt, &C))
+    return stlt_set_error(STLT_EINVAL, "%s: %s (B=%lld, g=(%lld,%lld,%lld,%lld), cells=(%lld,%lld,%lld))", who, why, (long long)B, (long long)Cch, (long long)T,
+                          (long long)H, (long long)W, (long long)ct, (long long)ch, (long long)cw);
+  if (B == 0) return 0;
+  if (B * C > 0x7fffffff) return stlt_set_error(STLT_EINVAL, "%s: %lld workgroups in one call (at most 2^31 - 1)", who, (long long)(B * C));
+  if (!g || !out) return stlt_set_error(STLT_EINVAL, "%s: null pointer", who);
+  hipStream_t s = (hipStream_t)stream;
+  StltProfScope ps(STLT_K_MISC, s);
+  stlt_prof_note("%s B=%lld g=(%lld,%lld,%lld,%lld) cells=%lld", who + 5, (long long)B, (long long)Cch, (long long)T, (long long)H, (long long)W, (long long)C);
+  hipLaunchKernelGGL(cell_pool_kernel<ABS>, dim3((unsigned)(B * C)), dim3(PT_THREADS), 0, s, g, geom, (int)Gt, out);
+  return stlt_check_launch(ABS ? "cell_pool_abs_kernel" : "cell_pool_sum_kernel");
 }
 
 }  // namespace
@@ -456,19 +477,11 @@ int stlt_perturb_apply_cells(const float* x, int64_t B, int64_t Cch, int64_t T, 
 }
 
 int stlt_cell_pool_abs(const float* g, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, float* out, stlt_stream_t stream) {
-  CellGeom geom;
-  int64_t Gt, C;
-  if (const char* why = cell_geometry(B, Cch, T, H, W, ct, ch, cw, &geom, &Gt, &C))
-    return stlt_set_error(STLT_EINVAL, "stlt_cell_pool_abs: %s (B=%lld, g=(%lld,%lld,%lld,%lld), cells=(%lld,%lld,%lld))", why, (long long)B, (long long)Cch, (long long)T,
-                          (long long)H, (long long)W, (long long)ct, (long long)ch, (long long)cw);
-  if (B == 0) return 0;
-  if (B * C > 0x7fffffff) return stlt_set_error(STLT_EINVAL, "stlt_cell_pool_abs: %lld workgroups in one call (at most 2^31 - 1)", (long long)(B * C));
-  if (!g || !out) return stlt_set_error(STLT_EINVAL, "stlt_cell_pool_abs: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  StltProfScope ps(STLT_K_MISC, s);
-  stlt_prof_note("cell_pool_abs B=%lld g=(%lld,%lld,%lld,%lld) cells=%lld", (long long)B, (long long)Cch, (long long)T, (long long)H, (long long)W, (long long)C);
-  hipLaunchKernelGGL(cell_pool_abs_kernel, dim3((unsigned)(B * C)), dim3(PT_THREADS), 0, s, g, geom, (int)Gt, out);
-  return stlt_check_launch("cell_pool_abs_kernel");
+  return cell_pool<true>("stlt_cell_pool_abs", g, B, Cch, T, H, W, ct, ch, cw, out, stream);
+}
+
+int stlt_cell_pool_sum(const float* g, int64_t B, int64_t Cch, int64_t T, int64_t H, int64_t W, int64_t ct, int64_t ch, int64_t cw, float* out, stlt_stream_t stream) {
+  return cell_pool<false>("stlt_cell_pool_sum", g, B, Cch, T, H, W, ct, ch, cw, out, stream);
 }
 
 }  // extern "C"

@@ -146,7 +146,7 @@ def perturb_curve(logits: torch.Tensor, target: Optional[torch.Tensor] = None, a
     return torch.where(valid[None], prob, torch.zeros(())), hit & valid[None], target
 
 
-_PERTURB_METHODS = ("relevance", "saliency", "attention", "random")
+_PERTURB_METHODS = ("relevance", "saliency", "attention", "random", "integrated_gradients")
 
 
 @torch.no_grad()
@@ -173,7 +173,8 @@ def _appearance_cls_attention(model, batch: Dict[str, torch.Tensor]) -> torch.Te
 def appearance_attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator: Optional[torch.Generator] = None, head: Optional[str] = None) -> torch.Tensor:
     """One (B,C) score per video cell (or feature column) from `method`, the appearance counterpart of attribution_scores: "relevance" —
     forward_relevance's appearance_relevance[:, 1:]; "saliency" — |video_frames_grad| (or |appearance_features_grad|) summed over each
-    cell and all channels (stlt_cell_pool_abs); "attention" — the CLS row of the last appearance self-attention
+    cell and all channels (stlt_cell_pool_abs); "integrated_gradients" — forward_integrated_gradients' cell_attribution, signed (stlt_cell_pool_sum);
+    "attention" — the CLS row of the last appearance self-attention
     (_appearance_cls_attention); "random" — uniform numbers from `generator`; or a callable (model, batch) -> scores.  `head` goes to the
     fusion models' forward_relevance / forward_saliency.  Resnet3D has neither attention nor relevance and refuses the two."""
     from . import collate, ops
@@ -190,6 +191,9 @@ def appearance_attribution_scores(model, batch: Dict[str, torch.Tensor], method,
                                                else batch)
     if method == "saliency":
         return ops.cell_pool_abs(model.forward_saliency(batch, **kw)[key + "_grad"].contiguous(), cell)
+    if method == "integrated_gradients":
+        side = {"modality": "appearance"} if "layout" in getattr(model, "perturb_modalities", ()) else {}
+        return model.forward_integrated_gradients(batch, **kw, **side)["cell_attribution"]
     if method == "random":
         return torch.rand((batch[key].shape[0], grid[0] * grid[1] * grid[2]), generator=generator, device=batch[key].device, dtype=torch.float32)
     raise StltHipError(f"method: expected one of {_PERTURB_METHODS} or a callable (model, batch) -> scores, got {method!r}")
@@ -197,7 +201,8 @@ def appearance_attribution_scores(model, batch: Dict[str, torch.Tensor], method,
 
 def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator: Optional[torch.Generator] = None, head: Optional[str] = None) -> torch.Tensor:
     """One (B,T,N) score per object slot from `method`: "relevance" — forward_relevance's map; "saliency" — |boxes_grad| summed over the four
-    coordinates, plus |scores_grad| when the batch has scores; "attention" — the last layers' raw attention joined like the relevance,
+    coordinates, plus |scores_grad| when the batch has scores; "integrated_gradients" — forward_integrated_gradients' signed
+    object_attribution (zero baseline, 16 steps); "attention" — the last layers' raw attention joined like the relevance,
     temporal_attention[-1][b, lengths[b]-1, t] * spatial_attention[-1][b,t,0,n]; "random" — uniform numbers from `generator`; or a callable
     (model, batch) -> scores.  `head` (the fusion models): the logits the relevance and the saliency are taken from."""
     if callable(method):
@@ -209,6 +214,9 @@ def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator:
         out = model.forward_saliency(batch, **kw)
         s = out["boxes_grad"].abs().sum(-1)
         return s + out["scores_grad"].abs() if "scores_grad" in out else s
+    if method == "integrated_gradients":
+        side = {"modality": "layout"} if "appearance" in getattr(model, "perturb_modalities", ()) else {}
+        return model.forward_integrated_gradients(batch, **kw, **side)["object_attribution"]
     if method == "attention":
         out = model.forward_attention(batch)
         B = batch["categories"].shape[0]

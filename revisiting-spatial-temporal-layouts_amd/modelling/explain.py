@@ -1,10 +1,13 @@
-"""The Python shell of the explanation calls — ``forward_attention``, ``forward_saliency``, ``forward_relevance``, ``forward_perturbed`` and
-``forward_prefixes`` — written once for Stlt, Resnet3D, TransformerResnet, CrossAttentionFusion, CrossAttentionCentralNetFusion and
+"""The Python shell of the explanation calls — ``forward_attention``, ``forward_saliency``, ``forward_relevance``, ``forward_perturbed``,
+``forward_integrated_gradients`` and ``forward_prefixes`` — written once for Stlt, Resnet3D, TransformerResnet, CrossAttentionFusion, CrossAttentionCentralNetFusion and
 LateConcatenationFusion: the refusals of an inference call (``require_inference``), the target of a saliency / relevance pass and its seed
 (``parse_target``, ``logit_seed``, ``saliency_seed``), the choice of a head (``pick_head``), and the perturbation test of Chefer, Gur and
 Wolf (2021) on the layout side, the appearance side, or both (``forward_perturbed``): rank (stlt_perturb_rank / stlt_perturb_rank_cells),
 delete for a rising k (stlt_perturb_apply / stlt_perturb_apply_cells), the model's ordinary forward on every reduced batch, one launch for
 the curves (stlt_perturb_curve).  Nothing is read back; the whole call is capturable once the model's workspaces have their size.
+``forward_integrated_gradients`` (Sundararajan, Taly, Yan 2017) is the same kind of shell around each model's own ``forward_saliency``:
+the path batches of a pass in one launch per input (stlt_ig_path / stlt_ig_path_dense), the model's sweep on them, the quadrature in a
+fixed order (stlt_ig_reduce), the completeness gap on the device (stlt_ig_delta).
 
 What an appearance token's deletion means is written down at ``collate.perturb_cells``: the reference's appearance encoder takes no
 key-padding mask (src/modelling/models.py:269), so the stride block of the token — its cell — is set to ``fill`` in the video.
@@ -35,8 +38,22 @@ def require_inference(who: str, *, dropout_live: bool = False, skip_padding: boo
         raise L.StltHipError(f"{who} runs on the GPU: {holder} CPU tensors (move the model and the batch to a cuda device)")
 
 
+class InputRowSeed:
+    """The target of a ``forward_saliency`` call on a step-major pass of ``forward_integrated_gradients`` whose last ``B`` rows are the
+    unperturbed input: every row is seeded with the top-1 class of its own clip's input row (stlt_saliency_seed on those rows, tiled), so
+    the class comes from logits the pass itself produces and nothing is read back."""
+
+    def __init__(self, B: int):
+        self.B = int(B)
+
+    def resolve(self, logits: torch.Tensor) -> torch.Tensor:
+        return _tile(logit_seed(logits[logits.shape[0] - self.B:].contiguous(), None, None), logits.shape[0] // self.B)
+
+
 def parse_target(who: str, target, B: int, K: int, device):
     """The three forms of a saliency / relevance target -> (int64 classes or None, float seed or None); both None: top-1."""
+    if isinstance(target, InputRowSeed):
+        return None, target
     if isinstance(target, torch.Tensor) and target.is_floating_point():
         if tuple(target.shape) != (B, K) or target.device != device:
             raise L.StltHipError(f"{who}: a float target is the (B, num_classes) = ({B}, {K}) seed on the batch's device, got {tuple(target.shape)} on {target.device}")
@@ -50,6 +67,8 @@ def parse_target(who: str, target, B: int, K: int, device):
 
 def logit_seed(logits: torch.Tensor, tgt, seed) -> torch.Tensor:
     """d(objective)/d(logits) of a saliency / relevance pass: the caller's float seed, or stlt_saliency_seed's one-hot rows"""
+    if isinstance(seed, InputRowSeed):
+        return seed.resolve(logits)
     if seed is None:
         seed = torch.empty_like(logits)
         with torch.cuda.device(logits.device):
@@ -179,4 +198,140 @@ def forward_perturbed(model, batch: Dict[str, torch.Tensor], scores, steps: int 
         result.update(removed=removed["appearance"], n_candidates=n_app)
     else:
         result.update(removed=removed["layout"], n_candidates=n_lay)
+    return result
+
+
+IG_BASELINE_KEYS = ("boxes", "scores", "video_frames", "appearance_features")
+
+
+@torch.no_grad()
+def forward_integrated_gradients(model, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass: Optional[int] = None,
+                                 head: Optional[str] = None, modality: Optional[str] = None, dropout_live: bool = False, modalities=MODALITIES,
+                                 has_trunk: bool = True, num_classes: Optional[int] = None, takes_head: bool = False) -> Dict[str, torch.Tensor]:
+    """See Stlt.forward_integrated_gradients and CrossAttentionFusion.forward_integrated_gradients.  ``modalities``: what this model reads
+    (its ``perturb_modalities``); ``dropout_live``: the model's own answer; ``has_trunk``: a fusion model built with
+    ``appearance_trunk=True``; ``num_classes``: the width of the logits when the model knows it before a forward (a float target is then
+    checked against it here); ``takes_head``: the model's ``forward_saliency`` takes ``head``.
+    Per pass of at most ``steps_per_pass`` steps, from the input end of the path downwards: one path launch per moved input, the model's
+    own ``forward_saliency`` on the pass's (n*B)-clip batch with the target tiled, one stlt_ig_reduce per moved input.  Within a pass the
+    steps are added in ascending s; the passes themselves run from the highest steps to the lowest, so the order of the sum is a function
+    of ``steps`` and ``steps_per_pass`` alone and two calls give the same bits."""
+    who = "forward_integrated_gradients"
+    require_inference(who, dropout_live=dropout_live)
+    has_lay, has_app = "layout" in modalities, "appearance" in modalities
+    if modality is None:
+        modality = "both" if has_lay and has_app else ("layout" if has_lay else "appearance")
+    if modality not in MODALITIES:
+        raise L.StltHipError(f"{who}: modality: expected one of {MODALITIES}, got {modality!r}")
+    if modality not in modalities:
+        raise L.StltHipError(f"{who}: this model reads the {'layout' if has_lay else 'appearance'} side only: modality {modality!r} is not one of {tuple(modalities)}")
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1 or steps >= 1 << 23:
+        raise L.StltHipError(f"{who}: steps must be an integer >= 1 (and below 2^23), got {steps!r}")
+    S = steps + 1
+    per = S if steps_per_pass is None else steps_per_pass
+    if isinstance(per, bool) or not isinstance(per, int) or per < 1:
+        raise L.StltHipError(f"{who}: steps_per_pass must be an integer >= 1, got {steps_per_pass!r}")
+    per = min(per, S)
+    if per > L.IG_MAX_STEPS:
+        raise L.StltHipError(f"{who}: one pass holds at most {L.IG_MAX_STEPS} steps, got {per} (set steps_per_pass)")
+    names = tuple(model.logit_names)
+    head = pick_head(who, names, head) if takes_head else names[-1]
+    do_app, do_lay = modality in ("appearance", "both"), modality in ("layout", "both")
+    app_key = None
+    if has_app:
+        app_key = "appearance_features" if has_lay and "appearance_features" in batch else "video_frames"
+        if app_key not in batch:
+            raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))" if has_lay
+                                 else f"{who}: the batch needs `video_frames`")
+        if has_lay and app_key == "video_frames" and not has_trunk:
+            raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))")
+    require_inference(who, tensors=([batch[app_key]] if has_app else []) + ([batch["categories"]] if has_lay else []))
+    first_t = batch["categories"] if has_lay else batch[app_key]
+    device, B = first_t.device, first_t.shape[0]
+    core = {k: batch[k].contiguous() for k in _LAYOUT_KEYS if k in batch} if has_lay else {}
+    counts = {k: batch[k] for k in ("num_real_tokens", "num_real_frames") if k in batch} if has_lay else {}
+    if any(isinstance(v, torch.Tensor) and v.is_cuda for v in counts.values()):
+        raise L.StltHipError("num_real_tokens / num_real_frames must be host integers (a device tensor would have to be read back, which is what they are there to avoid)")
+    counts = {k: int(v) for k, v in counts.items()}
+    x_app = ops._chk(batch[app_key].contiguous(), torch.float32, app_key) if has_app else None
+    moved = {}  # key -> the input the path moves, in the order the attributions are summed in
+    if do_lay:
+        moved["boxes"] = ops._chk(core["boxes"], torch.float32, "boxes")
+        if "scores" in core:
+            moved["scores"] = ops._chk(core["scores"], torch.float32, "scores")
+    if do_app:
+        moved[app_key] = x_app
+    if baseline is None:
+        baseline = {}
+    if not isinstance(baseline, dict):
+        raise L.StltHipError(f"{who}: baseline is None or a dict with any of {IG_BASELINE_KEYS}, got {type(baseline).__name__}")
+    for k, v in baseline.items():
+        if k not in IG_BASELINE_KEYS:
+            raise L.StltHipError(f"{who}: baseline: unknown key {k!r} (expected any of {IG_BASELINE_KEYS})")
+        if k not in moved:
+            raise L.StltHipError(f"{who}: baseline[{k!r}]: modality {modality!r} does not move `{k}` on this batch (it moves {tuple(moved)})")
+        x = moved[k]
+        if not isinstance(v, torch.Tensor) or tuple(v.shape) != tuple(x.shape) or v.dtype != x.dtype or v.device != x.device:
+            raise L.StltHipError(f"{who}: baseline[{k!r}] must have the input's shape, dtype and device — {tuple(x.shape)}, {x.dtype}, {x.device} — got "
+                                 f"{(tuple(v.shape), v.dtype, v.device) if isinstance(v, torch.Tensor) else type(v).__name__}")
+    base = {k: (baseline[k].contiguous() if k in baseline else None) for k in moved}
+    # a bad target is refused here, before a tape is overwritten; the width of a float seed is checked where the model knows it
+    if isinstance(target, torch.Tensor) and target.is_floating_point():
+        if target.dim() != 2 or target.shape[0] != B or target.device != device or (num_classes is not None and target.shape[1] != num_classes):
+            raise L.StltHipError(f"{who}: a float target is the (B, num_classes) = ({B}, {num_classes if num_classes is not None else 'K'}) seed on the batch's device, "
+                                 f"got {tuple(target.shape)} on {target.device}")
+        tgt, seed = None, target.detach().to(torch.float32).contiguous()
+    elif target is not None:
+        tgt, seed = parse_target(who, target, B, 0, device)
+    else:
+        tgt, seed = None, None
+    kw = {"head": head} if takes_head else {}
+    acc = {k: torch.empty_like(v) for k, v in moved.items()}
+    attr, obj, x_logits, out = {}, None, None, None
+    hi = steps
+    while hi >= 0:
+        lo = max(hi - per + 1, 0)
+        n = hi - lo + 1
+        if do_lay:
+            part = ops.ig_path(core, steps, lo, hi, base["boxes"], base.get("scores"))
+        else:
+            part = {k: _tile(v, n) for k, v in core.items()}
+        part.update({k: v * n for k, v in counts.items()})
+        if do_app:
+            part[app_key] = ops.ig_path_dense(x_app, steps, lo, hi, base[app_key])
+        elif has_app:
+            part[app_key] = _tile(x_app, n)
+        if seed is not None:
+            t_arg = _tile(seed, n)
+        elif tgt is not None:
+            t_arg = _tile(tgt, n)
+        else:
+            t_arg = InputRowSeed(B)  # the first pass ends with the input's rows: their top-1 seeds every step
+        out = model.forward_saliency(part, target=t_arg, **kw)
+        if x_logits is None:
+            x_logits = {k: out[k][(n - 1) * B:].contiguous() for k in names}
+            seed_bk = seed if seed is not None else logit_seed(x_logits[head], tgt, None)
+            if tgt is None and seed is None:
+                tgt = seed_bk.argmax(dim=1)  # the one-hot row's only 1, still on the device; the later passes are seeded with it
+        finish = lo == 0
+        for k in (["scores"] if "scores" in moved else []) + [k for k in moved if k != "scores"]:  # the score term is ready when the boxes are grouped
+            g = out[k + "_grad"].contiguous()
+            if not finish:
+                ops.ig_reduce(g, acc[k], steps, lo, hi, begin=hi == steps)
+            elif k == "boxes":
+                attr[k], obj = ops.ig_reduce(g, acc[k], steps, lo, hi, begin=hi == steps, finish=True, x=moved[k], baseline=base[k], group=4, extra=attr.get("scores"))
+            else:
+                attr[k], _ = ops.ig_reduce(g, acc[k], steps, lo, hi, begin=hi == steps, finish=True, x=moved[k], baseline=base[k])
+        hi = lo - 1
+    base_logits = out[head][:B].contiguous()
+    result = dict(x_logits)
+    result.update(baseline_logits=base_logits, target=target if target is not None else tgt)
+    result["delta"] = ops.ig_delta([attr[k] for k in moved], seed_bk, x_logits[head], base_logits)
+    for k in moved:
+        result[k + "_attribution"] = attr[k]
+    if do_lay:
+        result["object_attribution"] = obj
+    if do_app:
+        _, cell, _ = collate.appearance_cells({app_key: x_app})
+        result["cell_attribution"] = ops.cell_pool_sum(attr[app_key], cell)
     return result

@@ -197,6 +197,12 @@ class TransformerResnet(nn.Module):
         return explain.forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
                                          activation=activation, dropout_live=self.training, modalities=self.perturb_modalities)
 
+    def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None) -> Dict[str, torch.Tensor]:
+        """As Resnet3D.forward_integrated_gradients, every pass being this model's own ``forward_saliency``.  Training mode keeps the
+        encoder's dropout live and is refused."""
+        return explain.forward_integrated_gradients(self, batch, target=target, steps=steps, baseline=baseline, steps_per_pass=steps_per_pass,
+                                                    dropout_live=self.training, modalities=self.perturb_modalities, num_classes=self.classifier.weight.shape[0])
+
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
 
@@ -427,6 +433,11 @@ class CrossAttentionFusionBackbone(nn.Module):
         """forward_perturbed of the fusion models (modelling/explain.py) with this backbone's answers: is dropout live, is there a trunk"""
         return explain.forward_perturbed(owner, batch, scores, dropout_live=self._dropout_live(), has_trunk=getattr(self.appearance_branch, "resnet", None) is not None, **kw)
 
+    def run_integrated_gradients(self, owner: nn.Module, batch, **kw):
+        """forward_integrated_gradients of the fusion models (modelling/explain.py) with this backbone's answers, as run_perturbed gives them"""
+        return explain.forward_integrated_gradients(owner, batch, dropout_live=self._dropout_live(), modalities=explain.MODALITIES, takes_head=True,
+                                                    has_trunk=getattr(self.appearance_branch, "resnet", None) is not None, **kw)
+
     def _native_args(self, batch, fusion_head, layout_head, appearance_head):
         """Marshal a batch and the parameters for the whole-path native calls (stlt_caf_forward_flags, stlt_caf_forward_attention):
         -> (stlt_caf_params, stlt_inputs, keep-alive, feature map, (B, T, N, feature channels, appearance tokens, classes))"""
@@ -563,6 +574,20 @@ class CrossAttentionFusion(nn.Module):
         return self.caf_backbone.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
                                           steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
 
+    def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None, head=None,
+                                     modality: str = "both") -> Dict[str, torch.Tensor]:
+        """Integrated gradients (Sundararajan, Taly, Yan 2017) of one raw logit per clip of head ``head`` (one of ``logit_names``; default
+        the last): Stlt.forward_integrated_gradients on either modality or on both.  ``modality`` says which inputs move along the path —
+        "layout": boxes and scores; "appearance": ``appearance_features`` when the batch carries them, else ``video_frames``; "both" —; the
+        others stay at the input and get no attribution key.  ``baseline``: None or a dict with any of "boxes" / "scores" /
+        "video_frames" / "appearance_features" (the moved ones), each of the input's shape, dtype and device; a missing one is all zeros,
+        for the video the dataset mean after Normalize(0.5, 0.5).  -> the logits at the input under ``logit_names``, "baseline_logits"
+        (B,K) of ``head``, "target", "delta" (B,) over every moved input together, "<key>_attribution" per moved input,
+        "object_attribution" (B,T,N) for the layout and "cell_attribution" (B,C) — the signed sum per cell of collate.appearance_cells
+        (stlt_cell_pool_sum) — for the appearance side.  Every pass is this model's own ``forward_saliency`` on the path batch."""
+        return self.caf_backbone.run_integrated_gradients(self, batch, target=target, steps=steps, baseline=baseline, steps_per_pass=steps_per_pass, head=head,
+                                               modality=modality)
+
 
 class CrossAttentionCentralNetFusion(nn.Module):
     """CACNF (models.py:501-549): ``forward(batch) -> {"stlt", "resnet3d", "caf", "ensemble"}``."""
@@ -604,6 +629,12 @@ class CrossAttentionCentralNetFusion(nn.Module):
         """As CrossAttentionFusion.forward_perturbed with this model's four heads (``head`` default "ensemble")."""
         return self.backbone.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
                                           steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
+
+    def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None, head=None,
+                                     modality: str = "both") -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_integrated_gradients with this model's four heads (``head`` default "ensemble"); an input the chosen head does not read gets zeros."""
+        return self.backbone.run_integrated_gradients(self, batch, target=target, steps=steps, baseline=baseline, steps_per_pass=steps_per_pass, head=head,
+                                               modality=modality)
 
 
 class LateConcatenationFusion(nn.Module):
@@ -673,6 +704,12 @@ class LateConcatenationFusion(nn.Module):
         """As CrossAttentionFusion.forward_perturbed."""
         return self._runner.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
                                           steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
+
+    def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None, head=None,
+                                     modality: str = "both") -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_integrated_gradients."""
+        return self._runner.run_integrated_gradients(self, batch, target=target, steps=steps, baseline=baseline, steps_per_pass=steps_per_pass, head=head,
+                                               modality=modality)
 
 
 from .models import models_factory  # noqa: E402

@@ -667,6 +667,29 @@ class Stlt(nn.Module):
                                          steps_per_pass=steps_per_pass, dataset_name=dataset_name, activation=activation, modalities=self.perturb_modalities,
                                          run_pass=run_pass)
 
+    def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None,
+                                     steps_per_pass: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Integrated gradients (Sundararajan, Taly, Yan 2017) of one raw logit per clip with respect to the layout: the signed, complete
+        member of the gradient family.  attr = (x - x0) * the integral of d logit / d x along the straight path from a baseline x0 to the
+        input x, by the trapezoid rule on S = steps + 1 points (include/stlt_hip.h spells out the fp32 arithmetic); the attributions sum
+        to logit(x) - logit(x0) up to the quadrature's error, which "delta" reports per clip.  What the reference needs S copies, a loop
+        of requires_grad_ / backward and a torch accumulation for is here: stlt_ig_path (all the path batches of a pass in one launch),
+        ``forward_saliency`` on them (the tape forward and the input-only sweep), stlt_ig_reduce (the quadrature, fixed order), and one
+        stlt_ig_delta at the end.  Nothing is read back.
+        ``target`` as in forward_saliency: None — each clip's top-1 class at the unperturbed input, taken from the logits of step
+        ``steps`` that this very call computes; an int64 (B,) tensor; a float (B, num_classes) seed.  ``baseline``: None — all zeros — or a
+        dict with "boxes" and / or "scores", each of the input's shape, dtype and device.  ``steps_per_pass``: how many of the S steps one
+        tape forward and sweep hold (default: all).  Passes start at the input end of the path; inside a pass the steps are added in
+        ascending s, so the order of the sum — and every bit of the result — is a function of (steps, steps_per_pass) alone.
+        -> {"stlt": (B,K) logits at the input, "baseline_logits": (B,K), "target", "delta": (B,) = sum of the attributions -
+        seed . (logits - baseline_logits), "boxes_attribution": (B,T,N,4), "scores_attribution": (B,T,N) when the batch has scores,
+        "object_attribution": (B,T,N) = the four box terms plus the score term}.  Entries of padded object slots and frames are exactly
+        0.  Refuses what forward_saliency refuses (live dropout, CPU tensors), and bad ``steps``, baselines and targets, all before the
+        tape is overwritten.  Works with ``backbone.skip_padding`` on and off; touches no parameter's .grad."""
+        return explain.forward_integrated_gradients(self, batch, target=target, steps=steps, baseline=baseline, steps_per_pass=steps_per_pass,
+                                                    dropout_live=self.backbone._dropout_live(), modalities=self.perturb_modalities,
+                                                    num_classes=self.prediction_head.fc2.weight.shape[0])
+
 
 class _StltTrainFn(torch.autograd.Function):
     """Autograd shell of the native training step: forward = stlt_train_forward (records the tape), backward =

@@ -395,3 +395,13 @@ class Resnet3D(nn.Module):
         "n_candidates"}."""
         return explain.forward_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, target=target, steps_per_pass=steps_per_pass, fill=fill,
                                          activation=activation, modalities=self.perturb_modalities)  # no dropout in this model: never live
+
+    def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None) -> Dict[str, torch.Tensor]:
+        """Integrated gradients of one raw logit per clip with respect to the pixels: Stlt.forward_integrated_gradients with
+        ``video_frames`` as the moved input (stlt_ig_path_dense builds the path).  ``baseline``: None — all zeros, the dataset mean after
+        Normalize(0.5, 0.5) — or {"video_frames": a tensor of the input's shape, dtype and device}.
+        -> {"resnet3d": (B,K) logits at the input, "baseline_logits", "target", "delta" (B,), "video_frames_attribution" (B,3,T,H,W),
+        "cell_attribution" (B,C): the signed sum per cell of collate.appearance_cells (stlt_cell_pool_sum)}.  Every pass is
+        ``forward_saliency`` on the path batch: ``steps_per_pass`` bounds the clips one tape holds."""
+        return explain.forward_integrated_gradients(self, batch, target=target, steps=steps, baseline=baseline, steps_per_pass=steps_per_pass,
+                                                    modalities=self.perturb_modalities, num_classes=self.classifier.weight.shape[0])

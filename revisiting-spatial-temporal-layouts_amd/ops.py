@@ -462,6 +462,32 @@ PERTURB_KEYS = (("categories", torch.int64, 3), ("boxes", torch.float32, 4), ("s
                  ("frame_types", torch.int64, 2), ("src_key_padding_mask_frames", torch.uint8, 2), ("lengths", torch.int64, 1))
 
 
+def _layout_in_out(batch, n: int):
+    """The marshalling perturb_apply and ig_path share: the collated tensors of PERTURB_KEYS in `batch` (scores optional) checked and
+    packed into an stlt_inputs, and fresh outputs of the same keys for n * B clips (a bool mask comes back as bool).
+    -> (stlt_inputs, outputs, the checked input tensors — kept alive by the caller —, (B, T, N))"""
+    cats = _chk(batch["categories"], torch.int64, "categories")
+    if cats.dim() != 3:
+        raise L.StltHipError(f"categories must be (B,T,N), got {tuple(cats.shape)}")
+    B, T, N = cats.shape
+    shapes = {3: (B, T, N), 4: (B, T, N, 4), 2: (B, T), 1: (B,)}
+    inp, out, keep = L.Inputs(), {}, []
+    inp.B, inp.T, inp.N = B, T, N
+    for key, dtype, nd in PERTURB_KEYS:
+        if key == "scores" and key not in batch:
+            continue
+        t = batch[key]
+        if tuple(t.shape) != shapes[nd]:
+            raise L.StltHipError(f"{key}: expected shape {shapes[nd]}, got {tuple(t.shape)}")
+        was_bool = t.dtype == torch.bool
+        t = _mask_u8(t, key) if dtype == torch.uint8 else _chk(t, dtype, key)
+        keep.append(t)
+        o = torch.empty((n * B,) + shapes[nd][1:], device=cats.device, dtype=dtype)
+        out[key] = o.view(torch.bool) if was_bool else o
+        setattr(inp, {"src_key_padding_mask_boxes": "kpm_boxes", "src_key_padding_mask_frames": "kpm_frames"}.get(key, key), t.data_ptr())
+    return inp, out, keep, (B, T, N)
+
+
 def perturb_apply(batch, rank: torch.Tensor, n_candidates: torch.Tensor, steps: int, s0: int, s1: int, empty_frame_type: int, removed: Optional[torch.Tensor] = None):
     """Steps s0 .. s1 of the perturbation test's batches (include/stlt_hip.h: stlt_perturb_apply): `batch` holds the collated tensors
     (categories, boxes, [scores], both masks, frame_types, lengths), rank / n_candidates come from perturb_rank (rank (B,T,N): unit object,
@@ -479,23 +505,7 @@ def perturb_apply(batch, rank: torch.Tensor, n_candidates: torch.Tensor, steps: 
     if tuple(rank.shape) not in ((B, T, N), (B, T)) or tuple(n_candidates.shape) != (B,):
         raise L.StltHipError(f"rank is ({B},{T},{N}) (unit object) or ({B},{T}) (unit frame) and n_candidates ({B},), got {tuple(rank.shape)}, {tuple(n_candidates.shape)}")
     unit = 0 if rank.dim() == 3 else 1
-    shapes = {3: (B, T, N), 4: (B, T, N, 4), 2: (B, T), 1: (B,)}
-    n = s1 - s0 + 1
-    inp, out, keep = L.Inputs(), {}, []
-    inp.B, inp.T, inp.N = B, T, N
-    for key, dtype, nd in PERTURB_KEYS:
-        if key == "scores" and key not in batch:
-            continue
-        t = batch[key]
-        if tuple(t.shape) != shapes[nd]:
-            raise L.StltHipError(f"{key}: expected shape {shapes[nd]}, got {tuple(t.shape)}")
-        was_bool = t.dtype == torch.bool
-        t = _mask_u8(t, key) if dtype == torch.uint8 else _chk(t, dtype, key)
-        keep.append(t)
-        o = torch.empty((n * B,) + shapes[nd][1:], device=cats.device, dtype=dtype)
-        out[key] = o.view(torch.bool) if was_bool else o
-        setattr(inp, {"src_key_padding_mask_boxes": "kpm_boxes", "src_key_padding_mask_frames": "kpm_frames"}.get(key, key), t.data_ptr())
-        keep.append(o)
+    inp, out, keep, _ = _layout_in_out(batch, s1 - s0 + 1)
     if removed is None:
         removed = torch.full((steps + 1, B), -1, device=cats.device, dtype=torch.int32)
     else:
@@ -605,6 +615,152 @@ def cell_pool_abs(g: torch.Tensor, cell) -> torch.Tensor:
     out = torch.empty(B, grid[0] * grid[1] * grid[2], device=g.device, dtype=torch.float32)
     L.check(lib.stlt_cell_pool_abs(_p(g), B, Cch, T, H, W, ct, ch, cw, _p(out), _stream()), "stlt_cell_pool_abs")
     return out
+
+
+def cell_pool_sum(g: torch.Tensor, cell) -> torch.Tensor:
+    """The signed sum of g over every cell and all channels (include/stlt_hip.h: stlt_cell_pool_sum): cell_pool_abs without the magnitude,
+    for a signed attribution map.  g (B,Cch,T,H,W) float32, cell = (ct, ch, cw) -> (B,C) float32; the same fixed summation order."""
+    lib = L.load()
+    (B, Cch, T, H, W), (ct, ch, cw), grid = _cell_extents(g, cell, "g")
+    out = torch.empty(B, grid[0] * grid[1] * grid[2], device=g.device, dtype=torch.float32)
+    L.check(lib.stlt_cell_pool_sum(_p(g), B, Cch, T, H, W, ct, ch, cw, _p(out), _stream()), "stlt_cell_pool_sum")
+    return out
+
+
+def _ig_steps(steps, s0, s1):
+    steps, s0, s1 = int(steps), int(s0), int(s1)
+    if steps < 1 or not 0 <= s0 <= s1 <= steps:
+        raise L.StltHipError(f"steps >= 1 and 0 <= s0 <= s1 <= steps, got steps={steps}, s0={s0}, s1={s1}")
+    if s1 - s0 + 1 > L.IG_MAX_STEPS:
+        raise L.StltHipError(f"{s1 - s0 + 1} steps in one call (at most {L.IG_MAX_STEPS}; split the range)")
+    return steps, s0, s1
+
+
+def _ig_like(t: Optional[torch.Tensor], x: torch.Tensor, name: str) -> Optional[torch.Tensor]:
+    """a baseline (or a finishing call's input) of x's shape, float32, contiguous, on x's device — or None"""
+    if t is None:
+        return None
+    _chk(t, torch.float32, name)
+    if tuple(t.shape) != tuple(x.shape) or t.device != x.device:
+        raise L.StltHipError(f"{name}: expected shape {tuple(x.shape)} on {x.device}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def ig_path(batch, steps: int, s0: int, s1: int, boxes0: Optional[torch.Tensor] = None, scores0: Optional[torch.Tensor] = None):
+    """Steps s0 .. s1 of the integrated-gradients path of a layout batch (include/stlt_hip.h: stlt_ig_path): `batch` holds the collated
+    tensors of PERTURB_KEYS (scores optional); boxes and scores go to x0 + (s/steps) (x - x0) with the baselines boxes0 / scores0 (None:
+    zeros), step 0 being the baseline's bits and step `steps` the input's; the other tensors are replicated bit for bit.
+    -> dict of the same tensors for (s1-s0+1)*B clips, step-major."""
+    lib = L.load()
+    steps, s0, s1 = _ig_steps(steps, s0, s1)
+    inp, out, keep, _ = _layout_in_out(batch, s1 - s0 + 1)
+    boxes0 = _ig_like(boxes0, batch["boxes"], "boxes0")
+    if scores0 is not None and "scores" not in batch:
+        raise L.StltHipError("scores0: the batch has no scores")
+    scores0 = _ig_like(scores0, batch["scores"], "scores0") if scores0 is not None else None
+    L.check(lib.stlt_ig_path(C.byref(inp), _p(boxes0), _p(scores0), steps, s0, s1, _p(out["categories"]), _p(out["boxes"]), _p(out.get("scores")),
+                             _p(out["src_key_padding_mask_boxes"]), _p(out["frame_types"]), _p(out["src_key_padding_mask_frames"]), _p(out["lengths"]), _stream()),
+            "stlt_ig_path")
+    return out
+
+
+def ig_path_dense(x: torch.Tensor, steps: int, s0: int, s1: int, baseline: Optional[torch.Tensor] = None, fill: float = 0.0, out: Optional[torch.Tensor] = None):
+    """Steps s0 .. s1 of the path of one dense float32 tensor x (B, ...) (include/stlt_hip.h: stlt_ig_path_dense): baseline of x's shape,
+    or None: every baseline element is `fill`.  -> ((s1-s0+1)*B, ...) step-major.  `out`: write into this float32 tensor of that many
+    contiguous elements, whatever its alignment."""
+    lib = L.load()
+    _chk(x, torch.float32, "x")
+    if x.dim() < 1 or x.numel() == 0:
+        raise L.StltHipError(f"x: expected (B, ...) with at least one element, got {tuple(x.shape)}")
+    steps, s0, s1 = _ig_steps(steps, s0, s1)
+    baseline = _ig_like(baseline, x, "baseline")
+    B, n = x.shape[0], x.numel() // x.shape[0]
+    cnt = s1 - s0 + 1
+    if out is None:
+        out = torch.empty((cnt * B,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, torch.float32, "out")
+        if out.numel() != cnt * x.numel():
+            raise L.StltHipError(f"out: expected {cnt * x.numel()} elements, got {out.numel()}")
+    L.check(lib.stlt_ig_path_dense(_p(x), _p(baseline), float(fill), B, n, steps, s0, s1, _p(out), _stream()), "stlt_ig_path_dense")
+    return out
+
+
+def ig_reduce(g: torch.Tensor, acc: torch.Tensor, steps: int, s0: int, s1: int, begin: bool = False, finish: bool = False, x: Optional[torch.Tensor] = None,
+              baseline: Optional[torch.Tensor] = None, fill: float = 0.0, attr: Optional[torch.Tensor] = None, group: int = 1,
+              extra: Optional[torch.Tensor] = None, grouped: Optional[torch.Tensor] = None):
+    """The quadrature of integrated gradients (include/stlt_hip.h: stlt_ig_reduce): g ((s1-s0+1)*B, ...) — the gradients at steps s0 .. s1,
+    step-major — is added into acc (B, ...) in place, acc <- acc + w_s g_s for ascending s; `begin`: acc starts from 0 and is not read;
+    `finish`: also attr = (x - baseline) * acc (baseline None: `fill`), and with group > 1 the sum of every run of `group` consecutive
+    attributions plus `extra`.  -> acc, or with `finish` (attr, grouped-or-None); `attr` / `grouped`: write into these tensors."""
+    lib = L.load()
+    _chk(g, torch.float32, "g"); _chk(acc, torch.float32, "acc")
+    steps, s0, s1 = _ig_steps(steps, s0, s1)
+    cnt = s1 - s0 + 1
+    if acc.dim() < 1 or acc.numel() == 0 or g.numel() != cnt * acc.numel() or g.device != acc.device:
+        raise L.StltHipError(f"g: expected {cnt} steps of acc's {tuple(acc.shape)} on {acc.device}, got {tuple(g.shape)} on {g.device}")
+    B, n = acc.shape[0], acc.numel() // acc.shape[0]
+    flags = (L.IG_BEGIN if begin else 0) | (L.IG_FINISH if finish else 0)
+    group = int(group)
+    if not finish:
+        if x is not None or attr is not None or grouped is not None or extra is not None or group != 1:
+            raise L.StltHipError("x, attr, group, extra and grouped belong to the finishing call (finish=True)")
+        L.check(lib.stlt_ig_reduce(_p(g), B, n, steps, s0, s1, flags, _p(acc), None, None, 0.0, None, 1, None, None, _stream()), "stlt_ig_reduce")
+        return acc
+    if x is None:
+        raise L.StltHipError("the finishing call takes x, the input the attributions are of")
+    x = _ig_like(x, acc, "x")
+    baseline = _ig_like(baseline, acc, "baseline")
+    attr = torch.empty_like(acc) if attr is None else _ig_like(attr, acc, "attr")
+    if group < 1 or n % group:
+        raise L.StltHipError(f"group: expected a divisor of the {n} elements of a clip, got {group}")
+    if group > 1 or grouped is not None or extra is not None:
+        gshape = (tuple(acc.shape[:-1]) if acc.shape[-1] == group and acc.dim() > 1 else (B, n // group))
+        if grouped is None:
+            grouped = torch.empty(gshape, device=acc.device, dtype=torch.float32)
+        _chk(grouped, torch.float32, "grouped")
+        if grouped.numel() != B * (n // group) or grouped.device != acc.device:
+            raise L.StltHipError(f"grouped: expected {B * (n // group)} elements on {acc.device}, got {grouped.numel()} on {grouped.device}")
+        if extra is not None:
+            _chk(extra, torch.float32, "extra")
+            if extra.numel() != grouped.numel() or extra.device != acc.device:
+                raise L.StltHipError(f"extra: expected {grouped.numel()} elements on {acc.device}, got {extra.numel()} on {extra.device}")
+    L.check(lib.stlt_ig_reduce(_p(g), B, n, steps, s0, s1, flags, _p(acc), _p(x), _p(baseline), float(fill), _p(attr), group, _p(extra), _p(grouped), _stream()),
+            "stlt_ig_reduce")
+    return attr, grouped
+
+
+def ig_delta(attrs, seed: torch.Tensor, logits_x: torch.Tensor, logits_x0: torch.Tensor, max_blocks: int = 0, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The completeness gap of integrated gradients (include/stlt_hip.h: stlt_ig_delta): attrs — one to three float32 attribution tensors
+    (B, ...) —, seed / logits_x / logits_x0 (B,K) float32 -> delta (B,) = sum of clip b's attributions - sum_k seed (logits_x - logits_x0).
+    A fixed partition: `max_blocks` (0: the default grid) changes no bit.  `scratch`: a float32 tensor for the partials (default: a fresh one)."""
+    lib = L.load()
+    attrs = list(attrs)
+    if not 1 <= len(attrs) <= 3:
+        raise L.StltHipError(f"attrs: expected one to three tensors, got {len(attrs)}")
+    _chk(seed, torch.float32, "seed")
+    if seed.dim() != 2 or seed.shape[1] < 1:
+        raise L.StltHipError(f"seed: expected (B,K), got {tuple(seed.shape)}")
+    B, K = seed.shape
+    for name, t in (("logits_x", logits_x), ("logits_x0", logits_x0)):
+        _ig_like(t, seed, name)
+    ns = []
+    for i, a in enumerate(attrs):
+        _chk(a, torch.float32, f"attrs[{i}]")
+        if a.dim() < 1 or a.shape[0] != B or a.device != seed.device or (B and a.numel() == 0):
+            raise L.StltHipError(f"attrs[{i}]: expected ({B}, ...) on {seed.device}, got {tuple(a.shape)} on {a.device}")
+        ns.append(a.numel() // B if B else 0)
+    ptrs = [_p(a) for a in attrs] + [None] * (3 - len(attrs))
+    ns += [0] * (3 - len(ns))
+    need = lib.stlt_ig_delta_scratch_bytes(B, *ns)
+    if scratch is None:
+        scratch = torch.empty(max(need // 4, 1), device=seed.device, dtype=torch.float32)
+    else:
+        _chk(scratch, torch.float32, "scratch")
+    delta = torch.empty(B, device=seed.device, dtype=torch.float32)
+    L.check(lib.stlt_ig_delta(ptrs[0], ns[0], ptrs[1], ns[1], ptrs[2], ns[2], _p(seed), _p(logits_x), _p(logits_x0), B, K, int(max_blocks), _p(scratch),
+                              scratch.numel() * 4, _p(delta), _stream()), "stlt_ig_delta")
+    return delta
 
 
 def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
