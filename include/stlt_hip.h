@@ -711,6 +711,22 @@ size_t stlt_r3d_backward_inputs_workspace_bytes(int64_t B, int64_t T, int64_t H,
 int stlt_r3d_backward_inputs(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H,
                              int64_t W, const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate, float* dvideo,
                              void* workspace, size_t workspace_bytes, stlt_stream_t stream);
+/* ---- the trunk's stages, for class activation maps (csrc/r3d.hip; the reductions are further below: Grad-CAM) ----
+ * stlt_r3d_layer_geometry: layer 1 .. 4 -> dims[4] = (t, h, w, c) of that stage's output, (B, t, h, w, c) NDHWC on the tape, and the byte
+ *     offset of its slot in a stlt_r3d_train_forward tape (the output of the stage's last block, after its ReLU; 256-byte aligned).  Pure
+ *     host arithmetic from the trunk's plan, callable without a GPU; STLT_EINVAL for layer outside 1 .. 4, a NULL pointer, and exactly the
+ *     shapes stlt_r3d_tape_bytes returns 0 for.
+ * stlt_r3d_backward_layer: the reverse sweep of stlt_r3d_backward_inputs with dweight NULL (input-only: no weight-gradient launch), from the
+ *     top down to the first block of stage layer + 1, where it stops: dlayer (B, t, h, w, c) NDHWC, 16-byte aligned, receives the gradient
+ *     with respect to stage `layer`'s output AFTER its ReLU — the ReLU mask of that output is NOT applied, where the full sweep applies it
+ *     because its next consumer wants the pre-ReLU gradient: a hook on layerN's output in the reference's trunk sees the unmasked one, and
+ *     Grad-CAM needs that.  layer is 1 .. 3 (stage 4's gradient is the call's own dfeatures / dpooled); tape, dfeatures / dpooled, the
+ *     refusals and the workspace (stlt_r3d_backward_workspace_bytes) as stlt_r3d_backward_inputs; dgrad_w[0], the stem's thin copy, is not
+ *     read.  The launches above the stop are those of the input-only sweep, with its bits. */
+int stlt_r3d_layer_geometry(int64_t B, int64_t T, int64_t H, int64_t W, int layer, int64_t dims[4], size_t* tape_offset);
+int stlt_r3d_backward_layer(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H,
+                            int64_t W, const float* dfeatures, const float* dpooled, int layer, float* dlayer, void* workspace, size_t workspace_bytes,
+                            stlt_stream_t stream);
 
 /* ---- training step (reference src/train.py:119-135: forward, loss.backward(); optimiser step further below) ----
  * stlt_train_forward runs every layer on every row — except that the last layer of each tower runs its out-proj /
@@ -1210,6 +1226,40 @@ int stlt_ig_reduce(const float* g, int64_t B, int64_t n, int64_t steps, int64_t 
 size_t stlt_ig_delta_scratch_bytes(int64_t B, int64_t n0, int64_t n1, int64_t n2);
 int stlt_ig_delta(const float* a0, int64_t n0, const float* a1, int64_t n1, const float* a2, int64_t n2, const float* seed, const float* logits_x,
                   const float* logits_x0, int64_t B, int64_t K, int64_t max_blocks, void* scratch, size_t scratch_bytes, float* delta, stlt_stream_t stream);
+
+/* ---- class activation maps (csrc/gradcam.hip) ----
+ * Grad-CAM (Selvaraju et al., ICCV 2017) at a stage of the trunk: with a the stage's activations and g the gradient of one logit with
+ * respect to them, alpha[b,c] = mean over the positions p of g, cam[b,p] = relu(sum_c alpha[b,c] a[b,p,c]); HiResCAM (Draelos and Carin,
+ * 2020) multiplies element by element instead: cam[b,p] = relu(sum_c g[b,p,c] a[b,p,c]).  P is the number of positions (t h w), layout
+ * STLT_CAM_NDHWC: a and g are (B, P, C), as on the trunk's tape and as stlt_r3d_backward_layer writes; STLT_CAM_NCDHW: (B, C, P), as
+ * appearance_features and its gradient.  One contract: stream-ordered, no allocation, no synchronisation, no read-back, capturable; no
+ * float atomics, every sum owned by one wave or one fixed group of lanes and added in an order that depends on (P, C, layout) alone, so a
+ * clip's values are the same bits whatever B is and from run to run; STLT_EINVAL with a message and no launch on a NULL pointer, B < 0,
+ * P < 1, C < 1, a tensor of 2^31 elements or more, an unknown layout or a pointer off its element's 4 bytes; B == 0 returns 0.
+ *
+ * stlt_cam_weights: alpha (B,C)[b,c] = (sum_p g[b,p,c]) / P.  NDHWC: lanes along c — 16-byte loads when C % 4 == 0 and g is 16-byte
+ *     aligned, one float per lane otherwise, the same bits —, P cut into chunks of STLT_CAM_CHUNK positions (four accumulators, position p of
+ *     a chunk to accumulator p % 4, then (a0 + a1) + (a2 + a3)); more than one chunk: the partials go to scratch (B, chunks, C) and a second
+ *     launch adds them in ascending order; then one division by (float)P.  scratch: stlt_cam_scratch_bytes(B, P, C) bytes (pure host
+ *     arithmetic; 0 when P <= STLT_CAM_CHUNK or the shape is refused), 16-byte aligned, STLT_EWORKSPACE otherwise; not read for NCDHW.
+ *     NCDHW: a wave per (b,c) row, lane l adds elements l, l + 64, ... in order, then the DPP wave sum (csrc/wave_dpp.h).
+ *     Error against the exact mean: below P 2^-24 sum_p|g| / P plus the division's rounding.  Reads B P C floats, writes B C.
+ * stlt_cam_map: cam (B,P)[b,p] = sum_c w a, w = alpha (B,C) with per_element == 0 (Grad-CAM), w of a's shape and layout with
+ *     per_element != 0 (HiResCAM); relu != 0: a result that is not positive is stored as +0.  NDHWC: a wave per position, lane l an fmaf
+ *     chain over the channels of the quads l, l + 64, ... in ascending order (16-byte loads under the alignment rule above, the same bits either way), then the DPP wave sum.
+ *     NCDHW: a workgroup per 32 positions of a clip, 16 lane groups, group q an fmaf chain over channels q, q + 16, ..., the 16 partials
+ *     added in ascending order.  Error below (C + 1) 2^-24 sum_c|w a|.  Reads B P C floats of a (and of w when per_element), writes B P.
+ * stlt_cam_upsample: out (B,T,H,W) = the trilinear resize of cam (B,gt,gh,gw) by the rule of torch's
+ *     F.interpolate(mode="trilinear", align_corners=False): per axis the source coordinate of output index d is (in / out) (d + 0.5) - 0.5
+ *     in fp32, clamped at 0; its floor i0 and i1 = min(i0 + 1, in - 1) are blended with l1 = the fraction and l0 = 1 - l1, w innermost, then
+ *     h, then t.  One thread per output element, coalesced stores; extents from 1 to 65536.  Error below (18 max(gt,gh,gw) + 18) 2^-24 max|cam|. */
+#define STLT_CAM_NDHWC 0
+#define STLT_CAM_NCDHW 1
+#define STLT_CAM_CHUNK 32
+size_t stlt_cam_scratch_bytes(int64_t B, int64_t P, int64_t C);
+int stlt_cam_weights(const float* g, int64_t B, int64_t P, int64_t C, int layout, float* alpha, void* scratch, size_t scratch_bytes, stlt_stream_t stream);
+int stlt_cam_map(const float* a, const float* w, int per_element, int64_t B, int64_t P, int64_t C, int layout, int relu, float* cam, stlt_stream_t stream);
+int stlt_cam_upsample(const float* cam, int64_t B, int64_t gt, int64_t gh, int64_t gw, int64_t T, int64_t H, int64_t W, float* out, stlt_stream_t stream);
 
 /* ---- per-kernel timing (bench.py roofline leg): hipEvents around every launch of the whole-path calls ---- */
 #define STLT_K_EMBED 0

@@ -23,6 +23,8 @@ PERTURB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # STLT_PERTURB_SOFTMAX / _SI
 IG_BEGIN, IG_FINISH = 1, 2  # STLT_IG_BEGIN / _FINISH
 IG_MAX_STEPS = 256          # STLT_IG_MAX_STEPS: the steps of one stlt_ig_path / _path_dense / _reduce call
 IG_DELTA_CHUNK = 4096       # STLT_IG_DELTA_CHUNK
+CAM_LAYOUTS = {"ndhwc": 0, "ncdhw": 1}  # STLT_CAM_NDHWC / _NCDHW
+CAM_CHUNK = 32              # STLT_CAM_CHUNK: the positions of one partial of stlt_cam_weights in NDHWC
 
 _f = C.POINTER(C.c_float)
 _i64 = C.POINTER(C.c_int64)
@@ -324,6 +326,13 @@ SIGNATURES = {
     "stlt_r3d_backward_inputs_workspace_bytes": (C.c_size_t, [C.c_int64] * 4),
     "stlt_r3d_backward_inputs": (C.c_int, [C.POINTER(R3dParams), _vp, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int,
                                            _vp, _vp, C.c_size_t, _vp]),
+    "stlt_r3d_layer_geometry": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _vp, _vp]),
+    "stlt_r3d_backward_layer": (C.c_int, [C.POINTER(R3dParams), _vp, _vp, C.c_size_t, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, C.c_int, _vp, _vp,
+                                          C.c_size_t, _vp]),
+    "stlt_cam_scratch_bytes": (C.c_size_t, [C.c_int64] * 3),
+    "stlt_cam_weights": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "stlt_cam_map": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _vp, _vp]),
+    "stlt_cam_upsample": (C.c_int, [_vp] + [C.c_int64] * 7 + [_vp, _vp]),
 }
 
 _lib = None

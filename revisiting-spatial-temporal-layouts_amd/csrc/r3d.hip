@@ -1232,6 +1232,14 @@ int check_r3d_params(const stlt_r3d_params* p, const char* who) {
   return 0;
 }
 
+// the first block of stage `layer` (1 .. R3D_LAYERS: the layer-th block with a downsample); R3D_LAYERS + 1: one past the last block
+int stage_first_block(const TrunkPlan& P, int layer) {
+  int seen = 0;
+  for (int b = 0; b < R3D_NBLOCKS; ++b)
+    if (P.blk[b].ds && ++seen == layer) return b;
+  return R3D_NBLOCKS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1439,9 +1447,11 @@ int stlt_r3d_train_forward(const stlt_r3d_params* p, const float* video, int64_t
 }  // extern "C"
 
 // the trunk's reverse sweep, written once: stlt_r3d_backward (dweight, no dvideo) and stlt_r3d_backward_inputs (either or both)
+// (dlayer: stlt_r3d_backward_layer's stop — the sweep ends at the first block of stage `layer` + 1, whose input gradient goes to dlayer
+// without the ReLU mask of that input)
 static int r3d_backward_sweep(const char* who, const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B,
                               int64_t T, int64_t H, int64_t W, const float* dfeatures, const float* dpooled, float* const* dweight, int accumulate,
-                              float* dvideo, void* workspace, size_t workspace_bytes, stlt_stream_t stream) {
+                              float* dvideo, void* workspace, size_t workspace_bytes, stlt_stream_t stream, int layer = 0, float* dlayer = nullptr) {
   if (int e = check_r3d_params(p, who)) return e;
   if (!dgrad_w || !tape) return stlt_set_error(STLT_EINVAL, "%s: null pointer", who);
   if ((dfeatures == nullptr) == (dpooled == nullptr)) return stlt_set_error(STLT_EINVAL, "%s: pass exactly one of dfeatures and dpooled", who);
@@ -1467,6 +1477,7 @@ static int r3d_backward_sweep(const char* who, const stlt_r3d_params* p, const f
   float* GS = work(P.bws.gs);  // at the stem's output
   float* part = work(P.bws.part);
   const float eps = p->bn_eps;
+  const int stop = dlayer ? stage_first_block(P, layer + 1) : -1;  // the last block the sweep visits
   auto wgrad = [&](int i, const float* x, const float* g) -> int {
     if (!dweight) return 0;  // the input-only sweep: no weight-gradient product
     const ConvGeom& c = P.g[i];
@@ -1494,6 +1505,10 @@ static int r3d_backward_sweep(const char* who, const stlt_r3d_params* p, const f
     if (int e = wgrad(ci + 1, a1, G2)) return e;
     if (int e = dgrad(ci + 1, G2, a1, nullptr, G1)) return e;
     if (int e = wgrad(ci, x, G1)) return e;
+    if (bi == stop) {  // the same two products into dlayer, unmasked: the gradient at the stage's output after its ReLU, as a hook there sees it
+      if (int e = dgrad(ci, G1, nullptr, k.ds ? nullptr : G3, dlayer)) return e;
+      return k.ds ? dgrad(ci + 3, G3, nullptr, dlayer, dlayer) : 0;
+    }
     // block input: conv1's data gradient + the shortcut's (identity: G3 itself), masked by the input's ReLU
     if (int e = dgrad(ci, G1, xmask, k.ds ? nullptr : G3, GX)) return e;
     if (k.ds) {
@@ -1531,6 +1546,28 @@ int stlt_r3d_backward_inputs(const stlt_r3d_params* p, const float* const* dgrad
   if (!dweight && !dvideo) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward_inputs: dweight and dvideo are both null: nothing to compute");
   return r3d_backward_sweep("stlt_r3d_backward_inputs", p, dgrad_w, tape, tape_bytes, B, T, H, W, dfeatures, dpooled, dweight, accumulate, dvideo, workspace,
                             workspace_bytes, stream);
+}
+
+int stlt_r3d_layer_geometry(int64_t B, int64_t T, int64_t H, int64_t W, int layer, int64_t* dims, size_t* tape_offset) {
+  if (layer < 1 || layer > R3D_LAYERS) return stlt_set_error(STLT_EINVAL, "stlt_r3d_layer_geometry: layer is 1 to %d, got %d", R3D_LAYERS, layer);
+  if (!dims || !tape_offset) return stlt_set_error(STLT_EINVAL, "stlt_r3d_layer_geometry: null pointer");
+  TrunkPlan P;
+  if (!trunk_plan(B, T, H, W, &P)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_layer_geometry: bad video shape or too small for the trunk");
+  const TrunkBlock& k = P.blk[stage_first_block(P, layer + 1) - 1];  // the stage's last block
+  const ConvGeom& g = P.g[k.conv1 + 2];
+  dims[0] = g.To; dims[1] = g.Ho; dims[2] = g.Wo; dims[3] = g.N;
+  *tape_offset = (size_t)k.y;
+  return 0;
+}
+
+int stlt_r3d_backward_layer(const stlt_r3d_params* p, const float* const* dgrad_w, const void* tape, size_t tape_bytes, int64_t B, int64_t T, int64_t H,
+                            int64_t W, const float* dfeatures, const float* dpooled, int layer, float* dlayer, void* workspace, size_t workspace_bytes,
+                            stlt_stream_t stream) {
+  if (layer < 1 || layer >= R3D_LAYERS)
+    return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward_layer: layer is 1 to %d (the last stage's gradient is the call's own input), got %d", R3D_LAYERS - 1, layer);
+  if (!dlayer || ((uintptr_t)dlayer & 15)) return stlt_set_error(STLT_EINVAL, "stlt_r3d_backward_layer: dlayer is null or not 16-byte aligned");
+  return r3d_backward_sweep("stlt_r3d_backward_layer", p, dgrad_w, tape, tape_bytes, B, T, H, W, dfeatures, dpooled, nullptr, 0, nullptr, workspace,
+                            workspace_bytes, stream, layer, dlayer);
 }
 
 size_t stlt_conv3d_repack_dgrad_thin_floats(const stlt_conv3d_desc* d) {

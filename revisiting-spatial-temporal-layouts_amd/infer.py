@@ -146,7 +146,7 @@ def perturb_curve(logits: torch.Tensor, target: Optional[torch.Tensor] = None, a
     return torch.where(valid[None], prob, torch.zeros(())), hit & valid[None], target
 
 
-_PERTURB_METHODS = ("relevance", "saliency", "attention", "random", "integrated_gradients")
+_PERTURB_METHODS = ("relevance", "saliency", "attention", "random", "integrated_gradients", "gradcam")
 
 
 @torch.no_grad()
@@ -174,6 +174,7 @@ def appearance_attribution_scores(model, batch: Dict[str, torch.Tensor], method,
     """One (B,C) score per video cell (or feature column) from `method`, the appearance counterpart of attribution_scores: "relevance" —
     forward_relevance's appearance_relevance[:, 1:]; "saliency" — |video_frames_grad| (or |appearance_features_grad|) summed over each
     cell and all channels (stlt_cell_pool_abs); "integrated_gradients" — forward_integrated_gradients' cell_attribution, signed (stlt_cell_pool_sum);
+    "gradcam" — forward_gradcam's cell_attribution (Grad-CAM at the trunk's last stage, whose positions are the cells);
     "attention" — the CLS row of the last appearance self-attention
     (_appearance_cls_attention); "random" — uniform numbers from `generator`; or a callable (model, batch) -> scores.  `head` goes to the
     fusion models' forward_relevance / forward_saliency.  Resnet3D has neither attention nor relevance and refuses the two."""
@@ -194,6 +195,8 @@ def appearance_attribution_scores(model, batch: Dict[str, torch.Tensor], method,
     if method == "integrated_gradients":
         side = {"modality": "appearance"} if "layout" in getattr(model, "perturb_modalities", ()) else {}
         return model.forward_integrated_gradients(batch, **kw, **side)["cell_attribution"]
+    if method == "gradcam":
+        return model.forward_gradcam(batch, **kw)["cell_attribution"]
     if method == "random":
         return torch.rand((batch[key].shape[0], grid[0] * grid[1] * grid[2]), generator=generator, device=batch[key].device, dtype=torch.float32)
     raise StltHipError(f"method: expected one of {_PERTURB_METHODS} or a callable (model, batch) -> scores, got {method!r}")
@@ -204,7 +207,8 @@ def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator:
     coordinates, plus |scores_grad| when the batch has scores; "integrated_gradients" — forward_integrated_gradients' signed
     object_attribution (zero baseline, 16 steps); "attention" — the last layers' raw attention joined like the relevance,
     temporal_attention[-1][b, lengths[b]-1, t] * spatial_attention[-1][b,t,0,n]; "random" — uniform numbers from `generator`; or a callable
-    (model, batch) -> scores.  `head` (the fusion models): the logits the relevance and the saliency are taken from."""
+    (model, batch) -> scores.  `head` (the fusion models): the logits the relevance and the saliency are taken from.  "gradcam" is refused:
+    the layout side has no convolution."""
     if callable(method):
         return method(model, batch)
     kw = {} if head is None else {"head": head}
@@ -217,6 +221,9 @@ def attribution_scores(model, batch: Dict[str, torch.Tensor], method, generator:
     if method == "integrated_gradients":
         side = {"modality": "layout"} if "appearance" in getattr(model, "perturb_modalities", ()) else {}
         return model.forward_integrated_gradients(batch, **kw, **side)["object_attribution"]
+    if method == "gradcam":
+        raise StltHipError("method 'gradcam': a class activation map lives on the positions of the convolutional trunk, the video's cells; the layout side has no "
+                           "convolution (use modality='appearance')")
     if method == "attention":
         out = model.forward_attention(batch)
         B = batch["categories"].shape[0]
@@ -262,6 +269,9 @@ def run_perturbation_test(model, batches: Iterable[Dict[str, torch.Tensor]], met
         raise StltHipError(f"target: expected 'top1' or 'label', got {target!r}")
     if not callable(method) and method not in _PERTURB_METHODS:
         raise StltHipError(f"method: expected one of {_PERTURB_METHODS} or a callable (model, batch) -> scores, got {method!r}")
+    if method == "gradcam" and modality != "appearance":
+        raise StltHipError(f"method 'gradcam' with modality {modality!r}: a class activation map lives on the positions of the convolutional trunk, the video's "
+                           f"cells; the layout side has no convolution (use modality='appearance')")
     orders = tuple(orders)
     for o in orders:
         collate._perturb_args(o, unit)

@@ -8,6 +8,9 @@ the curves (stlt_perturb_curve).  Nothing is read back; the whole call is captur
 ``forward_integrated_gradients`` (Sundararajan, Taly, Yan 2017) is the same kind of shell around each model's own ``forward_saliency``:
 the path batches of a pass in one launch per input (stlt_ig_path / stlt_ig_path_dense), the model's sweep on them, the quadrature in a
 fixed order (stlt_ig_reduce), the completeness gap on the device (stlt_ig_delta).
+``forward_gradcam`` (Selvaraju et al. 2017; HiResCAM: Draelos and Carin 2020) is the shell of the class activation maps at a stage of the
+R3D-50 trunk for the five models that read appearance: the model's layers above the trunk give the gradient at the feature map, the
+sweep stopped at the stage (stlt_r3d_backward_layer) carries it down, stlt_cam_weights and stlt_cam_map reduce it with the activations.
 
 What an appearance token's deletion means is written down at ``collate.perturb_cells``: the reference's appearance encoder takes no
 key-padding mask (src/modelling/models.py:269), so the stride block of the token — its cell — is set to ``fill`` in the video.
@@ -334,4 +337,73 @@ def forward_integrated_gradients(model, batch: Dict[str, torch.Tensor], target=N
     if do_app:
         _, cell, _ = collate.appearance_cells({app_key: x_app})
         result["cell_attribution"] = ops.cell_pool_sum(attr[app_key], cell)
+    return result
+
+
+GRADCAM_VARIANTS = ("gradcam", "hirescam")
+
+
+@torch.no_grad()
+def forward_gradcam(model, batch: Dict[str, torch.Tensor], target=None, layer: int = 4, variant: str = "gradcam", relu: bool = True, upsample: bool = False,
+                    head: Optional[str] = None, dropout_live: bool = False, trunk=None, head_gradient: Optional[Callable] = None, takes_head: bool = False,
+                    takes_features: bool = False, pooled_head: bool = False) -> Dict[str, torch.Tensor]:
+    """See Resnet3D.forward_gradcam.  ``trunk``: (TrunkRunner, the trunk's nn.Sequential) or None (a fusion model without
+    ``appearance_trunk``); ``head_gradient(features, pooled, target, head)``: the model's part — its layers above the trunk on the feature
+    map as a leaf -> ({name: logits}, target as returned, d logit / d features (B, 2048, gt, gh, gw) or None, d logit / d pooled (B, 2048) or
+    None; exactly one of the two); ``takes_head``: the model has several logits; ``takes_features``: the model reads precomputed
+    ``appearance_features`` when the batch carries them; ``pooled_head``: the model's head reads the average-pooled features (Resnet3D);
+    ``dropout_live``: the model's own answer.
+    The last stage: the plain trunk forward (or the batch's features), the head's gradient, stlt_cam_weights and stlt_cam_map in NCDHW.
+    A stage below: the tape forward, the head's gradient, stlt_r3d_backward_layer, then the two launches in NDHWC on the tape's slot."""
+    who = "forward_gradcam"
+    if isinstance(layer, bool) or not isinstance(layer, int) or not 1 <= layer <= 4:
+        raise L.StltHipError(f"{who}: layer is a stage of the trunk, 1 to 4, got {layer!r}")
+    if variant not in GRADCAM_VARIANTS:
+        raise L.StltHipError(f"{who}: variant: expected one of {GRADCAM_VARIANTS}, got {variant!r}")
+    require_inference(who, dropout_live=dropout_live)
+    names = tuple(model.logit_names)
+    head = pick_head(who, names, head) if takes_head else names[-1]
+    from_features = takes_features and "appearance_features" in batch
+    if from_features and layer < 4:
+        raise L.StltHipError(f"{who}: layer {layer} lies inside the trunk: the batch carries only `appearance_features`, the trunk's output; it needs "
+                             f"`video_frames` (and MultimodalModelConfig(appearance_trunk=True)); layer 4 works on the features")
+    if not from_features and ("video_frames" not in batch or trunk is None):
+        raise L.StltHipError("the batch needs `appearance_features` (or `video_frames` with MultimodalModelConfig(appearance_trunk=True))" if takes_features
+                             else f"{who}: the batch needs `video_frames`")
+    app_key = "appearance_features" if from_features else "video_frames"
+    require_inference(who, tensors=(batch[app_key],))
+    x = ops._chk(batch[app_key].contiguous(), torch.float32, app_key)
+    if x.dim() != 5:
+        raise L.StltHipError(f"{app_key} must have five dimensions, got {tuple(x.shape)}")
+    if upsample and from_features:
+        raise L.StltHipError(f"{who}: upsample lays the map over `video_frames`, which this batch does not carry")
+    B = x.shape[0]
+    want_pooled = pooled_head
+    tape = None
+    if from_features:
+        feats, pooled = x, None
+    elif layer == 4:
+        feats, pooled = trunk[0].run(trunk[1], x, features=True, pooled=want_pooled)
+    else:
+        tape = trunk[0].run_tape(trunk[1], x, features=not want_pooled, pooled=want_pooled)
+        feats, pooled = tape.features, tape.pooled
+    logits, target, dfeatures, dpooled = head_gradient(feats, pooled, target, head)
+    if layer == 4:
+        a, layout = feats, "ncdhw"
+        if dfeatures is None:  # the pooled features' gradient, spread as the average pool spreads it: dpooled / P at every position
+            P = feats[0, 0].numel()
+            dfeatures = (dpooled / P).view(B, -1, 1, 1, 1).expand_as(feats).contiguous()
+        g = dfeatures.contiguous()
+    else:
+        a, layout = tape.stage(layer), "ndhwc"
+        g = tape.backward_layer(layer, dfeatures=None if dfeatures is None else dfeatures.contiguous(), dpooled=dpooled)
+    cam = ops.cam_map(a, ops.cam_weights(g, layout) if variant == "gradcam" else g, layout, relu=relu)
+    result = {k: logits[k] for k in names}
+    result.update(target=target, cam=cam)
+    if layer == 4:
+        result["cell_attribution"] = cam.flatten(1)
+    else:
+        result["cell_attribution"] = ops.cell_pool_sum(cam.view(B, 1, *cam.shape[1:]), (1 << (4 - layer),) * 3)
+    if upsample:
+        result["video_cam"] = ops.cam_upsample(cam, x.shape[2:])
     return result

@@ -163,7 +163,35 @@ class TransformerResnet(nn.Module):
         """As Resnet3D.forward_saliency: {"resnet3d": logits, "target", "video_frames_grad": (B, 3, T, H, W)} from the input-only sweep of
         the op-level Functions and the trunk (no weight-gradient product, no parameter's ``.grad`` touched).  Inference call: training mode
         keeps the appearance encoder's dropout live and is refused."""
+        if "video_frames" not in batch and "appearance_features" in batch:
+            return self._feature_saliency(batch, target)
         return video_saliency(self, batch, target, "resnet3d", dropout_live=self.training)
+
+    def _feature_saliency(self, batch: Dict[str, torch.Tensor], target, who: str = "forward_saliency") -> Dict[str, torch.Tensor]:
+        """forward_saliency on a batch that carries the trunk's feature map as ``appearance_features`` (B, 2048, gt, gh, gw) instead of
+        ``video_frames``: the layers above the trunk on the features as a leaf, input-only -> {"resnet3d", "target",
+        "appearance_features_grad"}.  No trunk launch (forward_gradcam's head gradient)."""
+        feats = batch["appearance_features"]
+        explain.require_inference(who, dropout_live=self.training, tensors=(feats,))
+        leaf = ops._chk(feats.contiguous(), torch.float32, "appearance_features").detach().requires_grad_(True)
+        with inputs_only(self), torch.enable_grad():
+            x = _appearance_tokens(self, leaf, self.config.num_attention_heads, 0.0)
+            logits = ops.LinearFn.apply(x[:, 0].contiguous(), self.classifier.weight, self.classifier.bias)
+            seed, target = explain.saliency_seed(logits, target, who)
+            (g,) = torch.autograd.grad(logits, leaf, seed)
+        return {"resnet3d": logits.detach(), "target": target, "appearance_features_grad": g}
+
+    def _gradcam_head(self, feats, pooled, target, head):
+        out = self.forward_saliency({"appearance_features": feats}, target=target)
+        return {"resnet3d": out["resnet3d"]}, out["target"], out["appearance_features_grad"], None
+
+    def forward_gradcam(self, batch: Dict[str, torch.Tensor], target=None, layer: int = 4, variant: str = "gradcam", relu: bool = True,
+                        upsample: bool = False) -> Dict[str, torch.Tensor]:
+        """As Resnet3D.forward_gradcam, the gradient at the feature map being ``appearance_features_grad`` of this model's own
+        ``forward_saliency`` on the trunk's features as a leaf (the projector, the encoder and the classifier, input-only).  Training
+        mode keeps the encoder's dropout live and is refused."""
+        return explain.forward_gradcam(self, batch, target=target, layer=layer, variant=variant, relu=relu, upsample=upsample, dropout_live=self.training,
+                                       trunk=(self.resnet._runner, self.resnet.resnet), head_gradient=self._gradcam_head)
 
     def forward_relevance(self, batch: Dict[str, torch.Tensor], target=None, return_layers: bool = False) -> Dict[str, torch.Tensor]:
         """The logits and the relevance of every appearance token for one raw logit per clip (the machinery of
@@ -438,6 +466,20 @@ class CrossAttentionFusionBackbone(nn.Module):
         return explain.forward_integrated_gradients(owner, batch, dropout_live=self._dropout_live(), modalities=explain.MODALITIES, takes_head=True,
                                                     has_trunk=getattr(self.appearance_branch, "resnet", None) is not None, **kw)
 
+    def run_gradcam(self, owner: nn.Module, batch, **kw):
+        """forward_gradcam of the fusion models (modelling/explain.py) with this backbone's answers: is dropout live, where is the trunk;
+        the gradient at the feature map is ``appearance_features_grad`` of the owner's own ``forward_saliency`` on the batch with the
+        features in place of the video"""
+        trunk = getattr(self.appearance_branch, "resnet", None)
+        rest = {k: v for k, v in batch.items() if k not in ("video_frames", "appearance_features")}
+
+        def head_gradient(feats, pooled, target, head):
+            out = owner.forward_saliency(dict(rest, appearance_features=feats), target=target, head=head)
+            return {k: out[k] for k in owner.logit_names}, out["target"], out["appearance_features_grad"], None
+
+        return explain.forward_gradcam(owner, batch, dropout_live=self._dropout_live(), trunk=None if trunk is None else (trunk._runner, trunk.resnet),
+                                       head_gradient=head_gradient, takes_head=True, takes_features=True, **kw)
+
     def _native_args(self, batch, fusion_head, layout_head, appearance_head):
         """Marshal a batch and the parameters for the whole-path native calls (stlt_caf_forward_flags, stlt_caf_forward_attention):
         -> (stlt_caf_params, stlt_inputs, keep-alive, feature map, (B, T, N, feature channels, appearance tokens, classes))"""
@@ -574,6 +616,16 @@ class CrossAttentionFusion(nn.Module):
         return self.caf_backbone.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
                                           steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
 
+    def forward_gradcam(self, batch: Dict[str, torch.Tensor], target=None, layer: int = 4, variant: str = "gradcam", relu: bool = True, upsample: bool = False,
+                        head=None) -> Dict[str, torch.Tensor]:
+        """Grad-CAM / HiResCAM of one raw logit per clip of head ``head`` (one of ``logit_names``; default the last) at stage ``layer`` of
+        the appearance trunk: Resnet3D.forward_gradcam, the gradient at the feature map being ``appearance_features_grad`` of this
+        model's own ``forward_saliency`` on the features as a leaf.  ``layer=4`` works on the batch's ``appearance_features`` (no trunk
+        launch) or on ``video_frames`` with ``appearance_trunk=True``; a stage below needs ``video_frames`` and the trunk, and a batch
+        with only ``appearance_features`` is refused.  -> the logits under ``logit_names``, "target", "cam" (B, gt, gh, gw),
+        "cell_attribution" (B, C), with ``upsample`` "video_cam" (B, T, H, W)."""
+        return self.caf_backbone.run_gradcam(self, batch, target=target, layer=layer, variant=variant, relu=relu, upsample=upsample, head=head)
+
     def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None, head=None,
                                      modality: str = "both") -> Dict[str, torch.Tensor]:
         """Integrated gradients (Sundararajan, Taly, Yan 2017) of one raw logit per clip of head ``head`` (one of ``logit_names``; default
@@ -629,6 +681,12 @@ class CrossAttentionCentralNetFusion(nn.Module):
         """As CrossAttentionFusion.forward_perturbed with this model's four heads (``head`` default "ensemble")."""
         return self.backbone.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
                                           steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
+
+    def forward_gradcam(self, batch: Dict[str, torch.Tensor], target=None, layer: int = 4, variant: str = "gradcam", relu: bool = True, upsample: bool = False,
+                        head=None) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_gradcam with this model's four heads (``head`` default "ensemble"); a head that does not read the
+        appearance side ("stlt") gives a zero gradient and a zero map."""
+        return self.backbone.run_gradcam(self, batch, target=target, layer=layer, variant=variant, relu=relu, upsample=upsample, head=head)
 
     def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None, head=None,
                                      modality: str = "both") -> Dict[str, torch.Tensor]:
@@ -704,6 +762,11 @@ class LateConcatenationFusion(nn.Module):
         """As CrossAttentionFusion.forward_perturbed."""
         return self._runner.run_perturbed(self, batch, scores, steps=steps, order=order, modality=modality, unit=unit, target=target, head=head,
                                           steps_per_pass=steps_per_pass, fill=fill, dataset_name=dataset_name, activation=activation)
+
+    def forward_gradcam(self, batch: Dict[str, torch.Tensor], target=None, layer: int = 4, variant: str = "gradcam", relu: bool = True, upsample: bool = False,
+                        head=None) -> Dict[str, torch.Tensor]:
+        """As CrossAttentionFusion.forward_gradcam."""
+        return self._runner.run_gradcam(self, batch, target=target, layer=layer, variant=variant, relu=relu, upsample=upsample, head=head)
 
     def forward_integrated_gradients(self, batch: Dict[str, torch.Tensor], target=None, steps: int = 16, baseline=None, steps_per_pass=None, head=None,
                                      modality: str = "both") -> Dict[str, torch.Tensor]:

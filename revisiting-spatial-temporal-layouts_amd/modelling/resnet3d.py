@@ -220,6 +220,56 @@ class TrunkRunner:
                                          None if pool is None else pool.data_ptr(), stream), "stlt_r3d_forward")
         return feats, pool
 
+    def run_tape(self, trunk: nn.Sequential, video: torch.Tensor, features: bool = True, pooled: bool = False) -> "TrunkTape":
+        """The tape forward outside autograd (stlt_r3d_train_forward; the features and the pooled features are bit for bit those of
+        ``run``), for a call that reads a stage's output off the tape and sends a gradient down to it (``forward_gradcam`` below the last
+        stage: ops.r3d_tape_stage, ops.r3d_backward_layer).  Frozen or trainable trunk alike: nothing here forms a weight gradient."""
+        video = ops._chk(video, torch.float32, "video_frames")
+        if video.dim() != 5 or video.shape[1] != 3:
+            raise L.StltHipError(f"video_frames must be (B, 3, T, H, W), got {tuple(video.shape)}")
+        if not features and not pooled:
+            raise L.StltHipError("run_tape: ask for the feature map, the pooled features or both")
+        B, _, T, H, W = video.shape
+        lib = L.load()
+        device = video.device
+        p = L.R3dParams()
+        p.bn_eps = BN_EPS
+        with torch.cuda.device(device), torch.no_grad():
+            for i, (conv, bn) in enumerate(trunk_convs(trunk)):
+                if abs(bn.eps - BN_EPS) > 0:
+                    raise L.StltHipError(f"BatchNorm3d eps must be {BN_EPS} (resnets3d.py), got {bn.eps}")
+                p.conv[i] = L.R3dConv(None, _dev_ptr(bn.weight), _dev_ptr(bn.bias), _dev_ptr(bn.running_mean), _dev_ptr(bn.running_var))
+            self._refresh(trunk, p, device)
+            nbytes = int(lib.stlt_r3d_tape_bytes(B, T, H, W))
+            if nbytes == 0:
+                raise L.StltHipError(f"video_frames {tuple(video.shape)}: no trunk for this shape")
+            tape = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            ws = self.ws.get(int(lib.stlt_r3d_workspace_bytes(B, T, H, W)), device)
+            To, Ho, Wo = _trunk_out(T), _trunk_out(H, 2), _trunk_out(W, 2)
+            feats = torch.empty(B, FEATURE_CHANNELS, To, Ho, Wo, device=device, dtype=torch.float32) if features else None
+            pool = torch.empty(B, FEATURE_CHANNELS, device=device, dtype=torch.float32) if pooled else None
+            L.check(lib.stlt_r3d_train_forward(C.byref(p), video.data_ptr(), B, T, H, W, ws.data_ptr(), ws.numel(), tape.data_ptr(), tape.numel(),
+                                               None if feats is None else feats.data_ptr(), None if pool is None else pool.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream), "stlt_r3d_train_forward")
+        return TrunkTape(self, L.R3dParams.from_buffer_copy(p), tape, (B, T, H, W), list(self.copies[2]), feats, pool)
+
+
+class TrunkTape:
+    """One tape forward of the trunk (TrunkRunner.run_tape): ``features`` / ``pooled`` as asked for, the ``tape``, the ``params`` and the
+    data-gradient copies ``dgrad`` it was made with, ``shape`` = (B, T, H, W).  ``stage(layer)``: that stage's output (B, t, h, w, c) NDHWC,
+    a view of the tape; ``backward_layer(layer, dfeatures=, dpooled=)``: the gradient there (ops.r3d_backward_layer) in the runner's
+    backward workspace."""
+
+    def __init__(self, runner, params, tape, shape, dgrad, features, pooled):
+        self.runner, self.params, self.tape, self.shape, self.dgrad, self.features, self.pooled = runner, params, tape, shape, dgrad, features, pooled
+
+    def stage(self, layer: int) -> torch.Tensor:
+        return ops.r3d_tape_stage(self.tape, self.shape, layer)
+
+    def backward_layer(self, layer: int, dfeatures: Optional[torch.Tensor] = None, dpooled: Optional[torch.Tensor] = None) -> torch.Tensor:
+        ws = self.runner.bws.get(int(L.load().stlt_r3d_backward_workspace_bytes(*self.shape)), self.tape.device)
+        return ops.r3d_backward_layer(self.params, self.dgrad, self.tape, self.shape, layer, dfeatures=dfeatures, dpooled=dpooled, workspace=ws)
+
 
 class R3dTrunkFn(torch.autograd.Function):
     """The trunk with a tape: forward = stlt_r3d_train_forward (the features or the pooled features, bit for bit those of
@@ -405,3 +455,28 @@ class Resnet3D(nn.Module):
         ``forward_saliency`` on the path batch: ``steps_per_pass`` bounds the clips one tape holds."""
         return explain.forward_integrated_gradients(self, batch, target=target, steps=steps, baseline=baseline, steps_per_pass=steps_per_pass,
                                                     modalities=self.perturb_modalities, num_classes=self.classifier.weight.shape[0])
+
+    def _gradcam_head(self, feats, pooled, target, head):
+        """forward_gradcam's part of this model: the classifier on the pooled features as a leaf -> its input gradient"""
+        leaf = pooled.detach().requires_grad_(True)
+        with inputs_only(self), torch.enable_grad():
+            logits = ops.LinearFn.apply(leaf, self.classifier.weight, self.classifier.bias)
+            seed, target = explain.saliency_seed(logits, target, "forward_gradcam")
+            (dpooled,) = torch.autograd.grad(logits, leaf, seed)
+        return {"resnet3d": logits.detach()}, target, None, dpooled
+
+    def forward_gradcam(self, batch: Dict[str, torch.Tensor], target=None, layer: int = 4, variant: str = "gradcam", relu: bool = True,
+                        upsample: bool = False) -> Dict[str, torch.Tensor]:
+        """Grad-CAM (Selvaraju et al., ICCV 2017) of one raw logit per clip at the output of stage ``layer`` (1 to 4) of the trunk: the
+        stage's activations summed over the channels, weighted by the logit's gradient with respect to them — by its mean over the
+        positions (``variant="gradcam"``) or element by element (``"hirescam"``, Draelos and Carin 2020) — and, with ``relu``, the
+        positive part.  The gradient is the one a hook on ``layerN``'s output sees in the reference's trunk (after the stage's ReLU).
+        -> {"resnet3d": (B, num_classes) logits, "target", "cam": (B, gt, gh, gw) float32, raw, not normalised, "cell_attribution": (B, C) on
+        the grid of collate.appearance_cells — ``cam`` flattened at the last stage, below it the sum over the 2^(4 - layer) cube of positions
+        of each cell (stlt_cell_pool_sum) —, with ``upsample`` "video_cam": (B, T, H, W), the trilinear resize of ``cam`` onto the video}.
+        ``layer=4`` needs no tape and no trunk backward: the plain trunk forward, the classifier's input gradient spread as the average
+        pool spreads it (dpooled / P), stlt_cam_weights and stlt_cam_map.  Below it: the tape forward, stlt_r3d_backward_layer — the
+        input-only sweep stopped at the stage — and the two launches on the tape's slot.  ``target`` as in ``forward_saliency``.  Nothing
+        is read back; no parameter's ``.grad`` is touched (``train_trunk`` is not needed).  Inference call; this model has no dropout."""
+        return explain.forward_gradcam(self, batch, target=target, layer=layer, variant=variant, relu=relu, upsample=upsample,
+                                       trunk=(self._runner, self.resnet), head_gradient=self._gradcam_head, pooled_head=True)

@@ -763,6 +763,125 @@ def ig_delta(attrs, seed: torch.Tensor, logits_x: torch.Tensor, logits_x0: torch
     return delta
 
 
+def _cam_layout(layout) -> int:
+    if layout not in L.CAM_LAYOUTS:
+        raise L.StltHipError(f"layout: expected one of {tuple(L.CAM_LAYOUTS)}, got {layout!r}")
+    return L.CAM_LAYOUTS[layout]
+
+
+def _cam_bpc(t: torch.Tensor, layout, name: str):
+    """(B, P, C) of a float32 contiguous activation or gradient tensor: "ndhwc" (B, ..., C), "ncdhw" (B, C, ...)"""
+    _chk(t, torch.float32, name)
+    if t.dim() < 3 or t.numel() == 0:
+        raise L.StltHipError(f"{name}: expected (B, ..., C) or (B, C, ...) with at least one position, got {tuple(t.shape)}")
+    B = t.shape[0]
+    Cn = t.shape[-1] if layout == "ndhwc" else t.shape[1]
+    return B, t.numel() // (B * Cn), Cn
+
+
+def cam_weights(g: torch.Tensor, layout: str = "ndhwc", scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Grad-CAM's channel weights (include/stlt_hip.h: stlt_cam_weights): the mean of g over the positions.  g float32, "ndhwc":
+    (B, t, h, w, C) or (B, P, C), as on the trunk's tape; "ncdhw": (B, C, t, h, w) or (B, C, P), as appearance_features -> alpha (B, C).
+    A fixed partition of the positions and a fixed order: a clip's row is the same bits whatever B.  `scratch`: a float32 tensor for the
+    partials (default: a fresh one)."""
+    lib = L.load()
+    code = _cam_layout(layout)
+    B, P, Cn = _cam_bpc(g, layout, "g")
+    need = lib.stlt_cam_scratch_bytes(B, P, Cn)
+    if scratch is None:
+        scratch = torch.empty(max(need // 4, 1), device=g.device, dtype=torch.float32)
+    else:
+        _chk(scratch, torch.float32, "scratch")
+    alpha = torch.empty(B, Cn, device=g.device, dtype=torch.float32)
+    L.check(lib.stlt_cam_weights(_p(g), B, P, Cn, code, _p(alpha), _p(scratch), scratch.numel() * 4, _stream()), "stlt_cam_weights")
+    return alpha
+
+
+def cam_map(a: torch.Tensor, w: torch.Tensor, layout: str = "ndhwc", relu: bool = True) -> torch.Tensor:
+    """A class activation map (include/stlt_hip.h: stlt_cam_map): cam[b,p] = sum_c w a over the channels, the positive part with `relu`.
+    a float32 in `layout` (as cam_weights' g); w (B, C): Grad-CAM with cam_weights' alpha; w of a's shape: the element-wise product of
+    HiResCAM -> cam float32 of a's position extents, (B, t, h, w) or (B, P).  A fixed order per element."""
+    lib = L.load()
+    code = _cam_layout(layout)
+    B, P, Cn = _cam_bpc(a, layout, "a")
+    _chk(w, torch.float32, "w")
+    if w.device != a.device or tuple(w.shape) not in ((B, Cn), tuple(a.shape)):
+        raise L.StltHipError(f"w: expected ({B}, {Cn}) channel weights or a's shape {tuple(a.shape)} on {a.device}, got {tuple(w.shape)} on {w.device}")
+    per = tuple(w.shape) == tuple(a.shape) and tuple(w.shape) != (B, Cn)
+    cam = torch.empty((B,) + (tuple(a.shape[1:-1]) if layout == "ndhwc" else tuple(a.shape[2:])), device=a.device, dtype=torch.float32)
+    L.check(lib.stlt_cam_map(_p(a), _p(w), int(per), B, P, Cn, code, int(bool(relu)), _p(cam), _stream()), "stlt_cam_map")
+    return cam
+
+
+def cam_upsample(cam: torch.Tensor, size) -> torch.Tensor:
+    """The trilinear resize of a map onto the video (include/stlt_hip.h: stlt_cam_upsample): cam (B, gt, gh, gw) float32, size = (T, H, W)
+    -> (B, T, H, W), the rule of F.interpolate(mode="trilinear", align_corners=False)."""
+    lib = L.load()
+    _chk(cam, torch.float32, "cam")
+    try:
+        T, H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise L.StltHipError(f"size: expected three positive extents (T, H, W), got {size!r}") from None
+    if cam.dim() != 4 or min(T, H, W) < 1:
+        raise L.StltHipError(f"cam_upsample: expected cam (B, gt, gh, gw) and three positive extents, got {tuple(cam.shape)} and {size!r}")
+    B, gt, gh, gw = cam.shape
+    out = torch.empty(B, T, H, W, device=cam.device, dtype=torch.float32)
+    L.check(lib.stlt_cam_upsample(_p(cam), B, gt, gh, gw, T, H, W, _p(out), _stream()), "stlt_cam_upsample")
+    return out
+
+
+def r3d_layer_geometry(B: int, T: int, H: int, W: int, layer: int):
+    """The output of stage `layer` (1 to 4) of the R3D-50 trunk on a (B, 3, T, H, W) video (include/stlt_hip.h: stlt_r3d_layer_geometry)
+    -> ((t, h, w, c), byte offset of its (B, t, h, w, c) slot on a stlt_r3d_train_forward tape).  Host arithmetic: needs no GPU."""
+    if isinstance(layer, bool) or not isinstance(layer, int):
+        raise L.StltHipError(f"layer: expected an integer from 1 to 4, got {layer!r}")
+    dims = (C.c_int64 * 4)()
+    off = C.c_size_t()
+    L.check(L.load().stlt_r3d_layer_geometry(int(B), int(T), int(H), int(W), layer, dims, C.byref(off)), "stlt_r3d_layer_geometry")
+    return tuple(int(v) for v in dims), int(off.value)
+
+
+def r3d_tape_stage(tape: torch.Tensor, shape, layer: int) -> torch.Tensor:
+    """Stage `layer`'s output (B, t, h, w, c) float32 NDHWC as a view of a trunk tape (uint8, stlt_r3d_train_forward's) of a video of
+    `shape` = (B, T, H, W)."""
+    B = int(shape[0])
+    (t, h, w, c), off = r3d_layer_geometry(*shape, layer)
+    n = B * t * h * w * c * 4
+    return tape[off:off + n].view(torch.float32).view(B, t, h, w, c)
+
+
+def r3d_backward_layer(params, dgrad, tape: torch.Tensor, shape, layer: int, dfeatures: Optional[torch.Tensor] = None, dpooled: Optional[torch.Tensor] = None,
+                       workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient at the output of stage `layer` (1 to 3) of the trunk (include/stlt_hip.h: stlt_r3d_backward_layer): the input-only
+    reverse sweep from the top, stopped at the first block of the next stage, without that output's ReLU mask.  params: the
+    ``_lib.R3dParams`` of the tape's forward; dgrad: its 53 data-gradient weight copies (tensors; the stem's is not read); tape / shape =
+    (B, T, H, W): a stlt_r3d_train_forward tape; exactly one of dfeatures (B, 2048, t, h, w) and dpooled (B, 2048) -> (B, t, h, w, c)
+    float32 NDHWC.  `workspace`: a uint8 tensor of stlt_r3d_backward_workspace_bytes (default: a fresh one); `out`: write here."""
+    lib = L.load()
+    if isinstance(layer, bool) or not isinstance(layer, int):
+        raise L.StltHipError(f"layer: expected an integer from 1 to 3, got {layer!r}")
+    _chk(tape, torch.uint8, "tape")
+    B, T, H, W = (int(v) for v in shape)
+    for name, t in (("dfeatures", dfeatures), ("dpooled", dpooled)):
+        if t is not None:
+            _chk(t, torch.float32, name)
+    if (dfeatures is None) == (dpooled is None):
+        raise L.StltHipError("r3d_backward_layer: pass exactly one of dfeatures and dpooled")
+    if out is None:
+        dims, _ = r3d_layer_geometry(B, T, H, W, min(max(layer, 1), 4))
+        out = torch.empty((B,) + dims, device=tape.device, dtype=torch.float32)
+    else:
+        _chk(out, torch.float32, "out")
+    if workspace is None:
+        workspace = torch.empty(int(lib.stlt_r3d_backward_workspace_bytes(B, T, H, W)), device=tape.device, dtype=torch.uint8)
+    else:
+        _chk(workspace, torch.uint8, "workspace")
+    ptrs = L.R3dPointers(*[t.data_ptr() for t in dgrad])
+    L.check(lib.stlt_r3d_backward_layer(C.byref(params), ptrs, _p(tape), tape.numel(), B, T, H, W, _p(dfeatures), _p(dpooled), layer, _p(out), _p(workspace),
+                                        workspace.numel(), _stream()), "stlt_r3d_backward_layer")
+    return out
+
+
 def attn_prefix_probe(qkv_frames: torch.Tensor, qkv_probes: torch.Tensor, kpm: torch.Tensor, num_heads: int):
     """Probe attention of the per-prefix forward (include/stlt_hip.h: stlt_attn_prefix_probe_fwd).  qkv_frames, qkv_probes: (S,T,3d) packed
     [q;k;v] rows of the frame and of the probe stream, kpm (S,T) bool/uint8 (True = frame masked as a key).  Probe (s,t) attends to the frame
