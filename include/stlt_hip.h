@@ -803,7 +803,8 @@ int stlt_attn_grad_probs(const float* qkv, const float* dctx, const uint8_t* kpm
  *   R_0 = I,   R_l = R_{l-1} + abar_l · R_{l-1}   for l = 1 .. n_layers    (layer 1 is abar[0], the layer next to the input)
  * ONE launch for the whole chain at every length: the columns of R never mix, so a workgroup keeps a block of columns of an item's R in LDS
  * (ping-pong) while the layers stream in from memory — every column for L <= 64 (several items per workgroup when L is small), blocks of 16
- * columns for 64 < L <= 256; no second buffer is needed from the caller at any length.  fp32 FMA over k in ascending order: the same bits
+ * columns for 64 < L <= 256; no second buffer is needed from the caller at any length.  fp32 FMA over k in ascending order from zero, the old
+ * R[i,j] added once, last (an element of R = 1 + 1e-2 keeps 2.5 u over four layers instead of 45 u): the same bits
  * on every run.  n_layers == 0 writes the identity (abar may then be NULL).  0 <= n_layers <= 64, 1 <= L <= 256; abar, R 4 bytes.
  * Every bad argument is STLT_EINVAL with a message and launches nothing. */
 int stlt_attn_rollout(const float* abar, int64_t n_layers, int64_t S, int64_t L, float* R, stlt_stream_t stream);
@@ -875,7 +876,7 @@ int stlt_attn_grad_probs_cross(const float* q, int64_t ldq, const float* k, cons
  * The maps have the geometry of stlt_caf_attention_maps: layout_to_appearance (n, S, T, A), appearance_to_layout (n, S, A, T), fusion_layout
  * (n, S, T, T), fusion_appearance (n, 2, S, A, A).  Only the non-zero quadrants are read.  ONE launch for the whole chain: the columns of R
  * never mix, so a workgroup keeps 16 columns of one item's R in LDS (ping-pong, 64 KB at J = 512) while the maps stream in from memory.
- * fp32 FMA over k in ascending order: the same bits on every run.  n_fusion == 0 (LCF) writes the block-diagonal (the maps may be NULL).
+ * fp32 FMA over k in ascending order from zero, the old R[i,j] added once, last: the same bits on every run.  n_fusion == 0 (LCF) writes the block-diagonal (the maps may be NULL).
  * 0 <= n_fusion <= 64, 1 <= T, A <= 256; every pointer 4 bytes.  Every bad argument is STLT_EINVAL with a message and launches nothing. */
 int stlt_attn_rollout_joint(const float* r_layout, const float* r_appearance, const float* layout_to_appearance, const float* appearance_to_layout,
                             const float* fusion_layout, const float* fusion_appearance, int64_t n_fusion, int64_t S, int64_t T, int64_t A, float* R,

@@ -7,13 +7,13 @@
 //   rollout:    R_0 = I, R_l = R_{l-1} + abar_l · R_{l-1}.  The columns of R never mix (column j of R_l depends on column j of R_{l-1} alone), so
 //               a workgroup keeps a block of columns of one item's R in LDS, ping-pong, for the WHOLE chain while the layers stream in from
 //               memory: one launch whatever the length.  L <= 64: the block is every column, and several items share a workgroup when L is small;
-//               64 < L <= 256: blocks of 16 columns, (L, 16) floats a side.  fp32 FMA over k in ascending order.
+//               64 < L <= 256: blocks of 16 columns, (L, 16) floats a side.  fp32 FMA over k in ascending order from zero, R_{l-1}[i,j] added last.
 //   combine:    rel[b,t,n] = R_temporal[b, lengths[b]-1, t] * R_spatial[b,t,0,n]  (row 0 of a frame is its CLS token, models.py:79; the head
 //               reads frame lengths-1 of a clip, models.py:189-192).
 //   joint rollout: R over the J = T + A stacked tokens, R_0 = blockdiag(r_layout, r_appearance), then per fusion layer three steps R <- R + X·R with
 //               X = [[0, l2a], [a2l, 0]], blockdiag(f_layout, f_appearance[.,0]), blockdiag(0, f_appearance[.,1]).  Only the non-zero quadrants are
 //               read.  The columns of R never mix, so a workgroup keeps 16 columns of one item's R in LDS, ping-pong, for the whole chain: one
-//               launch; 2 x 512 x 16 floats = 64 KB at the largest J.  fp32 FMA over k in ascending order.
+//               launch; 2 x 512 x 16 floats = 64 KB at the largest J.  fp32 FMA over k in ascending order from zero, the old R[i,j] added last.
 //   joint combine: row[b,:] = w_layout R[b, lengths[b]-1, :] + w_appearance R[b, T, :] (the frame the layout head reads, models.py:189-192, and the
 //               appearance CLS token, models.py:260-262); frame_rel = row[:T], app_rel = row[T:], rel[b,t,n] = frame_rel[b,t] * r_spatial[b,t,0,n].
 #include <cstdint>
@@ -58,13 +58,14 @@ __global__ __launch_bounds__(RO_THREADS) void attn_rollout_kernel(const RolloutG
       const int p = e / tile, rem = e - p * tile;
       const int i = rem / CB, j = rem - i * CB;
       const int64_t item = grp * P + p;
-      float a = old[e];
+      float a = 0.f;  // the chain starts from zero and the old value joins it once, last: started from old[e], every one of the L products
+                      // rounds at R's magnitude — 45 u on the diagonal of a map of scale 1e-2, where R = 1 + 1e-2 (profiles/explain_scale.md)
       if (item < geo.S) {  // (the items past the end keep their identity and are never stored)
         const float* arow = geo.abar + ((int64_t)l * geo.S + item) * map + (int64_t)i * L;
         const float* col = old + p * tile + j;
         for (int k = 0; k < L; ++k) a = fmaf(arow[k], col[k * CB], a);
       }
-      nxt[e] = a;
+      nxt[e] = old[e] + a;
     }
     __syncthreads();
     cur ^= 1;
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(JR_THREADS) void attn_rollout_joint_kernel(const Jo
     float* nxt = r_lds[cur ^ 1];
     for (int e = threadIdx.x; e < tile; e += JR_THREADS) {
       const int i = e / CB, j = e - i * CB;
-      float a = old[e];
+      float a = 0.f;  // from zero, the old value added last: see attn_rollout_kernel
       const bool top = i < T;
       const float* arow = top ? (map_t ? map_t + (int64_t)i * n_t : nullptr) : map_a + (int64_t)(i - T) * n_a;
       if (arow) {
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(JR_THREADS) void attn_rollout_joint_kernel(const Jo
         const float* col = old + (top ? k0_t : k0_a) * CB + j;
         for (int k = 0; k < n; ++k) a = fmaf(arow[k], col[k * CB], a);
       }
-      nxt[e] = a;
+      nxt[e] = old[e] + a;
     }
     __syncthreads();
     cur ^= 1;

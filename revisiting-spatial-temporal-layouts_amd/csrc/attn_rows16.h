@@ -109,8 +109,23 @@ __device__ __forceinline__ void scores16(const Rows& rows, bool causal, const f3
   }
 }
 
+// exp(x) for x <= 0 as exp2 of x * log2(e), the product carried with its rounding error and log2(e)'s own: t = fl(x * L), r = the rest
+// of x * log2(e), exp(x) = exp2(t) * (1 + r ln 2).  The plain __expf rounds the product to fp32 — an absolute error of up to ulp(t) / 2
+// in the exponent, a relative error of exp of |x| * u: 22 u at x = -40, which is the row's largest element of a gradient-weighted map
+// whose peak key has a negative gradient (profiles/explain_scale.md).  This form stays within 2 u (v_exp_f32: 1 ulp); x below -87
+// gives 0, as a masked score does — x is clamped at -128 first (exp2(-184) is 0 already), so that a spread near FLT_MAX cannot turn
+// t into -inf and 0 * inf into NaN.
+__device__ __forceinline__ float exp_nonpos(float x) {
+  constexpr float L = 1.44269502162933349609375f, L_REST = 1.92596299e-8f, LN2 = 0.693147182f;
+  x = fmaxf(x, -128.f);
+  const float t = x * L;
+  const float r = fmaf(x, L, -t) + x * L_REST;
+  return __builtin_amdgcn_exp2f(t) * fmaf(r, LN2, 1.0f);
+}
+
 // mask + softmax of a query's scores (4 per key block, over the 4 lanes lg = 0..3): st becomes exp(score - max), 0 where masked; returns
-// 1 / sum, 0 for a row whose keys are all masked (-> zeros)
+// 1 / sum, 0 for a row whose keys are all masked (-> zeros).  Domain: a masked score is -1e30 and a score above -1e29 counts as visible,
+// so visible scores must lie above -1e29 (those of any fp32 q, k of sane magnitude do).
 template <int NB>
 __device__ __forceinline__ float softmax16(f32x4 (&st)[NB], const bool (&ok)[NB][4], float scale) {
   float m = -1e30f;
@@ -127,7 +142,7 @@ __device__ __forceinline__ float softmax16(f32x4 (&st)[NB], const bool (&ok)[NB]
   for (int kb = 0; kb < NB; ++kb)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float p = st[kb][r] > -1e29f ? __expf(st[kb][r] - m) : 0.f;
+      const float p = st[kb][r] > -1e29f ? exp_nonpos(st[kb][r] - m) : 0.f;
       st[kb][r] = p;
       sum += p;
     }
